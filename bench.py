@@ -7,7 +7,7 @@ backward), AdamW step (train.py:209's torch.optim.AdamW semantics, fused HIP ker
 picotron_amd/optim.py) and, for N > 1, the DataParallelBucket
 all-reduce of the gradients over RCCL (dp = N, weak scaling: per-GPU work fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--model llama2-7b] [--tp T] [--cp C] [--seq S]
 
@@ -23,11 +23,20 @@ One-GPU per-rank compute proxies (no collectives; what one rank of the multi-GPU
                       + 7 half blocks per layer on every rank) and the reference's (the last rank: 1
                       causal + 7 full 4096 x 4096 d128 blocks) -- attention blocks and the layer's GEMMs
 
-Rank 0 prints ONE JSON line.  `value` is whole-job tokens/s (max wall time over ranks);
-tokens/s/GPU and MFU (utils.py:42-48 formula, N counted once, 2.5 PF bf16 dense peak) ride along.
-`roofline` is the MFMA GEMM (the dominant kernel), timed live with HIP events around every launch
-in the timed region; `cpu_baseline` is the oracle (a plain-torch fp32 restatement of the reference
-path, oracle/picotron_oracle.py) timed on this host's cores on a bounded sample.
+Rank 0 prints ONE JSON line.  `value` is whole-job tokens/s (max wall time over ranks) over the
+--steps timed steps, `ms_per_step` one timed step's wall time; tokens/s/GPU and MFU (utils.py:42-48
+formula, N counted once, 2.5 PF bf16 dense peak) ride along.  A plain run does only that: set up,
+warm up, time the steps, print the line (`roofline` and `cpu_baseline` are null).
+
+--full adds what the headline figure does not need: `roofline`, the MFMA GEMM (the dominant
+kernel) timed live with HIP events around its launches in the timed region (--no-probe: off), and
+`cpu_baseline`, the oracle (a plain-torch fp32 restatement of the reference path,
+oracle/picotron_oracle.py) timed on this host's cores on a bounded sample (--cpu-tokens 0: off).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step left its caller as
+DIR/<name>.npy (dump_outputs): the steps' losses and seeded samples of the updated parameters and
+of AdamW's first moments.  Model init, tokens and sample positions are seeded, so two builds run
+with the same arguments can be compared array for array.
 """
 import argparse
 import json
@@ -93,6 +102,36 @@ def cpu_baseline(cfg, tokens):
                       f"{torch.get_num_threads()} threads of {os.cpu_count()} host CPUs); the reference's own "
                       f"--use_cpu gloo path (config 1, 8 processes) runs ~113 tokens/s in the build container "
                       f"(BASELINE.md)"}
+
+
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: all arrays together (float32 samples)
+DUMP_MAX_SAMPLE = 65536          # elements sampled from one tensor
+
+
+def dump_outputs(out_dir, losses, model, optimizer):
+    """--dump-outputs: what the last timed step handed back -- `loss.npy`, the loss of every timed
+    step (float64, the last entry the last step's), and per parameter this rank holds
+    `param.<name>.npy`, the updated weights, and `adam_m.<name>.npy`, AdamW's first moment (the view
+    of the step's gradients that survives the step's zero_grad), as float32.  A tensor larger than
+    the per-array share of DUMP_BUDGET_BYTES is sampled at fixed positions drawn from a generator
+    seeded by its name, the same in every run and every build."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray(losses, dtype=np.float64))
+    named = list(model.named_parameters())
+    cap = max(1, min(DUMP_MAX_SAMPLE, DUMP_BUDGET_BYTES // 4 // max(1, 2 * len(named))))
+    for name, p in named:
+        idx = None
+        if p.numel() > cap:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randint(0, p.numel(), (cap,), generator=g).to(p.device)
+        for kind, t in (("param", p), ("adam_m", optimizer.state.get(p, {}).get("exp_avg"))):
+            if t is None:
+                continue
+            flat = t.detach().reshape(-1)
+            flat = flat if idx is None else flat[idx]
+            np.save(os.path.join(out_dir, f"{kind}.{name}.npy"), flat.float().cpu().numpy())
 
 
 MODELS = {"smollm-1.7b": ("SmolLM-1.7B", "SMOLLM_1_7B", 15), "llama2-7b": ("Llama-2-7B", "LLAMA2_7B", 32)}
@@ -586,6 +625,12 @@ def build_parser():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the GEMM roofline (HIP events around "
+                         "GEMM launches of the timed steps) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's results (losses, samples of the updated "
+                         "parameters and AdamW moments) as DIR/<name>.npy")
     ap.add_argument("--model", choices=sorted(MODELS), default="smollm-1.7b")
     ap.add_argument("--layers", type=int, default=0, help="decoder layers (0 = the config's: 15 / 32)")
     ap.add_argument("--tp", type=int, default=1, help="tensor-parallel degree (N GPUs = dp x tp x cp)")
@@ -603,8 +648,8 @@ def build_parser():
     ap.add_argument("--seq", type=int, default=1024)
     ap.add_argument("--grad-acc", type=int, default=None,
                     help="micro-batches per step (default 32; 4 with the TP micro-batch default)")
-    ap.add_argument("--cpu-tokens", type=int, default=1024, help="tokens in the cpu_baseline sample (0 = skip)")
-    ap.add_argument("--no-probe", action="store_true", help="do not time GEMM launches with events")
+    ap.add_argument("--cpu-tokens", type=int, default=1024, help="--full: tokens in the cpu_baseline sample (0 = skip)")
+    ap.add_argument("--no-probe", action="store_true", help="--full: do not time GEMM launches with events")
     ap.add_argument("--bucket-mb", type=float, default=25, help="DataParallelBucket bucket_cap_mb (reference: 25)")
     ap.add_argument("--grad-type", choices=["fp32", "bf16"], default="fp32",
                     help="DataParallelBucket grad_type: fp32 main_grad (reference default) or bf16")
@@ -636,8 +681,13 @@ def resolve_batch(args):
 
 
 def main():
-    args = resolve_batch(build_parser().parse_args())
+    ap = build_parser()
+    args = resolve_batch(ap.parse_args())
     proxy = bool(args.tp_proxy or args.cp_proxy)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (proxy or args.assemble_only):
+        ap.error("--dump-outputs writes the training step's results: not with a proxy or --assemble-only")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not proxy:
         # `python bench.py --gpus N`: start the N ranks ourselves (before any GPU call in this process)
         sys.exit(launch_ranks(sys.argv[1:], args.gpus))
@@ -777,7 +827,7 @@ def main():
     # step times every GEMM launch (the family average, and which launch kind dominates), the later
     # ones only the dominant kind's launches -- an event pair per launch idles the GPU a few us, ~1.3
     # ms for a micro-batch's whole family
-    use_probe = not (args.no_probe or pp > 1 or graphed is not None)
+    use_probe = args.full and not (args.no_probe or pp > 1 or graphed is not None)
     fam_probe, dom = None, None
 
     if world > 1:
@@ -812,6 +862,8 @@ def main():
         losses[-1] = lt.item()
     value = tokens / elapsed
     per_gpu = value / world
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, model, optimizer)
     fpt = flops_per_token(num_params, cfg)
     mfu = per_gpu * fpt / MI355X_BF16_DENSE_PEAK
 
@@ -875,7 +927,7 @@ def main():
                                                        for k, v in fam.by_label().items()}}}
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_tokens > 0 and args.model == "smollm-1.7b":
+    if args.full and rank == 0 and world == 1 and args.cpu_tokens > 0 and args.model == "smollm-1.7b":
         log("cpu baseline ...")
         cpu = cpu_baseline(cfg, args.cpu_tokens)
 

@@ -134,6 +134,82 @@ def test_pmc_kernel_key_for_dual_labels():
     assert k("linear_wgrad_grouped") == "linear_wgrad_grouped"
 
 
+def test_plain_run_options():
+    """--full and --dump-outputs are off by default; --steps 0 is refused before any GPU call."""
+    a = bench.build_parser().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    a = bench.build_parser().parse_args(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True,
+                       text=True, env=_env(), timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr and r.stdout == ""
+
+
+def test_dump_outputs_arrays(tmp_path, monkeypatch):
+    """dump_outputs writes float64 losses and float32 parameters / first moments; a tensor above the
+    per-array cap is sampled at positions that depend only on its name, so two dumps of the same
+    state agree element for element and the whole dump stays under its byte budget."""
+    import numpy as np
+    import torch
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(300, 70), torch.nn.Linear(70, 5, bias=False)).to(torch.bfloat16)
+    opt = torch.optim.AdamW(model.parameters(), lr=1e-2)
+    model(torch.randn(4, 300).to(torch.bfloat16)).float().sum().backward()
+    opt.step()
+    monkeypatch.setattr(bench, "DUMP_MAX_SAMPLE", 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [10.5, 10.25], model, opt)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["loss.npy"] + [f"{k}.{n}.npy" for k in ("param", "adam_m")
+                                           for n in ("0.weight", "0.bias", "1.weight")])
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float64 and loss.tolist() == [10.5, 10.25]
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all() and np.array_equal(x, y), n
+        total += x.nbytes
+    assert total <= bench.DUMP_BUDGET_BYTES
+    w = np.load(tmp_path / "a" / "param.0.weight.npy")              # 21000 elements: sampled
+    assert w.shape == (1000,) and np.isin(w, model[0].weight.detach().float().numpy()).all()
+    b = np.load(tmp_path / "a" / "param.0.bias.npy")                # 70 elements: whole
+    assert np.array_equal(b, model[0].bias.detach().float().numpy())
+    m = np.load(tmp_path / "a" / "adam_m.1.weight.npy")
+    assert np.array_equal(m, opt.state[model[1].weight]["exp_avg"].float().numpy().reshape(-1)) and np.abs(m).max() > 0
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_outputs(tmp_path):
+    """A plain 1-GPU run (2 layers, 2 micro-batches per step): --steps timed steps, a result line with
+    ms_per_step and without the --full figures, and the last step's arrays under --dump-outputs."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--layers", "2", "--grad-acc", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=_env(), timeout=300, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.strip().splitlines()
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["roofline"] is None and d["cpu_baseline"] is None
+    assert d["unit"] == "tokens/s" and d["higher_is_better"] is True and d["dtype"] == "bf16"
+    assert d["ms_per_step"] > 0
+    tokens_per_step = 2 * 4 * 1024
+    assert abs(d["value"] - tokens_per_step / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert r.stderr.count("[bench] step ") == 3 and "cpu baseline" not in r.stderr
+    loss = np.load(out / "loss.npy")
+    assert loss.shape == (3,) and loss[-1] == d["final_loss"]
+    files = sorted(os.listdir(out))
+    assert len(files) == 1 + 2 * (2 * 9 + 3)              # 9 tensors per layer + embedding, final norm, lm_head
+    total = 0
+    for f in files:
+        x = np.load(out / f)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), f
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.abs(np.load(out / "adam_m.final_proj.weight.npy")).max() > 0
+
+
 def test_resolve_batch_defaults():
     """Config 2's mbs 4 x grad_acc 32 by default; pure TP (config 3) mbs 32 x grad_acc 4 -- the same
     128 sequences per step -- unless either is given; cp / pp keep the config-2 defaults."""

@@ -4,7 +4,7 @@
 #
 # steps (run in the order given; the first failure ends the call -- no retries on the GPU):
 #   suite        pytest -m gpu (whole suite; TESTS=... files / node ids, TESTK=... a -k expression), then smoke()
-#   bench        bench.py N=1 (BENCH_RUNS=2 lines), default arguments
+#   bench        bench.py --full N=1 (BENCH_RUNS=2 lines: roofline and CPU baseline included), default arguments
 #   prof         rocprofv3 --kernel-trace --stats of bench.py --steps 2 (kernel table -> profiles via tools/prof_summary.py)
 #   pmc          GEMM/all-kernel HBM traffic: separate FETCH_SIZE and WRITE_SIZE passes over bench.py --grad-acc 2
 #   pmcx         extra counter sets over bench.py --grad-acc 1 (SQ busy/VALU/MFMA, TCC hit/miss/EA reads)
@@ -44,13 +44,13 @@ step_suite() {
 
 step_bench() {
   for i in $(seq 1 ${BENCH_RUNS:-1}); do
-    timeout -k 10 300 python -u bench.py $BENCH_ARGS > $O.bench$i.json 2> $O.bench$i.err || { echo bench failed; tail $O.bench$i.err; return 1; }
+    timeout -k 10 300 python -u bench.py --full $BENCH_ARGS > $O.bench$i.json 2> $O.bench$i.err || { echo bench failed; tail $O.bench$i.err; return 1; }
     jline $O.bench$i.json bench
   done
 }
 
 step_prof() {
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O.prof -o k -- python -u bench.py --steps 2 --warmup 1 --cpu-tokens 0 > $O.prof.log 2>&1 || { echo prof failed; tail $O.prof.log; return 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O.prof -o k -- python -u bench.py --full --steps 2 --warmup 1 --cpu-tokens 0 > $O.prof.log 2>&1 || { echo prof failed; tail $O.prof.log; return 1; }
   gzip -f $O.prof/k_kernel_trace.csv
   python tools/prof_summary.py --trace $O.prof/k_kernel_trace.csv.gz --steps 3 > $O.kernels.md || true
 }
@@ -73,7 +73,7 @@ step_pmcx() {
 }
 
 step_llama() {
-  timeout -k 10 400 python -u bench.py --model llama2-7b --grad-acc 8 --steps 2 --warmup 1 --cpu-tokens 0 > $O.llama.json 2> $O.llama.err || { echo llama failed; tail $O.llama.err; return 1; }
+  timeout -k 10 400 python -u bench.py --full --model llama2-7b --grad-acc 8 --steps 2 --warmup 1 --cpu-tokens 0 > $O.llama.json 2> $O.llama.err || { echo llama failed; tail $O.llama.err; return 1; }
   jline $O.llama.json llama2-7b
 }
 
@@ -90,7 +90,7 @@ step_cp() {
 step_configs() { step_llama && step_tp && step_cp; }
 
 step_gloo2() {
-  timeout -k 10 400 python -u bench.py --gpus 2 --backend gloo --steps 1 --warmup 1 --grad-acc 4 > $O.gloo2.json 2> $O.gloo2.err || { echo gloo2 failed; tail -20 $O.gloo2.err; return 1; }
+  timeout -k 10 400 python -u bench.py --full --gpus 2 --backend gloo --steps 1 --warmup 1 --grad-acc 4 > $O.gloo2.json 2> $O.gloo2.err || { echo gloo2 failed; tail -20 $O.gloo2.err; return 1; }
   [ $(wc -l < $O.gloo2.json) = 1 ] || { echo "gloo2: stdout is not one line"; return 1; }
   python -c "import json; d=json.load(open('$O.gloo2.json')); print('gloo2', d['n_gpus'], d['ranks'], d['backend'], d['config']['parallelism'], round(d['value']))"
 }
@@ -106,7 +106,7 @@ step_grid8() {   # every 8-rank grid the driver's 8-GPU run can launch, assemble
   while IFS='|' read -r tag args; do
     [ -n "$tag" ] || continue
     n=$((n+1))
-    timeout -k 10 ${GRID8_TIMEOUT:-420} python -u bench.py --gpus 8 --backend gloo --steps 1 --warmup 1 --cpu-tokens 0 $args > $O.grid8_$tag.json 2> $O.grid8_$tag.err || { echo "grid8 $tag failed"; tail -20 $O.grid8_$tag.err; return 1; }
+    timeout -k 10 ${GRID8_TIMEOUT:-420} python -u bench.py --full --gpus 8 --backend gloo --steps 1 --warmup 1 --cpu-tokens 0 $args > $O.grid8_$tag.json 2> $O.grid8_$tag.err || { echo "grid8 $tag failed"; tail -20 $O.grid8_$tag.err; return 1; }
     [ $(wc -l < $O.grid8_$tag.json) = 1 ] || { echo "grid8 $tag: stdout is not one line"; return 1; }
     python -c "import json; d=json.load(open('$O.grid8_$tag.json')); print('grid8 $tag', d['n_gpus'], d['ranks'], d['backend'], d['config']['parallelism'], round(d['value']), d['final_loss'])"
   done <<< "${GRID8:-dp8|--layers 2 --grad-acc 2
@@ -117,15 +117,15 @@ cfg5|--model llama2-7b --cp 8 --seq 32768 --mbs 1 --layers 2 --grad-acc 1}"
 
 step_dp() {
   for gt in fp32 bf16; do
-    timeout -k 10 300 python -u bench.py --dp-bucket --grad-type $gt --steps 3 --cpu-tokens 0 > $O.dp_$gt.json 2>/dev/null || { echo dp $gt failed; return 1; }
+    timeout -k 10 300 python -u bench.py --full --dp-bucket --grad-type $gt --steps 3 --cpu-tokens 0 > $O.dp_$gt.json 2>/dev/null || { echo dp $gt failed; return 1; }
     jline $O.dp_$gt.json dp-bucket-$gt
   done
-  timeout -k 10 300 python -u bench.py --steps 3 --cpu-tokens 0 > $O.plain.json 2>/dev/null || { echo plain failed; return 1; }
+  timeout -k 10 300 python -u bench.py --full --steps 3 --cpu-tokens 0 > $O.plain.json 2>/dev/null || { echo plain failed; return 1; }
   jline $O.plain.json plain
 }
 
 step_dpprof() {   # kernel table of the DP path on a 1-rank RCCL group (fp32 main_grad sinks), beside prof's plain table
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O.dpprof -o k -- python -u bench.py --dp-bucket --grad-type ${GT:-fp32} --steps 2 --warmup 1 --cpu-tokens 0 > $O.dpprof.log 2>&1 || { echo dpprof failed; tail $O.dpprof.log; return 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O.dpprof -o k -- python -u bench.py --full --dp-bucket --grad-type ${GT:-fp32} --steps 2 --warmup 1 --cpu-tokens 0 > $O.dpprof.log 2>&1 || { echo dpprof failed; tail $O.dpprof.log; return 1; }
   gzip -f $O.dpprof/k_kernel_trace.csv
   python tools/prof_summary.py --trace $O.dpprof/k_kernel_trace.csv.gz --steps 3 > $O.dpkernels.md || true
 }
@@ -185,7 +185,7 @@ step_envab() {
   for i in $(seq 1 ${ROUNDS:-3}); do
     for v in A B ${C:+C}; do
       if [ $v = A ]; then E=$A; elif [ $v = B ]; then E=$B; else E=$C; fi
-      env $E timeout -k 10 300 python -u bench.py --cpu-tokens 0 --steps 3 $BENCH_ARGS > $O.$v$i.json 2>/dev/null || { echo "bench $E failed"; return 1; }
+      env $E timeout -k 10 300 python -u bench.py --full --cpu-tokens 0 --steps 3 $BENCH_ARGS > $O.$v$i.json 2>/dev/null || { echo "bench $E failed"; return 1; }
       jline $O.$v$i.json "$E"
     done
   done
@@ -200,7 +200,7 @@ step_libab() {
     for f in "${L[@]}"; do
       cp "$f" $LIB || return 1
       n=$(basename $f .so)
-      timeout -k 10 300 python -u bench.py --cpu-tokens 0 --steps 3 $BENCH_ARGS > $O.${n}_$i.json 2>/dev/null || { echo "bench $n failed"; cp $O.orig.so $LIB; return 1; }
+      timeout -k 10 300 python -u bench.py --full --cpu-tokens 0 --steps 3 $BENCH_ARGS > $O.${n}_$i.json 2>/dev/null || { echo "bench $n failed"; cp $O.orig.so $LIB; return 1; }
       jline $O.${n}_$i.json $n
     done
   done
