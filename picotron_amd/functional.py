@@ -85,106 +85,52 @@ def wgrad_pairing(phase):
 def flush_wgrad_pairs():
     """Launch (unpaired) every weight gradient a micro-batch deferred and no pair completed."""
     pend, WgradPairing.pending = WgradPairing.pending, {}
-    ph, WgradPairing.phase = WgradPairing.phase, None
-    try:
-        for dy, x, params in pend.values():
-            wgrad(dy, x, params)
-    finally:
-        WgradPairing.phase = ph
+    for job in pend.values():
+        _launch_each(_resolve_sinks([job])[0], True)
 
 
 def pair_jobs(wjobs):
     """wjobs [(dy2d, x2d, params)] -> the jobs to launch in this backward: [] when it defers them
-    (phase 0), each paired with the previous micro-batch's job of the same parameters (phase 1)."""
+    (phase 0), each paired with the previous micro-batch's job of the same parameters (phase 1).
+    An older job that cannot wait for its pair -- its key deferred again, or the completing job has
+    another layout -- is launched here, on its own."""
     ph = WgradPairing.phase
     if ph is None or not wjobs:
         return wjobs
-    if ph == 0:
-        for dy, x, params in wjobs:
-            key = tuple(id(p) for p in params)
-            if key in WgradPairing.pending:   # deferred twice without a pair: the older one now
-                odx, ox, op = WgradPairing.pending.pop(key)
-                wgrad(odx, ox, op)
-            WgradPairing.pending[key] = (dy, x, params)
-        return []
     out = []
     for dy, x, params in wjobs:
-        prev = WgradPairing.pending.pop(tuple(id(p) for p in params), None)
-        if prev is not None and (prev[0].shape != dy.shape or prev[1].shape != x.shape or
+        key = tuple(id(p) for p in params)
+        prev = WgradPairing.pending.pop(key, None)
+        if prev is not None and (ph == 0 or prev[0].shape != dy.shape or prev[1].shape != x.shape or
                                  prev[0].stride() != dy.stride() or prev[1].stride() != x.stride()):
-            wgrad(*prev)            # not the same layout: the older one on its own first
+            _launch_each(_resolve_sinks([prev])[0], True)
             prev = None
-        out.append((dy, x, params) if prev is None else (K.KPair(prev[0], dy), K.KPair(prev[1], x), params))
+        if ph == 0:
+            WgradPairing.pending[key] = (dy, x, params)
+        else:
+            out.append((dy, x, params) if prev is None else (K.KPair(prev[0], dy), K.KPair(prev[1], x), params))
     return out
 
 
+# The three entries below settle their jobs once (pair_jobs: defer, pair, or pass through) and hand
+# them to the launchers, which take settled jobs and never look at the pairing phase.
 def wgrad(dy2d, x2d, params, notify=True):
     """dW_i = dY_i^T X for the column segments of dY; one launch when the sinks agree.  Parameters
     with requires_grad=False get no gradient (autograd leaves their .grad alone).  notify=False: a
     partial gradient (one token chunk of a chunked sequence-parallel layer, the sum is not complete
     yet): the owner is not told.  Under weight-gradient pairing (WgradPairing) the job may be
     deferred to, or paired with, the other micro-batch of its pair."""
-    if WgradPairing.phase is not None:
-        jobs = pair_jobs([(dy2d, x2d, params)])
-        if not jobs:
-            return
-        (dy2d, x2d, params), = jobs
-        ph = wgrad_pairing(None)   # settled: the per-parameter fallbacks launch it as it is
-        try:
-            return wgrad(dy2d, x2d, params, notify)
-        finally:
-            wgrad_pairing(ph)
-    if not all(p.requires_grad for p in params):
-        lo = 0
-        for p in params:
-            n = p.shape[0]
-            if p.requires_grad:
-                wgrad(dy2d[:, lo:lo + n], x2d, [p], notify)
-            lo += n
-        return
-    targets = [_wgrad_target(p) for p in params]
-    epis = {e for _, e in targets}
-    if len(epis) == 1:
-        K.linear_wgrad(dy2d, x2d, [t for t, _ in targets], epilogue=epis.pop())
-    else:  # mixed sinks (one grad already allocated, another not): one launch per parameter
-        lo = 0
-        for (t, e), p in zip(targets, params):
-            n = p.shape[0]
-            K.linear_wgrad(dy2d[:, lo:lo + n], x2d, [t], epilogue=e)
-            lo += n
-    if notify:
-        for p in params:
-            _grad_ready(p)
+    jobs = pair_jobs([(dy2d, x2d, params)])
+    if jobs:
+        _launch_each(_resolve_sinks(jobs)[0], notify)
 
 
 def wgrad_group(jobs, notify=True):
     """Several wgrads [(dy2d, x2d, params), ...] in one grouped launch when every sink takes the
-    same epilogue (else one wgrad() per job)."""
-    if WgradPairing.phase is not None:
-        jobs = pair_jobs(jobs)
-        if not jobs:
-            return
-    ph = wgrad_pairing(None)   # the jobs are settled: the per-job fallbacks below launch them as they are
-    try:
-        _wgrad_group(jobs, notify)
-    finally:
-        wgrad_pairing(ph)
-
-
-def _wgrad_group(jobs, notify):
-    frozen = any(not p.requires_grad for _, _, params in jobs for p in params)
-    targets = [] if frozen else [[_wgrad_target(p) for p in params] for _, _, params in jobs]
-    epis = {e for tg in targets for _, e in tg}
-    if frozen or len(epis) != 1:
-        for dy2d, x2d, params in jobs:
-            wgrad(dy2d, x2d, params, notify)
-        return
-    K.linear_wgrad_grouped([(dy2d, x2d, [t for t, _ in tg]) for (dy2d, x2d, _), tg in zip(jobs, targets)],
-                           epilogue=epis.pop())
-    if notify:
-        for _, _, params in jobs:
-            for p in params:
-                _grad_ready(p)
+    same epilogue (else one launch per job, or per parameter: _resolve_sinks)."""
+    jobs = pair_jobs(jobs)
+    if jobs:
+        _launch_group(*_resolve_sinks(jobs), notify)
 
 
 def dgrad_with_wgrad(dy2d, weights, wjobs, gu=None, keep_parts=False, split_min=None, order=None, notify=True):
@@ -194,49 +140,77 @@ def dgrad_with_wgrad(dy2d, weights, wjobs, gu=None, keep_parts=False, split_min=
     Returns dX / dg|du.  Under weight-gradient pairing a deferring micro-batch launches the dX alone
     (the split-K halves kept for the consumer as in the dual), the completing one the dual with the
     paired (K = 2 T) weight gradients."""
-    if WgradPairing.phase is not None:
-        wjobs = pair_jobs(wjobs)
-        if not wjobs:
-            if gu is not None:
-                return K.linear_dgrad_swiglu(dy2d, weights[0], gu)
-            return K.linear_dgrad(dy2d, weights, keep_parts=keep_parts, split_min=split_min)
-    ph = wgrad_pairing(None)
-    try:
-        return _dgrad_with_wgrad(dy2d, weights, wjobs, gu, keep_parts, split_min, order, notify)
-    finally:
-        wgrad_pairing(ph)
-
-
-def _dgrad_with_wgrad(dy2d, weights, wjobs, gu, keep_parts, split_min, order, notify):
+    pairing = WgradPairing.phase is not None
+    wjobs = pair_jobs(wjobs)
+    if pairing and not wjobs:
+        if gu is not None:
+            return K.linear_dgrad_swiglu(dy2d, weights[0], gu)
+        return K.linear_dgrad(dy2d, weights, keep_parts=keep_parts, split_min=split_min)
     frozen = any(not p.requires_grad for _, _, params in wjobs for p in params)
     mns = [(dy.shape[1], x.shape[1]) for dy, x, _ in wjobs]
     dmn = (dy2d.shape[0], gu.shape[1] // 2 if gu is not None else weights[0].shape[1])
-    if K.dual_enabled() and not frozen and K.dual_fits(dmn, mns):
-        targets = [[_wgrad_target(p) for p in params] for _, _, params in wjobs]
-        epis = {e for tg in targets for _, e in tg}
-        if len(epis) == 1:
-            epi = epis.pop()
-            wk = [(dy, x, [t for t, _ in tg]) for (dy, x, _), tg in zip(wjobs, targets)]
-            dx = K.linear_dgrad_dual(dy2d, weights, wk, epi, gu=gu, keep_parts=keep_parts, split_min=split_min,
-                                     order=order)
-            if dx is None:   # not tileable after all: the same sinks, separate launches
-                dx = K.linear_dgrad_swiglu(dy2d, weights[0], gu) if gu is not None else K.linear_dgrad(dy2d, weights)
-                K.linear_wgrad_grouped(wk, epilogue=epi)
-        else:   # mixed sinks: one launch per parameter (the targets exist now)
-            dx = K.linear_dgrad_swiglu(dy2d, weights[0], gu) if gu is not None else K.linear_dgrad(dy2d, weights)
-            for (dy, x, params), tg in zip(wjobs, targets):
-                lo = 0
-                for p, (t, e) in zip(params, tg):
-                    K.linear_wgrad(dy[:, lo:lo + p.shape[0]], x, [t], epilogue=e)
-                    lo += p.shape[0]
-        if notify:
-            for _, _, params in wjobs:
-                for p in params:
-                    _grad_ready(p)
-        return dx
-    dx = K.linear_dgrad_swiglu(dy2d, weights[0], gu) if gu is not None else K.linear_dgrad(dy2d, weights)
-    wgrad_group(wjobs, notify)
+    dual = K.dual_enabled() and not frozen and K.dual_fits(dmn, mns)
+    launches, epi = _resolve_sinks(wjobs)
+    dx = None
+    if dual and epi is not None:
+        dx = K.linear_dgrad_dual(dy2d, weights, [l[:3] for l in launches], epi, gu=gu, keep_parts=keep_parts,
+                                 split_min=split_min, order=order)
+    if dx is None:   # not tileable (after all), or mixed sinks: the same sinks, separate launches
+        dx = K.linear_dgrad_swiglu(dy2d, weights[0], gu) if gu is not None else K.linear_dgrad(dy2d, weights)
+        _launch_group(launches, epi, notify and not dual)
+    if notify and dual:   # the jobs of a dual launch tell their owners together
+        _notify(p for _, _, params in wjobs for p in params)
     return dx
+
+
+def _resolve_sinks(jobs):
+    """The gradient sinks of settled wgrad jobs [(dy2d, x2d, params)], resolved once (resolving
+    creates a missing .grad, which changes what a second look would see): -> (launches, epilogue).
+    launches [(dy2d, x2d, sinks, epilogue, ready)]: one per job whose parameters all take a gradient
+    through one epilogue; else one per parameter over its column segment of dY -- mixed sinks (one
+    .grad already allocated, another not), or frozen parameters, which get none.  ready: the
+    parameters whose owners may be told once that launch is queued (a frozen job's one by one, a
+    mixed job's after its last launch).  epilogue: the one every launch takes when every job is one
+    launch -- they can then share a grouped or dual launch -- else None."""
+    launches, whole = [], True
+    for dy, x, params in jobs:
+        frozen = not all(p.requires_grad for p in params)
+        tg = [_wgrad_target(p) if p.requires_grad else None for p in params]
+        if not frozen and len({e for _, e in tg}) == 1:
+            launches.append((dy, x, [t for t, _ in tg], tg[0][1], params))
+            continue
+        whole, lo = False, 0
+        for p, t in zip(params, tg):
+            n = p.shape[0]
+            if t is not None:
+                launches.append((dy[:, lo:lo + n], x, [t[0]], t[1], [p] if frozen else []))
+            lo += n
+        if not frozen:
+            launches[-1] = launches[-1][:4] + (params,)
+    epis = {l[3] for l in launches}
+    return launches, (epis.pop() if whole and len(epis) == 1 else None)
+
+
+def _notify(params):
+    for p in params:
+        _grad_ready(p)
+
+
+def _launch_each(launches, notify):
+    """Resolved wgrad launches, one K.linear_wgrad each."""
+    for dy, x, sinks, epi, ready in launches:
+        K.linear_wgrad(dy, x, sinks, epilogue=epi)
+        if notify:
+            _notify(ready)
+
+
+def _launch_group(launches, epi, notify):
+    """Resolved wgrad launches as ONE grouped launch when they share an epilogue, else one by one."""
+    if epi is None:
+        return _launch_each(launches, notify)
+    K.linear_wgrad_grouped([l[:3] for l in launches], epilogue=epi)
+    if notify:
+        _notify(p for l in launches for p in l[4])
 
 
 # Deferred RMSNorm weight-gradient sums: inside an autograd backward, a norm whose gradient has

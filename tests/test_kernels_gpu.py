@@ -269,7 +269,7 @@ def test_gemm_every_tile_every_layout(tile):
 
 
 @pytest.mark.parametrize("T,K,ns", [(100, 72, [40, 24]), (4000 // 8, 1376 // 8, [4000 // 8]), (192, 1376, [96]),
-                                    (256, 256, [200]), (512, 4096, [4000]), (512, 1376, [4096])])
+                                    (256, 256, [200]), (512, 4096, [4000]), (512, 1376, [4096]), (96, 128, [128])])
 def test_gemm_off_grid_shapes_run_padded(T, K, ns):
     """Projections whose T, K or output widths are not multiples of 64 (no GEMM tile covers them:
     Llama-2-7B at tp 8 has a vocab shard of 4000 and an intermediate shard of 1376) run on
@@ -1186,11 +1186,12 @@ def test_paired_wgrad_k_segments(epi):
         assert torch.equal(a, b)               # the same tiles, the same K order
 
 
-@pytest.mark.parametrize("ga", [4, 3])
-def test_paired_wgrad_training_matches_unpaired_and_oracle(ga):
+@pytest.mark.parametrize("ga,mbs,seq", [(4, 2, 256), (3, 2, 256), (2, 1, 96)])
+def test_paired_wgrad_training_matches_unpaired_and_oracle(ga, mbs, seq):
     """train_step with weight-gradient pairing (default) vs without (PICOTRON_WGRAD_PAIR=0) on a small
     Llama, ga micro-batches of one step (4: 2 pairs; 3: a pair and a last micro-batch launched on its
-    own), bf16 .grad sinks and fp32 main_grad (a one-rank
+    own; mbs 1 x seq 96: a pair's 2 T = 192 is on the GEMMs' 64-grid, each micro-batch's T is not, so
+    every pair runs as its two padded halves), bf16 .grad sinks and fp32 main_grad (a one-rank
     DataParallelBucket is not needed: the main_grad sink is exercised by test_golden_gpu's G8): the
     loss is identical and every gradient agrees to bf16 rounding; both agree with the fp32 oracle's
     accumulated gradients at north_star's tolerance."""
@@ -1209,7 +1210,7 @@ def test_paired_wgrad_training_matches_unpaired_and_oracle(ga):
         with torch.device(DEV):
             model = Llama(cfg)
         model.to(BF)
-        loader = SyntheticMicroBatchDataLoader(2, 256, ga, cfg.vocab_size, torch.device(DEV), seed=5)
+        loader = SyntheticMicroBatchDataLoader(mbs, seq, ga, cfg.vocab_size, torch.device(DEV), seed=5)
         with switches.override(wgrad_pair=pair):
             loss = train_step(model, loader, DEV)
         torch.cuda.synchronize()
@@ -1221,7 +1222,7 @@ def test_paired_wgrad_training_matches_unpaired_and_oracle(ga):
     for n in res[0][1]:
         assert rel_err(res[1][1][n], res[0][1][n]) < 1e-2, n
     c = dict(vars(cfg))
-    cos, sin = O.get_cos_sin(256, 64, base=10000.0)
+    cos, sin = O.get_cos_sin(seq, 64, base=10000.0)
     for x, t in ids_all:
         lo = O.llama_forward(x, params, c, cos.float(), sin.float(), norm=O.rmsnorm_flash_semantics)
         (F.cross_entropy(lo.reshape(-1, cfg.vocab_size), t.reshape(-1)) / ga).backward()

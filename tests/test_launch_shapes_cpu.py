@@ -49,6 +49,38 @@ def test_reduce_sink_alignment_decided_before_launch():
     assert not K._reduce_sink_ok(ok.t())                                     # column-major
 
 
+def test_wgrad_form_tile_and_slices():
+    """(tile, K-slices) of a wgrad launch, or None off the 64-grid: a pure function of the shapes,
+    the sinks' alignment and the switches (empty CPU tensors stand for the operands)."""
+    import torch
+
+    def job(t, n, k, widths=None, dtype=torch.bfloat16, pair=False):
+        dy, x = torch.empty(t, n, dtype=torch.bfloat16), torch.empty(t, k, dtype=torch.bfloat16)
+        if pair:
+            dy, x = K.KPair(dy, torch.empty_like(dy)), K.KPair(x, torch.empty_like(x))
+        return dy, x, [torch.empty(w, k, dtype=dtype) for w in (widths or [n])]
+    q, o = 3 * H // 8, H // 8
+    tp8 = [job(T, q, H, [o] * 3), job(T, H, o)]
+    assert K.wgrad_form([job(T, 3 * H, H, [H] * 3), job(T, H, H)], K.EPI_BF16) == (-1, 1)     # TP = 1: the auto tile
+    assert K.wgrad_form(tp8, K.EPI_BF16_ACC) == (15, 2)              # q|k|v + o_proj dW: tile 15 in 2 slices
+    assert K.wgrad_form(tp8, K.EPI_F32) == (-1, 1)                   # an f32 store is not a reduce-pass sink
+    assert K.wgrad_form(tp8, K.EPI_BF16_ACC, tile=13) == (13, 1)     # a tile asked for: unsliced
+    assert K.wgrad_form([job(T, 2 * I // 8, H, [I // 8] * 2)], K.EPI_F32_ACC, ) == (15, 1)   # gate|up dW
+    assert K.wgrad_form([job(1024, 1024, 256)], K.EPI_BF16) == (-1, 2)                       # wgrad_ksplit's slices
+    with switches.override(ksplit=0):
+        assert K.wgrad_form(tp8, K.EPI_BF16_ACC) == (-1, 1)
+    # a sink the reduce pass cannot address keeps the unsliced launch
+    buf = torch.empty(H * o + 8, dtype=torch.bfloat16)
+    bad = [tp8[0], (tp8[1][0], tp8[1][1], [buf[1:1 + H * o].view(H, o)])]
+    assert K.wgrad_form(bad, K.EPI_BF16_ACC) == (-1, 1)
+    # a pair: tile 12 unsliced, and the grid test is on each micro-batch's T (2 T = 192 is on the grid)
+    assert K.wgrad_form([job(T, H, o, pair=True)], K.EPI_BF16_ACC) == (12, 1)
+    assert K.wgrad_form([job(128, 128, 128, pair=True)], K.EPI_BF16) == (12, 1)
+    assert K.wgrad_form([job(96, 128, 128, pair=True)], K.EPI_BF16) is None
+    assert K.wgrad_form([job(96, 128, 128)], K.EPI_BF16) is None
+    assert K.wgrad_form([job(128, 128, 128), job(128, 40, 72)], K.EPI_BF16) is None          # one job off the grid
+
+
 def test_hq_form_for_tp_shards():
     """The 128x128 k-substep tile (15) for the few-tile TP-shard GEMMs, 2 K-slices where its tiles
     fill at most half a round at K >= 4096; not for the TP = 1 shapes or the shards that already tile."""

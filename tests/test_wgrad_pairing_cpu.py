@@ -37,6 +37,59 @@ def test_defer_then_pair():
         FN.WgradPairing.pending.clear()
 
 
+def _recorded_launches(monkeypatch):
+    """K.linear_wgrad / K.linear_wgrad_grouped replaced by recorders: [(dy2d, x2d, sinks, epilogue)]."""
+    calls = []
+    monkeypatch.setattr(K, "linear_wgrad", lambda dy, x, outs, epilogue=K.EPI_BF16, tile=-1:
+                        calls.append((dy, x, outs, epilogue)))
+    monkeypatch.setattr(K, "linear_wgrad_grouped", lambda jobs, epilogue=K.EPI_BF16, tile=-1:
+                        calls.extend((dy, x, outs, epilogue) for dy, x, outs in jobs))
+    return calls
+
+
+def _deferred_twice(monkeypatch, defer):
+    """Two jobs of one parameter deferred (phase 0) with no completing micro-batch between them, then
+    the flush: BOTH reach the sink, the older first (on its own, when the newer takes its place)."""
+    calls = _recorded_launches(monkeypatch)
+    w = torch.nn.Parameter(torch.zeros(4, 3))
+    a, b = _job(8, 4, 3, [w]), _job(8, 4, 3, [w])
+    old = FN.wgrad_pairing(0)
+    try:
+        defer(a, b)
+        assert [c[0] for c in calls] == [a[0]] and list(FN.WgradPairing.pending.values()) == [b]
+        FN.wgrad_pairing(None)
+        FN.flush_wgrad_pairs()
+        assert not FN.WgradPairing.pending
+    finally:
+        FN.wgrad_pairing(old)
+        FN.WgradPairing.pending.clear()
+    assert len(calls) == 2
+    (dy0, x0, s0, e0), (dy1, x1, s1, e1) = calls
+    assert dy0 is a[0] and x0 is a[1] and dy1 is b[0] and x1 is b[1]
+    assert s0[0] is w.grad and s1[0] is w.grad and (e0, e1) == (K.EPI_BF16, K.EPI_BF16_ACC)
+
+
+def test_key_deferred_twice_launches_the_older_job(monkeypatch):
+    _deferred_twice(monkeypatch, lambda a, b: (FN.wgrad(*a), FN.wgrad(*b)))
+
+
+def test_key_repeated_in_one_deferred_group(monkeypatch):
+    _deferred_twice(monkeypatch, lambda a, b: FN.wgrad_group([a, b]))
+
+
+def test_mixed_sinks_of_a_group_are_resolved_once(monkeypatch):
+    """One .grad present, the others not: resolving a sink creates the missing .grad, so a second
+    look would accumulate onto its uninitialised memory -- each parameter's first gradient is a store."""
+    calls = _recorded_launches(monkeypatch)
+    w1, w2, w3 = (torch.nn.Parameter(torch.zeros(4, 3)) for _ in range(3))
+    w1.grad = torch.zeros(4, 3)
+    a, b = _job(8, 8, 3, [w1, w2]), _job(8, 4, 3, [w3])
+    FN.wgrad_group([a, b])
+    assert [(c[2][0] is p.grad, c[3]) for c, p in zip(calls, (w1, w2, w3))] == \
+        [(True, K.EPI_BF16_ACC), (True, K.EPI_BF16), (True, K.EPI_BF16)]
+    assert torch.equal(calls[0][0], a[0][:, :4]) and torch.equal(calls[1][0], a[0][:, 4:]) and calls[2][0] is b[0]
+
+
 def test_train_step_phase_sequence():
     """Micro-batches (0, 1), (2, 3), ... pair; an odd last micro-batch runs alone (phase None)."""
     from picotron_amd.train import pairing_phase
