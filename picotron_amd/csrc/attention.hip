@@ -48,18 +48,24 @@ constexpr float kRescaleLog2 = 8.0f;
 constexpr int KT = 64;  // rows per staged K/V (or Q/dO) tile
 constexpr int NW = 4;   // waves per workgroup, 32 rows each
 
+// a token-major [B, S, H, D] strided view (d contiguous): base pointer and the (batch, seq, head)
+// strides in elements; row<R>() is the D contiguous elements of one (b, s, h), read as R
+template <typename T>
+struct View4 {
+  T* p;
+  int64_t sb, ss, sh;
+  template <typename R = T>
+  __device__ __forceinline__ R* row(int b, int64_t s, int h) const { return (R*)p + b * sb + s * ss + h * sh; }
+};
+
 struct AttnArgs {
-  const uint16_t* q; int64_t q_sb, q_ss, q_sh;
-  const uint16_t* k; int64_t k_sb, k_ss, k_sh;
-  const uint16_t* v; int64_t v_sb, v_ss, v_sh;
-  void* o; int64_t o_sb, o_ss, o_sh;            // bf16 output, or f32 accumulator when merge
+  View4<const uint16_t> q, k, v;
+  View4<void> o;                                 // bf16 output, or f32 accumulator when merge
   float* lse;                                    // [B, H, Sq] rows lse_ld apart
-  const uint16_t* dout; int64_t do_sb, do_ss, do_sh;
+  View4<const uint16_t> dout;
   const float* delta;                            // [B, H, Sq] rowsum(dO * O), rows lse_ld apart
   int64_t lse_ld;   // elements between consecutive (b, h) rows of lse / delta (Sq when dense)
-  void* dq; int64_t dq_sb, dq_ss, dq_sh;
-  void* dk; int64_t dk_sb, dk_ss, dk_sh;
-  void* dv; int64_t dv_sb, dv_ss, dv_sh;
+  View4<void> dq, dk, dv;
   int B, H, HKV, Sq, Sk;
   float scale;
   int causal;
@@ -151,17 +157,17 @@ __device__ __forceinline__ int crow(int r, int lane) { return (r & 3) + 8 * (r >
 // K/V (or Q/dO) tiles -- over 8 different L2s.  Remap so each XCD gets a contiguous range of
 // (block, head, batch) ids, blocks of one head adjacent: a head's tiles are fetched into one L2
 // and re-read from there (a head's K+V at S 1024, d 64 is 256 KiB; an XCD's L2 is 4 MiB).
-__device__ __forceinline__ void attn_coords(const AttnArgs& a, int& x, int& y, int& z) {
-  const int nx = gridDim.x, ny = gridDim.y, nwg = nx * ny * gridDim.z;
-  const int id = blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z);
+__device__ __forceinline__ int xcd_remap(int id, int nwg) {
   const int xcd = id & 7, q = nwg >> 3, r = nwg & 7;
-  const int pid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
+}
+__device__ __forceinline__ void attn_coords(int& x, int& y, int& z) {
+  const int nx = gridDim.x, ny = gridDim.y, nwg = nx * ny * gridDim.z;
+  const int pid = xcd_remap(blockIdx.x + nx * (blockIdx.y + ny * blockIdx.z), nwg);
   x = pid % nx;
   y = (pid / nx) % ny;
   z = pid / (nx * ny);
 }
-
-__device__ __forceinline__ int nqb_of(const AttnArgs& a) { return a.Sq / (NW * 32); }
 
 // v + (v of lane ^ 32) and max(v, v of lane ^ 32): one v_permlane32_swap (no LDS round trip)
 __device__ __forceinline__ float xor32_sum(float v) {
@@ -262,6 +268,49 @@ __device__ __forceinline__ void accum_T_f32(float* row_ptr, int dt, const f32x16
   }
 }
 
+// a split work item's f32 partial, in accum_T_f32's layout but stored: 16-byte chunk g4 of tile dt
+// of the lane's row, and all DT tiles of the row
+__device__ __forceinline__ void store_chunk_f32(float* row_ptr, int dt, int g4, const f32x16_t& x, float mul,
+                                                int lane) {
+  const int d = 32 * dt + 8 * g4 + 4 * (lane >> 5);
+  *(float4*)(row_ptr + d) = make_float4(x[4 * g4] * mul, x[4 * g4 + 1] * mul, x[4 * g4 + 2] * mul, x[4 * g4 + 3] * mul);
+}
+template <int DT>
+__device__ __forceinline__ void store_T_f32(float* row_ptr, const f32x16_t (&x)[DT], float mul, int lane) {
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) store_chunk_f32(row_ptr, dt, g4, x[dt], mul, lane);
+}
+
+// the dK/dV kernels' epilogue for key row `key` of (b, hk): dK scaled (and rotated back by RoPE when
+// tables are given) and dV, as bf16 stores, or both added into f32 accumulators (grad_f32)
+template <int DT>
+__device__ __forceinline__ void store_dkdv(const AttnArgs& a, int b, int key, int hk, const f32x16_t (&dk)[DT],
+                                           const f32x16_t (&dv)[DT], int lane) {
+  if (!a.grad_f32) {
+    uint16_t* dkr = a.dk.row<uint16_t>(b, key, hk);
+    uint16_t* dvr = a.dv.row<uint16_t>(b, key, hk);
+    if (a.rope_cos) {
+      store_T_bf16_unrope<DT>(dkr, dk, a.scale, a.rope_cos + (int64_t)key * a.rope_ld,
+                              a.rope_sin + (int64_t)key * a.rope_ld, lane);
+    } else {
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) store_T_bf16(dkr, dt, dk[dt], a.scale, lane);
+    }
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) store_T_bf16(dvr, dt, dv[dt], 1.0f, lane);
+  } else {
+    float* dkr = a.dk.row<float>(b, key, hk);
+    float* dvr = a.dv.row<float>(b, key, hk);
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      accum_T_f32(dkr, dt, dk[dt], a.scale, lane);
+      accum_T_f32(dvr, dt, dv[dt], 1.0f, lane);
+    }
+  }
+}
+
 template <int N>
 __device__ __forceinline__ void vm_wait() {
   if constexpr (N == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -338,13 +387,13 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
 
   bf16x8_t qf[KS];
   if constexpr (D != 64) {
-    const uint16_t* qrow = a.q + b * a.q_sb + (int64_t)myq * a.q_ss + h * a.q_sh;
+    const uint16_t* qrow = a.q.row(b, myq, h);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) qf[ks] = ld_row_frag(qrow, ks, lane);
   }
 
-  const uint16_t* kbase = a.k + b * a.k_sb + hk * a.k_sh;
-  const uint16_t* vbase = a.v + b * a.v_sb + hk * a.v_sh;
+  const uint16_t* kbase = a.k.row(b, 0, hk);
+  const uint16_t* vbase = a.v.row(b, 0, hk);
   const int kv_end = a.causal ? (qb + 1) * NWK * 32 : a.Sk;
   // this call's K/V tiles: all of the block's, or a split work item's [kt_lo, kt_hi)
   const int kt0 = kt_lo, nkt = (kt_hi < 0 ? kv_end / KT : kt_hi) - kt_lo;
@@ -358,8 +407,8 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
   constexpr int NS = fwd_stages<D, NWK>(), OPS = 2 * (KT * D * 2 / 1024) / NWK;
   auto stage = [&](int kt, int buf) {
     lds_u8* sk = smem + buf * 2 * TILE_B;
-    stage_rows<D, NWK>(kbase + (int64_t)(kt0 + kt) * KT * a.k_ss, a.k_ss, sk, wave, lane);
-    stage_rows<D, NWK>(vbase + (int64_t)(kt0 + kt) * KT * a.v_ss, a.v_ss, sk + TILE_B, wave, lane);
+    stage_rows<D, NWK>(kbase + (int64_t)(kt0 + kt) * KT * a.k.ss, a.k.ss, sk, wave, lane);
+    stage_rows<D, NWK>(vbase + (int64_t)(kt0 + kt) * KT * a.v.ss, a.v.ss, sk + TILE_B, wave, lane);
   };
   const int pre = nkt < NS - 1 ? nkt : NS - 1;
   if constexpr (D == 64) {
@@ -370,9 +419,9 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     constexpr int QI = NWK * 32 / KT, QS = QI / 2;   // 64-row Q images, K|V stages they take
     static_assert(QI % 2 == 0 && QS < NS, "Q images fill whole K|V stages");
     lds_u8* qimg = smem + (NS - QS) * 2 * TILE_B;
-    const uint16_t* qbase = a.q + b * a.q_sb + h * a.q_sh + (int64_t)qb * NWK * 32 * a.q_ss;
+    const uint16_t* qbase = a.q.row(b, 0, h) + (int64_t)qb * NWK * 32 * a.q.ss;
 #pragma unroll
-    for (int i = 0; i < QI; ++i) stage_rows<D, NWK>(qbase + (int64_t)i * KT * a.q_ss, a.q_ss, qimg + i * TILE_B, wave, lane);
+    for (int i = 0; i < QI; ++i) stage_rows<D, NWK>(qbase + (int64_t)i * KT * a.q.ss, a.q.ss, qimg + i * TILE_B, wave, lane);
     const int pre0 = nkt < NS - QS ? nkt : NS - QS;   // tiles in flight beside Q
     for (int t = 0; t < pre0; ++t) stage(t, t);
     if (pre0 >= 3) vm_wait<2 * OPS>();   // the younger tiles 1 .. pre0 - 1 may stay in flight
@@ -500,15 +549,7 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     // (every query row sees at least one key of every item: split_ck is even)
     const float inv_l = l > 0.f ? 1.0f / l : 0.f;
     const int row = wave * 32 + (lane & 31);
-    float* orow = a.split_o + ((int64_t)item * (NWK * 32) + row) * D;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = 32 * dt + 8 * g4 + 4 * (lane >> 5);
-        *(float4*)(orow + d) = make_float4(o[dt][4 * g4] * inv_l, o[dt][4 * g4 + 1] * inv_l,
-                                           o[dt][4 * g4 + 2] * inv_l, o[dt][4 * g4 + 3] * inv_l);
-      }
+    store_T_f32<DT>(a.split_o + ((int64_t)item * (NWK * 32) + row) * D, o, inv_l, lane);
     if (lane < 32) a.split_lse[(int64_t)item * (NWK * 32) + row] = l > 0.f ? m * kLn2 + __logf(l) : -INFINITY;
     return;
   }
@@ -516,13 +557,13 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
   const float lse = m * kLn2 + __logf(l);
   float* lse_p = a.lse + ((int64_t)b * a.H + h) * a.lse_ld + myq;
   if (!a.merge) {
-    uint16_t* orow = (uint16_t*)a.o + b * a.o_sb + (int64_t)myq * a.o_ss + h * a.o_sh;
+    uint16_t* orow = a.o.row<uint16_t>(b, myq, h);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) store_T_bf16(orow, dt, o[dt], inv_l, lane);
     if (lane < 32) *lse_p = lse;
   } else {
     // update_out_and_lse: out <- out*exp(lse_old - lse_new) + blk*exp(lse_blk - lse_new)
-    float* orow = (float*)a.o + b * a.o_sb + (int64_t)myq * a.o_ss + h * a.o_sh;
+    float* orow = a.o.row<float>(b, myq, h);
     const float lold = *lse_p;
     const float lnew = fmaxf(lold, lse) + log1pf(__expf(-fabsf(lold - lse)));
     const float wold = lold == -INFINITY ? 0.f : __expf(lold - lnew);
@@ -547,7 +588,7 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
 template <int D, int NWK>
 __global__ __launch_bounds__(NWK * 64) void attn_fwd_kernel(AttnArgs a) {
   int bx, hh, b;
-  attn_coords(a, bx, hh, b);
+  attn_coords(bx, hh, b);
   for (int pass = 0; pass <= a.pair; ++pass) {  // one inlined body: no register growth
     if (pass) __syncthreads();
     attn_fwd_block<D, NWK>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b);
@@ -560,21 +601,38 @@ __global__ __launch_bounds__(NWK * 64) void attn_fwd_kernel(AttnArgs a) {
 // K/V tiles of one query block (the dK/dV kernel: split_ck (head, Q tile) steps of one key block),
 // each writing an f32 partial that a merge / reduce pass combines.  Items per (batch, head): the
 // blocks heaviest first (query blocks descending, key blocks ascending), each cut into chunks.
-__device__ __forceinline__ int split_nq_tiles(const AttnArgs& a, int qb) {   // K tiles of query block qb
-  return a.causal ? (qb + 1) * (NW * 32 / KT) : a.Sk / KT;
+// The enumeration below is the only one: the kernels, the merge / reduce passes and the host's item
+// counts and workspace sizes (split_row_items) all walk it.
+__host__ __device__ inline int split_nq_tiles(int causal, int Sk, int qb) {   // K tiles of query block qb
+  return causal ? (qb + 1) * (NW * 32 / KT) : Sk / KT;
 }
-__device__ __forceinline__ int split_nk_steps(const AttnArgs& a, int kb) {   // (head, Q tile) steps of key block kb
-  const int qt_begin = a.causal ? (kb * NW * 32) / KT : 0;
-  return (a.Sq / KT - qt_begin) * (a.H / a.HKV);
+// (head, Q tile) steps of key block kb
+__host__ __device__ inline int split_nk_steps(int causal, int Sq, int H, int HKV, int kb) {
+  const int qt_begin = causal ? (kb * NW * 32) / KT : 0;
+  return (Sq / KT - qt_begin) * (H / HKV);
 }
-// work item i -> (row bh, block, chunk c); q_side: the forward / dQ enumeration, else dK/dV's
+// the blocks of one (batch, head) row in item order, each with its chunk count; q_side: the forward /
+// dQ enumeration, else dK/dV's
+struct SplitWalk {
+  const AttnArgs& a;   // its shape and split_ck (the host fills just those), read where they are used
+  const bool q_side;
+  const int nb = q_side ? a.Sq / (NW * 32) : a.Sk / (NW * 32);
+  int j = 0;
+  __host__ __device__ bool more() const { return j < nb; }
+  __host__ __device__ void step() { ++j; }
+  __host__ __device__ int blk() const { return q_side ? nb - 1 - j : j; }
+  __host__ __device__ int chunks() const {
+    return ((q_side ? split_nq_tiles(a.causal, a.Sk, blk()) : split_nk_steps(a.causal, a.Sq, a.H, a.HKV, blk())) +
+            a.split_ck - 1) / a.split_ck;
+  }
+};
+// work item i -> (row bh, block, chunk c)
 __device__ __forceinline__ void split_item(const AttnArgs& a, int i, bool q_side, int& bh, int& blk, int& c) {
   bh = i / a.split_per_bh;
   int r = i - bh * a.split_per_bh;
-  const int nb = q_side ? a.Sq / (NW * 32) : a.Sk / (NW * 32);
-  for (int j = 0; j < nb; ++j) {
-    blk = q_side ? nb - 1 - j : j;
-    const int n = ((q_side ? split_nq_tiles(a, blk) : split_nk_steps(a, blk)) + a.split_ck - 1) / a.split_ck;
+  for (SplitWalk w{a, q_side}; w.more(); w.step()) {
+    blk = w.blk();
+    const int n = w.chunks();
     if (r < n) { c = r; return; }
     r -= n;
   }
@@ -583,11 +641,9 @@ __device__ __forceinline__ void split_item(const AttnArgs& a, int i, bool q_side
 // first item of (bh, blk) and its chunk count
 __device__ __forceinline__ int split_base(const AttnArgs& a, int bh, int blk, bool q_side, int& nch) {
   int s = bh * a.split_per_bh;
-  const int nb = q_side ? a.Sq / (NW * 32) : a.Sk / (NW * 32);
-  for (int j = 0; j < nb; ++j) {
-    const int bb = q_side ? nb - 1 - j : j;
-    const int n = ((q_side ? split_nq_tiles(a, bb) : split_nk_steps(a, bb)) + a.split_ck - 1) / a.split_ck;
-    if (bb == blk) { nch = n; return s; }
+  for (SplitWalk w{a, q_side}; w.more(); w.step()) {
+    const int n = w.chunks();
+    if (w.blk() == blk) { nch = n; return s; }
     s += n;
   }
   nch = 0;
@@ -595,11 +651,7 @@ __device__ __forceinline__ int split_base(const AttnArgs& a, int bh, int blk, bo
 }
 // XCD-aware item order (attn_coords' remap on a 1-D grid): an XCD takes a contiguous item range,
 // so the items of one (batch, head) share that XCD's L2
-__device__ __forceinline__ int split_item_id() {
-  const int nwg = gridDim.x, id = blockIdx.x;
-  const int xcd = id & 7, q = nwg >> 3, r = nwg & 7;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (id >> 3);
-}
+__device__ __forceinline__ int split_item_id() { return xcd_remap(blockIdx.x, gridDim.x); }
 
 template <int D>
 __global__ __launch_bounds__(NW * 64) void attn_fwd_split_kernel(AttnArgs a) {
@@ -607,7 +659,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_split_kernel(AttnArgs a) {
   int bh, qb, c;
   split_item(a, i, true, bh, qb, c);
   const int nqb = a.Sq / (NW * 32);
-  const int lo = c * a.split_ck, hi = min(lo + a.split_ck, split_nq_tiles(a, qb));
+  const int lo = c * a.split_ck, hi = min(lo + a.split_ck, split_nq_tiles(a.causal, a.Sk, qb));
   attn_fwd_block<D, NW>(a, a.causal ? nqb - 1 - qb : qb, bh % a.H, bh / a.H, lo, hi, i);
 }
 
@@ -637,37 +689,38 @@ __global__ __launch_bounds__(256) void attn_split_merge_kernel(AttnArgs a, int D
       acc[4] += w * x1.x; acc[5] += w * x1.y; acc[6] += w * x1.z; acc[7] += w * x1.w;
     }
     const int b = bh / a.H, h = bh % a.H;
-    st8((uint16_t*)a.o + b * a.o_sb + (int64_t)q * a.o_ss + h * a.o_sh + ch * 8, pack8(acc));
+    st8(a.o.row<uint16_t>(b, q, h) + ch * 8, pack8(acc));
     if (ch == 0) a.lse[(int64_t)bh * a.lse_ld + q] = lse;
   }
 }
 
 // ======================================================================= delta = rowsum(dO * O)
-// one thread per (b, h, q) row; d in 16-byte chunks.  D is passed in a.dq_sh.
+// delta [B, H, Sq] f32 with rows ld apart; Dh = the head dim
 // rows in memory order (b, s, h: one row = D contiguous bf16 of the token-major layout), D/8 lanes
 // per row each loading one 16-B chunk of dO and O, the row's partial dots reduced over those lanes
 // by shuffles -- every wave instruction reads whole contiguous rows (coalesced), no serial chain
-__global__ __launch_bounds__(256) void attn_delta_kernel(AttnArgs a, const uint16_t* __restrict__ o) {
-  const int Dh = (int)a.dq_sh;
+__global__ __launch_bounds__(256) void attn_delta_kernel(View4<const uint16_t> dout, View4<const uint16_t> o,
+                                                         float* __restrict__ delta, int64_t ld, int B, int H, int Sq,
+                                                         int Dh) {
   const int lpr = Dh / 8;  // lanes per row (8 or 16)
-  const int64_t rows = (int64_t)a.B * a.Sq * a.H;
+  const int64_t rows = (int64_t)B * Sq * H;
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nthreads = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = tid; t < rows * lpr; t += nthreads) {
     const int64_t row = t / lpr;
     const int c = (int)(t - row * lpr);
-    const int h = (int)(row % a.H);
-    const int64_t bs = row / a.H;
-    const int qq = (int)(bs % a.Sq);
-    const int b = (int)(bs / a.Sq);
+    const int h = (int)(row % H);
+    const int64_t bs = row / H;
+    const int qq = (int)(bs % Sq);
+    const int b = (int)(bs / Sq);
     float x[8], y[8];
-    unpack8(ld8(a.dout + b * a.do_sb + (int64_t)qq * a.do_ss + h * a.do_sh + c * 8), x);
-    unpack8(ld8(o + b * a.o_sb + (int64_t)qq * a.o_ss + h * a.o_sh + c * 8), y);
+    unpack8(ld8(dout.row(b, qq, h) + c * 8), x);
+    unpack8(ld8(o.row(b, qq, h) + c * 8), y);
     float acc = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc += x[j] * y[j];
     for (int off = lpr >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
-    if (c == 0) a.lse[((int64_t)b * a.H + h) * a.lse_ld + qq] = acc;  // the delta buffer travels in the lse slot
+    if (c == 0) delta[((int64_t)b * H + h) * ld + qq] = acc;
   }
 }
 
@@ -685,8 +738,8 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
   const int mykey = k0 + (lane & 31);
   const int group = a.H / a.HKV;
 
-  const uint16_t* krow = a.k + b * a.k_sb + (int64_t)mykey * a.k_ss + hk * a.k_sh;
-  const uint16_t* vrow = a.v + b * a.v_sb + (int64_t)mykey * a.v_ss + hk * a.v_sh;
+  const uint16_t* krow = a.k.row(b, mykey, hk);
+  const uint16_t* vrow = a.v.row(b, mykey, hk);
   bf16x8_t kf[KS], vf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -712,8 +765,9 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
   float lse_next = 0.f;
   auto stage = [&](int hq, int qt, int buf) {
     lds_u8* sq = smem + buf * STAGE_B;
-    stage_rows<D>(a.q + b * a.q_sb + (int64_t)qt * KT * a.q_ss + hq * a.q_sh, a.q_ss, sq, wave, lane);
-    stage_rows<D>(a.dout + b * a.do_sb + (int64_t)qt * KT * a.do_ss + hq * a.do_sh, a.do_ss, sq + TILE_B, wave, lane);
+    // (spelled out, not a.q.row(): through row() the few-head split kernel's registers are allocated differently)
+    stage_rows<D>(a.q.p + b * a.q.sb + (int64_t)qt * KT * a.q.ss + hq * a.q.sh, a.q.ss, sq, wave, lane);
+    stage_rows<D>(a.dout.row(b, (int64_t)qt * KT, hq), a.dout.ss, sq + TILE_B, wave, lane);
     if (wave == 0) {  // 64 delta floats = 256 B: one 4-byte DMA per lane
       const int64_t ro = ((int64_t)b * a.H + hq) * a.lse_ld + qt * KT;
       lse_next = a.lse[ro + lane];
@@ -805,36 +859,13 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = 32 * dt + 8 * g4 + 4 * (lane >> 5);
-        *(float4*)(a.split_o + ro + d) = make_float4(dk[dt][4 * g4] * a.scale, dk[dt][4 * g4 + 1] * a.scale,
-                                                     dk[dt][4 * g4 + 2] * a.scale, dk[dt][4 * g4 + 3] * a.scale);
-        *(float4*)(a.split_dv + ro + d) = make_float4(dv[dt][4 * g4], dv[dt][4 * g4 + 1], dv[dt][4 * g4 + 2],
-                                                      dv[dt][4 * g4 + 3]);
+      for (int g4 = 0; g4 < 4; ++g4) {   // the two rows' chunks alternate
+        store_chunk_f32(a.split_o + ro, dt, g4, dk[dt], a.scale, lane);
+        store_chunk_f32(a.split_dv + ro, dt, g4, dv[dt], 1.0f, lane);
       }
     return;
   }
-  if (!a.grad_f32) {
-    uint16_t* dkr = (uint16_t*)a.dk + b * a.dk_sb + (int64_t)mykey * a.dk_ss + hk * a.dk_sh;
-    uint16_t* dvr = (uint16_t*)a.dv + b * a.dv_sb + (int64_t)mykey * a.dv_ss + hk * a.dv_sh;
-    if (a.rope_cos) {
-      store_T_bf16_unrope<DT>(dkr, dk, a.scale, a.rope_cos + (int64_t)mykey * a.rope_ld,
-                              a.rope_sin + (int64_t)mykey * a.rope_ld, lane);
-    } else {
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) store_T_bf16(dkr, dt, dk[dt], a.scale, lane);
-    }
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) store_T_bf16(dvr, dt, dv[dt], 1.0f, lane);
-  } else {
-    float* dkr = (float*)a.dk + b * a.dk_sb + (int64_t)mykey * a.dk_ss + hk * a.dk_sh;
-    float* dvr = (float*)a.dv + b * a.dv_sb + (int64_t)mykey * a.dv_ss + hk * a.dv_sh;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) {
-      accum_T_f32(dkr, dt, dk[dt], a.scale, lane);
-      accum_T_f32(dvr, dt, dv[dt], 1.0f, lane);
-    }
-  }
+  store_dkdv<DT>(a, b, mykey, hk, dk, dv, lane);
 }
 
 template <int D>
@@ -843,7 +874,7 @@ void attn_bwd_dkdv_split_kernel(AttnArgs a) {
   const int i = split_item_id();
   int bh, kb, c;
   split_item(a, i, false, bh, kb, c);
-  const int lo = c * a.split_ck, hi = min(lo + a.split_ck, split_nk_steps(a, kb));
+  const int lo = c * a.split_ck, hi = min(lo + a.split_ck, split_nk_steps(a.causal, a.Sq, a.H, a.HKV, kb));
   attn_bwd_dkdv_block<D>(a, kb, bh % a.HKV, bh / a.HKV, lo, hi, i);
 }
 
@@ -851,7 +882,7 @@ template <int D>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(D == 64 ? 2 : 1)))
 void attn_bwd_dkdv_kernel(AttnArgs a) {
   int bx, hh, b;
-  attn_coords(a, bx, hh, b);
+  attn_coords(bx, hh, b);
   for (int pass = 0; pass <= a.pair; ++pass) {  // one inlined body: no register growth
     if (pass) __syncthreads();
     attn_bwd_dkdv_block<D>(a, pass ? a.Sk / (NW * 32) - 1 - bx : bx, hh, b);
@@ -874,8 +905,6 @@ void attn_bwd_dkdv_kernel(AttnArgs a) {
 // operands and their order per accumulator are those of attn_bwd_dkdv_block: dK and dV are
 // bit-identical.
 constexpr int kXchB = 4 * 2 * 2 * 1024;  // one step's P|dS hand-off: 4 pairs x 2 k-steps x 2 kinds x 1 KiB
-constexpr int kStampB = 0;
-
 
 template <int D>
 __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int bx, int hk, int b) {
@@ -906,9 +935,8 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
   int st_hq = hk * group, st_qt = qt_begin, st_buf = 0;
   auto stage_next = [&]() {
     lds_u8* sq = smem + st_buf * STAGE_B;
-    stage_rows<D, 8>(a.q + b * a.q_sb + (int64_t)st_qt * KT * a.q_ss + st_hq * a.q_sh, a.q_ss, sq, wave, lane);
-    stage_rows<D, 8>(a.dout + b * a.do_sb + (int64_t)st_qt * KT * a.do_ss + st_hq * a.do_sh, a.do_ss, sq + TILE_B,
-                     wave, lane);
+    stage_rows<D, 8>(a.q.row(b, (int64_t)st_qt * KT, st_hq), a.q.ss, sq, wave, lane);
+    stage_rows<D, 8>(a.dout.row(b, (int64_t)st_qt * KT, st_hq), a.dout.ss, sq + TILE_B, wave, lane);
     if (wave == 0) {
       const int64_t ro = ((int64_t)b * a.H + st_hq) * a.lse_ld + st_qt * KT;
       pt_glds4(a.lse + ro, lane * 4u, (__attribute__((address_space(3))) void*)(sq + 2 * TILE_B));
@@ -927,9 +955,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
   };
   // step j (odd, j = 2t + 1) issues tile t + 2; its end waits for tile t + 1 (used from step 2t + 2)
   auto issue = [&](int j) { return (j & 1) && (j >> 1) + 2 < n_tiles; };
-  auto stamp = [&](int, int) {};
   auto end_step = [&](int j) {
-    stamp(j, 3);
     if (j & 1) wait_keep(issue(j));
     __syncthreads();
   };
@@ -939,8 +965,8 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
   // the q tile of the step this wave works on (A: step j, B: step j - 1), advanced every second step
   int qt = qt_begin;
   if (score) {
-    const uint16_t* krow = a.k + b * a.k_sb + (int64_t)mykey * a.k_ss + hk * a.k_sh;
-    const uint16_t* vrow = a.v + b * a.v_sb + (int64_t)mykey * a.v_ss + hk * a.v_sh;
+    const uint16_t* krow = a.k.row(b, mykey, hk);
+    const uint16_t* vrow = a.v.row(b, mykey, hk);
     bf16x8_t kf[KS], vf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -951,7 +977,6 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
     __syncthreads();
     int buf = 0;
     for (int j = 0; j <= n_steps; ++j) {
-      stamp(j, 0);
       if (issue(j)) stage_next();
       const int qh = j & 1;
       const int qs = qt * KT + 32 * qh;
@@ -1022,7 +1047,6 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
     __syncthreads();
     int buf = 0;
     for (int j = 0; j <= n_steps; ++j) {
-      stamp(j, 0);
       if (issue(j)) stage_next();
       const int h = j - 1, qh = h & 1;
       if (j > 0 && !(a.causal && qt * KT + 32 * qh + 31 < k0)) {
@@ -1058,34 +1082,14 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
       }
       end_step(j);
     }
-    if (!a.grad_f32) {
-      uint16_t* dkr = (uint16_t*)a.dk + b * a.dk_sb + (int64_t)mykey * a.dk_ss + hk * a.dk_sh;
-      uint16_t* dvr = (uint16_t*)a.dv + b * a.dv_sb + (int64_t)mykey * a.dv_ss + hk * a.dv_sh;
-      if (a.rope_cos) {
-        store_T_bf16_unrope<DT>(dkr, dk, a.scale, a.rope_cos + (int64_t)mykey * a.rope_ld,
-                                a.rope_sin + (int64_t)mykey * a.rope_ld, lane);
-      } else {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) store_T_bf16(dkr, dt, dk[dt], a.scale, lane);
-      }
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) store_T_bf16(dvr, dt, dv[dt], 1.0f, lane);
-    } else {
-      float* dkr = (float*)a.dk + b * a.dk_sb + (int64_t)mykey * a.dk_ss + hk * a.dk_sh;
-      float* dvr = (float*)a.dv + b * a.dv_sb + (int64_t)mykey * a.dv_ss + hk * a.dv_sh;
-#pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        accum_T_f32(dkr, dt, dk[dt], a.scale, lane);
-        accum_T_f32(dvr, dt, dv[dt], 1.0f, lane);
-      }
-    }
+    store_dkdv<DT>(a, b, mykey, hk, dk, dv, lane);
   }
 }
 
 template <int D>
 __global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_kernel(AttnArgs a) {
   int bx, hh, b;
-  attn_coords(a, bx, hh, b);
+  attn_coords(bx, hh, b);
   for (int pass = 0; pass <= a.pair; ++pass) {
     if (pass) __syncthreads();
     attn_bwd_dkdv_pair_block<D>(a, pass ? a.Sk / 128 - 1 - bx : bx, hh, b);
@@ -1108,8 +1112,8 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   const int q0 = qb * NW * 32 + wave * 32;
   const int myq = q0 + (lane & 31);
 
-  const uint16_t* qrow = a.q + b * a.q_sb + (int64_t)myq * a.q_ss + h * a.q_sh;
-  const uint16_t* dorow = a.dout + b * a.do_sb + (int64_t)myq * a.do_ss + h * a.do_sh;
+  const uint16_t* qrow = a.q.row(b, myq, h);
+  const uint16_t* dorow = a.dout.row(b, myq, h);
   bf16x8_t qf[KS], dof[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
@@ -1124,7 +1128,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   bf16x8_t of[KS];
   float del = 0.f;
   if (a.delta_w) {
-    const uint16_t* orow = (const uint16_t*)a.o + b * a.o_sb + (int64_t)myq * a.o_ss + h * a.o_sh;
+    const uint16_t* orow = a.o.row<const uint16_t>(b, myq, h);
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) of[ks] = ld_row_frag(orow, ks, lane);
   } else {
@@ -1132,8 +1136,8 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   }
   const float c2 = a.scale * kLog2e;
 
-  const uint16_t* kbase = a.k + b * a.k_sb + hk * a.k_sh;
-  const uint16_t* vbase = a.v + b * a.v_sb + hk * a.v_sh;
+  const uint16_t* kbase = a.k.row(b, 0, hk);
+  const uint16_t* vbase = a.v.row(b, 0, hk);
   const int kv_end = a.causal ? (qb + 1) * NW * 32 : a.Sk;
   // this call's K/V tiles: all of the block's, or a split work item's [kt_lo, kt_hi)
   const int kt0 = kt_lo, nkt = (kt_hi < 0 ? kv_end / KT : kt_hi) - kt_lo;
@@ -1144,8 +1148,8 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   constexpr int NS = dq_stages<D>(), OPS = 2 * (KT * D * 2 / 1024) / NW;
   auto stage = [&](int kt, int buf) {
     lds_u8* sk = smem + buf * 2 * TILE_B;
-    stage_rows<D>(kbase + (int64_t)(kt0 + kt) * KT * a.k_ss, a.k_ss, sk, wave, lane);
-    stage_rows<D>(vbase + (int64_t)(kt0 + kt) * KT * a.v_ss, a.v_ss, sk + TILE_B, wave, lane);
+    stage_rows<D>(kbase + (int64_t)(kt0 + kt) * KT * a.k.ss, a.k.ss, sk, wave, lane);
+    stage_rows<D>(vbase + (int64_t)(kt0 + kt) * KT * a.v.ss, a.v.ss, sk + TILE_B, wave, lane);
   };
   const int pre = nkt < NS - 1 ? nkt : NS - 1;
   for (int t = 0; t < pre; ++t) stage(t, t);
@@ -1233,15 +1237,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   }
 
   if (item >= 0) {   // a split work item: its dQ partial (scaled, f32), summed by attn_split_reduce_kernel
-    float* prow = a.split_o + ((int64_t)item * (NW * 32) + wave * 32 + (lane & 31)) * D;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = 32 * dt + 8 * g4 + 4 * (lane >> 5);
-        *(float4*)(prow + d) = make_float4(dq[dt][4 * g4] * a.scale, dq[dt][4 * g4 + 1] * a.scale,
-                                           dq[dt][4 * g4 + 2] * a.scale, dq[dt][4 * g4 + 3] * a.scale);
-      }
+    store_T_f32<DT>(a.split_o + ((int64_t)item * (NW * 32) + wave * 32 + (lane & 31)) * D, dq, a.scale, lane);
     return;
   }
   if (!a.grad_f32) {
@@ -1250,7 +1246,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
     // that spilled them to scratch)
     int myq_e = myq, lane_e = lane;
     asm volatile("" : "+v"(myq_e), "+v"(lane_e));
-    uint16_t* dqr = (uint16_t*)a.dq + b * a.dq_sb + (int64_t)myq_e * a.dq_ss + h * a.dq_sh;
+    uint16_t* dqr = a.dq.row<uint16_t>(b, myq_e, h);
     if (a.rope_cos) {
       store_T_bf16_unrope<DT>(dqr, dq, a.scale, a.rope_cos + (int64_t)myq_e * a.rope_ld,
                               a.rope_sin + (int64_t)myq_e * a.rope_ld, lane_e);
@@ -1259,7 +1255,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
       for (int dt = 0; dt < DT; ++dt) store_T_bf16(dqr, dt, dq[dt], a.scale, lane);
     }
   } else {
-    float* dqr = (float*)a.dq + b * a.dq_sb + (int64_t)myq * a.dq_ss + h * a.dq_sh;
+    float* dqr = a.dq.row<float>(b, myq, h);
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) accum_T_f32(dqr, dt, dq[dt], a.scale, lane);
   }
@@ -1269,10 +1265,10 @@ template <int D>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(D == 128 ? 2 : 1)))
 void attn_bwd_dq_kernel(AttnArgs a) {
   int bx, hh, b;
-  attn_coords(a, bx, hh, b);
+  attn_coords(bx, hh, b);
   for (int pass = 0; pass <= a.pair; ++pass) {  // one inlined body: no register growth
     if (pass) __syncthreads();
-    attn_bwd_dq_block<D>(a, pass ? nqb_of(a) - 1 - bx : bx, hh, b);
+    attn_bwd_dq_block<D>(a, pass ? a.Sq / (NW * 32) - 1 - bx : bx, hh, b);
   }
 }
 
@@ -1283,7 +1279,7 @@ void attn_bwd_dq_split_kernel(AttnArgs a) {
   int bh, qb, c;
   split_item(a, i, true, bh, qb, c);
   const int nqb = a.Sq / (NW * 32);
-  const int lo = c * a.split_ck, hi = min(lo + a.split_ck, split_nq_tiles(a, qb));
+  const int lo = c * a.split_ck, hi = min(lo + a.split_ck, split_nq_tiles(a.causal, a.Sk, qb));
   attn_bwd_dq_block<D>(a, a.causal ? nqb - 1 - qb : qb, bh % a.H, bh / a.H, lo, hi, i);
 }
 
@@ -1316,9 +1312,8 @@ __global__ __launch_bounds__(256) void attn_split_reduce_kernel(AttnArgs a, int 
         hi[4] += y1.x; hi[5] += y1.y; hi[6] += y1.z; hi[7] += y1.w;
       }
       const int b = bh / heads, h = bh % heads;
-      uint16_t* dst = part ? (uint16_t*)a.dv + b * a.dv_sb + (int64_t)pos * a.dv_ss + h * a.dv_sh
-                           : (uint16_t*)(q_side ? a.dq : a.dk) + b * (q_side ? a.dq_sb : a.dk_sb) +
-                                 (int64_t)pos * (q_side ? a.dq_ss : a.dk_ss) + h * (q_side ? a.dq_sh : a.dk_sh);
+      const View4<void> g = q_side ? a.dq : a.dk;
+      uint16_t* dst = part ? a.dv.row<uint16_t>(b, pos, h) : g.row<uint16_t>(b, pos, h);
       if (!part && a.rope_cos) {
         float c[8], sn[8], o1[8], o2[8];
         unpack8(ld8(a.rope_cos + (int64_t)pos * a.rope_ld + d0), c);
@@ -1340,9 +1335,21 @@ __global__ __launch_bounds__(256) void attn_split_reduce_kernel(AttnArgs a, int 
   }
 }
 
+// ============================================================================ host
 template <typename K>
 void set_smem(K kern, int bytes) {
   (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+}
+// a kernel with dynamic LDS: its limit is raised on every launch
+template <typename... P>
+void launch(void (*kern)(P...), dim3 grid, int block, int smem, hipStream_t stream, const AttnArgs& a) {
+  set_smem(kern, smem);
+  kern<<<grid, block, smem, stream>>>(a);
+}
+// grid of a streaming pass of `total` threads, 256 per block
+unsigned stream_grid(int64_t total) {
+  const int64_t g = (total + 255) / 256;
+  return (unsigned)(g > 4 * PT_STREAM_GRID_CAP ? 4 * PT_STREAM_GRID_CAP : g);
 }
 
 // causal block pairing (variant "attn_pair"; 0 = off, A/B measurement only)
@@ -1352,6 +1359,29 @@ bool pair_enabled() { return pt_variant(PT_VAR_ATTN_PAIR) == 1; }
 // split; default d128 only
 int split_mask() { return pt_variant(PT_VAR_ATTN_SPLIT); }
 
+// a base pointer and its (batch, seq, head) strides as the view a kernel takes
+struct StridedPtr {
+  const void* p;
+  const int64_t* st;
+  template <typename T>
+  operator View4<T>() const { return {(T*)const_cast<void*>(p), st[0], st[1], st[2]}; }
+};
+StridedPtr view(const void* p, const int64_t* str) { return {p, str}; }
+// what the 16-byte stores of a bf16 view need: the pointer 16-byte aligned, the strides multiples of 8
+bool view_aligned(const void* p, const int64_t* st) {
+  return pt_aligned16(p) && !((st[0] & 7) || (st[1] & 7) || (st[2] & 7));
+}
+
+// the operands every attention launch has
+struct Problem {
+  const void* q; const int64_t* q_str;
+  const void* k; const int64_t* k_str;
+  const void* v; const int64_t* v_str;
+  int64_t B, H, HKV, Sq, Sk, D;
+  float scale;
+  int causal;
+};
+
 int check_common(const AttnArgs& a, int D) {
   if (D != 64 && D != 128) return PT_EUNSUPPORTED;
   if (a.B <= 0 || a.H <= 0 || a.HKV <= 0 || a.H % a.HKV) return PT_EINVAL;
@@ -1359,14 +1389,119 @@ int check_common(const AttnArgs& a, int D) {
   if (a.causal && a.Sq != a.Sk) return PT_EUNSUPPORTED;
   return PT_OK;
 }
+// fills the part of AttnArgs common to all launches and checks it
+int fill_common(AttnArgs& a, const Problem& p) {
+  a.q = view(p.q, p.q_str);
+  a.k = view(p.k, p.k_str);
+  a.v = view(p.v, p.v_str);
+  a.B = (int)p.B; a.H = (int)p.H; a.HKV = (int)p.HKV; a.Sq = (int)p.Sq; a.Sk = (int)p.Sk;
+  a.scale = p.scale; a.causal = p.causal;
+  return check_common(a, (int)p.D);
+}
 
-int attn_bwd_impl(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
-                  const int64_t* v_str, const void* dout, const int64_t* do_str, const float* lse,
-                  const float* delta, void* dq, const int64_t* dq_str, void* dk, const int64_t* dk_str, void* dv,
-                  const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D,
-                  float scale, int causal, int grad_f32, const void* rope_cos, const void* rope_sin,
-                  int64_t rope_stride, const void* o, const int64_t* o_str, float* delta_w, int64_t lse_ld,
-                  hipStream_t stream, int parts = 3);
+template <int D, int NWK>
+void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
+  // (d64: the Q image shares the last ring stage)
+  launch(attn_fwd_kernel<D, NWK>, grid, NWK * 64, fwd_stages<D, NWK>() * 2 * KT * D * 2, stream, a);
+}
+
+// the backward's operands beyond Problem; what an entry point does not have stays zero
+struct BwdCall {
+  Problem p;
+  const void* dout; const int64_t* do_str;
+  const float* lse;
+  void* dq; const int64_t* dq_str;
+  void* dk; const int64_t* dk_str;
+  void* dv; const int64_t* dv_str;
+  int64_t lse_ld;
+  const float* delta;          // given, or formed by the dQ kernel from o and written to delta_w
+  const void* o; const int64_t* o_str;
+  float* delta_w;
+  int grad_f32;
+  const void* rope_cos; const void* rope_sin;
+  int64_t rope_stride;
+  int parts;                   // bit 0: dQ, bit 1: dK / dV
+};
+
+// dQ first: with delta_w set it produces the D the dK/dV kernel reads (same stream, in order)
+template <int D>
+int launch_bwd(AttnArgs& a, int parts, dim3 gq, dim3 gk, bool wave_pairs, hipStream_t stream) {
+  constexpr int stage_q = 2 * KT * D * 2 + 2 * KT * 4;   // Q tile, dO tile, lse [64], delta [64]
+  if (parts & 1) {
+    launch(attn_bwd_dq_kernel<D>, gq, NW * 64, dq_stages<D>() * 2 * KT * D * 2, stream, a);
+    PT_CHECK_LAUNCH();
+  }
+  a.delta = a.delta_w ? a.delta_w : a.delta;
+  a.delta_w = nullptr;
+  if (!(parts & 2)) {
+  } else if (wave_pairs) {
+    launch(attn_bwd_dkdv_pair_kernel<D>, gk, 8 * 64, 3 * stage_q + 2 * kXchB, stream, a);
+  } else {
+    launch(attn_bwd_dkdv_kernel<D>, gk, NW * 64, 2 * stage_q, stream, a);
+  }
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int attn_bwd(const BwdCall& c, hipStream_t stream) {
+  const Problem& p = c.p;
+  const int parts = c.parts;
+  if (!p.q || !p.k || !p.v || !c.dout || !c.lse || parts < 1 || parts > 3) return PT_EINVAL;
+  if (((parts & 1) && (!c.dq || !c.dq_str)) || ((parts & 2) && (!c.dk || !c.dv || !c.dk_str || !c.dv_str)))
+    return PT_EINVAL;
+  if (c.delta_w && parts != 3) return PT_EINVAL;   // the fused delta comes from the dQ kernel, for dK/dV
+  if (c.lse_ld != 0 && c.lse_ld < p.Sq) return PT_EINVAL;
+  if (c.rope_cos && (!c.rope_sin || c.grad_f32 || p.Sq != p.Sk || (c.rope_stride & 3) ||
+                     !pt_aligned16(c.rope_cos) || !pt_aligned16(c.rope_sin)))
+    return PT_EINVAL;
+  AttnArgs a{};
+  a.dout = view(c.dout, c.do_str);
+  a.lse = (float*)c.lse; a.delta = c.delta;
+  a.lse_ld = c.lse_ld ? c.lse_ld : p.Sq;
+  if (parts & 1) a.dq = view(c.dq, c.dq_str);
+  if (parts & 2) {
+    a.dk = view(c.dk, c.dk_str);
+    a.dv = view(c.dv, c.dv_str);
+  }
+  a.grad_f32 = c.grad_f32;
+  a.rope_cos = (const uint16_t*)c.rope_cos; a.rope_sin = (const uint16_t*)c.rope_sin; a.rope_ld = c.rope_stride;
+  if (c.delta_w) {
+    a.o = view(c.o, c.o_str);
+    a.delta_w = c.delta_w;
+  }
+  int rc = fill_common(a, p);
+  if (rc) return rc;
+  if (p.Sk % (NW * 32)) return PT_EUNSUPPORTED;
+  const int nqb = (int)(p.Sq / (NW * 32)), nkb = (int)(p.Sk / (NW * 32));
+  a.pair = p.causal && nqb % 2 == 0 && nkb % 2 == 0 && pair_enabled();
+  const dim3 gq((unsigned)(a.pair ? nqb / 2 : nqb), (unsigned)p.H, (unsigned)p.B);
+  const dim3 gk((unsigned)(a.pair ? nkb / 2 : nkb), (unsigned)p.HKV, (unsigned)p.B);
+  const bool wave_pairs = (split_mask() >> (p.D == 64 ? 0 : 1)) & 1;
+  return p.D == 64 ? launch_bwd<64>(a, parts, gq, gk, wave_pairs, stream)
+                   : launch_bwd<128>(a, parts, gq, gk, wave_pairs, stream);
+}
+
+// ---- few-head split forms: plan and launches
+// the work-item chunk when the split forms apply (0: they do not): d64, and the regular launch (one
+// workgroup per causal block pair) would put fewer than 128 workgroups on the 256 CUs
+int split_ck_for(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D, int causal) {
+  const int ck = pt_variant(PT_VAR_ATTN_KV_CHUNK);
+  if (ck <= 0 || (ck & 1) || D != 64 || Sq % (NW * 32) || Sk % (NW * 32) || (causal && Sq != Sk)) return 0;
+  const int64_t nqb = Sq / (NW * 32);
+  const int64_t wgs = B * H * ((causal && nqb % 2 == 0) ? nqb / 2 : nqb);
+  return wgs < 128 ? ck : 0;
+}
+// items per (batch, head) row: forward / dQ (q_side) or dK / dV (per (batch, kv head))
+int64_t split_row_items(int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int causal, int ck, bool q_side) {
+  AttnArgs a{};
+  a.H = (int)H; a.HKV = (int)HKV; a.Sq = (int)Sq; a.Sk = (int)Sk; a.causal = causal; a.split_ck = ck;
+  int64_t items = 0;
+  for (SplitWalk w{a, q_side}; w.more(); w.step()) items += w.chunks();
+  return items;
+}
+inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+// bytes of `items` f32 partial tiles of NW * 32 rows x `width`, as the workspace lays them out
+inline int64_t split_tile_bytes(int64_t items, int64_t width) { return align256(items * NW * 32 * width * 4); }
 
 }  // namespace
 
@@ -1383,14 +1518,10 @@ int pt_attn_fwd(const void* q, const int64_t* q_str, const void* k, const int64_
   if (lse_ld != 0 && lse_ld < Sq) return PT_EINVAL;
   AttnArgs a{};
   a.lse_ld = lse_ld ? lse_ld : Sq;
-  a.q = (const uint16_t*)q; a.q_sb = q_str[0]; a.q_ss = q_str[1]; a.q_sh = q_str[2];
-  a.k = (const uint16_t*)k; a.k_sb = k_str[0]; a.k_ss = k_str[1]; a.k_sh = k_str[2];
-  a.v = (const uint16_t*)v; a.v_sb = v_str[0]; a.v_ss = v_str[1]; a.v_sh = v_str[2];
-  a.o = o; a.o_sb = o_str[0]; a.o_ss = o_str[1]; a.o_sh = o_str[2];
+  a.o = view(o, o_str);
   a.lse = lse;
-  a.B = (int)B; a.H = (int)H; a.HKV = (int)HKV; a.Sq = (int)Sq; a.Sk = (int)Sk;
-  a.scale = scale; a.causal = causal; a.merge = merge;
-  int rc = check_common(a, (int)D);
+  a.merge = merge;
+  int rc = fill_common(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal});
   if (rc) return rc;
   // 8-wave workgroups (the K|V tiles staged once for 256 queries) at d128; at d64 measured equal or
   // slower (round 5: 35.6 vs 34.8 us, bit-identical), so 4
@@ -1398,20 +1529,9 @@ int pt_attn_fwd(const void* q, const int64_t* q_str, const void* k, const int64_
   const int nqb = (int)(Sq / (nwk * 32));
   a.pair = causal && nqb % 2 == 0 && pair_enabled();
   const dim3 grid((unsigned)(a.pair ? nqb / 2 : nqb), (unsigned)H, (unsigned)B);
-  const int stage_b = 2 * KT * (int)D * 2;
-  if (D == 64) {
-    const int smem = fwd_stages<64, NW>() * stage_b;   // the Q image shares the last stage
-    set_smem(attn_fwd_kernel<64, NW>, smem);
-    attn_fwd_kernel<64, NW><<<grid, NW * 64, smem, stream>>>(a);
-  } else if (nwk == 8) {
-    const int smem = fwd_stages<128, 8>() * stage_b;
-    set_smem(attn_fwd_kernel<128, 8>, smem);
-    attn_fwd_kernel<128, 8><<<grid, 8 * 64, smem, stream>>>(a);
-  } else {
-    const int smem = fwd_stages<128, NW>() * stage_b;
-    set_smem(attn_fwd_kernel<128, NW>, smem);
-    attn_fwd_kernel<128, NW><<<grid, NW * 64, smem, stream>>>(a);
-  }
+  if (D == 64) launch_fwd<64, NW>(a, grid, stream);
+  else if (nwk == 8) launch_fwd<128, 8>(a, grid, stream);
+  else launch_fwd<128, NW>(a, grid, stream);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -1421,18 +1541,10 @@ int pt_attn_bwd_delta(const void* dout, const int64_t* do_str, const void* o, co
                       int64_t B, int64_t H, int64_t Sq, int64_t D, int64_t lse_ld, hipStream_t stream) {
   if (!dout || !o || !delta || D % 8) return PT_EINVAL;
   if (lse_ld != 0 && lse_ld < Sq) return PT_EINVAL;
-  AttnArgs a{};
-  a.lse_ld = lse_ld ? lse_ld : Sq;
-  a.dout = (const uint16_t*)dout; a.do_sb = do_str[0]; a.do_ss = do_str[1]; a.do_sh = do_str[2];
-  a.o_sb = o_str[0]; a.o_ss = o_str[1]; a.o_sh = o_str[2];
-  a.lse = delta;
-  a.dq_sh = D;
-  a.B = (int)B; a.H = (int)H; a.Sq = (int)Sq;
   if (D != 64 && D != 128) return PT_EUNSUPPORTED;
-  const int64_t total = B * H * Sq * (D / 8);  // one thread per 16-B chunk
-  int64_t g = (total + 255) / 256;
-  if (g > 4 * PT_STREAM_GRID_CAP) g = 4 * PT_STREAM_GRID_CAP;
-  attn_delta_kernel<<<(int)g, 256, 0, stream>>>(a, (const uint16_t*)o);
+  // one thread per 16-B chunk
+  attn_delta_kernel<<<stream_grid(B * H * Sq * (D / 8)), 256, 0, stream>>>(
+      view(dout, do_str), view(o, o_str), delta, lse_ld ? lse_ld : Sq, (int)B, (int)H, (int)Sq, (int)D);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -1446,129 +1558,47 @@ int pt_attn_bwd(const void* q, const int64_t* q_str, const void* k, const int64_
                 int grad_f32, const void* rope_cos, const void* rope_sin, int64_t rope_stride, int64_t lse_ld,
                 hipStream_t stream) {
   if (!delta) return PT_EINVAL;
-  return attn_bwd_impl(q, q_str, k, k_str, v, v_str, dout, do_str, lse, delta, dq, dq_str, dk, dk_str, dv, dv_str,
-                       B, H, HKV, Sq, Sk, D, scale, causal, grad_f32, rope_cos, rope_sin, rope_stride, nullptr,
-                       nullptr, nullptr, lse_ld, stream);
+  BwdCall c{{q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal},
+            dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, lse_ld, delta};
+  c.grad_f32 = grad_f32;
+  c.rope_cos = rope_cos; c.rope_sin = rope_sin; c.rope_stride = rope_stride;
+  c.parts = 3;
+  return attn_bwd(c, stream);
 }
 
-}  // extern "C"
-
-namespace {
-
-int attn_bwd_impl(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
-                  const int64_t* v_str, const void* dout, const int64_t* do_str, const float* lse,
-                  const float* delta, void* dq, const int64_t* dq_str, void* dk, const int64_t* dk_str, void* dv,
-                  const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D,
-                  float scale, int causal, int grad_f32, const void* rope_cos, const void* rope_sin,
-                  int64_t rope_stride, const void* o, const int64_t* o_str, float* delta_w, int64_t lse_ld,
-                  hipStream_t stream, int parts) {
-  if (!q || !k || !v || !dout || !lse || parts < 1 || parts > 3) return PT_EINVAL;
-  if (((parts & 1) && (!dq || !dq_str)) || ((parts & 2) && (!dk || !dv || !dk_str || !dv_str))) return PT_EINVAL;
-  if (delta_w && parts != 3) return PT_EINVAL;   // the fused delta comes from the dQ kernel, for dK/dV
-  if (lse_ld != 0 && lse_ld < Sq) return PT_EINVAL;
-  if (rope_cos && (!rope_sin || grad_f32 || Sq != Sk || (rope_stride & 3) || !pt_aligned16(rope_cos) ||
-                   !pt_aligned16(rope_sin)))
-    return PT_EINVAL;
-  AttnArgs a{};
-  a.q = (const uint16_t*)q; a.q_sb = q_str[0]; a.q_ss = q_str[1]; a.q_sh = q_str[2];
-  a.k = (const uint16_t*)k; a.k_sb = k_str[0]; a.k_ss = k_str[1]; a.k_sh = k_str[2];
-  a.v = (const uint16_t*)v; a.v_sb = v_str[0]; a.v_ss = v_str[1]; a.v_sh = v_str[2];
-  a.dout = (const uint16_t*)dout; a.do_sb = do_str[0]; a.do_ss = do_str[1]; a.do_sh = do_str[2];
-  a.lse = (float*)lse; a.delta = delta;
-  a.lse_ld = lse_ld ? lse_ld : Sq;
-  if (parts & 1) { a.dq = dq; a.dq_sb = dq_str[0]; a.dq_ss = dq_str[1]; a.dq_sh = dq_str[2]; }
-  if (parts & 2) {
-    a.dk = dk; a.dk_sb = dk_str[0]; a.dk_ss = dk_str[1]; a.dk_sh = dk_str[2];
-    a.dv = dv; a.dv_sb = dv_str[0]; a.dv_ss = dv_str[1]; a.dv_sh = dv_str[2];
-  }
-  a.B = (int)B; a.H = (int)H; a.HKV = (int)HKV; a.Sq = (int)Sq; a.Sk = (int)Sk;
-  a.scale = scale; a.causal = causal; a.grad_f32 = grad_f32;
-  a.rope_cos = (const uint16_t*)rope_cos; a.rope_sin = (const uint16_t*)rope_sin; a.rope_ld = rope_stride;
-  if (delta_w) {
-    a.o = const_cast<void*>(o); a.o_sb = o_str[0]; a.o_ss = o_str[1]; a.o_sh = o_str[2];
-    a.delta_w = delta_w;
-  }
-  int rc = check_common(a, (int)D);
-  if (rc) return rc;
-  if (Sk % (NW * 32)) return PT_EUNSUPPORTED;
-  const int smem_kv = (D == 64 ? dq_stages<64>() : dq_stages<128>()) * 2 * KT * (int)D * 2;
-  const int smem_q = 2 * (2 * KT * (int)D * 2 + 2 * KT * 4);
-  const int nqb = (int)(Sq / (NW * 32)), nkb = (int)(Sk / (NW * 32));
-  a.pair = causal && nqb % 2 == 0 && nkb % 2 == 0 && pair_enabled();
-  const dim3 gq((unsigned)(a.pair ? nqb / 2 : nqb), (unsigned)H, (unsigned)B);
-  const dim3 gk((unsigned)(a.pair ? nkb / 2 : nkb), (unsigned)HKV, (unsigned)B);
-  const int smem_pair = 3 * (2 * KT * (int)D * 2 + 2 * KT * 4) + 2 * kXchB + kStampB;
-  const bool split = (split_mask() >> (D == 64 ? 0 : 1)) & 1;
-  // dQ first: with delta_w set it produces the D the dK/dV kernel reads (same stream, in order)
-  if (D == 64) {
-    if (parts & 1) {
-      set_smem(attn_bwd_dq_kernel<64>, smem_kv);
-      attn_bwd_dq_kernel<64><<<gq, NW * 64, smem_kv, stream>>>(a);
-      PT_CHECK_LAUNCH();
-    }
-    a.delta = a.delta_w ? a.delta_w : a.delta;
-    a.delta_w = nullptr;
-    if (!(parts & 2)) {
-    } else if (split) {
-      set_smem(attn_bwd_dkdv_pair_kernel<64>, smem_pair);
-      attn_bwd_dkdv_pair_kernel<64><<<gk, 8 * 64, smem_pair, stream>>>(a);
-    } else {
-      set_smem(attn_bwd_dkdv_kernel<64>, smem_q);
-      attn_bwd_dkdv_kernel<64><<<gk, NW * 64, smem_q, stream>>>(a);
-    }
-  } else {
-    if (parts & 1) {
-      set_smem(attn_bwd_dq_kernel<128>, smem_kv);
-      attn_bwd_dq_kernel<128><<<gq, NW * 64, smem_kv, stream>>>(a);
-      PT_CHECK_LAUNCH();
-    }
-    a.delta = a.delta_w ? a.delta_w : a.delta;
-    a.delta_w = nullptr;
-    if (!(parts & 2)) {
-    } else if (split) {
-      set_smem(attn_bwd_dkdv_pair_kernel<128>, smem_pair);
-      attn_bwd_dkdv_pair_kernel<128><<<gk, 8 * 64, smem_pair, stream>>>(a);
-    } else {
-      set_smem(attn_bwd_dkdv_kernel<128>, smem_q);
-      attn_bwd_dkdv_kernel<128><<<gk, NW * 64, smem_q, stream>>>(a);
-    }
-  }
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+// pt_attn_bwd computing only dQ (parts 1) or only dK / dV (parts 2): the full-mesh context-parallel
+// backward runs each rank's dQ against the visiting K / V and its own keys' dK / dV against the
+// visiting queries (the other pointers may be NULL)
+int pt_attn_bwd_part(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, const void* dout, const int64_t* do_str, const float* lse,
+                     const float* delta, void* dq, const int64_t* dq_str, void* dk, const int64_t* dk_str, void* dv,
+                     const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D,
+                     float scale, int causal, int grad_f32, int64_t lse_ld, int parts, hipStream_t stream) {
+  if (!delta) return PT_EINVAL;
+  BwdCall c{{q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal},
+            dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, lse_ld, delta};
+  c.grad_f32 = grad_f32;
+  c.parts = parts;
+  return attn_bwd(c, stream);
 }
 
-// ---- few-head split forms: plan and launches
-// the work-item chunk when the split forms apply (0: they do not): d64, and the regular launch (one
-// workgroup per causal block pair) would put fewer than 128 workgroups on the 256 CUs
-int split_ck_for(int64_t B, int64_t H, int64_t Sq, int64_t Sk, int64_t D, int causal) {
-  const int ck = pt_variant(PT_VAR_ATTN_KV_CHUNK);
-  if (ck <= 0 || (ck & 1) || D != 64 || Sq % (NW * 32) || Sk % (NW * 32) || (causal && Sq != Sk)) return 0;
-  const int64_t nqb = Sq / (NW * 32);
-  const int64_t wgs = B * H * ((causal && nqb % 2 == 0) ? nqb / 2 : nqb);
-  return wgs < 128 ? ck : 0;
+// pt_attn_bwd with D = rowsum(dO * O) computed inside the dQ kernel from o (bf16, strides o_str)
+// and written to delta_out [B, H, Sq] f32 (replaces the separate pt_attn_bwd_delta pass)
+int pt_attn_bwd_fused_delta(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str,
+                            const void* v, const int64_t* v_str, const void* o, const int64_t* o_str,
+                            const void* dout, const int64_t* do_str, const float* lse, float* delta_out, void* dq,
+                            const int64_t* dq_str, void* dk, const int64_t* dk_str, void* dv,
+                            const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk,
+                            int64_t D, float scale, int causal, const void* rope_cos, const void* rope_sin,
+                            int64_t rope_stride, int64_t lse_ld, hipStream_t stream) {
+  if (!o || !delta_out || !o_str) return PT_EINVAL;
+  if (!view_aligned(o, o_str)) return PT_EALIGN;
+  BwdCall c{{q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal},
+            dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, lse_ld, nullptr, o, o_str, delta_out};
+  c.rope_cos = rope_cos; c.rope_sin = rope_sin; c.rope_stride = rope_stride;
+  c.parts = 3;
+  return attn_bwd(c, stream);
 }
-// items per (batch, head) row: forward / dQ (q_side) or dK / dV (per (batch, kv head))
-int64_t split_row_items(int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int causal, int ck, bool q_side) {
-  int64_t n = 0;
-  if (q_side) {
-    for (int64_t qb = 0; qb < Sq / (NW * 32); ++qb) {
-      const int64_t nt = causal ? (qb + 1) * (NW * 32 / KT) : Sk / KT;
-      n += (nt + ck - 1) / ck;
-    }
-  } else {
-    for (int64_t kb = 0; kb < Sk / (NW * 32); ++kb) {
-      const int64_t qt_begin = causal ? (kb * NW * 32) / KT : 0;
-      const int64_t steps = (Sq / KT - qt_begin) * (H / HKV);
-      n += (steps + ck - 1) / ck;
-    }
-  }
-  return n;
-}
-inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
-}  // namespace
-
-extern "C" {
 
 // Few-head attention (a TP shard's 4 heads): whether the split work-item forms apply to this shape and
 // the f32 workspace they need -- forward (backward = 0): partial O and LSE per item; backward: partial
@@ -1580,12 +1610,11 @@ int pt_attn_split_plan(int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk
   const int ck = split_ck_for(B, H, Sq, Sk, D, causal);
   if (!ck) return 0;
   const int64_t iq = B * H * split_row_items(H, HKV, Sq, Sk, causal, ck, true);
-  const int64_t rows = NW * 32;
   if (!backward) {
-    *ws_bytes = align256(iq * rows * D * 4) + align256(iq * rows * 4);
+    *ws_bytes = split_tile_bytes(iq, D) + split_tile_bytes(iq, 1);
   } else {
     const int64_t ik = B * HKV * split_row_items(H, HKV, Sq, Sk, causal, ck, false);
-    *ws_bytes = align256(iq * rows * D * 4) + 2 * align256(ik * rows * D * 4);
+    *ws_bytes = split_tile_bytes(iq, D) + 2 * split_tile_bytes(ik, D);
   }
   return 1;
 }
@@ -1600,31 +1629,22 @@ int pt_attn_fwd_split(const void* q, const int64_t* q_str, const void* k, const 
   int64_t need = 0;
   if (pt_attn_split_plan(B, H, HKV, Sq, Sk, D, causal, 0, &need) != 1) return PT_EUNSUPPORTED;
   if (ws_bytes < need || !pt_aligned16(ws)) return PT_EINVAL;
-  if ((o_str[0] & 7) || (o_str[1] & 7) || (o_str[2] & 7) || !pt_aligned16(o)) return PT_EALIGN;
+  if (!view_aligned(o, o_str)) return PT_EALIGN;
   AttnArgs a{};
   a.lse_ld = Sq;
-  a.q = (const uint16_t*)q; a.q_sb = q_str[0]; a.q_ss = q_str[1]; a.q_sh = q_str[2];
-  a.k = (const uint16_t*)k; a.k_sb = k_str[0]; a.k_ss = k_str[1]; a.k_sh = k_str[2];
-  a.v = (const uint16_t*)v; a.v_sb = v_str[0]; a.v_ss = v_str[1]; a.v_sh = v_str[2];
-  a.o = o; a.o_sb = o_str[0]; a.o_ss = o_str[1]; a.o_sh = o_str[2];
+  a.o = view(o, o_str);
   a.lse = lse;
-  a.B = (int)B; a.H = (int)H; a.HKV = (int)HKV; a.Sq = (int)Sq; a.Sk = (int)Sk;
-  a.scale = scale; a.causal = causal;
-  int rc = check_common(a, (int)D);
+  int rc = fill_common(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal});
   if (rc) return rc;
   a.split_ck = split_ck_for(B, H, Sq, Sk, D, causal);
   a.split_per_bh = (int)split_row_items(H, HKV, Sq, Sk, causal, a.split_ck, true);
   const int64_t items = B * H * a.split_per_bh;
   a.split_o = (float*)ws;
-  a.split_lse = (float*)((char*)ws + align256(items * NW * 32 * D * 4));
-  const int smem = fwd_stages<64, NW>() * 2 * KT * 64 * 2;   // the Q image shares the last stage
-  set_smem(attn_fwd_split_kernel<64>, smem);
-  attn_fwd_split_kernel<64><<<(unsigned)items, NW * 64, smem, stream>>>(a);
+  a.split_lse = (float*)((char*)ws + split_tile_bytes(items, D));
+  // (the Q image shares the last ring stage)
+  launch(attn_fwd_split_kernel<64>, (unsigned)items, NW * 64, fwd_stages<64, NW>() * 2 * KT * 64 * 2, stream, a);
   PT_CHECK_LAUNCH();
-  const int64_t total = B * H * Sq * (D / 8);
-  int64_t g = (total + 255) / 256;
-  if (g > 4 * PT_STREAM_GRID_CAP) g = 4 * PT_STREAM_GRID_CAP;
-  attn_split_merge_kernel<<<(unsigned)g, 256, 0, stream>>>(a, (int)D);
+  attn_split_merge_kernel<<<stream_grid(B * H * Sq * (D / 8)), 256, 0, stream>>>(a, (int)D);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -1641,48 +1661,34 @@ int pt_attn_bwd_split(const void* q, const int64_t* q_str, const void* k, const 
   int64_t need = 0;
   if (pt_attn_split_plan(B, H, HKV, Sq, Sk, D, causal, 1, &need) != 1) return PT_EUNSUPPORTED;
   if (ws_bytes < need || !pt_aligned16(ws)) return PT_EINVAL;
-  if (!pt_aligned16(o) || (o_str[0] & 7) || (o_str[1] & 7) || (o_str[2] & 7)) return PT_EALIGN;
-  for (const int64_t* st : {dq_str, dk_str, dv_str})
-    if ((st[0] & 7) || (st[1] & 7) || (st[2] & 7)) return PT_EALIGN;
-  if (!pt_aligned16(dq) || !pt_aligned16(dk) || !pt_aligned16(dv)) return PT_EALIGN;
+  if (!view_aligned(o, o_str)) return PT_EALIGN;
+  if (!view_aligned(dq, dq_str) || !view_aligned(dk, dk_str) || !view_aligned(dv, dv_str)) return PT_EALIGN;
   if (rope_cos && (!rope_sin || Sq != Sk || (rope_stride & 7) || !pt_aligned16(rope_cos) || !pt_aligned16(rope_sin)))
     return PT_EINVAL;
   AttnArgs a{};
-  a.q = (const uint16_t*)q; a.q_sb = q_str[0]; a.q_ss = q_str[1]; a.q_sh = q_str[2];
-  a.k = (const uint16_t*)k; a.k_sb = k_str[0]; a.k_ss = k_str[1]; a.k_sh = k_str[2];
-  a.v = (const uint16_t*)v; a.v_sb = v_str[0]; a.v_ss = v_str[1]; a.v_sh = v_str[2];
-  a.dout = (const uint16_t*)dout; a.do_sb = do_str[0]; a.do_ss = do_str[1]; a.do_sh = do_str[2];
-  a.o = const_cast<void*>(o); a.o_sb = o_str[0]; a.o_ss = o_str[1]; a.o_sh = o_str[2];
+  a.dout = view(dout, do_str);
+  a.o = view(o, o_str);
   a.lse = (float*)lse; a.lse_ld = Sq;
   a.delta_w = delta_out;
-  a.dq = dq; a.dq_sb = dq_str[0]; a.dq_ss = dq_str[1]; a.dq_sh = dq_str[2];
-  a.dk = dk; a.dk_sb = dk_str[0]; a.dk_ss = dk_str[1]; a.dk_sh = dk_str[2];
-  a.dv = dv; a.dv_sb = dv_str[0]; a.dv_ss = dv_str[1]; a.dv_sh = dv_str[2];
-  a.B = (int)B; a.H = (int)H; a.HKV = (int)HKV; a.Sq = (int)Sq; a.Sk = (int)Sk;
-  a.scale = scale; a.causal = causal;
+  a.dq = view(dq, dq_str);
+  a.dk = view(dk, dk_str);
+  a.dv = view(dv, dv_str);
   a.rope_cos = (const uint16_t*)rope_cos; a.rope_sin = (const uint16_t*)rope_sin; a.rope_ld = rope_stride;
-  int rc = check_common(a, (int)D);
+  int rc = fill_common(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal});
   if (rc) return rc;
-  const int ck = split_ck_for(B, H, Sq, Sk, D, causal);
-  const int64_t per_q = split_row_items(H, HKV, Sq, Sk, causal, ck, true);
-  const int64_t per_k = split_row_items(H, HKV, Sq, Sk, causal, ck, false);
+  a.split_ck = split_ck_for(B, H, Sq, Sk, D, causal);
+  const int64_t per_q = split_row_items(H, HKV, Sq, Sk, causal, a.split_ck, true);
+  const int64_t per_k = split_row_items(H, HKV, Sq, Sk, causal, a.split_ck, false);
   const int64_t iq = B * H * per_q, ik = B * HKV * per_k;
-  char* w = (char*)ws;
-  float* pdq = (float*)w;
-  float* pdk = (float*)(w + align256(iq * NW * 32 * D * 4));
-  float* pdv = (float*)((char*)pdk + align256(ik * NW * 32 * D * 4));
-  a.split_ck = ck;
+  float* pdq = (float*)ws;
+  float* pdk = (float*)((char*)pdq + split_tile_bytes(iq, D));
+  float* pdv = (float*)((char*)pdk + split_tile_bytes(ik, D));
   // dQ items
   a.split_per_bh = (int)per_q;
   a.split_o = pdq;
-  const int smem_kv = dq_stages<64>() * 2 * KT * 64 * 2;
-  set_smem(attn_bwd_dq_split_kernel<64>, smem_kv);
-  attn_bwd_dq_split_kernel<64><<<(unsigned)iq, NW * 64, smem_kv, stream>>>(a);
+  launch(attn_bwd_dq_split_kernel<64>, (unsigned)iq, NW * 64, dq_stages<64>() * 2 * KT * 64 * 2, stream, a);
   PT_CHECK_LAUNCH();
-  const int64_t tq = B * H * Sq * (D / 16);
-  int64_t g = (tq + 255) / 256;
-  if (g > 4 * PT_STREAM_GRID_CAP) g = 4 * PT_STREAM_GRID_CAP;
-  attn_split_reduce_kernel<<<(unsigned)g, 256, 0, stream>>>(a, (int)D, 1);
+  attn_split_reduce_kernel<<<stream_grid(B * H * Sq * (D / 16)), 256, 0, stream>>>(a, (int)D, 1);
   PT_CHECK_LAUNCH();
   // dK / dV items read the D the dQ items stored
   a.delta = delta_out;
@@ -1690,46 +1696,11 @@ int pt_attn_bwd_split(const void* q, const int64_t* q_str, const void* k, const 
   a.split_per_bh = (int)per_k;
   a.split_o = pdk;
   a.split_dv = pdv;
-  const int smem_q = 2 * (2 * KT * 64 * 2 + 2 * KT * 4);
-  set_smem(attn_bwd_dkdv_split_kernel<64>, smem_q);
-  attn_bwd_dkdv_split_kernel<64><<<(unsigned)ik, NW * 64, smem_q, stream>>>(a);
+  launch(attn_bwd_dkdv_split_kernel<64>, (unsigned)ik, NW * 64, 2 * (2 * KT * 64 * 2 + 2 * KT * 4), stream, a);
   PT_CHECK_LAUNCH();
-  const int64_t tk = B * HKV * Sk * (D / 16);
-  g = (tk + 255) / 256;
-  if (g > 4 * PT_STREAM_GRID_CAP) g = 4 * PT_STREAM_GRID_CAP;
-  attn_split_reduce_kernel<<<(unsigned)g, 256, 0, stream>>>(a, (int)D, 0);
+  attn_split_reduce_kernel<<<stream_grid(B * HKV * Sk * (D / 16)), 256, 0, stream>>>(a, (int)D, 0);
   PT_CHECK_LAUNCH();
   return PT_OK;
-}
-
-// pt_attn_bwd computing only dQ (parts 1) or only dK / dV (parts 2): the full-mesh context-parallel
-// backward runs each rank's dQ against the visiting K / V and its own keys' dK / dV against the
-// visiting queries (the other pointers may be NULL)
-int pt_attn_bwd_part(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
-                     const int64_t* v_str, const void* dout, const int64_t* do_str, const float* lse,
-                     const float* delta, void* dq, const int64_t* dq_str, void* dk, const int64_t* dk_str, void* dv,
-                     const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D,
-                     float scale, int causal, int grad_f32, int64_t lse_ld, int parts, hipStream_t stream) {
-  if (!delta) return PT_EINVAL;
-  return attn_bwd_impl(q, q_str, k, k_str, v, v_str, dout, do_str, lse, delta, dq, dq_str, dk, dk_str, dv, dv_str,
-                       B, H, HKV, Sq, Sk, D, scale, causal, grad_f32, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-                       lse_ld, stream, parts);
-}
-
-// pt_attn_bwd with D = rowsum(dO * O) computed inside the dQ kernel from o (bf16, strides o_str)
-// and written to delta_out [B, H, Sq] f32 (replaces the separate pt_attn_bwd_delta pass)
-int pt_attn_bwd_fused_delta(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str,
-                            const void* v, const int64_t* v_str, const void* o, const int64_t* o_str,
-                            const void* dout, const int64_t* do_str, const float* lse, float* delta_out, void* dq,
-                            const int64_t* dq_str, void* dk, const int64_t* dk_str, void* dv,
-                            const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk,
-                            int64_t D, float scale, int causal, const void* rope_cos, const void* rope_sin,
-                            int64_t rope_stride, int64_t lse_ld, hipStream_t stream) {
-  if (!o || !delta_out || !o_str) return PT_EINVAL;
-  if (!pt_aligned16(o) || (o_str[0] & 7) || (o_str[1] & 7) || (o_str[2] & 7)) return PT_EALIGN;
-  return attn_bwd_impl(q, q_str, k, k_str, v, v_str, dout, do_str, lse, nullptr, dq, dq_str, dk, dk_str, dv,
-                       dv_str, B, H, HKV, Sq, Sk, D, scale, causal, 0, rope_cos, rope_sin, rope_stride, o, o_str,
-                       delta_out, lse_ld, stream);
 }
 
 }  // extern "C"

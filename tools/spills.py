@@ -2,42 +2,14 @@
 
     python tools/spills.py [--all]      (reads picotron_amd/lib/obj/*.o; exit 1 if any kernel spills)
 
-Each object's .hip_fatbin bundle is unbundled to its gfx950 code object and the AMDGPU metadata
-notes are read (llvm-readelf --notes): .vgpr_spill_count, .sgpr_spill_count and
-.private_segment_fixed_size (scratch bytes per lane) per kernel."""
+Each object's gfx950 code object is unbundled and its AMDGPU metadata notes are read
+(tools/codeobj.py): .vgpr_spill_count, .sgpr_spill_count and .private_segment_fixed_size (scratch
+bytes per lane) per kernel."""
 import glob
 import os
-import re
-import subprocess
 import sys
-import tempfile
 
-LLVM = "/opt/rocm/lib/llvm/bin"
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def kernels(obj):
-    with tempfile.TemporaryDirectory() as td:
-        fb, co = os.path.join(td, "f.bin"), os.path.join(td, "k.co")
-        r = subprocess.run([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fb}", obj, os.path.join(td, "o")],
-                           capture_output=True)
-        if r.returncode:   # no device code in this object (host-only source)
-            return []
-        subprocess.run([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                        f"--input={fb}", f"--output={co}", "--unbundle"], check=True, capture_output=True)
-        notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
-    out = []
-    for blk in notes.split("\n      - ")[1:]:
-        def g(k):
-            m = re.search(r"\." + k + r":\s+(\S+)", blk)
-            return m.group(1) if m else "0"
-        if ".symbol:" not in blk:
-            continue
-        out.append({"name": g("name"), "vgpr": int(g("vgpr_count")), "agpr": int(g("agpr_count")),
-                    "vspill": int(g("vgpr_spill_count")), "sspill": int(g("sgpr_spill_count")),
-                    "scratch": int(g("private_segment_fixed_size")), "lds": int(g("group_segment_fixed_size"))})
-    return out
+from codeobj import ROOT, kernels
 
 
 def main():
