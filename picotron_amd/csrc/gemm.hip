@@ -19,12 +19,19 @@
 // applied to the per-lane SOURCE address and undone on the ds_read -- tools/lds_swizzle_search.py:
 // conflict-free for ds_read_b128 on K-contiguous images and ds_read_b64_tr_b16 on MN-contiguous
 // images):
-//  * gemm_8ph_kernel (tile 12, 256x256) and gemm_4ph_kernel (tile 13, 256x128): phased,
-//    wave-group ping-pong schedules with one counted vmcnt per K-tile (see each kernel) -- every
-//    projection of the layer, 1.0-1.38 PF/s (profiles/r01_gemm_tiles_8ph.md).
-//  * gemm_kernel (tiles 2 / 3 / 4 / 5 / 8 / 9): the simple two-stage loop, for shapes the phased
-//    kernels do not divide.
-// One launch may carry up to 4 independent problems (pt_gemm_grouped) to fill the CUs.
+//  * gemm_8ph_kernel (tile 12, 256x256): the phased, wave-group ping-pong schedule with one counted
+//    vmcnt per K-tile -- every projection of the layer, 1.0-1.38 PF/s (profiles/r01_gemm_tiles_8ph.md).
+//  * gemm_4ph_kernel / gemm_kh_kernel (tiles 13 / 14, 256x128): one three-K-tile ring body with two
+//    wave decompositions, for the N = 2048 shapes (14: the K >= 4096 ones).
+//  * gemm_hq_kernel (tile 15, 128x128, a 4-deep ring) and gemm_kernel (tiles 2 / 3, 128x128 / 64x64:
+//    the simple two-stage loop): the TP shards' few-tile problems and shapes the larger tiles do not
+//    divide.
+//  * gemm_8ph_dual_kernel: two independent groups (a dX and a weight gradient) in one launch of
+//    256x256 tiles; gemm_mix_kernel: the q|k|v projection with RoPE as 256x256 and 256x128 tiles in
+//    one launch.
+//  * splitk_reduce_kernel / splitk_sum2_kernel: the finishing passes of split-K launches.
+// One launch may carry up to 4 independent problems (pt_gemm_grouped) to fill the CUs.  The launch
+// layer (kTiles, dispatch, launch_kernel) says which (tile, layout, epilogue) combinations are built.
 //
 // Epilogue: the wave's tile is staged through LDS as bf16 rows and written as whole 16-byte row
 // segments; fp32 epilogues (main_grad accumulation) write the accumulator directly.
@@ -33,10 +40,13 @@
 #include <limits.h>
 #include <stdlib.h>
 #include <type_traits>
+#include <utility>
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
 namespace {
@@ -50,7 +60,6 @@ constexpr int BK = 64;
 // 128 LDS write instructions).  Same products and summation order as the (A, B) order.
 __device__ __forceinline__ int acc_row(int i, int lane) { return i * 16 + (lane & 15); }
 __device__ __forceinline__ int acc_col(int j, int r, int lane) { return j * 16 + (lane >> 4) * 4 + r; }
-typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 template <typename V, typename A>
 __device__ __forceinline__ A mfma16(const V& a, const V& b, const A& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(b, a, c, 0, 0, 0);
@@ -77,8 +86,13 @@ enum Epilogue {
   EPI_CE_STATS = 8
 };
 
-// SwiGLU element math, the same expressions as csrc/swiglu.hip (torch's bf16 roundings)
-__device__ __forceinline__ float silu_sig(float x) { return pt_sigmoid(x); }
+// SwiGLU backward of one element, the same expressions as csrc/swiglu.hip (torch's bf16 roundings):
+// d = dh (already a bf16 value), g / u the forward's activations -> og = dg, ou = du
+__device__ __forceinline__ void swiglu_bwd_elem(float d, float g, float u, float& og, float& ou) {
+  const float sg = pt_sigmoid(g);
+  ou = d * round_bf(g * sg);
+  og = round_bf(d * u) * (sg * (1.0f + g * (1.0f - sg)));
+}
 
 struct GemmArgs {
   const uint16_t* A;
@@ -116,6 +130,14 @@ struct GemmArgs {
 __device__ __forceinline__ int swz_k(int r) { return (r >> 1) & 7; }                    // 128-B rows
 __device__ __forceinline__ int swz_mn(int r, int row_bytes) {
   return row_bytes >= 256 ? 2 * ((r & 3) | ((r >> 1) & 4)) : 2 * (((r >> 1) & 1) | ((r >> 2) & 2));
+}
+
+// 16 bytes (8 bf16) of an LDS staging area
+__device__ __forceinline__ bf16x8 lds_ld8(const lds_u8* p) {
+  const u32x4_t raw = *(const __attribute__((address_space(3))) u32x4_t*)p;
+  bf16x8 v;
+  v.w[0] = raw[0]; v.w[1] = raw[1]; v.w[2] = raw[2]; v.w[3] = raw[3];
+  return v;
 }
 
 __device__ __forceinline__ void glds16(const void* gsrc, lds_u8* lds_base) {
@@ -198,11 +220,20 @@ struct GemmGroup {
 
 // tile order: XCD remap over the whole grid (consecutive ids share an XCD), then the problem,
 // then group `group_m` tile-rows so an XCD's consecutive tiles form a compact block of the
-// output (A and B panels shared through that XCD's L2): 6 rows (group_m_for: measured faster
+// output (A and B panels shared through that XCD's L2): 6 rows (PT_GROUP_M: measured faster
 // than the 8 / 4 rows that made 32 tiles one 2048 x 1024 / 1024 x 1024 block)
 // tile id pid_all (already in XCD order) of group g -> its problem and (tile_m, tile_n)
 // (split-K: the K-slice is the outermost index of a problem's tiles, so an XCD's consecutive tiles
 // share one slice's A / B panels)
+__device__ __forceinline__ void raster_tile(int pid, int tiles_m, int tiles_n, int group, int& tile_m, int& tile_n) {
+  const int group_span = group * tiles_n;
+  const int gid = pid / group_span;
+  const int first_m = gid * group;
+  const int gsize = min(tiles_m - first_m, group);
+  tile_m = first_m + (pid % group_span) % gsize;
+  tile_n = (pid % group_span) / gsize;
+}
+
 __device__ __forceinline__ const GemmArgs& select_problem_pid(const GemmGroup& g, int pid_all, int& tile_m,
                                                               int& tile_n, int& kslice) {
   int pi = 0;
@@ -214,20 +245,12 @@ __device__ __forceinline__ const GemmArgs& select_problem_pid(const GemmGroup& g
   const int per_slice = a.tiles_m * a.tiles_n;
   kslice = a.ksplit > 1 ? pid / per_slice : 0;
   pid -= kslice * per_slice;
-  const int GROUP = a.group_m;
-  const int group_span = GROUP * a.tiles_n;
-  const int gid = pid / group_span;
-  const int first_m = gid * GROUP;
-  const int gsize = min(a.tiles_m - first_m, GROUP);
-  tile_m = first_m + (pid % group_span) % gsize;
-  tile_n = (pid % group_span) / gsize;
+  raster_tile(pid, a.tiles_m, a.tiles_n, a.group_m, tile_m, tile_n);
   return a;
 }
 
-__device__ __forceinline__ const GemmArgs& select_problem(const GemmGroup& g, int& tile_m, int& tile_n, int& kslice,
-                                                          int bid = -1, int nwg = -1) {
-  const int pid_all = bid < 0 ? xcd_remap(blockIdx.x, gridDim.x) : xcd_remap(bid, nwg);
-  return select_problem_pid(g, pid_all, tile_m, tile_n, kslice);
+__device__ __forceinline__ const GemmArgs& select_problem(const GemmGroup& g, int& tile_m, int& tile_n, int& kslice) {
+  return select_problem_pid(g, xcd_remap(blockIdx.x, gridDim.x), tile_m, tile_n, kslice);
 }
 
 // K range of split-K slice ks: first element, and the slice's K-tile count
@@ -285,7 +308,6 @@ __device__ __forceinline__ void swiglu_bwd_tail(const GemmArgs& a, const lds_u8*
                                                 int64_t ldc, uint16_t* C, int lane) {
   constexpr int ROWB = TN * 2 + 16, CPR = TN / 8, RPI = 64 / CPR, NIT = TM / RPI, SG = kSwigluGroup;
   static_assert(NIT % SG == 0, "chunk groups");
-  typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
   const int lrow = lane / CPR, ch = lane % CPR;
   const uint32_t roff = (uint32_t)(lrow * a.ldr + ch * 8) * 2u;  // bytes from the row group's base
   const uint32_t coff = (uint32_t)(lrow * ldc + ch * 8) * 2u;
@@ -307,19 +329,12 @@ __device__ __forceinline__ void swiglu_bwd_tail(const GemmArgs& a, const lds_u8*
 #pragma unroll
     for (int k = 0; k < SG; ++k) {
       const int q = q0 + k, row = q * RPI + lrow;
-      const u32x4_t raw = *(const __attribute__((address_space(3))) u32x4_t*)(st + row * ROWB + ch * 16);
-      bf16x8 v;
-      v.w[0] = raw[0]; v.w[1] = raw[1]; v.w[2] = raw[2]; v.w[3] = raw[3];
       float d[8], gg[8], uu[8], og[8], ou[8];
-      unpack8(v, d);
+      unpack8(lds_ld8(st + row * ROWB + ch * 16), d);
       unpack8(g[k], gg);
       unpack8(u[k], uu);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float sg = silu_sig(gg[e]);
-        ou[e] = d[e] * round_bf(gg[e] * sg);
-        og[e] = round_bf(d[e] * uu[e]) * (sg * (1.0f + gg[e] * (1.0f - sg)));
-      }
+      for (int e = 0; e < 8; ++e) swiglu_bwd_elem(d[e], gg[e], uu[e], og[e], ou[e]);
       st8((uint16_t*)(cbase + q * cstep + coff), pack8(og));
       st8((uint16_t*)(cbase + q * cstep + ustep + coff), pack8(ou));
     }
@@ -420,7 +435,6 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
       if (ncol0 < a.rope_cols) {
         // the wave's 64 columns are one head: lane = (row, chunk ch < 4) rotates chunk ch with
         // its partner ch + 4 (d, d + 32) from the bf16 staging, as csrc/rope.hip does
-        typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
         // every row's cos / sin chunk loaded before the first store (C may alias the tables as far
         // as the compiler knows: loaded per row, they were one table round trip per 16 rows)
         constexpr int NR = TM / 16;
@@ -438,14 +452,9 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
           const int row = it * 16 + lane / 4, ch = lane % 4;
           asm volatile("" : "+v"(cv[it].w[0]), "+v"(cv[it].w[1]), "+v"(cv[it].w[2]), "+v"(cv[it].w[3]));
           asm volatile("" : "+v"(sv[it].w[0]), "+v"(sv[it].w[1]), "+v"(sv[it].w[2]), "+v"(sv[it].w[3]));
-          const u32x4_t r1 = *(const __attribute__((address_space(3))) u32x4_t*)(st + row * ROWB + ch * 16);
-          const u32x4_t r2 = *(const __attribute__((address_space(3))) u32x4_t*)(st + row * ROWB + (ch + 4) * 16);
           float x1[8], x2[8], c[8], sn[8], o1[8], o2[8];
-          bf16x8 v1, v2;
-          v1.w[0] = r1[0]; v1.w[1] = r1[1]; v1.w[2] = r1[2]; v1.w[3] = r1[3];
-          v2.w[0] = r2[0]; v2.w[1] = r2[1]; v2.w[2] = r2[2]; v2.w[3] = r2[3];
-          unpack8(v1, x1);
-          unpack8(v2, x2);
+          unpack8(lds_ld8(st + row * ROWB + ch * 16), x1);
+          unpack8(lds_ld8(st + row * ROWB + (ch + 4) * 16), x2);
           unpack8(cv[it], c);
           unpack8(sv[it], sn);
 #pragma unroll
@@ -463,17 +472,18 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
     constexpr int CPR = TN / 8;          // 16-B chunks per row
     constexpr int RPI = 64 / CPR;        // rows per wave instruction
     constexpr int NIT = TM / RPI;
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
     // the epilogues that READ memory (g|u, the residual, the accumulated gradient) issue all their
     // loads first, then consume them: C may alias R / the old gradient, so the compiler would keep
     // every load behind the previous iteration's store -- one HBM round trip per row group
     // (all NIT chunks -- 4 NIT VGPRs, the accumulators are dead once staged -- before any store,
     // so the wave's epilogue is one memory round trip)
     constexpr bool RD = EPI == EPI_BF16_ACC || EPI == EPI_BF16_RES;
+    // (one group of all NIT chunks; kept as a loop: written without it, the EPI_BF16_RES kernels
+    // compile to other code)
     constexpr int GRP = NIT;
 #pragma unroll
     for (int g0 = 0; g0 < NIT; g0 += GRP) {
-      bf16x8 pre[GRP][1];
+      bf16x8 pre[GRP];
       if constexpr (RD) {
 #pragma unroll
         for (int q = 0; q < GRP; ++q) {
@@ -482,16 +492,14 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
                                                     : a.R + (mrow0 + row) * a.ldr + ncol0 + ch * 8;
           // the accumulated weight gradient (.grad): read-modify-written once per micro-batch,
           // non-temporal (as the f32 main_grad in f32_acc_tail); the residual: read once, too
-          pre[q][0] = ld8_nt(src);
+          pre[q] = ld8_nt(src);
         }
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
       for (int q = 0; q < GRP; ++q) {
         const int row = (g0 + q) * RPI + lane / CPR, ch = lane % CPR;
-        const u32x4_t raw = *(const __attribute__((address_space(3))) u32x4_t*)(st + row * ROWB + ch * 16);
-        bf16x8 v;
-        v.w[0] = raw[0]; v.w[1] = raw[1]; v.w[2] = raw[2]; v.w[3] = raw[3];
+        bf16x8 v = lds_ld8(st + row * ROWB + ch * 16);
         uint16_t* dst = C + (mrow0 + row) * ldc + ncol0 + ch * 8;
         if constexpr (EPI == EPI_CE_STATS) {
           // the row's TN = 64 columns of this wave are the CPR = 8 consecutive lanes sharing
@@ -508,12 +516,12 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
           se = sum8(se);
           if (ch == 0) xs_wave[row] = make_float2(mx, se);
         }
-        if constexpr (EPI == EPI_BF16_ACC || EPI == EPI_BF16_RES) {
+        if constexpr (RD) {
           // opaque: keeps chunk q's unpacking (and so its wait) here, after every load is issued
-          asm volatile("" : "+v"(pre[q][0].w[0]), "+v"(pre[q][0].w[1]), "+v"(pre[q][0].w[2]), "+v"(pre[q][0].w[3]));
+          asm volatile("" : "+v"(pre[q].w[0]), "+v"(pre[q].w[1]), "+v"(pre[q].w[2]), "+v"(pre[q].w[3]));
           float o[8], f[8];
           unpack8(v, f);
-          unpack8(pre[q][0], o);
+          unpack8(pre[q], o);
           // acc was rounded to bf16 once above; add in f32 and round again (== torch's bf16 add)
 #pragma unroll
           for (int e = 0; e < 8; ++e) o[e] += f[e];
@@ -575,10 +583,7 @@ __device__ __forceinline__ void write_128x32(lds_u8* st, int lane, uint16_t* dst
 #pragma unroll
   for (int it = 0; it < 128 / 16; ++it) {
     const int row = it * 16 + lane / 4, ch = lane % 4;
-    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-    const u32x4_t raw = *(const __attribute__((address_space(3))) u32x4_t*)(st + row * ROWB + ch * 16);
-    bf16x8 v;
-    v.w[0] = raw[0]; v.w[1] = raw[1]; v.w[2] = raw[2]; v.w[3] = raw[3];
+    const bf16x8 v = lds_ld8(st + row * ROWB + ch * 16);
     st8(dst + row * ld + ch * 8, v);
   }
   __builtin_amdgcn_s_waitcnt(0xc07f);  // the staging area is reused by the next call
@@ -601,17 +606,16 @@ __device__ __forceinline__ void epilogue_swiglu_fwd(const GemmArgs& a, f32x4_t (
   write_128x32(st, lane, GU + row0 * ldgu + a.N + hc0, ldgu, [&](int i, int j, int r) { return acc[i][j + 2][r]; });
   write_128x32(st, lane, H + row0 * ldh + hc0, ldh, [&](int i, int j, int r) {
     const float g = acc[i][j][r];
-    return round_bf(g * silu_sig(g)) * acc[i][j + 2][r];
+    return round_bf(g * pt_sigmoid(g)) * acc[i][j + 2][r];
   });
 }
 
-// B operand image base for the tile at (n0, k0) (+ n_off columns inside the tile)
+// B operand image base (k = 0) for the tile at n0: the N-segment n0 lies in, or the first K-segment
 // Segment selection by a compare chain on constant indices: every kernarg load is loop-invariant
 // (hoisted into SGPRs) -- an indexed a.B[s] load would put a dependent scalar-memory round trip
 // in front of every DMA issue.
-__device__ __forceinline__ const uint16_t* b_image_ptr(const GemmArgs& a, bool bkc, int n0, int k0, int n_off,
-                                                       int64_t& ldb) {
-  const int64_t x = a.bdim == 0 ? n0 : k0;
+__device__ __forceinline__ const uint16_t* b_image_ptr(const GemmArgs& a, bool bkc, int n0, int64_t& ldb) {
+  const int64_t x = a.bdim == 0 ? n0 : 0;
   const uint16_t* Bp = a.B[0];
   int64_t ld = a.ldb[0], base = 0;
 #pragma unroll
@@ -622,8 +626,8 @@ __device__ __forceinline__ const uint16_t* b_image_ptr(const GemmArgs& a, bool b
     base = in ? a.bseg[i] : base;
   }
   ldb = ld;
-  const int64_t nl = (a.bdim == 0 ? n0 - base : n0) + n_off;
-  const int64_t kl = a.bdim == 1 ? k0 - base : k0;
+  const int64_t nl = a.bdim == 0 ? n0 - base : n0;
+  const int64_t kl = a.bdim == 1 ? -base : 0;
   return bkc ? Bp + nl * ld + kl : Bp + kl * ld + nl;
 }
 
@@ -655,7 +659,7 @@ __device__ __forceinline__ int64_t bimg_seg_base(const GemmArgs& a, bool bkc, in
 __device__ __forceinline__ BImg bimg_make(const GemmArgs& a, bool bkc, int n0) {
   BImg r;
   int64_t ld;
-  r.b0 = b_image_ptr(a, bkc, n0, 0, 0, ld);
+  r.b0 = b_image_ptr(a, bkc, n0, ld);
   r.ld = ld;
   const int64_t p0 = (int64_t)(intptr_t)r.b0;
   const int64_t p1 = bimg_seg_base(a, bkc, n0, 1, r.s1);
@@ -707,6 +711,13 @@ __device__ __forceinline__ uint32_t himg_voff(int i, int lane, int64_t ld, int o
     const int tc = (col / SPAN) * 2 * SPAN + col % SPAN + off;
     return (uint32_t)(r * ld + tc);
   }
+}
+
+// the barrier between two phases, fenced so the scheduler moves nothing across it
+__device__ __forceinline__ void phase_bar() {
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
 }
 
 __device__ __forceinline__ void glds16_asm(const uint16_t* base, uint32_t voff_elems, lds_u8* dst) {
@@ -794,11 +805,6 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
   }
   __builtin_amdgcn_s_barrier();
 
-  auto bar = [] {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
   bf16x8_t af[4][2], b0[2][2], b1[2][2];
   auto mma = [&](int i0, int j0, const bf16x8_t (&A)[4][2], const bf16x8_t (&Bf)[2][2]) {
     __builtin_amdgcn_s_setprio(1);
@@ -812,7 +818,7 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
     __builtin_amdgcn_s_setprio(0);
   };
   const bool late = __builtin_amdgcn_readfirstlane(wm) == 1;
-  if (late) bar();
+  if (late) phase_bar();
 
   auto ktile = [&](int t, auto bufc) {
     constexpr int buf = decltype(bufc)::value;
@@ -832,9 +838,9 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
       for (int s = 0; s < 2; ++s) b0[j][s] = read_frag<128, BKC>(sBl, wn * 32 + j * 16, s, lane);
     if (n1) stage(t + 1, buf ^ 1, 3);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
+    phase_bar();
     mma(0, 0, af, b0);
-    bar();
+    phase_bar();
     // phase 2: Br cols; stage At(t+2); quadrant (0, 1)
 #pragma unroll
     for (int j = 0; j < 2; ++j)
@@ -842,9 +848,9 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
       for (int s = 0; s < 2; ++s) b1[j][s] = read_frag<128, BKC>(sBr, wn * 32 + j * 16, s, lane);
     if (n2) stage(t + 2, buf, 0);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
+    phase_bar();
     mma(0, 2, af, b1);
-    bar();
+    phase_bar();
     // phase 3: Ab rows; stage Bl(t+2); quadrant (1, 1)
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -852,9 +858,9 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
       for (int s = 0; s < 2; ++s) af[i][s] = read_frag<128, AK>(sAb, wm * 64 + i * 16, s, lane);
     if (n2) stage(t + 2, buf, 1);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
+    phase_bar();
     mma(4, 2, af, b1);
-    bar();
+    phase_bar();
     // phase 4: no reads; stage Br(t+2); retire K-tile t+1; quadrant (1, 0)
     if (n2) {
       stage(t + 2, buf, 2);
@@ -862,9 +868,9 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
     } else if (n1) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    bar();
+    phase_bar();
     mma(4, 0, af, b0);
-    bar();
+    phase_bar();
   };
 
   int t = 0;
@@ -873,12 +879,12 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
     ktile(t + 1, std::integral_constant<int, 1>{});
   }
   if (t < nk) ktile(t, std::integral_constant<int, 0>{});
-  if (!late) bar();  // balance the barrier count of the two wave groups
+  if (!late) phase_bar();  // balance the barrier count of the two wave groups
   __syncthreads();
   if constexpr (PAIR) {
     epilogue_swiglu_fwd(a, acc, smem + wave * (TM * (32 * 2 + 16)), m0 + wm * TM, tile_n * 128 + wn * 32, lane);
   } else {
-    // EPI_CE_STATS: per-wave row statistics beside the 8 staging areas (launch_8ph sizes the LDS)
+    // EPI_CE_STATS: per-wave row statistics beside the 8 staging areas (kTiles sizes the LDS)
     float2* xs = (float2*)(smem + 8 * (TM * (TN * 2 + 16)));
     epilogue<TM, TN, EPI>(a, acc, smem + wave * (TM * (TN * 2 + 16)), m0, n0, wm, wn, lane, xs + wave * TM,
                           (int64_t)ks * a.kpart_stride);
@@ -938,29 +944,42 @@ __global__ __launch_bounds__(512) void gemm_8ph_dual_kernel(const GemmGroup g0, 
   }
 }
 
-// ============================================================================ 4-phase 256x128
+// ============================================================ 256x128, three-K-tile ring (tiles 13, 14)
 // For the N = 2048 shapes (o_proj, down_proj forward, every dX GEMM of the layer, the lm_head dX),
-// where 256x256 tiles put only 128 workgroups on the 256 CUs.  256x128 tile, BK = 64, 8 waves as
-// 4(M) x 2(N), each wave a 64 x 64 output (4 x 4 accumulators): the same A + B fragment bytes per
-// MFMA as the 8-wave 256x256 kernel's 128 x 64 wave tiles.  Three images per K-tile:
-//   At = tile rows {0-31, 64-95, 128-159, 192-223} (rows 0-31 of each M-wave's 64)  read in phase 1
-//   Ab = the other 128 rows                                                           read in phase 2
-//   B  = all 128 columns                                                              read in phase 1
-// K-tile t = 2 phases (upper / lower 32 x 64 half of the wave's output, 16 MFMAs each), same
-// phase anatomy and wave-group stagger as the 8-phase kernel.  With 48 KiB per K-tile the LDS holds
-// THREE K-tiles (144 KiB): K-tile t+2 is staged during K-tile t into the buffer K-tile t-1 freed
-// (At in phase 1, B and Ab in phase 2), and the one wait per K-tile (phase 2, vmcnt(6)) retires
-// K-tile t+1 with t+2 in flight -- every DMA has >= 1.5 K-tiles to land.
-template <bool AK, bool BKC, int EPI>
-__device__ __forceinline__ void gemm_4ph_tile(const GemmArgs& a, const int tile_m, const int tile_n, const int ks = 0) {
-  constexpr int TM = 64, TN = 64, FM = 4, FN = 4;
+// where 256x256 tiles put only 128 workgroups on the 256 CUs.  256x128 tile, BK = 64, 8 waves, three
+// images of 128 rows / columns x 64 k per K-tile:
+//   At = rows 0 .. SPAN-1 of every 2 SPAN rows of the tile     read in phase 1
+//   Ab = the other 128 rows                                     read in phase 2
+//   B  = all 128 columns                                        read in phase 1
+// K-tile t = 2 phases, each { LDS reads; LDS-DMA; lgkmcnt(0); barrier; 16 MFMAs; barrier }: the 8-phase
+// kernel's phase anatomy and wave-group stagger (the late group runs one barrier behind).  With 48 KiB
+// per K-tile the LDS holds THREE K-tiles (144 KiB): K-tile t+2 is staged during K-tile t into the
+// buffer K-tile t-1 freed (At in phase 1, B and Ab in phase 2), and the one wait per K-tile (phase 2,
+// vmcnt(6)) retires K-tile t+1 with t+2 in flight -- every DMA has >= 1.5 K-tiles to land.
+// Two wave decompositions:
+//  * tile 13 (KH = false, "4-phase"): waves as 4(M) x 2(N), each a 64 x 64 output (4 x 4 accumulators),
+//    SPAN = 32: a phase is the upper / lower 32 x 64 half of the wave's output over both k-substeps --
+//    the same A + B fragment bytes per MFMA as the 256x256 kernel's 128 x 64 wave tiles.  Waves of
+//    M-rows 2-3 run late.
+//  * tile 14 (KH = true, "K-halves"): the two wave groups (waves 0-3, 4-7) take the two k-substeps of
+//    every K-tile (k 0-31 / 32-63), and inside a group 2(M) x 2(N) waves each own a 128 x 64 output
+//    (8 x 4 accumulators), SPAN = 64 (the 8-phase kernel's A half images) -- 12 LDS fragment reads per
+//    32 MFMAs instead of tile 13's 16, the LDS read rate the 8-phase kernel runs at.  Group 1 runs
+//    late.  After the K loop the groups swap halves through LDS: group 0 finishes rows 0-63 of each
+//    wave tile, group 1 rows 64-127 (each adds the other group's partial: g0 + g1 for every element),
+//    and each wave writes its 64 x 64 through the common epilogue.
+template <bool KH, bool AK, bool BKC, int EPI>
+__device__ __forceinline__ void gemm_ring3_tile(const GemmArgs& a, const int tile_m, const int tile_n, const int ks) {
+  constexpr int SPAN = KH ? 64 : 32;          // rows of one A image per 2 SPAN tile rows
+  constexpr int NI = SPAN / 16, FM = 2 * NI;  // A fragments per phase; accumulator rows of a wave
+  constexpr int NS = KH ? 1 : 2;              // k-substeps a wave multiplies
   constexpr int IMG = 128 * BK * 2;           // 16 KiB
   constexpr int BUF = 3 * IMG;                // At, B, Ab
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
   lds_u8* smem = (lds_u8*)smem_raw;
 
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: an SGPR
-  const int wm = wave >> 1, wn = wave & 1;
+  const int grp = wave >> 2, wm = KH ? (wave >> 1) & 1 : wave >> 1, wn = wave & 1;
   const int m0 = tile_m * 256, n0 = tile_n * 128;
 
   const BImg bi = bimg_make(a, BKC, n0);
@@ -970,159 +989,8 @@ __device__ __forceinline__ void gemm_4ph_tile(const GemmArgs& a, const int tile_
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int i = it * 8 + wave;
-    vA[0][it] = himg_voff<AK, 32>(i, lane, lda, 0);
-    vA[1][it] = himg_voff<AK, 32>(i, lane, lda, 32);
-    vB[it] = himg_voff<BKC, 128>(i, lane, ldb, 0);
-  }
-  const int kb = kslice_begin(a, ks);
-  const uint16_t* Ab0 = AK ? a.A + (int64_t)m0 * lda + kb : a.A + m0 + (int64_t)kb * lda;
-  auto a_ptr = [&](int t) { return AK ? Ab0 + t * BK : Ab0 + (int64_t)t * BK * lda; };
-  auto b_ptr = [&](int t) { return bimg_ptr(bi, BKC, kb + t * BK); };
-  // image h (0 At, 1 B, 2 Ab) of K-tile t into buffer buf
-  // DMA instruction `it` (of 2 per wave) of image h (0 At, 1 B, 2 Ab) of K-tile t into buffer buf
-  auto stage1 = [&](int t, int buf, int h, int it) {
-    lds_u8* dst = smem + buf * BUF + h * IMG;
-    const uint16_t* base = h == 1 ? b_ptr(t) : a_ptr(t);
-    const uint32_t vo = h == 1 ? vB[it] : vA[h == 2 ? 1 : 0][it];
-    glds16_asm(base, vo, dst + (it * 8 + wave) * 1024);
-  };
-  auto stage = [&](int t, int buf, int h) {
-    stage1(t, buf, h, 0);
-    stage1(t, buf, h, 1);
-  };
-
-  f32x4_t acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-
-  const int nk = kslice_tiles(a);
-  stage(0, 0, 0); stage(0, 0, 1); stage(0, 0, 2);
-  if (nk > 1) {
-    stage(1, 1, 0); stage(1, 1, 1); stage(1, 1, 2);
-    asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  } else {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  }
-  __builtin_amdgcn_s_barrier();
-
-  auto bar = [] {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  bf16x8_t af[2][2], bf[4][2];
-  auto mma = [&](int i0) {
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[i0 + i][j] = mfma16(af[i][s], bf[j][s], acc[i0 + i][j]);
-    __builtin_amdgcn_s_setprio(0);
-  };
-  const bool late = __builtin_amdgcn_readfirstlane(wm) >= 2;
-  if (late) bar();
-
-  auto ktile = [&](int t, auto bufc) {
-    constexpr int buf = decltype(bufc)::value;
-    constexpr int nbuf = (buf + 2) % 3;  // K-tile t+2's buffer (freed by K-tile t-1)
-    const lds_u8* sAt = smem + buf * BUF;
-    const lds_u8* sB = sAt + IMG;
-    const lds_u8* sAb = sAt + 2 * IMG;
-    const bool n1 = t + 1 < nk, n2 = t + 2 < nk;
-    // phase 1: At rows + all B cols; stage At(t+2); upper half
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) af[i][s] = read_frag<128, AK>(sAt, wm * 32 + i * 16, s, lane);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) bf[j][s] = read_frag<128, BKC>(sB, wn * 64 + j * 16, s, lane);
-    if (n2) stage(t + 2, nbuf, 0);  // (measured: moving DMA between the phases only loses)
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    mma(0);
-    bar();
-    // phase 2: Ab rows; stage B, Ab of t+2; retire K-tile t+1; lower half
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) af[i][s] = read_frag<128, AK>(sAb, wm * 32 + i * 16, s, lane);
-    if (n2) {
-      stage(t + 2, nbuf, 1);
-      stage(t + 2, nbuf, 2);
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    } else if (n1) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    mma(2);
-    bar();
-  };
-
-  int t = 0;
-  for (; t + 2 < nk; t += 3) {
-    ktile(t, std::integral_constant<int, 0>{});
-    ktile(t + 1, std::integral_constant<int, 1>{});
-    ktile(t + 2, std::integral_constant<int, 2>{});
-  }
-  if (t < nk) ktile(t, std::integral_constant<int, 0>{});
-  if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
-  if (!late) bar();
-  __syncthreads();
-  float2* xs = (float2*)(smem + 8 * (TM * (TN * 2 + 16)));  // EPI_CE_STATS row statistics
-  epilogue<TM, TN, EPI>(a, acc, smem + wave * (TM * (TN * 2 + 16)), m0, n0, wm, wn, lane, xs + wave * TM,
-                        (int64_t)ks * a.kpart_stride);
-  if constexpr (EPI == EPI_CE_STATS) {
-    __syncthreads();
-    if (wn == 0) ce_stats_merge<2, TM, TN>(a, xs, m0, n0, wm, lane);
-  }
-}
-
-template <bool AK, bool BKC, int EPI>
-__global__ __launch_bounds__(512) void gemm_4ph_kernel(const GemmGroup g) {
-  int tile_m, tile_n, ks;
-  const GemmArgs& a = select_problem(g, tile_m, tile_n, ks);
-  gemm_4ph_tile<AK, BKC, EPI>(a, tile_m, tile_n, ks);
-}
-
-// ================================================================ 256x128, K-halves (tile 14)
-// The 4-phase kernel's tile and images with the 8-phase kernel's wave tile: the two wave groups
-// (waves 0-3, 4-7) take the two k-substeps of every K-tile (k 0-31 / 32-63), and inside a group
-// 2(M) x 2(N) waves each own a 128 x 64 output (8 x 4 accumulators) -- 12 LDS fragment reads per
-// 32 MFMAs instead of the 4-phase kernel's 16 (64 x 64 wave tiles), the LDS read rate the 8-phase
-// kernel runs at.  Images per K-tile: At / Ab = the 8-phase kernel's A half images (rows 0-63 /
-// 64-127 of each M-wave's 128), B = all 128 columns; the 4-phase kernel's three-K-tile ring, phase
-// anatomy, single counted wait per K-tile and wave-group stagger, unchanged.  After the K loop the
-// groups swap halves through LDS: group 0 finishes rows 0-63 of each wave tile, group 1 rows
-// 64-127 (each adds the other group's partial: g0 + g1 for every element), and each wave writes
-// its 64 x 64 through the common epilogue.
-template <bool AK, bool BKC, int EPI>
-__device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, const int tile_m, const int tile_n, const int ks = 0) {
-  constexpr int IMG = 128 * BK * 2;           // 16 KiB
-  constexpr int BUF = 3 * IMG;                // At, B, Ab
-  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
-  lds_u8* smem = (lds_u8*)smem_raw;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // wave-uniform: an SGPR
-  const int grp = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-  const int m0 = tile_m * 256, n0 = tile_n * 128;
-
-  const BImg bi = bimg_make(a, BKC, n0);
-  const int64_t ldb = bi.ld;
-  const int64_t lda = a.lda;
-  uint32_t vA[2][2], vB[2];
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int i = it * 8 + wave;
-    vA[0][it] = himg_voff<AK, 64>(i, lane, lda, 0);
-    vA[1][it] = himg_voff<AK, 64>(i, lane, lda, 64);
+    vA[0][it] = himg_voff<AK, SPAN>(i, lane, lda, 0);
+    vA[1][it] = himg_voff<AK, SPAN>(i, lane, lda, SPAN);
     vB[it] = himg_voff<BKC, 128>(i, lane, ldb, 0);
   }
   const int kb = kslice_begin(a, ks);
@@ -1140,9 +1008,9 @@ __device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, const int tile_m
     }
   };
 
-  f32x4_t acc[8][4];
+  f32x4_t acc[FM][4];
 #pragma unroll
-  for (int i = 0; i < 8; ++i)
+  for (int i = 0; i < FM; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
 
@@ -1156,23 +1024,20 @@ __device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, const int tile_m
   }
   __builtin_amdgcn_s_barrier();
 
-  auto bar = [] {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  const int s = __builtin_amdgcn_readfirstlane(grp);  // this group's k-substep
-  bf16x8_t af[4], bf[4];
+  const int s = __builtin_amdgcn_readfirstlane(grp);  // KH: this group's k-substep
+  bf16x8_t af[NI][NS], bf[4][NS];
   auto mma = [&](int i0) {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int ss = 0; ss < NS; ++ss)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc[i0 + i][j] = mfma16(af[i], bf[j], acc[i0 + i][j]);
+      for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i0 + i][j] = mfma16(af[i][ss], bf[j][ss], acc[i0 + i][j]);
     __builtin_amdgcn_s_setprio(0);
   };
-  const bool late = s == 1;
-  if (late) bar();
+  const bool late = KH ? s == 1 : __builtin_amdgcn_readfirstlane(wm) >= 2;
+  if (late) phase_bar();
 
   auto ktile = [&](int t, auto bufc) {
     constexpr int buf = decltype(bufc)::value;
@@ -1181,19 +1046,25 @@ __device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, const int tile_m
     const lds_u8* sB = sAt + IMG;
     const lds_u8* sAb = sAt + 2 * IMG;
     const bool n1 = t + 1 < nk, n2 = t + 2 < nk;
-    // phase 1: At rows + B cols of substep s; stage At(t+2); rows 0-63 of the wave tile
+    // phase 1: At rows + all B cols; stage At(t+2); the upper half of the wave's output
 #pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = read_frag<128, AK>(sAt, wm * 64 + i * 16, s, lane);
+    for (int i = 0; i < NI; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) bf[j] = read_frag<128, BKC>(sB, wn * 64 + j * 16, s, lane);
-    if (n2) stage(t + 2, nbuf, 0);
+      for (int ss = 0; ss < NS; ++ss) af[i][ss] = read_frag<128, AK>(sAt, wm * SPAN + i * 16, KH ? s : ss, lane);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int ss = 0; ss < NS; ++ss) bf[j][ss] = read_frag<128, BKC>(sB, wn * 64 + j * 16, KH ? s : ss, lane);
+    if (n2) stage(t + 2, nbuf, 0);  // (measured: moving DMA between the phases only loses)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
+    phase_bar();
     mma(0);
-    bar();
-    // phase 2: Ab rows; stage B, Ab of t+2; retire K-tile t+1; rows 64-127
+    phase_bar();
+    // phase 2: Ab rows; stage B, Ab of t+2; retire K-tile t+1; the lower half
 #pragma unroll
-    for (int i = 0; i < 4; ++i) af[i] = read_frag<128, AK>(sAb, wm * 64 + i * 16, s, lane);
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+      for (int ss = 0; ss < NS; ++ss) af[i][ss] = read_frag<128, AK>(sAb, wm * SPAN + i * 16, KH ? s : ss, lane);
     if (n2) {
       stage(t + 2, nbuf, 1);
       stage(t + 2, nbuf, 2);
@@ -1202,9 +1073,9 @@ __device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, const int tile_m
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
-    mma(4);
-    bar();
+    phase_bar();
+    mma(NI);
+    phase_bar();
   };
 
   int t = 0;
@@ -1215,43 +1086,69 @@ __device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, const int tile_m
   }
   if (t < nk) ktile(t, std::integral_constant<int, 0>{});
   if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
-  if (!late) bar();
+  if (!late) phase_bar();
   __syncthreads();
-  // swap halves: wave w hands the 4 x 4 fragments the partner wave (w ^ 4) finishes -- group 0 its
-  // rows 64-127, group 1 its rows 0-63 -- through slot w (16 B per lane, lane-contiguous)
-  typedef __attribute__((address_space(3))) f32x4_t lds_f4;
-  lds_f4* slot = (lds_f4*)smem + wave * 16 * 64 + lane;
-  // (constant accumulator indices in each branch: an index that depends on the group would put
-  // the accumulators in scratch)
-  if (s == 0) {
+  if constexpr (KH) {
+    // swap halves: wave w hands the 4 x 4 fragments the partner wave (w ^ 4) finishes -- group 0 its
+    // rows 64-127, group 1 its rows 0-63 -- through slot w (16 B per lane, lane-contiguous)
+    typedef __attribute__((address_space(3))) f32x4_t lds_f4;
+    lds_f4* slot = (lds_f4*)smem + wave * 16 * 64 + lane;
+    // (constant accumulator indices in each branch: an index that depends on the group would put
+    // the accumulators in scratch)
+    if (s == 0) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+      for (int i = 0; i < 4; ++i)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) slot[(i * 4 + j) * 64] = acc[4 + i][j];
+        for (int j = 0; j < 4; ++j) slot[(i * 4 + j) * 64] = acc[4 + i][j];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) slot[(i * 4 + j) * 64] = acc[i][j];
+    }
+    __syncthreads();
+    const lds_f4* peer = (const lds_f4*)smem + (wave ^ 4) * 16 * 64 + lane;
+    f32x4_t out[4][4];
+    if (s == 0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[i][j] = acc[i][j] + peer[(i * 4 + j) * 64];       // g0 + g1
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) out[i][j] = peer[(i * 4 + j) * 64] + acc[4 + i][j];   // g0 + g1
+    }
+    __syncthreads();
+    // the wave's 64 x 64 output: tile rows wm * 128 + s * 64 .., columns wn * 64 ..
+    epilogue<64, 64, EPI>(a, out, smem + wave * (64 * (64 * 2 + 16)), m0, n0, wm * 2 + s, wn, lane, nullptr,
+                          (int64_t)ks * a.kpart_stride);
   } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) slot[(i * 4 + j) * 64] = acc[i][j];
+    float2* xs = (float2*)(smem + 8 * (64 * (64 * 2 + 16)));  // EPI_CE_STATS row statistics
+    epilogue<64, 64, EPI>(a, acc, smem + wave * (64 * (64 * 2 + 16)), m0, n0, wm, wn, lane, xs + wave * 64,
+                          (int64_t)ks * a.kpart_stride);
+    if constexpr (EPI == EPI_CE_STATS) {
+      __syncthreads();
+      if (wn == 0) ce_stats_merge<2, 64, 64>(a, xs, m0, n0, wm, lane);
+    }
   }
-  __syncthreads();
-  const lds_f4* peer = (const lds_f4*)smem + (wave ^ 4) * 16 * 64 + lane;
-  f32x4_t out[4][4];
-  if (s == 0) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) out[i][j] = acc[i][j] + peer[(i * 4 + j) * 64];       // g0 + g1
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) out[i][j] = peer[(i * 4 + j) * 64] + acc[4 + i][j];   // g0 + g1
-  }
-  __syncthreads();
-  // the wave's 64 x 64 output: tile rows wm * 128 + s * 64 .., columns wn * 64 ..
-  epilogue<64, 64, EPI>(a, out, smem + wave * (64 * (64 * 2 + 16)), m0, n0, wm * 2 + s, wn, lane, nullptr,
-                        (int64_t)ks * a.kpart_stride);
+}
+
+template <bool AK, bool BKC, int EPI>
+__device__ __forceinline__ void gemm_4ph_tile(const GemmArgs& a, int tile_m, int tile_n, int ks = 0) {
+  gemm_ring3_tile<false, AK, BKC, EPI>(a, tile_m, tile_n, ks);
+}
+template <bool AK, bool BKC, int EPI>
+__device__ __forceinline__ void gemm_kh_tile(const GemmArgs& a, int tile_m, int tile_n, int ks = 0) {
+  gemm_ring3_tile<true, AK, BKC, EPI>(a, tile_m, tile_n, ks);
+}
+
+template <bool AK, bool BKC, int EPI>
+__global__ __launch_bounds__(512) void gemm_4ph_kernel(const GemmGroup g) {
+  int tile_m, tile_n, ks;
+  const GemmArgs& a = select_problem(g, tile_m, tile_n, ks);
+  gemm_4ph_tile<AK, BKC, EPI>(a, tile_m, tile_n, ks);
 }
 
 template <bool AK, bool BKC, int EPI>
@@ -1329,14 +1226,9 @@ __device__ __forceinline__ void gemm_hq_tile(const GemmArgs& a, const int tile_m
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  auto bar = [] {
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
   const int s = __builtin_amdgcn_readfirstlane(grp);  // this group's k-substep
   const bool late = s == 1;
-  if (late) bar();
+  if (late) phase_bar();
   bf16x8_t af[4], bf[4];
 
   auto ktile = [&](int t, auto bufc) {
@@ -1361,14 +1253,14 @@ __device__ __forceinline__ void gemm_hq_tile(const GemmArgs& a, const int tile_m
       else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    bar();
+    phase_bar();
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(af[i], bf[j], acc[i][j]);
     __builtin_amdgcn_s_setprio(0);
-    bar();
+    phase_bar();
   };
 
   int t = 0;
@@ -1381,7 +1273,7 @@ __device__ __forceinline__ void gemm_hq_tile(const GemmArgs& a, const int tile_m
   if (t < nk) ktile(t, std::integral_constant<int, 0>{});
   if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
   if (t + 2 < nk) ktile(t + 2, std::integral_constant<int, 2>{});
-  if (!late) bar();
+  if (!late) phase_bar();
   __syncthreads();
   // swap halves: wave w hands the 2 x 4 fragments its partner (w ^ 4) finishes -- group 0 its rows
   // 32-63, group 1 its rows 0-31 -- through slot w (16 B per lane, lane-contiguous)
@@ -1438,27 +1330,20 @@ struct MixMap {
   int nsplit_t1;              // n_split / 128: the 4-phase part's first tile column
 };
 
-__device__ __forceinline__ void grouped_tile(int pid, int tiles_m, int tiles_n, int group, int& tm, int& tn) {
-  const int span = group * tiles_n, gid = pid / span, first = gid * group;
-  const int gsize = min(tiles_m - first, group);
-  tm = first + (pid % span) % gsize;
-  tn = (pid % span) / gsize;
-}
-
 template <bool AK, bool BKC, int EPI>
 __global__ __launch_bounds__(512) void gemm_mix_kernel(const GemmArgs a, const MixMap m) {
   int pid, tile_m, tile_n;
   if (dual_select(m.d, pid) == 0) {
-    grouped_tile(pid, m.tiles_m, m.tn0, 8, tile_m, tile_n);
+    raster_tile(pid, m.tiles_m, m.tn0, 8, tile_m, tile_n);
     gemm_8ph_tile<AK, BKC, EPI>(a, tile_m, tile_n);
   } else {
-    grouped_tile(pid, m.tiles_m, m.tn1, 4, tile_m, tile_n);
+    raster_tile(pid, m.tiles_m, m.tn1, 4, tile_m, tile_n);
     gemm_4ph_tile<AK, BKC, EPI>(a, tile_m, m.nsplit_t1 + tile_n);
   }
 }
 
 // ================================================================================= simple
-template <int BM, int BN, int WM, int WN, bool AK, bool BKC, int EPI, int SCHED>
+template <int BM, int BN, int WM, int WN, bool AK, bool BKC, int EPI>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmGroup g) {
   constexpr int NT = WM * WN * 64;
   constexpr int TM = BM / WM, TN = BN / WN;
@@ -1503,62 +1388,107 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmGroup g) {
     if (kt + 1 < nk) stage(kt + 1, buf ^ 1);
     const lds_u8* sa = smem + buf * STAGE_BYTES;
     const lds_u8* sb = sa + A_BYTES;
-    if (SCHED == 0) {
 #pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        bf16x8_t af[FM], bfr[FN];
+    for (int s = 0; s < 2; ++s) {
+      bf16x8_t af[FM], bfr[FN];
 #pragma unroll
-        for (int i = 0; i < FM; ++i) af[i] = read_frag<BM, AK>(sa, wm * TM + i * 16, s, lane);
+      for (int i = 0; i < FM; ++i) af[i] = read_frag<BM, AK>(sa, wm * TM + i * 16, s, lane);
 #pragma unroll
-        for (int j = 0; j < FN; ++j) bfr[j] = read_frag<BN, BKC>(sb, wn * TN + j * 16, s, lane);
-#pragma unroll
-        for (int i = 0; i < FM; ++i)
-#pragma unroll
-          for (int j = 0; j < FN; ++j)
-            acc[i][j] = mfma16(af[i], bfr[j], acc[i][j]);
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    } else {
-      // both k-substeps' fragments in flight at once (two register sets, B first so the first
-      // MFMA row can start after FN + 1 reads), MFMAs in one prioritised cluster, raw barrier
-      bf16x8_t a0[FM], b0[FN], a1[FM], b1[FN];
-#pragma unroll
-      for (int j = 0; j < FN; ++j) b0[j] = read_frag<BN, BKC>(sb, wn * TN + j * 16, 0, lane);
-#pragma unroll
-      for (int i = 0; i < FM; ++i) a0[i] = read_frag<BM, AK>(sa, wm * TM + i * 16, 0, lane);
-#pragma unroll
-      for (int j = 0; j < FN; ++j) b1[j] = read_frag<BN, BKC>(sb, wn * TN + j * 16, 1, lane);
-#pragma unroll
-      for (int i = 0; i < FM; ++i) a1[i] = read_frag<BM, AK>(sa, wm * TM + i * 16, 1, lane);
-      __builtin_amdgcn_s_setprio(1);
+      for (int j = 0; j < FN; ++j) bfr[j] = read_frag<BN, BKC>(sb, wn * TN + j * 16, s, lane);
 #pragma unroll
       for (int i = 0; i < FM; ++i)
 #pragma unroll
         for (int j = 0; j < FN; ++j)
-          acc[i][j] = mfma16(a0[i], b0[j], acc[i][j]);
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = mfma16(a1[i], b1[j], acc[i][j]);
-      __builtin_amdgcn_s_setprio(0);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
+          acc[i][j] = mfma16(af[i], bfr[j], acc[i][j]);
     }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
   }
   epilogue<TM, TN, EPI>(a, acc, smem + wave * (TM * (TN * 2 + 16)), m0, n0, wm, wn, lane, nullptr,
                         (int64_t)ks * a.kpart_stride);
 }
 
 // ================================================================================== launch
-template <typename Kern>
-void set_smem_once(Kern k, int smem) {
-  (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+// Tile ids (ABI: the callers pass them; -1 = auto).  Ids 4, 5, 8, 9 (the simple 256x256 / 256x128
+// kernels and their two-substep forms) were never picked once the phased kernels existed and are no
+// longer built; 0, 1, 6, 7, 10, 11 were pipelining experiments, measured slower and retired.
+enum Tile {
+  TILE_S128 = 2,   // simple 128x128
+  TILE_S64 = 3,    // simple 64x64 (the TP shards' few-tile problems)
+  TILE_8PH = 12,   // 8-phase 256x256 (two half-image wave groups, one wait per K-tile)
+  TILE_4PH = 13,   // 4-phase 256x128 (three K-tiles resident)
+  TILE_KH = 14,    // 256x128 with the K-tile's two k-substeps over two wave groups (128 x 64 wave tiles)
+  TILE_HQ = 15     // 128x128 with the two k-substeps over two wave groups (64 x 64 wave tiles, 4-deep ring)
+};
+
+constexpr unsigned epi_bit(int e) { return 1u << e; }
+constexpr unsigned layout_bit(bool ak, bool bkc) { return 1u << (2 * ak + bkc); }
+constexpr unsigned kEpiPlain =
+    epi_bit(EPI_BF16) | epi_bit(EPI_BF16_ACC) | epi_bit(EPI_F32) | epi_bit(EPI_F32_ACC) | epi_bit(EPI_BF16_RES);
+constexpr unsigned kAllLayouts = 15u;
+// A M-contiguous with B K-contiguous: no layer GEMM takes this layout, so only the simple tiles are
+// built for it (pick_group_tile knows)
+constexpr unsigned kPhasedLayouts = kAllLayouts & ~layout_bit(false, true);
+// the layouts an epilogue is built for: the plain sinks every one; the residual, RoPE, CE-statistics
+// and SwiGLU forward projections the forward's (weights K-contiguous); the SwiGLU backward the dX's
+constexpr unsigned epi_layouts(int e) {
+  return e <= EPI_F32_ACC ? kAllLayouts : e == EPI_SWIGLU_BWD ? layout_bit(true, false) : layout_bit(true, true);
 }
 
-// per-problem tile grid + consecutive tile ids; returns the total tile count
-// tile-rows per group of the tile order: 6 for both phased tiles.  Whole-step A/B (round 4,
+// What the launch layer knows of a tile: its block, the LDS of its main loop (the ring of operand
+// images), of what follows it (per-wave epilogue staging, TM x (64 bf16 + 16 B pad) rows; tiles 14 /
+// 15: the half swap, 16 B per lane and fragment) and of EPI_CE_STATS beside the staging (a float2 per
+// wave row), and the epilogues and layouts it is built for.
+struct TileDesc {
+  int id, bm, bn, threads;
+  int smem_main, smem_epi, smem_ce;
+  unsigned epis, layouts;
+  bool phased;   // a phased kernel keeps one B ld per tile (K-segments share it)
+};
+constexpr int kWaveStage64 = 64 * 2 + 16;   // bytes per staged row of a 64-column wave tile
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+constexpr TileDesc kTiles[] = {
+    {TILE_S128, 128, 128, 256, 2 * (128 + 128) * BK * 2, 4 * 64 * kWaveStage64, 0, kEpiPlain, kAllLayouts, false},
+    {TILE_S64, 64, 64, 256, 2 * (64 + 64) * BK * 2, 4 * 32 * (32 * 2 + 16), 0, kEpiPlain, kAllLayouts, false},
+    {TILE_8PH, 256, 256, 512, 2 * 4 * 128 * BK * 2, 8 * 128 * kWaveStage64, 8 * 128 * 8,
+     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_SWIGLU_FWD) | epi_bit(EPI_SWIGLU_BWD),
+     kPhasedLayouts, true},
+    {TILE_4PH, 256, 128, 512, 3 * 3 * 128 * BK * 2, 8 * 64 * kWaveStage64, 8 * 64 * 8,
+     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS), kPhasedLayouts, true},
+    {TILE_KH, 256, 128, 512, 3 * 3 * 128 * BK * 2, cmax(8 * 16 * 64 * 16, 8 * 64 * kWaveStage64), 0,
+     kEpiPlain | epi_bit(EPI_ROPE), kPhasedLayouts, true},
+    {TILE_HQ, 128, 128, 512, 4 * 2 * 128 * BK * 2, cmax(8 * 8 * 64 * 16, 8 * 32 * kWaveStage64), 0, kEpiPlain,
+     kPhasedLayouts, true},
+};
+constexpr int kNumTileDescs = sizeof(kTiles) / sizeof(kTiles[0]);
+
+constexpr const TileDesc* tile_desc(int id) {   // nullptr: not a tile that is built
+  for (int i = 0; i < kNumTileDescs; ++i)
+    if (kTiles[i].id == id) return &kTiles[i];
+  return nullptr;
+}
+constexpr bool tile_built(const TileDesc& t, bool ak, bool bkc, int epi) {
+  return (t.epis & epi_bit(epi)) && (t.layouts & epi_layouts(epi) & layout_bit(ak, bkc));
+}
+constexpr int tile_smem(const TileDesc& t, int epi) {
+  return cmax(t.smem_main, t.smem_epi + (epi == EPI_CE_STATS ? t.smem_ce : 0));
+}
+
+// The one launch: the kernel's dynamic-LDS attribute is set on the first launch of each instantiation.
+template <auto Kern, int SMEM, typename... Args>
+int launch_kernel(int grid, int block, hipStream_t stream, const Args&... args) {
+  static_assert(SMEM <= 160 * 1024, "LDS budget");
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+    attr_set = true;
+  }
+  Kern<<<grid, block, SMEM, stream>>>(args...);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+// tile-rows per group of the tile order: 6 for every tile.  Whole-step A/B (round 4,
 // profiles/r04/group_m/, two boxes, interleaved): 6 -> 156.6-157.5 k, 5 / 7 -> 156.2-157.8 k,
 // 4 -> 155.4-155.9 k, the previous 8 (256x256) / 4 (256x128) -> 154.9-155.0 k tokens/s
 // (the A/B variant that overrode it is retired: every other count measured slower)
@@ -1567,18 +1497,14 @@ void set_smem_once(Kern k, int smem) {
 #ifndef PT_GROUP_M
 #define PT_GROUP_M 6
 #endif
-int group_m_for(int bm, int bn) {
-  (void)bm; (void)bn;
-  return PT_GROUP_M;
-}
 
+// per-problem tile grid + consecutive tile ids; returns the total tile count
 inline int group_tiles(GemmGroup& g, int bm, int bn) {
   int n = 0;
-  const int gm = group_m_for(bm, bn);
   for (int i = 0; i < g.nprob; ++i) {
     g.p[i].tiles_m = g.p[i].M / bm;
     g.p[i].tiles_n = g.p[i].N / bn;
-    g.p[i].group_m = gm;
+    g.p[i].group_m = PT_GROUP_M;
     g.start[i] = n;
     n += g.p[i].tiles_m * g.p[i].tiles_n * (g.p[i].ksplit > 1 ? g.p[i].ksplit : 1);
   }
@@ -1586,160 +1512,126 @@ inline int group_tiles(GemmGroup& g, int bm, int bn) {
   return n;
 }
 
-template <int BM, int BN, int WM, int WN, bool AK, bool BKC, int EPI, int SCHED = 0>
-int launch_t(GemmGroup g, hipStream_t stream) {
-  const int tiles = group_tiles(g, BM, BN);
-  constexpr int smem_main = 2 * (BM + BN) * BK * 2;
-  constexpr int smem_epi = WM * WN * (BM / WM) * ((BN / WN) * 2 + 16);
-  constexpr int smem = smem_main > smem_epi ? smem_main : smem_epi;
-  static_assert(smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_kernel<BM, BN, WM, WN, AK, BKC, EPI, SCHED>, smem);
-    attr_set = true;
-  }
-  gemm_kernel<BM, BN, WM, WN, AK, BKC, EPI, SCHED><<<tiles, WM * WN * 64, smem, stream>>>(g);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+template <int T, bool AK, bool BKC, int EPI>
+constexpr auto tile_kernel() {
+  constexpr TileDesc t = *tile_desc(T);
+  if constexpr (T == TILE_8PH) return gemm_8ph_kernel<AK, BKC, EPI>;
+  else if constexpr (T == TILE_4PH) return gemm_4ph_kernel<AK, BKC, EPI>;
+  else if constexpr (T == TILE_KH) return gemm_kh_kernel<AK, BKC, EPI>;
+  else if constexpr (T == TILE_HQ) return gemm_hq_kernel<AK, BKC, EPI>;
+  else return gemm_kernel<t.bm, t.bn, 2, 2, AK, BKC, EPI>;
 }
 
-template <bool AK, bool BKC, int EPI>
-int launch_8ph(GemmGroup g, hipStream_t stream) {
-  const int tiles = group_tiles(g, 256, EPI == EPI_SWIGLU_FWD ? 128 : 256);
-  constexpr int smem_main = 8 * 128 * BK * 2;
-  constexpr int smem_epi = 8 * 128 * (64 * 2 + 16) + (EPI == EPI_CE_STATS ? 8 * 128 * 8 : 0);
-  constexpr int smem = smem_main > smem_epi ? smem_main : smem_epi;
-  static_assert(smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_8ph_kernel<AK, BKC, EPI>, smem);
-    attr_set = true;
+// One dispatcher: (tile, layouts, epilogue) -> the launch of the kernel built for it, PT_EUNSUPPORTED
+// where none is (kTiles / epi_layouts say which are), PT_EINVAL for an unknown epilogue.
+template <int I, bool AK, bool BKC, int EPI>
+int launch_tile(GemmGroup& g, hipStream_t s) {
+  constexpr TileDesc t = kTiles[I];
+  if constexpr (!tile_built(t, AK, BKC, EPI)) {
+    return PT_EUNSUPPORTED;
+  } else {
+    // EPI_SWIGLU_FWD consumes B in paired tiles: the grid is 256 x 128 of h
+    const int tiles = group_tiles(g, t.bm, EPI == EPI_SWIGLU_FWD ? t.bn / 2 : t.bn);
+    return launch_kernel<tile_kernel<t.id, AK, BKC, EPI>(), tile_smem(t, EPI)>(tiles, t.threads, s, g);
   }
-  gemm_8ph_kernel<AK, BKC, EPI><<<tiles, 512, smem, stream>>>(g);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+}
+
+template <bool AK, bool BKC, int EPI, int... I>
+int dispatch_tile(GemmGroup& g, int tile, hipStream_t s, std::integer_sequence<int, I...>) {
+  int rc = PT_EUNSUPPORTED;
+  (void)((tile == kTiles[I].id && (rc = launch_tile<I, AK, BKC, EPI>(g, s), true)) || ...);
+  return rc;
+}
+
+template <int EPI>
+int dispatch_layout(GemmGroup& g, int tile, int a_kcontig, int b_kcontig, hipStream_t s) {
+  constexpr auto all = std::make_integer_sequence<int, kNumTileDescs>{};
+  if (a_kcontig && b_kcontig) return dispatch_tile<true, true, EPI>(g, tile, s, all);
+  if (a_kcontig && !b_kcontig) return dispatch_tile<true, false, EPI>(g, tile, s, all);
+  if (!a_kcontig && !b_kcontig) return dispatch_tile<false, false, EPI>(g, tile, s, all);
+  return dispatch_tile<false, true, EPI>(g, tile, s, all);
+}
+
+int dispatch(GemmGroup& g, int tile, int a_kcontig, int b_kcontig, int epilogue, hipStream_t s) {
+  switch (epilogue) {
+    case EPI_BF16: return dispatch_layout<EPI_BF16>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_BF16_ACC: return dispatch_layout<EPI_BF16_ACC>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_F32: return dispatch_layout<EPI_F32>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_F32_ACC: return dispatch_layout<EPI_F32_ACC>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_BF16_RES: return dispatch_layout<EPI_BF16_RES>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_SWIGLU_FWD: return dispatch_layout<EPI_SWIGLU_FWD>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_SWIGLU_BWD: return dispatch_layout<EPI_SWIGLU_BWD>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_ROPE: return dispatch_layout<EPI_ROPE>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_CE_STATS: return dispatch_layout<EPI_CE_STATS>(g, tile, a_kcontig, b_kcontig, s);
+    default: return PT_EINVAL;
+  }
 }
 
 template <bool AK0, bool BKC0, int EPI0, bool AK1, bool BKC1, int EPI1>
 int launch_dual_t(GemmGroup g0, GemmGroup g1, int order, hipStream_t stream) {
-  const int t0 = group_tiles(g0, 256, 256), t1 = group_tiles(g1, 256, 256);  // (x ksplit)
+  constexpr TileDesc t = *tile_desc(TILE_8PH);
+  const int t0 = group_tiles(g0, t.bm, t.bn), t1 = group_tiles(g1, t.bm, t.bn);  // (x ksplit)
   if (t0 % 8 || t1 % 8) return PT_EUNSUPPORTED;  // equal per-XCD shares of both groups
   const DualMap m{t0 / 8, t1 / 8, order};
-  constexpr int smem = 8 * 128 * (64 * 2 + 16);  // epilogue staging (> the 128 KiB main loop)
-  static_assert(smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_8ph_dual_kernel<AK0, BKC0, EPI0, AK1, BKC1, EPI1>, smem);
-    attr_set = true;
+  return launch_kernel<gemm_8ph_dual_kernel<AK0, BKC0, EPI0, AK1, BKC1, EPI1>, cmax(tile_smem(t, EPI0), tile_smem(t, EPI1))>(
+      t0 + t1, t.threads, stream, g0, g1, m);
+}
+
+// Validate one problem (with its split-K and A-segment fields) and fill its kernel arguments.
+// Returns PT_OK or a PT_E* code.  EPI_SWIGLU_FWD: B = {W_gate, W_up} ([N/2, K] each, same ld),
+// C = {h [M, N/2], g|u [M, N]}; N = 2 I.
+int fill_args(GemmArgs& a, const pt_gemm_problem& q, int epilogue) {
+  const int nb = q.nb, nc = q.nc;
+  const int64_t M = q.M, N = q.N, K = q.K;
+  const bool fwd = epilogue == EPI_SWIGLU_FWD;
+  if (!q.A || nb < 1 || nb > 4 || nc < 1 || nc > 4 || M <= 0 || N <= 0 || K <= 0) return PT_EINVAL;
+  if (epilogue == EPI_BF16_RES && (!q.residual || nc != 1 || !pt_aligned16(q.residual) || (q.ldr & 7)))
+    return PT_EINVAL;
+  if (fwd) {
+    if (nb != 2 || q.b_seg_dim != 0 || nc != 2 || (N & 1) || q.ldb[0] != q.ldb[1]) return PT_EINVAL;
+    if (q.b_bounds[0] != 0 || q.b_bounds[1] != N / 2 || q.b_bounds[2] != N) return PT_EINVAL;
   }
-  gemm_8ph_dual_kernel<AK0, BKC0, EPI0, AK1, BKC1, EPI1><<<t0 + t1, 512, smem, stream>>>(g0, g1, m);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-template <bool AK, bool BKC, int EPI>
-int launch_4ph(GemmGroup g, hipStream_t stream) {
-  const int tiles = group_tiles(g, 256, 128);
-  constexpr int smem_main = 9 * 128 * BK * 2;
-  constexpr int smem_epi = 8 * 64 * (64 * 2 + 16) + (EPI == EPI_CE_STATS ? 8 * 64 * 8 : 0);
-  constexpr int smem = smem_main > smem_epi ? smem_main : smem_epi;
-  static_assert(smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_4ph_kernel<AK, BKC, EPI>, smem);
-    attr_set = true;
+  if (epilogue == EPI_SWIGLU_BWD &&
+      (!q.residual || nc != 1 || !pt_aligned16(q.residual) || (q.ldr & 7) || (q.ldc[0] & 7)))
+    return PT_EINVAL;
+  if (!fwd) {   // (the paired projection answers K % BK with PT_EALIGN, below)
+    if (K % BK) return PT_EUNSUPPORTED;
+    if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return PT_EUNSUPPORTED;
   }
-  gemm_4ph_kernel<AK, BKC, EPI><<<tiles, 512, smem, stream>>>(g);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-template <bool AK, bool BKC, int EPI>
-int launch_kh(GemmGroup g, hipStream_t stream) {
-  static_assert(EPI != EPI_CE_STATS && EPI != EPI_SWIGLU_FWD && EPI != EPI_SWIGLU_BWD, "tile 14 epilogues");
-  const int tiles = group_tiles(g, 256, 128);
-  constexpr int smem = 9 * 128 * BK * 2;  // 144 KiB: the ring; the half swap (128 KiB) and staging fit
-  static_assert(8 * 16 * 64 * 16 <= smem && 8 * 64 * (64 * 2 + 16) <= smem && smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_kh_kernel<AK, BKC, EPI>, smem);
-    attr_set = true;
+  a = GemmArgs{};
+  a.A = (const uint16_t*)q.A;
+  a.lda = q.lda;
+  a.nbseg = nb;
+  a.bdim = q.b_seg_dim;
+  const int64_t bfull = q.b_seg_dim ? K : N;
+  for (int i = 0; i < nb; ++i) {
+    if (!q.B[i] || !pt_aligned16(q.B[i]) || (q.ldb[i] & 7)) return PT_EALIGN;
+    a.B[i] = (const uint16_t*)q.B[i];
+    a.ldb[i] = q.ldb[i];
   }
-  gemm_kh_kernel<AK, BKC, EPI><<<tiles, 512, smem, stream>>>(g);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-template <bool AK, bool BKC, int EPI>
-int launch_hq(GemmGroup g, hipStream_t stream) {
-  static_assert(EPI != EPI_CE_STATS && EPI != EPI_SWIGLU_FWD && EPI != EPI_SWIGLU_BWD && EPI != EPI_ROPE,
-                "tile 15 epilogues");
-  const int tiles = group_tiles(g, 128, 128);
-  constexpr int smem = 4 * 2 * 128 * BK * 2;  // 128 KiB: the ring; the half swap (64 KiB) and staging fit
-  static_assert(8 * 8 * 64 * 16 <= smem && 8 * 32 * (64 * 2 + 16) <= smem && smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_hq_kernel<AK, BKC, EPI>, smem);
-    attr_set = true;
+  for (int i = 0; i <= nb; ++i) a.bseg[i] = q.b_bounds[i];
+  if (a.bseg[0] != 0 || a.bseg[nb] != bfull) return PT_EINVAL;
+  a.ncseg = fwd ? 1 : nc;   // the paired projection's two outputs are not row segments
+  for (int i = 0; i < nc; ++i) {
+    if (!q.C[i] || !pt_aligned16(q.C[i]) || (fwd && (q.ldc[i] & 7))) return PT_EALIGN;
+    a.C[i] = q.C[i];
+    a.ldc[i] = q.ldc[i];
   }
-  gemm_hq_kernel<AK, BKC, EPI><<<tiles, 512, smem, stream>>>(g);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-// tile ids: 2 = simple 128x128, 3 = simple 64x64 (the TP shards' few-tile problems),
-//           12 = 8-phase 256x256 (two half-image wave groups, one wait per K-tile)
-//           13 = 4-phase 256x128 (three K-tiles resident)
-//           14 = 256x128 with the K-tile's two k-substeps over two wave groups (128 x 64 wave tiles)
-//           15 = 128x128 with the K-tile's two k-substeps over two wave groups (64 x 64 wave tiles,
-//                a 4-deep ring): the TP shards' few-tile problems
-//           (ids 4, 5, 8, 9 -- the simple 256x256 / 256x128 kernels and their two-substep forms --
-//           were never picked once the phased kernels existed, and the 256x256 ones spilled: dropped
-//           from the library in round 4; ids 0, 1, 6, 7, 10, 11 were pipelining experiments, measured slower and retired; so
-//           was round 2's 14: the 8-phase tile with ONE barrier per K-tile and free-running
-//           phases, 3-13 % slower on every layer shape -- the per-phase ping-pong pays for its
-//           barriers)
-constexpr int kNumTiles = 16;
-const int kTileBM[kNumTiles] = {0, 0, 128, 64, 0, 0, 0, 0, 0, 0, 0, 0, 256, 256, 256, 128};
-const int kTileBN[kNumTiles] = {0, 0, 128, 64, 0, 0, 0, 0, 0, 0, 0, 0, 256, 128, 128, 128};
-
-template <bool AK, bool BKC, int EPI>
-int launch_layout(const GemmGroup& a, int tile, hipStream_t s) {
-  if constexpr (!AK && BKC) {  // A M-contiguous with B K-contiguous: no layer GEMM takes this layout,
-    switch (tile) {            // so only the simple tiles are built for it (pick_group_tile knows)
-      case 2: return launch_t<128, 128, 2, 2, AK, BKC, EPI>(a, s);
-      case 3: return launch_t<64, 64, 2, 2, AK, BKC, EPI>(a, s);
-      default: return PT_EUNSUPPORTED;
-    }
-  } else {
-    switch (tile) {
-      case 12: return launch_8ph<AK, BKC, EPI>(a, s);
-      case 13: return launch_4ph<AK, BKC, EPI>(a, s);
-      case 14: return launch_kh<AK, BKC, EPI>(a, s);
-      case 15: return launch_hq<AK, BKC, EPI>(a, s);
-      case 2: return launch_t<128, 128, 2, 2, AK, BKC, EPI>(a, s);
-      case 3: return launch_t<64, 64, 2, 2, AK, BKC, EPI>(a, s);
-      default: return PT_EUNSUPPORTED;
-    }
+  for (int i = 0; i <= a.ncseg; ++i) a.cseg[i] = fwd ? (i == 0 ? 0 : M) : q.c_bounds[i];
+  if (a.cseg[0] != 0 || a.cseg[a.ncseg] != M) return PT_EINVAL;
+  for (int i = a.ncseg + 1; i < 5; ++i) a.cseg[i] = M;
+  for (int i = nb + 1; i < 5; ++i) a.bseg[i] = bfull;
+  if (!pt_aligned16(q.A) || (q.lda & 7) || (fwd && K % BK)) return PT_EALIGN;
+  a.M = (int)M;
+  a.N = (int)(fwd ? N / 2 : N);  // paired: h columns; the tile grid is 256 x 128 of h
+  a.K = (int)K;
+  if (!fwd) {
+    a.R = (const uint16_t*)q.residual;
+    a.ldr = q.ldr;
   }
-}
-
-template <int EPI>
-int launch_epi(const GemmGroup& a, int a_kcontig, int b_kcontig, int tile, hipStream_t s) {
-  if (a_kcontig && b_kcontig) return launch_layout<true, true, EPI>(a, tile, s);
-  if (a_kcontig && !b_kcontig) return launch_layout<true, false, EPI>(a, tile, s);
-  if (!a_kcontig && !b_kcontig) return launch_layout<false, false, EPI>(a, tile, s);
-  return launch_layout<false, true, EPI>(a, tile, s);
-}
-
-}  // namespace
-
-namespace {
-
-// split-K fields of a grouped problem: ksplit slices of K / ksplit (a multiple of BK) written as f32
-// partials kpart_stride elements apart (EPI_F32 only).
-int fill_split(GemmArgs& a, const pt_gemm_problem& q, int epilogue) {
-  a.A2 = nullptr;
+  if (q.b_seg_dim == 1)  // K-segment boundaries must be multiples of BK: a K-tile never straddles one
+    for (int i = 0; i <= nb; ++i)
+      if (a.bseg[i] % BK) return PT_EUNSUPPORTED;
   a.ak2 = INT32_MAX;
   if (q.A2) {   // A K-segmented at a_k2 (a BK multiple inside K; A2 aligned like A)
     if (q.a_k2 <= 0 || q.a_k2 >= a.K || q.a_k2 % BK) return PT_EINVAL;
@@ -1747,98 +1639,50 @@ int fill_split(GemmArgs& a, const pt_gemm_problem& q, int epilogue) {
     a.A2 = (const uint16_t*)q.A2;
     a.ak2 = (int)q.a_k2;
   }
+  // split-K: ksplit slices of K / ksplit (a multiple of BK) written as f32 partials kpart_stride
+  // elements apart (EPI_F32 only)
   a.ksplit = q.ksplit > 1 ? q.ksplit : 1;
   a.kpart_stride = q.kpart_stride;
   if (a.ksplit == 1) return PT_OK;
   if (epilogue != EPI_F32 || q.kpart_stride <= 0 || a.ksplit > 64) return PT_EINVAL;
   if (a.K % (a.ksplit * BK)) return PT_EUNSUPPORTED;
-  if (a.bdim == 1)  // a K-tile never straddles a K-segment boundary (segments are BK multiples)
-    for (int i = 0; i <= a.nbseg; ++i)
-      if (a.bseg[i] % BK) return PT_EUNSUPPORTED;
   return PT_OK;
 }
 
-// Validate one problem and fill its kernel arguments.  Returns PT_OK or a PT_E* code.
-int fill_args(GemmArgs& a, const void* A, int64_t lda, const void* const* B, const int64_t* ldb,
-              const int64_t* b_bounds, int nb, int b_seg_dim, void* const* C, const int64_t* ldc,
-              const int64_t* c_bounds, int nc, int64_t M, int64_t N, int64_t K, int epilogue, const void* residual,
-              int64_t ldr) {
-  if (!A || !B || !C || nb < 1 || nb > 4 || nc < 1 || nc > 4 || M <= 0 || N <= 0 || K <= 0) return PT_EINVAL;
-  if (epilogue == EPI_BF16_RES && (!residual || nc != 1 || !pt_aligned16(residual) || (ldr & 7))) return PT_EINVAL;
-  if (epilogue == EPI_SWIGLU_FWD) {
-    // B = {W_gate, W_up} ([N/2, K] each, same ld), C = {h [M, N/2], g|u [M, N]}; N = 2 I
-    if (nb != 2 || b_seg_dim != 0 || nc != 2 || (N & 1) || ldb[0] != ldb[1]) return PT_EINVAL;
-    if (b_bounds && (b_bounds[0] != 0 || b_bounds[1] != N / 2 || b_bounds[2] != N)) return PT_EINVAL;
-    a = GemmArgs{};
-    a.A = (const uint16_t*)A;
-    a.lda = lda;
-    a.nbseg = 2;
-    for (int i = 0; i < 2; ++i) {
-      if (!B[i] || !pt_aligned16(B[i]) || (ldb[i] & 7) || !C[i] || !pt_aligned16(C[i]) || (ldc[i] & 7))
-        return PT_EALIGN;
-      a.B[i] = (const uint16_t*)B[i];
-      a.ldb[i] = ldb[i];
-      a.C[i] = C[i];
-      a.ldc[i] = ldc[i];
-    }
-    a.bseg[1] = N / 2;
-    for (int i = 2; i < 5; ++i) a.bseg[i] = N;
-    a.ncseg = 1;
-    for (int i = 1; i < 5; ++i) a.cseg[i] = M;
-    if (!pt_aligned16(A) || (lda & 7) || K % BK) return PT_EALIGN;
-    a.M = (int)M;
-    a.N = (int)(N / 2);  // h columns; the tile grid is 256 x 128 of h
-    a.K = (int)K;
-    return PT_OK;
-  }
-  if (epilogue == EPI_SWIGLU_BWD && (!residual || nc != 1 || !pt_aligned16(residual) || (ldr & 7) || (ldc[0] & 7)))
-    return PT_EINVAL;
-  if (K % BK) return PT_EUNSUPPORTED;
-  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return PT_EUNSUPPORTED;
-  a = GemmArgs{};
-  a.A = (const uint16_t*)A;
-  a.lda = lda;
-  a.nbseg = nb;
-  a.bdim = b_seg_dim;
-  for (int i = 0; i < nb; ++i) {
-    if (!B[i] || !pt_aligned16(B[i]) || (ldb[i] & 7)) return PT_EALIGN;
-    a.B[i] = (const uint16_t*)B[i];
-    a.ldb[i] = ldb[i];
-  }
-  for (int i = 0; i <= nb; ++i) a.bseg[i] = b_bounds ? b_bounds[i] : (i == 0 ? 0 : (b_seg_dim ? K : N));
-  if (a.bseg[0] != 0 || a.bseg[nb] != (b_seg_dim ? K : N)) return PT_EINVAL;
-  a.ncseg = nc;
-  for (int i = 0; i < nc; ++i) {
-    if (!C[i] || !pt_aligned16(C[i])) return PT_EALIGN;
-    a.C[i] = C[i];
-    a.ldc[i] = ldc[i];
-  }
-  for (int i = 0; i <= nc; ++i) a.cseg[i] = c_bounds ? c_bounds[i] : (i == 0 ? 0 : M);
-  if (a.cseg[0] != 0 || a.cseg[nc] != M) return PT_EINVAL;
-  for (int i = nc + 1; i < 5; ++i) a.cseg[i] = M;
-  for (int i = nb + 1; i < 5; ++i) a.bseg[i] = b_seg_dim ? K : N;
-  if (!pt_aligned16(A) || (lda & 7)) return PT_EALIGN;
-  a.M = (int)M;
-  a.N = (int)N;
-  a.K = (int)K;
-  a.R = (const uint16_t*)residual;
-  a.ldr = ldr;
-  if (b_seg_dim == 1)  // K-segment boundaries must be multiples of BK
-    for (int i = 0; i <= nb; ++i)
-      if (a.bseg[i] % BK) return PT_EUNSUPPORTED;
-  return PT_OK;
+// The pointer-array form of the operands (pt_gemm, pt_gemm_rope) into a problem: absent boundaries
+// are the unsegmented ones.  False: counts fill_args refuses (PT_EINVAL), nothing was copied.
+bool problem_b(pt_gemm_problem& q, const void* const* B, const int64_t* ldb, const int64_t* bounds, int nb,
+               int seg_dim) {
+  if (!B || nb < 1 || nb > 4) return false;
+  q.nb = nb;
+  q.b_seg_dim = seg_dim;
+  for (int i = 0; i < nb; ++i) q.B[i] = B[i], q.ldb[i] = ldb[i];
+  for (int i = 0; i <= nb; ++i) q.b_bounds[i] = bounds ? bounds[i] : (i == 0 ? 0 : (seg_dim ? q.K : q.N));
+  return true;
+}
+bool problem_c(pt_gemm_problem& q, void* const* C, const int64_t* ldc, const int64_t* bounds, int nc) {
+  if (!C || nc < 1 || nc > 4) return false;
+  q.nc = nc;
+  for (int i = 0; i < nc; ++i) q.C[i] = C[i], q.ldc[i] = ldc[i];
+  for (int i = 0; i <= nc; ++i) q.c_bounds[i] = bounds ? bounds[i] : (i == 0 ? 0 : q.M);
+  return true;
+}
+pt_gemm_problem problem_a(const void* A, int64_t lda, int64_t M, int64_t N, int64_t K) {
+  pt_gemm_problem q{};
+  q.A = A, q.lda = lda, q.M = M, q.N = N, q.K = K;
+  return q;
 }
 
 bool args_fit(const GemmArgs& a, int tile) {
-  if (tile < 0 || tile >= kNumTiles || kTileBM[tile] == 0) return false;
-  const int bm = kTileBM[tile], bn = kTileBN[tile];
-  if (a.M % bm || a.N % bn) return false;
+  const TileDesc* t = tile_desc(tile);
+  if (!t) return false;
+  if (a.M % t->bm || a.N % t->bn) return false;
   for (int i = 0; i <= a.ncseg; ++i)
-    if (a.cseg[i] % bm) return false;
+    if (a.cseg[i] % t->bm) return false;
   if (a.bdim == 0)
     for (int i = 0; i <= a.nbseg; ++i)
-      if (a.bseg[i] % bn) return false;
-  if (tile >= 12 && a.bdim == 1)  // the phased kernels keep one B ld per tile
+      if (a.bseg[i] % t->bn) return false;
+  if (t->phased && a.bdim == 1)
     for (int i = 1; i < a.nbseg; ++i)
       if (a.ldb[i] != a.ldb[0]) return false;
   return true;
@@ -1860,29 +1704,29 @@ int pick_group_tile(const GemmGroup& g, bool simple_only = false) {
   auto ntiles = [&](int t) {
     int64_t tiles = 0;
     for (int i = 0; i < g.nprob; ++i)
-      tiles += (int64_t)(g.p[i].M / kTileBM[t]) * (g.p[i].N / kTileBN[t]) * (g.p[i].ksplit > 1 ? g.p[i].ksplit : 1);
+      tiles += (int64_t)(g.p[i].M / tile_desc(t)->bm) * (g.p[i].N / tile_desc(t)->bn) *
+               (g.p[i].ksplit > 1 ? g.p[i].ksplit : 1);
     return tiles;
   };
   auto fill = [&](int t) {
     const int64_t tiles = ntiles(t);
     return (double)tiles / (double)(((tiles + 255) / 256) * 256);
   };
-  const bool f12 = !simple_only && fits(12), f13 = !simple_only && fits(13);
-  const int phased = f12 && (!f13 || fill(12) >= fill(13)) ? 12 : (f13 ? 13 : -1);
+  const bool f12 = !simple_only && fits(TILE_8PH), f13 = !simple_only && fits(TILE_4PH);
+  const int phased = f12 && (!f13 || fill(TILE_8PH) >= fill(TILE_4PH)) ? TILE_8PH : (f13 ? TILE_4PH : -1);
   if (phased >= 0 && ntiles(phased) >= 128) return phased;
-  const int cand[4] = {12, 13, 2, 3};
+  const int cand[4] = {TILE_8PH, TILE_4PH, TILE_S128, TILE_S64};
   const double rate[4] = {1.30, 1.20, 0.85, 0.45};
   int best = -1;
   double best_cost = 0.0;
   for (int i = simple_only ? 2 : 0; i < 4; ++i) {
     if (!fits(cand[i])) continue;
-    const double c = (double)((ntiles(cand[i]) + 255) / 256) * kTileBM[cand[i]] * kTileBN[cand[i]] / rate[i];
+    const TileDesc* t = tile_desc(cand[i]);
+    const double c = (double)((ntiles(cand[i]) + 255) / 256) * t->bm * t->bn / rate[i];
     if (best < 0 || c < best_cost) best = cand[i], best_cost = c;
   }
   return best;
 }
-
-int launch_swiglu(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int tile, hipStream_t stream);
 
 // variant "gemm_mix" = 0 turns the mixed-tile q|k|v launch off (A/B measurement only)
 bool mix_enabled() { return pt_variant(PT_VAR_GEMM_MIX) == 1; }
@@ -1903,32 +1747,35 @@ bool kh_enabled(const GemmGroup& g) {
 // q|k|v + RoPE as one mixed-tile launch: the rotated columns [0, rope_cols) in 256x256 tiles, the
 // rest (v) in 256x128 tiles.  PT_EUNSUPPORTED when the shape does not split that way (the caller
 // then launches one tile shape as before).
-int launch_mix_rope(const GemmArgs& a0, hipStream_t stream) {
-  const int ns = a0.rope_cols;
-  if (ns <= 0 || ns >= a0.N || ns % 256 || (a0.N - ns) % 128) return PT_EUNSUPPORTED;
-  if (!args_fit(a0, 12) || !args_fit(a0, 13)) return PT_EUNSUPPORTED;
+int launch_mix_rope(const GemmArgs& a, hipStream_t stream) {
+  constexpr TileDesc t8 = *tile_desc(TILE_8PH), t4 = *tile_desc(TILE_4PH);
+  const int ns = a.rope_cols;
+  if (ns <= 0 || ns >= a.N || ns % t8.bn || (a.N - ns) % t4.bn) return PT_EUNSUPPORTED;
+  if (!args_fit(a, TILE_8PH) || !args_fit(a, TILE_4PH)) return PT_EUNSUPPORTED;
   MixMap m{};
-  m.tiles_m = a0.M / 256;
-  m.tn0 = ns / 256;
-  m.tn1 = (a0.N - ns) / 128;
-  m.nsplit_t1 = ns / 128;
+  m.tiles_m = a.M / t8.bm;
+  m.tn0 = ns / t8.bn;
+  m.tn1 = (a.N - ns) / t4.bn;
+  m.nsplit_t1 = ns / t4.bn;
   const int t0 = m.tiles_m * m.tn0, t1 = m.tiles_m * m.tn1;
   // the two parts must each divide over the 8 XCDs; the 8-phase part at most one round: the gain is
   // the round quantization (SmolLM-1.7B: 3 rounds -> 2, +0.8 % step); Llama-2-7B's 512 + 512 tiles
   // (6 whole rounds either way) measured neutral, the CP=8 proxy's 4096 + 4096 within noise
   if (t0 % 8 || t1 % 8 || t0 > 256) return PT_EUNSUPPORTED;
   m.d = DualMap{t0 / 8, t1 / 8, 0};
-  GemmArgs a = a0;
-  constexpr int smem = 8 * 128 * (64 * 2 + 16);  // = the 4-phase main loop's 144 KiB
-  static_assert(smem >= 9 * 128 * BK * 2 && smem <= 160 * 1024, "LDS budget");
-  static bool attr_set = false;
-  if (!attr_set) {
-    set_smem_once(gemm_mix_kernel<true, true, EPI_ROPE>, smem);
-    attr_set = true;
+  return launch_kernel<gemm_mix_kernel<true, true, EPI_ROPE>, cmax(tile_smem(t8, EPI_ROPE), tile_smem(t4, EPI_ROPE))>(
+      t0 + t1, t8.threads, stream, a, m);
+}
+
+// the SwiGLU-fused projections: 8-phase kernel only
+int launch_swiglu(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int tile, hipStream_t stream) {
+  if (tile != -1 && tile != TILE_8PH) return PT_EUNSUPPORTED;
+  for (int i = 0; i < g.nprob; ++i) {
+    const GemmArgs& a = g.p[i];
+    if (a.M % 256 || a.N % (epilogue == EPI_SWIGLU_FWD ? 128 : 256)) return PT_EUNSUPPORTED;
+    if (epilogue == EPI_SWIGLU_BWD && (a.ncseg != 1 || a.bdim != 0 || a.nbseg != 1)) return PT_EUNSUPPORTED;
   }
-  gemm_mix_kernel<true, true, EPI_ROPE><<<t0 + t1, 512, smem, stream>>>(a, m);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  return dispatch(g, TILE_8PH, a_kcontig, b_kcontig, epilogue, stream);
 }
 
 int launch_group(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int tile, hipStream_t stream) {
@@ -1941,51 +1788,13 @@ int launch_group(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int t
     if (rc != PT_EUNSUPPORTED) return rc;
   }
   const bool auto_tile = tile < 0;
-  if (epilogue == EPI_ROPE && tile < 0) tile = args_fit(g.p[0], 13) ? 13 : 12;
+  if (epilogue == EPI_ROPE && tile < 0) tile = args_fit(g.p[0], TILE_4PH) ? TILE_4PH : TILE_8PH;
   if (tile < 0) tile = pick_group_tile(g, !a_kcontig && b_kcontig);
-  if (auto_tile && tile == 13 && kh_enabled(g) && epilogue != EPI_CE_STATS) tile = 14;
-  if (epilogue == EPI_ROPE) {
-    if (!a_kcontig || !b_kcontig) return PT_EUNSUPPORTED;
-    for (int i = 0; i < g.nprob; ++i)
-      if (!args_fit(g.p[i], tile)) return PT_EUNSUPPORTED;
-    if (tile == 12) return launch_8ph<true, true, EPI_ROPE>(g, stream);
-    if (tile == 13) return launch_4ph<true, true, EPI_ROPE>(g, stream);
-    if (tile == 14) return launch_kh<true, true, EPI_ROPE>(g, stream);
-    return PT_EUNSUPPORTED;
-  }
+  if (auto_tile && tile == TILE_4PH && kh_enabled(g) && epilogue != EPI_CE_STATS) tile = TILE_KH;
+  // A K-segmented (A2): the 8-phase kernel only; the RoPE projection has no such operand
   for (int i = 0; i < g.nprob; ++i)
-    if (!args_fit(g.p[i], tile) || (g.p[i].A2 && tile != 12)) return PT_EUNSUPPORTED;
-  switch (epilogue) {
-    case EPI_BF16: return launch_epi<EPI_BF16>(g, a_kcontig, b_kcontig, tile, stream);
-    case EPI_BF16_ACC: return launch_epi<EPI_BF16_ACC>(g, a_kcontig, b_kcontig, tile, stream);
-    case EPI_F32: return launch_epi<EPI_F32>(g, a_kcontig, b_kcontig, tile, stream);
-    case EPI_F32_ACC: return launch_epi<EPI_F32_ACC>(g, a_kcontig, b_kcontig, tile, stream);
-    case EPI_BF16_RES:  // forward projections only (weights K-contiguous)
-      if (!a_kcontig || !b_kcontig) return PT_EUNSUPPORTED;
-      return launch_layout<true, true, EPI_BF16_RES>(g, tile, stream);
-    case EPI_CE_STATS:  // the lm_head forward: the phased kernels (64-column wave tiles)
-      if (!a_kcontig || !b_kcontig) return PT_EUNSUPPORTED;
-      if (tile == 12) return launch_8ph<true, true, EPI_CE_STATS>(g, stream);
-      if (tile == 13) return launch_4ph<true, true, EPI_CE_STATS>(g, stream);
-      return PT_EUNSUPPORTED;
-    default: return PT_EINVAL;
-  }
-}
-
-// the SwiGLU-fused projections: 8-phase kernel only (tile 12)
-int launch_swiglu(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int tile, hipStream_t stream) {
-  if (tile != -1 && tile != 12) return PT_EUNSUPPORTED;
-  for (int i = 0; i < g.nprob; ++i) {
-    const GemmArgs& a = g.p[i];
-    if (a.M % 256 || a.N % (epilogue == EPI_SWIGLU_FWD ? 128 : 256)) return PT_EUNSUPPORTED;
-    if (epilogue == EPI_SWIGLU_BWD && (a.ncseg != 1 || a.bdim != 0 || a.nbseg != 1)) return PT_EUNSUPPORTED;
-  }
-  if (epilogue == EPI_SWIGLU_FWD) {
-    if (!a_kcontig || !b_kcontig) return PT_EUNSUPPORTED;
-    return launch_8ph<true, true, EPI_SWIGLU_FWD>(g, stream);
-  }
-  if (!a_kcontig || b_kcontig) return PT_EUNSUPPORTED;
-  return launch_8ph<true, false, EPI_SWIGLU_BWD>(g, stream);
+    if (!args_fit(g.p[i], tile) || (g.p[i].A2 && tile != TILE_8PH && epilogue != EPI_ROPE)) return PT_EUNSUPPORTED;
+  return dispatch(g, tile, a_kcontig, b_kcontig, epilogue, stream);
 }
 
 // group 0: dX (A = dY K-contiguous, B = W N-contiguous) with EPI_BF16 or EPI_SWIGLU_BWD;
@@ -2005,15 +1814,25 @@ int launch_dual(GemmGroup& g0, int ak0, int bk0, int e0, GemmGroup& g1, int ak1,
                 hipStream_t s) {
   if (!ak0 || bk0 || ak1 || bk1 || order < 0 || order > 2) return PT_EUNSUPPORTED;
   for (int i = 0; i < g0.nprob; ++i) {
-    if (!args_fit(g0.p[i], 12)) return PT_EUNSUPPORTED;
+    if (!args_fit(g0.p[i], TILE_8PH)) return PT_EUNSUPPORTED;
     if (e0 == EPI_SWIGLU_BWD && (g0.p[i].ncseg != 1 || g0.p[i].bdim != 0 || g0.p[i].nbseg != 1)) return PT_EUNSUPPORTED;
   }
   for (int i = 0; i < g1.nprob; ++i)
-    if (!args_fit(g1.p[i], 12)) return PT_EUNSUPPORTED;
+    if (!args_fit(g1.p[i], TILE_8PH)) return PT_EUNSUPPORTED;
   if (e0 == EPI_BF16) return launch_dual_e1<EPI_BF16>(g0, g1, e1, order, s);
   if (e0 == EPI_SWIGLU_BWD) return launch_dual_e1<EPI_SWIGLU_BWD>(g0, g1, e1, order, s);
   if (e0 == EPI_F32) return launch_dual_e1<EPI_F32>(g0, g1, e1, order, s);  // split-K dX halves
   return PT_EUNSUPPORTED;
+}
+
+// fill every problem of a group; PT_OK or the first problem's refusal
+int fill_group(GemmGroup& g, const pt_gemm_problem* probs, int nprob, int epilogue) {
+  g.nprob = nprob;
+  for (int i = 0; i < nprob; ++i) {
+    const int rc = fill_args(g.p[i], probs[i], epilogue);
+    if (rc) return rc;
+  }
+  return PT_OK;
 }
 
 }  // namespace
@@ -2029,10 +1848,13 @@ int pt_gemm(const void* A, int64_t lda, int a_kcontig, const void* const* B, con
             const int64_t* b_bounds, int nb, int b_kcontig, int b_seg_dim, void* const* C, const int64_t* ldc,
             const int64_t* c_bounds, int nc, int64_t M, int64_t N, int64_t K, int epilogue,
             const void* residual, int64_t ldr, int tile, hipStream_t stream) {
+  pt_gemm_problem q = problem_a(A, lda, M, N, K);
+  if (!problem_b(q, B, ldb, b_bounds, nb, b_seg_dim) || !problem_c(q, C, ldc, c_bounds, nc)) return PT_EINVAL;
+  if (!b_bounds && epilogue == EPI_SWIGLU_FWD) q.b_bounds[1] = N / 2;   // gate | up: the paired halves
+  q.residual = residual;
+  q.ldr = ldr;
   GemmGroup g{};
-  g.nprob = 1;
-  const int rc = fill_args(g.p[0], A, lda, B, ldb, b_bounds, nb, b_seg_dim, C, ldc, c_bounds, nc, M, N, K, epilogue,
-                           residual, ldr);
+  const int rc = fill_group(g, &q, 1, epilogue);
   if (rc) return rc;
   return launch_group(g, a_kcontig, b_kcontig, epilogue, tile, stream);
 }
@@ -2042,14 +1864,8 @@ int pt_gemm_grouped(const pt_gemm_problem* probs, int nprob, int a_kcontig, int 
                     hipStream_t stream) {
   if (!probs || nprob < 1 || nprob > kMaxProb) return PT_EINVAL;
   GemmGroup g{};
-  g.nprob = nprob;
-  for (int i = 0; i < nprob; ++i) {
-    const pt_gemm_problem& q = probs[i];
-    int rc = fill_args(g.p[i], q.A, q.lda, q.B, q.ldb, q.b_bounds, q.nb, q.b_seg_dim, q.C, q.ldc, q.c_bounds,
-                       q.nc, q.M, q.N, q.K, epilogue, q.residual, q.ldr);
-    if (!rc) rc = fill_split(g.p[i], q, epilogue);
-    if (rc) return rc;
-  }
+  const int rc = fill_group(g, probs, nprob, epilogue);
+  if (rc) return rc;
   return launch_group(g, a_kcontig, b_kcontig, epilogue, tile, stream);
 }
 
@@ -2101,11 +1917,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs r) 
       const float u[4] = {lo_bf(uw.x), hi_bf(uw.x), lo_bf(uw.y), hi_bf(uw.y)};
       float og[4], ou[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = round_bf(v[e]), sg = silu_sig(g[e]);
-        ou[e] = d * round_bf(g[e] * sg);
-        og[e] = round_bf(d * u[e]) * (sg * (1.0f + g[e] * (1.0f - sg)));
-      }
+      for (int e = 0; e < 4; ++e) swiglu_bwd_elem(round_bf(v[e]), g[e], u[e], og[e], ou[e]);
       uint16_t* o = (uint16_t*)r.C[0] + off;
       *(uint2*)o = make_uint2(pack_bf2(og[0], og[1]), pack_bf2(og[2], og[3]));
       *(uint2*)(o + r.N) = make_uint2(pack_bf2(ou[0], ou[1]), pack_bf2(ou[2], ou[3]));
@@ -2219,18 +2031,9 @@ int pt_gemm_dual(const pt_gemm_problem* p0, int n0, int a_kcontig0, int b_kconti
                  hipStream_t stream) {
   if (!p0 || !p1 || n0 < 1 || n0 > kMaxProb || n1 < 1 || n1 > kMaxProb) return PT_EINVAL;
   GemmGroup g[2]{};
-  const pt_gemm_problem* ps[2] = {p0, p1};
-  const int ns[2] = {n0, n1}, es[2] = {epilogue0, epilogue1};
-  for (int k = 0; k < 2; ++k) {
-    g[k].nprob = ns[k];
-    for (int i = 0; i < ns[k]; ++i) {
-      const pt_gemm_problem& q = ps[k][i];
-      int rc = fill_args(g[k].p[i], q.A, q.lda, q.B, q.ldb, q.b_bounds, q.nb, q.b_seg_dim, q.C, q.ldc,
-                         q.c_bounds, q.nc, q.M, q.N, q.K, es[k], q.residual, q.ldr);
-      if (!rc) rc = fill_split(g[k].p[i], q, es[k]);
-      if (rc) return rc;
-    }
-  }
+  int rc = fill_group(g[0], p0, n0, epilogue0);
+  if (!rc) rc = fill_group(g[1], p1, n1, epilogue1);
+  if (rc) return rc;
   return launch_dual(g[0], a_kcontig0, b_kcontig0, epilogue0, g[1], a_kcontig1, b_kcontig1, epilogue1, order,
                      stream);
 }
@@ -2243,11 +2046,10 @@ int pt_gemm_rope(const void* A, int64_t lda, const void* const* B, const int64_t
                  hipStream_t stream) {
   if (!cos_table || !sin_table || seq_len <= 0 || rot_cols < 0 || rot_cols > N) return PT_EINVAL;
   if (head_dim != 64 || rot_cols % 64) return PT_EUNSUPPORTED;
+  pt_gemm_problem q = problem_a(A, lda, M, N, K);
+  if (!problem_b(q, B, ldb, b_bounds, nb, 0) || !problem_c(q, &C, &ldc, nullptr, 1)) return PT_EINVAL;
   GemmGroup g{};
-  g.nprob = 1;
-  void* const Cs[1] = {C};
-  const int64_t ldcs[1] = {ldc};
-  const int rc = fill_args(g.p[0], A, lda, B, ldb, b_bounds, nb, 0, Cs, ldcs, nullptr, 1, M, N, K, EPI_ROPE, nullptr, 0);
+  const int rc = fill_group(g, &q, 1, EPI_ROPE);
   if (rc) return rc;
   GemmArgs& a = g.p[0];
   a.rope_cos = (const uint16_t*)cos_table;
@@ -2266,15 +2068,12 @@ int pt_gemm_ce_stats(const void* A, int64_t lda, const void* W, int64_t ldw, voi
                      int64_t block, int64_t M, int64_t N, int64_t K, hipStream_t stream) {
   if (!stats || !pt_aligned16(stats)) return PT_EINVAL;
   if (block != 256 && block != 128) return PT_EUNSUPPORTED;
-  const int tile = block == 256 ? 12 : 13;
+  const int tile = block == 256 ? TILE_8PH : TILE_4PH;
+  pt_gemm_problem q = problem_a(A, lda, M, N, K);
+  problem_b(q, &W, &ldw, nullptr, 1, 0);
+  problem_c(q, &C, &ldc, nullptr, 1);
   GemmGroup g{};
-  g.nprob = 1;
-  const void* const Bs[1] = {W};
-  const int64_t ldbs[1] = {ldw};
-  void* const Cs[1] = {C};
-  const int64_t ldcs[1] = {ldc};
-  const int rc = fill_args(g.p[0], A, lda, Bs, ldbs, nullptr, 1, 0, Cs, ldcs, nullptr, 1, M, N, K, EPI_CE_STATS,
-                           nullptr, 0);
+  const int rc = fill_group(g, &q, 1, EPI_CE_STATS);
   if (rc) return rc;
   if (!args_fit(g.p[0], tile)) return PT_EUNSUPPORTED;
   if (ldc & 7) return PT_EALIGN;

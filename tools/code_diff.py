@@ -1,6 +1,6 @@
 """Compare the compiled gfx950 code of two builds, kernel by kernel.
 
-    python tools/code_diff.py OBJDIR_A OBJDIR_B [--source attention]
+    python tools/code_diff.py OBJDIR_A OBJDIR_B [--source attention] [--rename PATTERN=REPL ...]
 
 OBJDIR_*: the object directories of two builds (picotron_amd/lib/obj of each tree).  For every
 kernel symbol of every object (or of --source NAME's object only) the disassembly of the unbundled
@@ -12,7 +12,10 @@ per kernel:
     reordered   the same multiset of instruction lines in another order; the moved lines follow
     different   anything else; the unified diff follows
 
-A kernel whose parameter list changed (another mangled name) is paired with its namesake.  Exit 1 if
+A kernel whose parameter list changed (another mangled name) is paired with its namesake.  A kernel
+whose template arguments changed needs --rename: PATTERN (a Python regular expression) is replaced by
+REPL in side A's symbols before pairing, e.g. --rename '(gemm_kernelI.*)Li0E(EEv)=\\1\\2' for a
+dropped last argument.  Exit 1 if
 any kernel is different, missing on one side, or has other metadata.  A text comparison only: what
 an instruction does is not looked at."""
 import argparse
@@ -121,7 +124,10 @@ def main(argv):
     ap.add_argument("objdir_a")
     ap.add_argument("objdir_b")
     ap.add_argument("--source", help="compare only this source's object (e.g. attention)")
+    ap.add_argument("--rename", action="append", default=[], metavar="PATTERN=REPL",
+                    help="re.sub applied to side A's symbols before pairing (repeatable)")
     ns = ap.parse_args(argv)
+    renames = [r.split("=", 1) for r in ns.rename]
     dir_a, dir_b, source = ns.objdir_a, ns.objdir_b, ns.source
     objs = sorted({os.path.basename(p) for d in (dir_a, dir_b) for p in glob.glob(os.path.join(d, "*.o"))})
     if source:
@@ -135,6 +141,8 @@ def main(argv):
             ok = False
             continue
         a, b = listing(pa), listing(pb)
+        for pat, repl in renames:
+            a = {re.sub(pat, repl, n): k for n, k in a.items()}
         if not a and not b:
             print("  (no device code)")
         for label, na, nb in pair_up(a, b):
