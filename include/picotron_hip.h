@@ -184,6 +184,8 @@ int pt_adamw_step_multi(const void* tensors, const int64_t* chunk_start, int nte
  * C[M,N] (op)= A[M,K] B[K,N].  a_kcontig: A stored [M,K] (else [K,M]); b_kcontig: B stored
  * [N,K] (weights; else [K,N]).  B may be split into nb pointer segments along N (b_seg_dim 0)
  * or K (1), C into nc segments along M; *_bounds hold n+1 boundaries (NULL = one segment).
+ * N-segments and C segments have their own leading dimensions; K-segments share one ldb
+ * (PT_EUNSUPPORTED otherwise: a tile's B image is stepped with one stride through all of K).
  * epilogue 0: C bf16 = acc, 1: C bf16 += acc, 2: C f32 = acc, 3: C f32 += acc,
  * 4: C bf16 = residual + acc (residual [M, N] bf16, leading dim ldr; the residual add of
  * model.py:207-208 fused into the producing projection).  tile -1 = auto. */

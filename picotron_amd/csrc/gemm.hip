@@ -1443,22 +1443,21 @@ struct TileDesc {
   int id, bm, bn, threads;
   int smem_main, smem_epi, smem_ce;
   unsigned epis, layouts;
-  bool phased;   // a phased kernel keeps one B ld per tile (K-segments share it)
 };
 constexpr int kWaveStage64 = 64 * 2 + 16;   // bytes per staged row of a 64-column wave tile
 constexpr int cmax(int a, int b) { return a > b ? a : b; }
 constexpr TileDesc kTiles[] = {
-    {TILE_S128, 128, 128, 256, 2 * (128 + 128) * BK * 2, 4 * 64 * kWaveStage64, 0, kEpiPlain, kAllLayouts, false},
-    {TILE_S64, 64, 64, 256, 2 * (64 + 64) * BK * 2, 4 * 32 * (32 * 2 + 16), 0, kEpiPlain, kAllLayouts, false},
+    {TILE_S128, 128, 128, 256, 2 * (128 + 128) * BK * 2, 4 * 64 * kWaveStage64, 0, kEpiPlain, kAllLayouts},
+    {TILE_S64, 64, 64, 256, 2 * (64 + 64) * BK * 2, 4 * 32 * (32 * 2 + 16), 0, kEpiPlain, kAllLayouts},
     {TILE_8PH, 256, 256, 512, 2 * 4 * 128 * BK * 2, 8 * 128 * kWaveStage64, 8 * 128 * 8,
      kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_SWIGLU_FWD) | epi_bit(EPI_SWIGLU_BWD),
-     kPhasedLayouts, true},
+     kPhasedLayouts},
     {TILE_4PH, 256, 128, 512, 3 * 3 * 128 * BK * 2, 8 * 64 * kWaveStage64, 8 * 64 * 8,
-     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS), kPhasedLayouts, true},
+     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS), kPhasedLayouts},
     {TILE_KH, 256, 128, 512, 3 * 3 * 128 * BK * 2, cmax(8 * 16 * 64 * 16, 8 * 64 * kWaveStage64), 0,
-     kEpiPlain | epi_bit(EPI_ROPE), kPhasedLayouts, true},
+     kEpiPlain | epi_bit(EPI_ROPE), kPhasedLayouts},
     {TILE_HQ, 128, 128, 512, 4 * 2 * 128 * BK * 2, cmax(8 * 8 * 64 * 16, 8 * 32 * kWaveStage64), 0, kEpiPlain,
-     kPhasedLayouts, true},
+     kPhasedLayouts},
 };
 constexpr int kNumTileDescs = sizeof(kTiles) / sizeof(kTiles[0]);
 
@@ -1682,7 +1681,9 @@ bool args_fit(const GemmArgs& a, int tile) {
   if (a.bdim == 0)
     for (int i = 0; i <= a.nbseg; ++i)
       if (a.bseg[i] % t->bn) return false;
-  if (t->phased && a.bdim == 1)
+  // every kernel steps a tile's B image with ONE leading dimension (BImg folds the segment bases into
+  // pointer deltas before the K loop), so K-segments share it -- on the simple tiles too
+  if (a.bdim == 1)
     for (int i = 1; i < a.nbseg; ++i)
       if (a.ldb[i] != a.ldb[0]) return false;
   return true;

@@ -337,6 +337,22 @@ REFUSALS = [
 ]
 
 
+# Refusals the host code gained after the golden file was written, pinned beside it in
+# tests/golden/gemm_host_added.json (gemm_host.json is not regenerated; no code in it changed).
+#   * K-segments of B with different leading dimensions on the simple tiles 2 / 3 (and the auto pick
+#     that would land on them): every kernel steps a tile's B image with one leading dimension since
+#     the segment bases moved into registers (BImg), but only the phased tiles refused such a call;
+#     the simple kernels launched and read the later segments at the first one's stride, outside them.
+#     Found by tests/test_gemm_conformance_gpu.py's K-segment test while reading bimg_ptr for bounds.
+ADDED_GOLDEN = os.path.join(ROOT, "tests", "golden", "gemm_host_added.json")
+ADDED_REFUSALS = [
+    (G, "tile2_kseg_ldb", dict(KSEG, ldb=[256, 264], tile=2)),             # launch_group: args_fit (one ld over K-segments)
+    (G, "tile3_kseg_ldb", dict(KSEG, ldb=[256, 264], tile=3)),             # launch_group: args_fit (one ld over K-segments)
+    (G, "auto_kseg_ldb", dict(KSEG, ldb=[256, 264])),                      # launch_group: args_fit (auto pick: -1)
+    (GG, "second_kseg_ldb_tile3", dict(probs=[{}, dict(KSEG, ldb=[256, 264])], tile=3)),  # launch_group: args_fit
+]
+
+
 def library():
     from picotron_amd import _C
     if not os.path.exists(_C.LIB_PATH):
@@ -494,6 +510,16 @@ def test_refusals_match_golden():
     wrong = {k: (got[k], want[k]) for k in want if got[k] != want[k]}
     assert not wrong, wrong
     assert all(rc < 0 for rc in got.values())
+
+
+def test_added_refusals_match_their_golden():
+    lib = library()
+    want = json.load(open(ADDED_GOLDEN))["refusals"]
+    keep = []
+    with variants_default(lib):
+        got = {f"{e}/{c}": call(lib, e, over, keep) for e, c, over in ADDED_REFUSALS}
+    assert got == want and all(rc < 0 for rc in got.values())
+    assert not set(got) & set(json.load(open(GOLDEN))["refusals"])
 
 
 if __name__ == "__main__":
