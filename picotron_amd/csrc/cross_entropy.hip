@@ -117,6 +117,7 @@ __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __re
     float cm = m;
 #pragma unroll
     for (int j = 0; j < 8; ++j) cm = fmaxf(cm, f[j]);
+    if (cm == -INFINITY) continue;  // nothing finite seen yet: exp(-inf - -inf) would be NaN
     s *= __expf(m - cm);
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += __expf(f[j] - cm);
@@ -491,6 +492,7 @@ extern "C" int pt_cross_entropy_fwd_bwd(const void* logits, int64_t logits_strid
   if (!logits || !targets || !row_loss || rows <= 0 || vocab <= 0) return PT_EINVAL;
   if ((vocab & 7) || (logits_stride & 7) || (dlogits && (dlogits_stride & 7))) return PT_EALIGN;
   if (!pt_aligned16(logits) || (dlogits && !pt_aligned16(dlogits))) return PT_EALIGN;
+  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
   const auto* L = (const uint16_t*)logits;
   auto* D = (uint16_t*)dlogits;
   const int nc = (int)((vocab / 8 + kThreads - 1) / kThreads);
