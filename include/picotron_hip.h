@@ -28,6 +28,7 @@ typedef struct ihipStream_t* hipStream_t;
  * shapes) set a bit here instead of trapping -- the analogue of torch's device-side assert.  The
  * host reads it when it synchronises anyway (picotron_amd.kernels.device_status). */
 #define PT_STATUS_BAD_TARGET 1
+#define PT_STATUS_NONFINITE_GRAD 2   /* the global gradient norm is inf / NaN: the step was skipped */
 
 /* ---- RMSNorm ------------------------------------------------------------------------------
  * replaces picotron/model.py:51-65 (TritonRMSNorm -> flash-attn layer_norm_fn, mode 0) and
@@ -177,6 +178,46 @@ typedef struct {
 int pt_adamw_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
                         float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
                         hipStream_t stream);
+
+/* ---- global gradient-norm clipping, fused into the AdamW step ------------------------------
+ * replaces torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) in front of the optimizer
+ * step (what a Llama training recipe adds in front of train.py:235): the L2 norm over every gradient
+ * in f32, and the scaling by clip_coef = min(1, max_norm / (total_norm + 1e-6)) applied where the
+ * AdamW kernel loads the gradient -- the clipped gradients are never written, the coefficient
+ * never leaves the device.
+ *
+ * Sum of squares: sq[0] = (accumulate ? sq[0] : 0) + weight * sum g^2, over the grad field of the
+ * pt_adam_tensor list pt_adamw_step_multi takes (same table, same chunk_start), or over one tensor
+ * (dtype 0 bf16 at any alignment, 1 f32).  Two launches: one f32 partial per workgroup into
+ * `workspace` (pt_grad_sq_workspace() floats, caller-owned, reusable by the next call on the
+ * stream), then one workgroup sums them in a fixed order -- no float atomics, bit-reproducible.
+ * Several lists and tensors accumulate into one scalar in stream order; `weight` scales a list's
+ * share (1 / tp for gradients replicated over a tensor-parallel group, so an all-reduce of sq over
+ * the group counts them once). */
+int pt_grad_sq_workspace(void);
+int pt_grad_sq_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                     float weight, int accumulate, float* workspace, float* sq, hipStream_t stream);
+int pt_grad_sq(const void* grad, int64_t n, int dtype, float weight, int accumulate, float* workspace, float* sq,
+               hipStream_t stream);
+/* Every consumer below reads grad_sq[0] on the device and computes the same clip_coef (IEEE sqrt and
+ * division).  If grad_sq[0] is inf or NaN it does NOTHING and sets PT_STATUS_NONFINITE_GRAD in
+ * *status (may be NULL) -- torch would write NaN into every weight.  max_norm > 0.
+ * In-place scale, grad = r(grad * clip_coef) (the stand-alone clip_grad_norm_; torch's
+ * _foreach_mul_); clip_coef == 1 stores nothing. */
+int pt_grad_scale_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                        const float* grad_sq, float max_norm, int* status, hipStream_t stream);
+int pt_grad_scale(void* grad, int64_t n, int dtype, const float* grad_sq, float max_norm, int* status,
+                  hipStream_t stream);
+/* pt_adamw_step / pt_adamw_step_multi on g' = r(grad * clip_coef): bit-identical to the in-place
+ * scale followed by the unclipped step, without the gradients' second read and their rewrite (the
+ * gradients are not modified). */
+int pt_adamw_step_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
+                       float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                       const float* grad_sq, float max_norm, int* status, hipStream_t stream);
+int pt_adamw_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                             float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                             float step_size, const float* grad_sq, float max_norm, int* status,
+                             hipStream_t stream);
 
 /* ---- bf16 GEMM, f32 accumulate -------------------------------------------------------------
  * replaces every F.linear / matmul of the layer: model.py:124-126,161,186,270,

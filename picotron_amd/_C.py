@@ -40,6 +40,15 @@ SIGNATURES = {
     "pt_embedding_bwd": (_i32, [_vp, _vp, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp]),
     "pt_adamw_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
     "pt_adamw_step_multi": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "pt_grad_sq_workspace": (_i32, []),
+    "pt_grad_sq_multi": (_i32, [_vp, _vp, _i32, _i64, _f32, _i32, _vp, _vp, _vp]),
+    "pt_grad_sq": (_i32, [_vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "pt_grad_scale_multi": (_i32, [_vp, _vp, _i32, _i64, _vp, _f32, _vp, _vp]),
+    "pt_grad_scale": (_i32, [_vp, _i64, _i32, _vp, _f32, _vp, _vp]),
+    "pt_adamw_step_clip": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32,
+                                  _vp, _vp]),
+    "pt_adamw_step_multi_clip": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _vp,
+                                        _vp]),
     "pt_rmsnorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pt_rmsnorm_colsum_batch": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "pt_rmsnorm_bwd_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),

@@ -14,6 +14,11 @@
 // the roundings, so its result matches torch's bit for bit up to f32 contraction differences --
 // but reads each of the four tensors once and writes three (14 bytes per bf16 parameter instead
 // of ~44 over the eight passes).  Scalars arrive as f32, as torch's foreach kernels cast them.
+//
+// Also here, because they walk the same tensor table: global gradient-norm clipping
+// (torch.nn.utils.clip_grad_norm_ in front of the step) -- the f32 sum of squares of every
+// gradient, and the clip coefficient applied where the AdamW kernels load the gradient (a
+// compile-time variant of each) or in place.
 #include "common.h"
 
 namespace {
@@ -41,10 +46,48 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   p = r(p + s.step * (m / d));
 }
 
+// ---- global gradient-norm clipping ---------------------------------------------------------
+// torch.nn.utils.clip_grad_norm_'s coefficient, clip_coef = max_norm / (total_norm + 1e-6) clamped
+// to 1, from the device scalar sq = sum g^2 (IEEE sqrt and division: every consumer computes the
+// same bits).  false: sq is inf or NaN -- the consumer does nothing and posts the status bit.
+// The kernels take the scale as a compile-time variant: the unclipped instantiation's ClipArgs is
+// empty and its code is what it was before there was a variant.
+template <bool CLIP>
+struct ClipArgs {};
+template <>
+struct ClipArgs<true> {
+  const float* sq;
+  float max_norm;
+  int* status;
+};
+
+__device__ __forceinline__ bool clip_coef(const ClipArgs<true>& c, float& coef) {
+  const float sq = c.sq[0];
+  if (!(sq <= 3.402823466e+38f)) {
+    if (c.status && blockIdx.x == 0 && threadIdx.x == 0) atomicOr(c.status, PT_STATUS_NONFINITE_GRAD);
+    return false;
+  }
+  coef = fminf(1.0f, c.max_norm / (sqrtf(sq) + 1e-6f));
+  return true;
+}
+// the clipped gradient as torch's in-place _foreach_mul_ leaves it: one rounded f32 product (never
+// contracted into adam_elem's g - m, which would differ from the stored-and-reloaded f32
+// gradient), rounded to the storage dtype
+__device__ __forceinline__ float clip_grad(float g, float coef, bool bf) {
+#pragma clang fp contract(off)
+  const float x = g * coef;
+  return bf ? round_bf(x) : x;
+}
+
 // bf16 tensors: 8 elements per thread (16-byte loads / stores on all four streams)
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(uint16_t* __restrict__ param, const uint16_t* __restrict__ grad,
                                                          uint16_t* __restrict__ m, uint16_t* __restrict__ v,
-                                                         int64_t n8, AdamScalars s) {
+                                                         int64_t n8, AdamScalars s, ClipArgs<CLIP> clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
     float p[8], g[8], a[8], b[8];
     unpack8(ld8(param + i * 8), p);
@@ -52,7 +95,10 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(uint16_t* __restrict__ 
     unpack8(ld8(m + i * 8), a);
     unpack8(ld8(v + i * 8), b);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) adam_elem(p[j], g[j], a[j], b[j], s, true);
+    for (int j = 0; j < 8; ++j) {
+      if constexpr (CLIP) g[j] = clip_grad(g[j], coef, true);
+      adam_elem(p[j], g[j], a[j], b[j], s, true);
+    }
     st8(param + i * 8, pack8(p));
     st8(m + i * 8, pack8(a));
     st8(v + i * 8, pack8(b));
@@ -60,13 +106,18 @@ __global__ __launch_bounds__(256) void adamw_bf16_kernel(uint16_t* __restrict__ 
 }
 
 // scalar tail (n % 8) of a bf16 tensor, and f32 tensors
-template <typename T>
+template <typename T, bool CLIP>
 __global__ __launch_bounds__(256) void adamw_scalar_kernel(T* __restrict__ param, const T* __restrict__ grad,
                                                            T* __restrict__ m, T* __restrict__ v, int64_t n,
-                                                           AdamScalars s) {
+                                                           AdamScalars s, ClipArgs<CLIP> clip) {
   constexpr bool bf = sizeof(T) == 2;
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     float p = ld_as_f(param, i), g = ld_as_f(grad, i), a = ld_as_f(m, i), b = ld_as_f(v, i);
+    if constexpr (CLIP) g = clip_grad(g, coef, bf);
     adam_elem(p, g, a, b, s, bf);
     if (bf) {
       ((uint16_t*)param)[i] = f2bf(p);
@@ -79,7 +130,6 @@ __global__ __launch_bounds__(256) void adamw_scalar_kernel(T* __restrict__ param
     }
   }
 }
-
 // Multi-tensor form: ONE launch per step over every bf16 parameter (torch's foreach AdamW works on
 // the whole list too).  The tensors are a virtual concatenation of 8-element chunks; workgroup b
 // owns a contiguous run of chunks, finds the tensor its run starts in by binary search over the
@@ -93,9 +143,17 @@ struct AdamTensor {   // pt_adam_tensor (include/picotron_hip.h)
   int64_t n;
 };
 
+// CLIP: the gradient is scaled by the clip coefficient as it is loaded (g' = bf16(g * coef), what an
+// in-place scale pass would have stored).
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor* __restrict__ ts,
                                                                const int64_t* __restrict__ chunk_start, int nt,
-                                                               int64_t per_block, AdamScalars s) {
+                                                               int64_t per_block, AdamScalars s,
+                                                               ClipArgs<CLIP> clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
   const int64_t total = chunk_start[nt];
   const int64_t lo = (int64_t)blockIdx.x * per_block;
   const int64_t hi = lo + per_block < total ? lo + per_block : total;
@@ -129,7 +187,10 @@ __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor*
       float p[8], g[8], m[8], v[8];
       unpack8(cur[0], p); unpack8(cur[1], g); unpack8(cur[2], m); unpack8(cur[3], v);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) adam_elem(p[j], g[j], m[j], v[j], s, true);
+      for (int j = 0; j < 8; ++j) {
+        if constexpr (CLIP) g[j] = clip_grad(g[j], coef, true);
+        adam_elem(p[j], g[j], m[j], v[j], s, true);
+      }
       st8_nt(T.p + c * 8, pack8(p));
       st8_nt(T.m + c * 8, pack8(m));
       st8_nt(T.v + c * 8, pack8(v));
@@ -144,13 +205,17 @@ __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor*
         unpack8(ld8(T.m + c * 8), m);
         unpack8(ld8(T.v + c * 8), v);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) adam_elem(p[j], g[j], m[j], v[j], s, true);
+        for (int j = 0; j < 8; ++j) {
+          if constexpr (CLIP) g[j] = clip_grad(g[j], coef, true);
+          adam_elem(p[j], g[j], m[j], v[j], s, true);
+        }
         st8(T.p + c * 8, pack8(p));
         st8(T.m + c * 8, pack8(m));
         st8(T.v + c * 8, pack8(v));
       } else {   // the ragged last chunk
         for (int64_t i = c * 8; i < T.n; ++i) {
           float p = bf2f(T.p[i]), g = bf2f(T.g[i]), m = bf2f(T.m[i]), v = bf2f(T.v[i]);
+          if constexpr (CLIP) g = clip_grad(g, coef, true);
           adam_elem(p, g, m, v, s, true);
           T.p[i] = f2bf(p);
           T.m[i] = f2bf(m);
@@ -161,9 +226,157 @@ __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor*
   }
 }
 
+// ---- sum of squares of the gradients (the global norm) and the in-place scale ---------------
+// Both walk the AdamW table the same way and touch only its grad field: workgroup b's run of
+// chunks, tensor by tensor; fn(T, from, to) gets the run's chunk range inside tensor T.
+template <typename F>
+__device__ __forceinline__ void for_each_run(const AdamTensor* __restrict__ ts, const int64_t* __restrict__ chunk_start,
+                                             int nt, int64_t per_block, F fn) {
+  const int64_t total = chunk_start[nt];
+  const int64_t lo = (int64_t)blockIdx.x * per_block;
+  const int64_t hi = lo + per_block < total ? lo + per_block : total;
+  if (lo >= hi) return;
+  int a = 0, b = nt - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (chunk_start[mid] <= lo) a = mid; else b = mid - 1;
+  }
+  for (int t = a; t < nt && chunk_start[t] < hi; ++t) {
+    const int64_t c0 = chunk_start[t], c1 = chunk_start[t + 1];
+    fn(ts[t], (lo > c0 ? lo : c0) - c0, (hi < c1 ? hi : c1) - c0);
+  }
+}
+
+__device__ __forceinline__ float sq8(const bf16x8& x, float acc) {
+  float g[8];
+  unpack8(x, g);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc = fmaf(g[j], g[j], acc);
+  return acc;
+}
+
+// the workgroup's sum in a fixed order (wave butterfly, then the four waves in index order):
+// thread 0 returns it
+__device__ __forceinline__ float block_sum_256(float v) {
+  __shared__ float part[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// One f32 partial per workgroup: partial[b] = sum g^2 over workgroup b's run.  Nothing is stored
+// on the way, so four chunks per thread are simply loaded together and summed into four
+// independent accumulators (a thread's longest add chain: 8 * ceil(chunks per thread / 4)).
+__global__ __launch_bounds__(256) void grad_sq_multi_kernel(const AdamTensor* __restrict__ ts,
+                                                            const int64_t* __restrict__ chunk_start, int nt,
+                                                            int64_t per_block, float* __restrict__ partial) {
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamTensor& T, int64_t from, int64_t to) {
+    const int64_t full = T.n >> 3;
+    const int64_t end = to < full ? to : full;
+    const int64_t bd = blockDim.x;
+    int64_t c = from + threadIdx.x;
+    for (; c + 3 * bd < end; c += 4 * bd) {
+      bf16x8 x[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[q] = ld8_nt(T.g + (c + q * bd) * 8);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = sq8(x[q], acc[q]);
+    }
+    for (int q = 0; c < end; c += bd, ++q) acc[q & 3] = sq8(ld8_nt(T.g + c * 8), acc[q & 3]);
+    if (to > full && threadIdx.x == 0) {   // the ragged last chunk
+      for (int64_t i = full * 8; i < T.n; ++i) {
+        const float g = bf2f(T.g[i]);
+        acc[3] = fmaf(g, g, acc[3]);
+      }
+    }
+  });
+  const float sum = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+// single tensor (f32, or bf16 at any alignment): element by element, grid-strided
+template <typename T>
+__global__ __launch_bounds__(256) void grad_sq_kernel(const T* __restrict__ grad, int64_t n,
+                                                      float* __restrict__ partial) {
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * stride < n; i += 4 * stride) {
+    float g[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q] = ld_as_f(grad, i + q * stride);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = fmaf(g[q], g[q], acc[q]);
+  }
+  for (int q = 0; i < n; i += stride, ++q) {
+    const float g = ld_as_f(grad, i);
+    acc[q & 3] = fmaf(g, g, acc[q & 3]);
+  }
+  const float sum = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+// sq[0] = (accumulate ? sq[0] : 0) + weight * sum of the n partials, one workgroup, fixed order
+// (thread t takes partials t, t + 256, ... in index order): bit-reproducible, no float atomics
+__global__ __launch_bounds__(256) void grad_sq_final_kernel(const float* __restrict__ partial, int n, float weight,
+                                                            int accumulate, float* __restrict__ sq) {
+  float acc = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+  const float sum = block_sum_256(acc);
+  if (threadIdx.x == 0) sq[0] = accumulate ? sq[0] + weight * sum : weight * sum;
+}
+
+// grad = bf16(grad * coef) in place over the list (the stand-alone clip_grad_norm_); coef == 1
+// (no clipping) stores nothing
+__global__ __launch_bounds__(256) void grad_scale_multi_kernel(const AdamTensor* __restrict__ ts,
+                                                               const int64_t* __restrict__ chunk_start, int nt,
+                                                               int64_t per_block, ClipArgs<true> clip) {
+  float coef;
+  if (!clip_coef(clip, coef) || coef == 1.0f) return;
+  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamTensor& T, int64_t from, int64_t to) {
+    uint16_t* G = const_cast<uint16_t*>(T.g);
+    const int64_t full = T.n >> 3;
+    const int64_t end = to < full ? to : full;
+    for (int64_t c = from + threadIdx.x; c < end; c += blockDim.x) {
+      float g[8];
+      unpack8(ld8_nt(G + c * 8), g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) g[j] = clip_grad(g[j], coef, false);   // pack8 rounds
+      st8_nt(G + c * 8, pack8(g));
+    }
+    if (to > full && threadIdx.x == 0) {
+      for (int64_t i = full * 8; i < T.n; ++i) G[i] = f2bf(clip_grad(bf2f(G[i]), coef, false));
+    }
+  });
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void grad_scale_kernel(T* __restrict__ grad, int64_t n, ClipArgs<true> clip) {
+  float coef;
+  if (!clip_coef(clip, coef) || coef == 1.0f) return;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float g = clip_grad(ld_as_f(grad, i), coef, false);
+    if (sizeof(T) == 2) ((uint16_t*)grad)[i] = f2bf(g); else ((float*)grad)[i] = g;
+  }
+}
+
 int grid_for(int64_t work) {
   int64_t g = (work + 255) / 256;
   return (int)(g < PT_STREAM_GRID_CAP ? (g < 1 ? 1 : g) : PT_STREAM_GRID_CAP);
+}
+
+// the multi-tensor launches' geometry: one resident round, 4 blocks of 4 waves per CU at <= 128
+// VGPRs (2 chunks per thread in flight)
+struct MultiGrid {
+  unsigned blocks;
+  int64_t per_block;
+};
+MultiGrid multi_grid(int64_t total_chunks, int64_t cap = 1024) {
+  const int64_t want = (total_chunks + 511) / 512;
+  const int64_t blocks = want < 1 ? 1 : (want < cap ? want : cap);
+  return {(unsigned)blocks, (total_chunks + blocks - 1) / blocks};
 }
 
 }  // namespace
@@ -184,18 +397,18 @@ int pt_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq
     const bool vec = pt_aligned16(P) && pt_aligned16(G) && pt_aligned16(M) && pt_aligned16(V);
     const int64_t n8 = vec ? n / 8 : 0;
     if (n8) {
-      adamw_bf16_kernel<<<grid_for(n8), 256, 0, stream>>>(P, G, M, V, n8, s);
+      adamw_bf16_kernel<false><<<grid_for(n8), 256, 0, stream>>>(P, G, M, V, n8, s, {});
       PT_CHECK_LAUNCH();
     }
     const int64_t done = n8 * 8;
     if (done < n) {
-      adamw_scalar_kernel<uint16_t><<<grid_for(n - done), 256, 0, stream>>>(P + done, G + done, M + done, V + done,
-                                                                             n - done, s);
+      adamw_scalar_kernel<uint16_t, false><<<grid_for(n - done), 256, 0, stream>>>(P + done, G + done, M + done,
+                                                                                    V + done, n - done, s, {});
       PT_CHECK_LAUNCH();
     }
   } else if (dtype == 1) {  // f32
-    adamw_scalar_kernel<float><<<grid_for(n), 256, 0, stream>>>((float*)param, (const float*)grad, (float*)exp_avg,
-                                                                (float*)exp_avg_sq, n, s);
+    adamw_scalar_kernel<float, false><<<grid_for(n), 256, 0, stream>>>((float*)param, (const float*)grad,
+                                                                       (float*)exp_avg, (float*)exp_avg_sq, n, s, {});
     PT_CHECK_LAUNCH();
   } else {
     return PT_EINVAL;
@@ -212,12 +425,114 @@ int pt_adamw_step_multi(const void* tensors, const int64_t* chunk_start, int nte
   if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0) return PT_EINVAL;
   if (total_chunks == 0) return PT_OK;
   const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
-  // one resident round: 4 blocks of 4 waves per CU at <= 128 VGPRs (2 chunks per thread in flight)
-  const int64_t cap = 1024, want = (total_chunks + 511) / 512;
-  const int64_t blocks = want < 1 ? 1 : (want < cap ? want : cap);
-  const int64_t per_block = (total_chunks + blocks - 1) / blocks;
-  adamw_multi_bf16_kernel<<<(unsigned)blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
-                                                                per_block, s);
+  const MultiGrid g = multi_grid(total_chunks);
+  adamw_multi_bf16_kernel<false><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
+                                                               g.per_block, s, {});
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+// ---- global gradient-norm clipping ---------------------------------------------------------
+// the norm pass and the scale only read / write 2 bytes per parameter at few VGPRs: 8 blocks per CU
+static constexpr int PT_GRAD_SQ_BLOCKS = PT_STREAM_GRID_CAP;
+
+int pt_grad_sq_workspace(void) { return PT_GRAD_SQ_BLOCKS; }
+
+int pt_grad_sq_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                     float weight, int accumulate, float* workspace, float* sq, hipStream_t stream) {
+  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !workspace || !sq) return PT_EINVAL;
+  unsigned blocks = 0;
+  if (total_chunks) {
+    const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+    blocks = g.blocks;
+    grad_sq_multi_kernel<<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
+                                                       g.per_block, workspace);
+    PT_CHECK_LAUNCH();
+  }
+  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, (int)blocks, weight, accumulate, sq);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_grad_sq(const void* grad, int64_t n, int dtype, float weight, int accumulate, float* workspace, float* sq,
+               hipStream_t stream) {
+  if (!grad || n < 0 || !workspace || !sq || (dtype != 0 && dtype != 1)) return PT_EINVAL;
+  const int blocks = n ? grid_for(n) : 0;
+  if (n && dtype == 0) grad_sq_kernel<uint16_t><<<blocks, 256, 0, stream>>>((const uint16_t*)grad, n, workspace);
+  if (n && dtype == 1) grad_sq_kernel<float><<<blocks, 256, 0, stream>>>((const float*)grad, n, workspace);
+  PT_CHECK_LAUNCH();
+  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, blocks, weight, accumulate, sq);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_grad_scale_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                        const float* grad_sq, float max_norm, int* status, hipStream_t stream) {
+  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !grad_sq || !(max_norm > 0.0f))
+    return PT_EINVAL;
+  if (total_chunks == 0) return PT_OK;
+  const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+  grad_scale_multi_kernel<<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
+                                                        g.per_block, ClipArgs<true>{grad_sq, max_norm, status});
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_grad_scale(void* grad, int64_t n, int dtype, const float* grad_sq, float max_norm, int* status,
+                  hipStream_t stream) {
+  if (!grad || n < 0 || !grad_sq || !(max_norm > 0.0f) || (dtype != 0 && dtype != 1)) return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  const ClipArgs<true> clip{grad_sq, max_norm, status};
+  if (dtype == 0) grad_scale_kernel<uint16_t><<<grid_for(n), 256, 0, stream>>>((uint16_t*)grad, n, clip);
+  else grad_scale_kernel<float><<<grid_for(n), 256, 0, stream>>>((float*)grad, n, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_adamw_step_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
+                       float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                       const float* grad_sq, float max_norm, int* status, hipStream_t stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !grad_sq || !(max_norm > 0.0f)) return PT_EINVAL;
+  if (dtype != 0 && dtype != 1) return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
+  const ClipArgs<true> clip{grad_sq, max_norm, status};
+  if (dtype == 0) {  // bf16: the same split as pt_adamw_step
+    auto* P = (uint16_t*)param;
+    auto* G = (const uint16_t*)grad;
+    auto* M = (uint16_t*)exp_avg;
+    auto* V = (uint16_t*)exp_avg_sq;
+    const bool vec = pt_aligned16(P) && pt_aligned16(G) && pt_aligned16(M) && pt_aligned16(V);
+    const int64_t n8 = vec ? n / 8 : 0;
+    if (n8) {
+      adamw_bf16_kernel<true><<<grid_for(n8), 256, 0, stream>>>(P, G, M, V, n8, s, clip);
+      PT_CHECK_LAUNCH();
+    }
+    const int64_t done = n8 * 8;
+    if (done < n) {
+      adamw_scalar_kernel<uint16_t, true><<<grid_for(n - done), 256, 0, stream>>>(P + done, G + done, M + done,
+                                                                                  V + done, n - done, s, clip);
+      PT_CHECK_LAUNCH();
+    }
+  } else {
+    adamw_scalar_kernel<float, true><<<grid_for(n), 256, 0, stream>>>((float*)param, (const float*)grad,
+                                                                     (float*)exp_avg, (float*)exp_avg_sq, n, s, clip);
+    PT_CHECK_LAUNCH();
+  }
+  return PT_OK;
+}
+
+int pt_adamw_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                             float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                             float step_size, const float* grad_sq, float max_norm, int* status,
+                             hipStream_t stream) {
+  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !grad_sq || !(max_norm > 0.0f))
+    return PT_EINVAL;
+  if (total_chunks == 0) return PT_OK;
+  const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
+  const MultiGrid g = multi_grid(total_chunks);
+  adamw_multi_bf16_kernel<true><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
+                                                             g.per_block, s, ClipArgs<true>{grad_sq, max_norm, status});
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

@@ -219,16 +219,12 @@ def adamw_step(p, grad, exp_avg, exp_avg_sq, decay, w1, beta2, c2, bc2_sqrt, eps
 _ADAM_DESC = {}
 
 
-def adamw_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
-    """One launch of the fused AdamW update over a list of bf16 (param, grad, exp_avg, exp_avg_sq)
-    tuples (pt_adamw_step_multi).  The device descriptor table is cached per pointer set (the
-    tensors of a model stay put across steps; a re-allocated gradient makes a new table).  A new
-    table is staged in pinned host memory and copied on the current stream without a host sync
-    (the caching host allocator keeps the staging buffer alive until that copy has run)."""
-    for p, g, m, v in items:
-        for t in (p, g, m, v):
-            _req(t.dtype == BF16 and t.is_contiguous() and t.numel() == p.numel() and t.data_ptr() % 16 == 0,
-                 "adamw multi: contiguous, 16-byte aligned bf16 tensors of one length per parameter")
+def _adam_desc(items):
+    """(device pt_adam_tensor table, device chunk_start, total chunks) of a list of 4-tuples of
+    tensors, cached per pointer set (the tensors of a model stay put across steps; a re-allocated
+    gradient makes a new table).  A new table is staged in pinned host memory and copied on the
+    current stream without a host sync (the caching host allocator keeps the staging buffer alive
+    until that copy has run)."""
     key = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, g, m, v in items)
     ent = _ADAM_DESC.get(key)
     if ent is None:
@@ -242,11 +238,153 @@ def adamw_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
         if len(_ADAM_DESC) > 64:
             _ADAM_DESC.clear()
         _ADAM_DESC[key] = ent
-    desc, chunk_t, total = ent
+    return ent
+
+
+def _adam_items_ok(items):
+    _req(len(items) > 0, "adamw multi: an empty tensor list")
+    for p, g, m, v in items:
+        for t in (p, g, m, v):
+            _req(t.dtype == BF16 and t.is_contiguous() and t.numel() == p.numel() and t.data_ptr() % 16 == 0,
+                 "adamw multi: contiguous, 16-byte aligned bf16 tensors of one length per parameter")
+
+
+def adamw_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
+    """One launch of the fused AdamW update over a list of bf16 (param, grad, exp_avg, exp_avg_sq)
+    tuples (pt_adamw_step_multi), on the cached descriptor table of _adam_desc."""
+    _adam_items_ok(items)
+    desc, chunk_t, total = _adam_desc(items)
     rc = _C.lib().pt_adamw_step_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(decay), float(w1),
                                       float(beta2), float(c2), float(bc2_sqrt), float(eps), float(step_size),
                                       _C.stream_ptr(items[0][0].device))
     _C.check(rc, "pt_adamw_step_multi")
+
+
+# -------------------------------------------------------------- global gradient-norm clipping
+_GRAD_WS = {}   # device index -> f32 workspace of the norm pass (one partial per workgroup)
+
+
+def _grad_ws(device):
+    i = _dev_index(device)
+    w = _GRAD_WS.get(i)
+    if w is None:
+        w = _GRAD_WS[i] = torch.empty(_C.lib().pt_grad_sq_workspace(), dtype=torch.float32,
+                                      device=torch.device("cuda", i))
+    return w
+
+
+def _grad_dtype(t, what):
+    _req(t.is_cuda and t.is_contiguous(), f"{what}: a contiguous device tensor")
+    if t.dtype == BF16:
+        return 0
+    if t.dtype == torch.float32:
+        return 1
+    raise _C.HipKernelError(f"{what}: unsupported dtype {t.dtype}")
+
+
+def _sq_ok(sq, device):
+    _req(sq.dtype == torch.float32 and sq.numel() == 1 and sq.device == device, "grad_sq: one f32 on the device")
+
+
+class _clip_status:
+    """The status word of a clip consumer's launch.  A caller that issues several of them for one
+    step (optim.AdamW) passes its own word (status_word(device), fetched once) and posts it once
+    after the last (_status_posted), so the poll in front of a launch never raises mid-step for a
+    bit the same step's earlier launch set."""
+
+    def __init__(self, device, status):
+        self.device, self.own = device, status is None
+        self.word = status_word(device) if status is None else status
+
+    def __enter__(self):
+        return _ptr(self.word)
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.own and exc_type is None:
+            _status_posted(self.device)
+
+
+def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
+    """out[0] (+)= weight * sum of g^2, in f32 and bit-reproducible (csrc/adamw.hip: per-workgroup
+    partials, then one workgroup sums them in a fixed order).  items: bf16 (param, grad, exp_avg,
+    exp_avg_sq) tuples as adamw_step_multi takes them -- one launch over the list on the SAME cached
+    table, of which only the grad field is read (gradients alone: (g, g, g, g)); tensors: single
+    gradients of what the list form does not take (f32, unaligned bf16).  Everything accumulates
+    into the one device scalar in stream order; returns it (a [1] f32 tensor)."""
+    items, tensors = list(items), list(tensors)
+    _req(items or tensors, "grad_sqnorm: nothing to sum")
+    dev = (items[0][1] if items else tensors[0]).device
+    if out is None:
+        _req(not accumulate, "grad_sqnorm: accumulate needs the scalar to add to")
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    _sq_ok(out, dev)
+    ws, lib, acc = _grad_ws(dev), _C.lib(), bool(accumulate)
+    if items:
+        _adam_items_ok(items)
+        desc, chunk_t, total = _adam_desc(items)
+        rc = lib.pt_grad_sq_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(weight), int(acc),
+                                  _ptr(ws), _ptr(out), _C.stream_ptr(dev))
+        _C.check(rc, "pt_grad_sq_multi")
+        acc = True
+    for g in tensors:
+        _req(g.device == dev, "grad_sqnorm: gradients on one device")
+        rc = lib.pt_grad_sq(_ptr(g), g.numel(), _grad_dtype(g, "grad_sqnorm"), float(weight), int(acc), _ptr(ws),
+                            _ptr(out), _C.stream_ptr(dev))
+        _C.check(rc, "pt_grad_sq")
+        acc = True
+    return out
+
+
+def grad_scale_multi(items, sq, max_norm, status=None):
+    """grad = bf16(grad * coef) in place over the list (items as in grad_sqnorm), coef = min(1,
+    max_norm / (sqrt(sq[0]) + 1e-6)) computed on the device; a non-finite sq leaves the gradients
+    alone and posts STATUS_NONFINITE_GRAD (status: see _clip_status)."""
+    _adam_items_ok(items)
+    dev = items[0][1].device
+    _sq_ok(sq, dev)
+    desc, chunk_t, total = _adam_desc(items)
+    with _clip_status(dev, status) as st:
+        rc = _C.lib().pt_grad_scale_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), _ptr(sq),
+                                          float(max_norm), st, _C.stream_ptr(dev))
+        _C.check(rc, "pt_grad_scale_multi")
+
+
+def grad_scale(grad, sq, max_norm, status=None):
+    """grad_scale_multi for one tensor of any alignment, bf16 or f32."""
+    _sq_ok(sq, grad.device)
+    with _clip_status(grad.device, status) as st:
+        rc = _C.lib().pt_grad_scale(_ptr(grad), grad.numel(), _grad_dtype(grad, "grad_scale"), _ptr(sq),
+                                    float(max_norm), st, _C.stream_ptr(grad.device))
+        _C.check(rc, "pt_grad_scale")
+
+
+def adamw_step_multi_clip(items, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
+    """adamw_step_multi on the clipped gradients bf16(grad * coef), coef as in grad_scale_multi,
+    applied where the kernel loads the gradient: bit-identical to grad_scale_multi followed by
+    adamw_step_multi, and the gradients are not modified.  A non-finite sq skips the update."""
+    _adam_items_ok(items)
+    dev = items[0][0].device
+    _sq_ok(sq, dev)
+    desc, chunk_t, total = _adam_desc(items)
+    with _clip_status(dev, status) as st:
+        rc = _C.lib().pt_adamw_step_multi_clip(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(decay),
+                                               float(w1), float(beta2), float(c2), float(bc2_sqrt), float(eps),
+                                               float(step_size), _ptr(sq), float(max_norm), st, _C.stream_ptr(dev))
+        _C.check(rc, "pt_adamw_step_multi_clip")
+
+
+def adamw_step_clip(p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
+    """adamw_step on the clipped gradient (one tensor, bf16 or f32, any alignment)."""
+    for t, nm in ((grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _req(t.dtype == p.dtype and t.numel() == p.numel() and t.device == p.device, f"adamw: {nm} must match param")
+        _req(t.is_contiguous(), "adamw: dense tensors")
+    _sq_ok(sq, p.device)
+    with _clip_status(p.device, status) as st:
+        rc = _C.lib().pt_adamw_step_clip(_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(),
+                                         _grad_dtype(p, "adamw"), float(decay), float(w1), float(beta2), float(c2),
+                                         float(bc2_sqrt), float(eps), float(step_size), _ptr(sq), float(max_norm), st,
+                                         _C.stream_ptr(p.device))
+        _C.check(rc, "pt_adamw_step_clip")
 
 
 # ------------------------------------------------------------------------------------ RoPE
@@ -295,6 +433,7 @@ def residual_add(x, r):
 
 # ---------------------------------------------------------------------------- device status
 STATUS_BAD_TARGET = 1   # PT_STATUS_BAD_TARGET (include/picotron_hip.h)
+STATUS_NONFINITE_GRAD = 2   # PT_STATUS_NONFINITE_GRAD
 _STATUS = {}
 
 
@@ -357,6 +496,9 @@ def check_device_status(device=None):
         raise _C.HipKernelError("cross_entropy: a target index is outside [0, vocab) and is not ignore_index "
                                 "(torch: 'Assertion `t >= 0 && t < n_classes` failed'); its row loss and "
                                 "gradient were set to NaN")
+    if v & STATUS_NONFINITE_GRAD:
+        raise _C.HipKernelError("gradient clipping: the global gradient norm is not finite (inf or NaN); the "
+                                "optimizer step (or the in-place scale) it belonged to was skipped")
     if v:
         raise _C.HipKernelError(f"device status word {v:#x}")
 

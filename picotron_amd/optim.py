@@ -5,20 +5,105 @@ Same constructor, defaults, param_groups and state layout as torch.optim.AdamW (
 float tensor, state['exp_avg'] / state['exp_avg_sq'] in the parameter's dtype), so a checkpoint of
 one loads into the other; the per-element math is torch's multi-tensor (foreach) Adam with
 decoupled weight decay, op for op with the same roundings to the storage dtype.
+
+Global gradient-norm clipping (what a Llama recipe puts between the backward and the step,
+torch.nn.utils.clip_grad_norm_) is part of the step: AdamW(..., max_grad_norm=M), or the stand-alone
+clip_grad_norm_ below.  Both compute ONE norm for the whole model -- over tensor- and pipeline-
+parallel ranks too -- in f32 on the device, and nothing of it is read on the host.
 """
 import torch
+import torch.distributed as dist
 
 from . import kernels as K
+from . import process_group_manager as pgm
+
+
+def grad_norm_plan(params, tp_size, pp_size):
+    """How the global gradient norm is put together on a (tp, pp) grid; pure.  Returns
+    (sharded, replicated, groups, replicated_weight):
+
+      sharded      the parameters marked `tensor_model_parallel` (Column / VocabParallel weights and
+                   biases, RowParallel weights: each tp rank holds another block),
+      replicated   the rest: identical on every tp rank after the backward (sequence parallelism
+                   sums the norm weights' partial gradients over the group itself),
+      groups       the process-group names to all-reduce (SUM) the squared norm over, in order:
+                   "tp" if tp_size > 1, then "pp" if pp_size > 1 (stages hold disjoint layers; cp
+                   and dp ranks hold identical gradients after their sync and are not reduced),
+      replicated_weight   1 / tp_size: a rank adds sq(sharded) + sq(replicated) / tp, so the tp sum
+                   counts every replicated tensor once (a division by a power of two: exact).
+
+    Every rank then holds the same bits, hence the same clip coefficient."""
+    if tp_size < 1 or pp_size < 1:
+        raise ValueError(f"grad_norm_plan: tp_size={tp_size} pp_size={pp_size}")
+    sharded, replicated = [], []
+    for p in params:
+        (sharded if getattr(p, "tensor_model_parallel", False) else replicated).append(p)
+    groups = tuple(name for name, size in (("tp", tp_size), ("pp", pp_size)) if size > 1)
+    return sharded, replicated, groups, 1.0 / tp_size
+
+
+def _listable(*tensors):
+    """What the multi-tensor launches take: contiguous, 16-byte aligned bf16."""
+    return all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def _global_sq(batches):
+    """batches: [(multi, [(param, x)])] -- multi: every x is a (param, grad, exp_avg, exp_avg_sq)
+    tuple and the batch is one multi-tensor list (summed on the descriptor table its AdamW launch
+    uses); else every x is a single gradient.  Returns the [1] f32 device scalar holding the squared
+    L2 norm over all of them and over the model-parallel grid (grad_norm_plan), or None if there is
+    no gradient."""
+    m = pgm.current()
+    flat = [(p, b, multi, x) for b, (multi, entries) in enumerate(batches) for p, x in entries]
+    _, _, groups, w_rep = grad_norm_plan([], m.tp_world_size, m.pp_world_size)
+    if w_rep == 1.0:   # nothing is replicated over a group: one pass, every batch as it stands
+        parts = [(flat, 1.0)]
+    else:
+        sharded = {id(p) for p in grad_norm_plan([e[0] for e in flat], m.tp_world_size, m.pp_world_size)[0]}
+        parts = [([e for e in flat if id(e[0]) in sharded], 1.0), ([e for e in flat if id(e[0]) not in sharded], w_rep)]
+    sq = None
+    for part, weight in parts:
+        i = 0
+        while i < len(part):   # a batch's entries are consecutive
+            j = i
+            while j < len(part) and part[j][1] == part[i][1]:
+                j += 1
+            xs = [e[3] for e in part[i:j]]
+            sq = K.grad_sqnorm(items=xs if part[i][2] else (), tensors=() if part[i][2] else xs, out=sq,
+                               accumulate=sq is not None, weight=weight)
+            i = j
+    if sq is None:
+        return None
+    for name in groups:
+        dist.all_reduce(sq, op=dist.ReduceOp.SUM, group=getattr(m, f"{name}_group"))
+    return sq
 
 
 class AdamW(torch.optim.Optimizer):
+    """max_grad_norm=None: the plain step.  max_grad_norm=M > 0: every step() first takes the global
+    L2 norm of all gradients (one f32 pass, every param group, every model-parallel rank: see
+    grad_norm_plan) and applies g * min(1, M / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_'s
+    coefficient -- where the AdamW kernel loads the gradient.  The .grad tensors are not modified,
+    and no value is read on the host: `last_grad_norm` is a 0-dim f32 DEVICE tensor with the
+    pre-clip norm, to be read when the caller synchronises anyway.
+
+    A norm that is inf or NaN skips the update on the device: parameters and both moments stay
+    bit-unchanged and a status bit is set, which the next kernels.check_device_status /
+    train.read_step_loss raises as HipKernelError.  (Deliberately not torch: clip_grad_norm_ with
+    error_if_nonfinite=False would scale by NaN and the step would write NaN into every weight.)
+    The host cannot know of the skip without a synchronisation, so state['step'] still counts it."""
+
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 maximize=False):
+                 maximize=False, max_grad_norm=None):
         if amsgrad or maximize:
             raise ValueError("picotron_amd.optim.AdamW: amsgrad / maximize are not used by picotron (train.py:209)")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"invalid AdamW hyper-parameters lr={lr} betas={betas} eps={eps}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"invalid AdamW max_grad_norm={max_grad_norm}: a positive number or None")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -29,33 +114,88 @@ class AdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self.max_grad_norm is not None:
+            self._step_clipped()
+            return loss
         for group in self.param_groups:
-            lr, (beta1, beta2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
-            batches = {}
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if p.grad.is_sparse:
-                    raise RuntimeError("AdamW does not support sparse gradients")
-                st = self.state[p]
-                if len(st) == 0:
-                    st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["step"] += 1
-                t = st["step"].item()
-                item = (p, p.grad, st["exp_avg"], st["exp_avg_sq"])
-                multi = p.dtype == torch.bfloat16 and all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) \
-                    and p.grad.dtype == p.dtype
-                batches.setdefault((t, multi), []).append(item)
-            for (t, multi), items in batches.items():
-                bc1 = 1 - beta1 ** t
-                bc2 = 1 - beta2 ** t
-                sc = dict(decay=1 - lr * wd, w1=1 - beta1, beta2=beta2, c2=1 - beta2, bc2_sqrt=bc2 ** 0.5, eps=eps,
-                          step_size=(lr / bc1) * -1)
+            for sc, multi, items in self._batches(group):
                 if multi:
                     K.adamw_step_multi(items, **sc)
                 else:
                     for p, g, m, v in items:
                         K.adamw_step(p, g, m, v, **sc)
         return loss
+
+    def _batches(self, group):
+        """[(kernel scalars, multi, [(param, grad, exp_avg, exp_avg_sq)])] of one param group; counts
+        the step."""
+        lr, (beta1, beta2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+        batches = {}
+        for p in group["params"]:
+            if p.grad is None:
+                continue
+            if p.grad.is_sparse:
+                raise RuntimeError("AdamW does not support sparse gradients")
+            st = self.state[p]
+            if len(st) == 0:
+                st["step"] = torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["step"] += 1
+            t = st["step"].item()
+            item = (p, p.grad, st["exp_avg"], st["exp_avg_sq"])
+            multi = p.dtype == torch.bfloat16 and all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) \
+                and p.grad.dtype == p.dtype
+            batches.setdefault((t, multi), []).append(item)
+        out = []
+        for (t, multi), items in batches.items():
+            bc1 = 1 - beta1 ** t
+            bc2 = 1 - beta2 ** t
+            sc = dict(decay=1 - lr * wd, w1=1 - beta1, beta2=beta2, c2=1 - beta2, bc2_sqrt=bc2 ** 0.5, eps=eps,
+                      step_size=(lr / bc1) * -1)
+            out.append((sc, multi, items))
+        return out
+
+    def _step_clipped(self):
+        work = [b for group in self.param_groups for b in self._batches(group)]
+        sq = _global_sq([(multi, [(it[0], it if multi else it[1]) for it in items]) for _, multi, items in work])
+        if sq is None:   # no gradients at all
+            return
+        self.last_grad_norm = sq.sqrt().reshape(())
+        status = K.status_word(sq.device)   # one word, posted once: see kernels._clip_status
+        for sc, multi, items in work:
+            if multi:
+                K.adamw_step_multi_clip(items, sq, self.max_grad_norm, status=status, **sc)
+            else:
+                for p, g, m, v in items:
+                    K.adamw_step_clip(p, g, m, v, sq, self.max_grad_norm, status=status, **sc)
+        K._status_posted(sq.device)
+
+
+@torch.no_grad()
+def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=False, foreach=None):
+    """torch.nn.utils.clip_grad_norm_ for a reference-style train.py (in front of optimizer.step()):
+    the global L2 norm in f32 over every gradient and every tensor- / pipeline-parallel rank
+    (grad_norm_plan), then grad = r(grad * min(1, max_norm / (norm + 1e-6))) in place -- all on the
+    device.  Returns the total norm as a 0-dim f32 device tensor.  L2 only.  A non-finite norm
+    leaves the gradients alone and is raised by the next kernels.check_device_status, whatever
+    error_if_nonfinite says (checking it here would be a host synchronisation)."""
+    if float(norm_type) != 2.0:
+        raise ValueError(f"picotron_amd.optim.clip_grad_norm_: only the L2 norm (norm_type=2), got {norm_type}")
+    if not float(max_norm) > 0.0:
+        raise ValueError(f"clip_grad_norm_: max_norm={max_norm} must be positive")
+    if isinstance(parameters, torch.Tensor):
+        parameters = [parameters]
+    params = [p for p in parameters if p.grad is not None]
+    if not params:
+        return torch.tensor(0.0)
+    multi = [(p, (p.grad,) * 4) for p in params if _listable(p.grad)]
+    single = [(p, p.grad) for p in params if not _listable(p.grad)]
+    sq = _global_sq([(True, multi), (False, single)])
+    status = K.status_word(sq.device)
+    if multi:
+        K.grad_scale_multi([x for _, x in multi], sq, max_norm, status=status)
+    for _, g in single:
+        K.grad_scale(g, sq, max_norm, status=status)
+    K._status_posted(sq.device)
+    return sq.sqrt().reshape(())

@@ -77,6 +77,11 @@ class ColumnParallelLinear(torch.nn.Module):
             self.bias = nn.Parameter(torch.zeros(self.output_size_per_partition))
         else:
             self.register_parameter("bias", None)
+        # each tp rank holds another block: the global gradient norm sums these over the tp group
+        # (optim.grad_norm_plan); an attribute only
+        self.weight.tensor_model_parallel = True
+        if bias:
+            self.bias.tensor_model_parallel = True
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -123,6 +128,7 @@ class RowParallelLinear(nn.Module):
             self.bias = nn.Parameter(torch.zeros(self.out_features))
         else:
             self.register_parameter("bias", None)
+        self.weight.tensor_model_parallel = True   # the bias is replicated: added after the reduce
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -154,6 +160,7 @@ class VocabParallelEmbedding(nn.Module):
             self.num_embeddings, self.tp_rank, self.tp_world_size)
         self.num_embeddings_per_partition = self.vocab_end_index - self.vocab_start_index
         self.weight = nn.Parameter(torch.empty(self.num_embeddings_per_partition, self.embedding_dim))
+        self.weight.tensor_model_parallel = True
         self.reset_parameters()
 
     def _vocab_range_from_global_vocab_size(self, global_vocab_size: int, rank: int, world_size: int):

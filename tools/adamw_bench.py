@@ -2,7 +2,10 @@
 sizes): us per step (graph-timed) and HBM rate on 14 B per parameter; --old: another build's
 pt_adamw_step_multi in the same process; --calib: beside it torch's fused AdamW on the same tensors and
 the HBM rate of torch's copy (1 read : 1 write) and add (2 : 1) over the same bytes, which bracket
-AdamW's 8 : 6 mix.  python tools/adamw_bench.py [--old lib.so] [--calib]"""
+AdamW's 8 : 6 mix; --clip: global gradient-norm clipping -- (a) the plain step, (b) the norm pass alone
+(rate on 2 B per parameter, beside torch's x.sum() over the same bytes), (c) norm pass + clipped step,
+(c') the clipped step alone, (d) torch.nn.utils.clip_grad_norm_(foreach=True) + (a), alternating over three rounds in one call.
+python tools/adamw_bench.py [--old lib.so] [--calib] [--clip]"""
 import argparse
 import json
 import os
@@ -22,6 +25,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--old", default="")
     ap.add_argument("--calib", action="store_true")
+    ap.add_argument("--clip", action="store_true")
     a = ap.parse_args()
     H, I, V, L = 2048, 8192, 49152, 15
     shapes = [(V, H)] + [s for _ in range(L) for s in ((H,), (H, H), (H, H), (H, H), (H, H), (I, H), (I, H), (H, I), (H,))] + [(H,)]
@@ -44,6 +48,45 @@ def main():
                   flush=True)
     if a.calib:
         calib(items, n, args)
+    if a.clip:
+        clip(items, n, args)
+
+
+def clip(items, n, args):
+    dev = items[0][0].device
+    sq = torch.zeros(1, dtype=torch.float32, device=dev)
+    status = K.status_word(dev)
+    params = []
+    for p, g, _, _ in items:   # torch's clip wants parameters with .grad: the same gradient tensors
+        q = torch.nn.Parameter(p, requires_grad=True)
+        q.grad = g
+        params.append(q)
+    max_norm = 1.0   # the gradients' norm is ~35: clipping is active
+    x = torch.empty(n, dtype=torch.bfloat16, device=dev).normal_()
+
+    def torch_clip_then_step():
+        torch.nn.utils.clip_grad_norm_(params, max_norm, foreach=True)
+        K.adamw_step_multi(items, *args)
+
+    def fused():
+        K.grad_sqnorm(items=items, out=sq)
+        K.adamw_step_multi_clip(items, sq, max_norm, *args, status=status)
+    variants = [("a: adamw_step_multi", lambda: K.adamw_step_multi(items, *args), 14),
+                ("b: grad_sqnorm", lambda: K.grad_sqnorm(items=items, out=sq), 2),
+                ("probe: sum 1r", lambda: x.sum(), 2),
+                ("c: grad_sqnorm + adamw_step_multi_clip", fused, 16),
+                ("c': adamw_step_multi_clip alone", lambda: K.adamw_step_multi_clip(items, sq, max_norm, *args, status=status), 14),
+                ("d: torch clip_grad_norm_ + adamw_step_multi", torch_clip_then_step, None)]
+    for rnd in range(3):
+        for name, fn, bpp in variants:
+            us = graph_us(fn, 3)
+            rec = {"clip": name, "round": rnd, "params": n, "us": round(us, 1)}
+            if bpp:
+                rec["TBps"] = round(bpp * n / us / 1e6, 2)
+            print(json.dumps(rec), flush=True)
+    torch.cuda.synchronize()
+    print(json.dumps({"clip": "grad norm", "value": round(float(sq.sqrt()), 4),
+                      "status": K.device_status(dev)}), flush=True)
 
 
 def calib(items, n, args):
