@@ -219,6 +219,42 @@ int pt_adamw_step_multi_clip(const void* tensors, const int64_t* chunk_start, in
                              float step_size, const float* grad_sq, float max_norm, int* status,
                              hipStream_t stream);
 
+/* ---- AdamW with fp32 master weights and moments ---------------------------------------------
+ * The mixed-precision recipe on top of train.py:209: an f32 master copy of every bf16 weight and
+ * both moments in f32.  Per element, in f32, each operation rounded on its own: g32 = float(grad)
+ * (grad_dtype 0 bf16, 1 f32; with clipping g32 *= clip_coef, never rounded to bf16), torch's foreach
+ * f32 AdamW sequence on (master, g32, exp_avg, exp_avg_sq), then param = bf16(master), round to
+ * nearest even.  28 B per parameter with bf16 gradients, 30 B with f32 gradients.
+ * List form: `tensors` is a device array of pt_adam_master_tensor (every pointer 16-byte aligned,
+ * all gradients of the launch of one dtype), chunk_start / total_chunks as for pt_adamw_step_multi.
+ * Single-tensor form: any alignment.  The *_clip forms and pt_grad_sq_master_multi (the sum of
+ * squares over the grad field of the list) behave as their pt_adam_tensor namesakes above. */
+typedef struct {
+  float* master;
+  void* param;      /* bf16, written only */
+  const void* grad; /* bf16 or f32 */
+  float* exp_avg;
+  float* exp_avg_sq;
+  int64_t n;
+} pt_adam_master_tensor;
+int pt_adamw_master_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                               int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                               float step_size, hipStream_t stream);
+int pt_adamw_master_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors,
+                                    int64_t total_chunks, int grad_dtype, float decay, float w1, float beta2, float c2,
+                                    float bc2_sqrt, float eps, float step_size, const float* grad_sq, float max_norm,
+                                    int* status, hipStream_t stream);
+int pt_adamw_master_step(float* master, void* param, const void* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                         int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                         float step_size, hipStream_t stream);
+int pt_adamw_master_step_clip(float* master, void* param, const void* grad, float* exp_avg, float* exp_avg_sq,
+                              int64_t n, int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt,
+                              float eps, float step_size, const float* grad_sq, float max_norm, int* status,
+                              hipStream_t stream);
+int pt_grad_sq_master_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                            int grad_dtype, float weight, int accumulate, float* workspace, float* sq,
+                            hipStream_t stream);
+
 /* ---- bf16 GEMM, f32 accumulate -------------------------------------------------------------
  * replaces every F.linear / matmul of the layer: model.py:124-126,161,186,270,
  * tensor_parallel.py:186, tp_communications.py:79,93,98,105.

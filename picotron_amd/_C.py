@@ -49,6 +49,14 @@ SIGNATURES = {
                                   _vp, _vp]),
     "pt_adamw_step_multi_clip": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _f32, _vp,
                                         _vp]),
+    "pt_adamw_master_step_multi": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "pt_adamw_master_step_multi_clip": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                               _vp, _f32, _vp, _vp]),
+    "pt_adamw_master_step": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                    _vp]),
+    "pt_adamw_master_step_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32,
+                                         _f32, _vp, _f32, _vp, _vp]),
+    "pt_grad_sq_master_multi": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
     "pt_rmsnorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pt_rmsnorm_colsum_batch": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "pt_rmsnorm_bwd_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),

@@ -18,7 +18,8 @@
 // Also here, because they walk the same tensor table: global gradient-norm clipping
 // (torch.nn.utils.clip_grad_norm_ in front of the step) -- the f32 sum of squares of every
 // gradient, and the clip coefficient applied where the AdamW kernels load the gradient (a
-// compile-time variant of each) or in place.
+// compile-time variant of each) or in place.  And the opt-in mixed-precision form of the step: f32
+// master weights and moments behind the bf16 parameters (adamw_master_* below).
 #include "common.h"
 
 namespace {
@@ -229,8 +230,8 @@ __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor*
 // ---- sum of squares of the gradients (the global norm) and the in-place scale ---------------
 // Both walk the AdamW table the same way and touch only its grad field: workgroup b's run of
 // chunks, tensor by tensor; fn(T, from, to) gets the run's chunk range inside tensor T.
-template <typename F>
-__device__ __forceinline__ void for_each_run(const AdamTensor* __restrict__ ts, const int64_t* __restrict__ chunk_start,
+template <typename TT, typename F>
+__device__ __forceinline__ void for_each_run(const TT* __restrict__ ts, const int64_t* __restrict__ chunk_start,
                                              int nt, int64_t per_block, F fn) {
   const int64_t total = chunk_start[nt];
   const int64_t lo = (int64_t)blockIdx.x * per_block;
@@ -362,6 +363,189 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(T* __restrict__ grad, i
   }
 }
 
+// ---- fp32 master weights and moments (optim.AdamW(master_weights=True)) ----------------------
+// The mixed-precision recipe on top of the bf16 one above: the optimizer owns an f32 copy of every
+// bf16 weight and both moments in f32, updates them with torch's foreach *f32* AdamW sequence (no
+// rounding between the ops) and publishes param = bf16(master), round to nearest even.  In bf16
+// state v * 0.999 rounds back to v (1 - beta2 is below half an ulp) and an update below half an
+// ulp of the weight is lost; here neither happens.  The gradient is bf16 or f32 (a property of
+// the launch); with clipping it is scaled in f32 as it is loaded and never rounded to bf16.
+// Traffic per parameter: master, grad, m, v read (14 / 16 B), master, param, m, v written (14 B).
+struct AdamMasterTensor {   // pt_adam_master_tensor (include/picotron_hip.h)
+  float* w;
+  uint16_t* p;
+  const void* g;
+  float* m;
+  float* v;
+  int64_t n;
+};
+
+// The f32 sequence (adam_elem with bf = false) with its contraction spelled out: a fused
+// multiply-add where torch's lerp / addcmul / addcdiv kernels have one, everything else rounded on
+// its own.  Nothing is left to the compiler, so the bf16- and the f32-gradient instantiations,
+// clipped or not, list or single tensor, are the same arithmetic on the same f32 inputs and give
+// the same bits.
+__device__ __forceinline__ void adam_elem_master(float& p, float g, float& m, float& v, const AdamScalars& s) {
+#pragma clang fp contract(off)
+  p = p * s.decay;
+  m = fmaf(s.w1, g - m, m);
+  v = v * s.beta2;
+  v = fmaf(s.c2, g * g, v);
+  float d = sqrtf(v);
+  d = d / s.bc2s;
+  d = d + s.eps;
+  p = fmaf(s.step, m / d, p);
+}
+
+// 8 x f32 as two 16-byte vectors, non-temporal
+typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) pt_f32x4 pt_g_f32x4;
+struct f32x8 { pt_f32x4 lo, hi; };
+__device__ __forceinline__ f32x8 ld8f_nt(const float* p) {
+  return f32x8{__builtin_nontemporal_load((const pt_g_f32x4*)(p)), __builtin_nontemporal_load((const pt_g_f32x4*)(p + 4))};
+}
+__device__ __forceinline__ void st8f_nt(float* p, const f32x8& x) {
+  __builtin_nontemporal_store(x.lo, (pt_g_f32x4*)(p));
+  __builtin_nontemporal_store(x.hi, (pt_g_f32x4*)(p + 4));
+}
+__device__ __forceinline__ void unpack8(const f32x8& x, float* f) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { f[j] = x.lo[j]; f[4 + j] = x.hi[j]; }
+}
+__device__ __forceinline__ f32x8 pack8f(const float* f) {
+  return f32x8{pt_f32x4{f[0], f[1], f[2], f[3]}, pt_f32x4{f[4], f[5], f[6], f[7]}};
+}
+// a chunk of the gradient stream in its storage type
+template <typename GT> struct GradVec;
+template <> struct GradVec<uint16_t> {
+  typedef bf16x8 type;
+  static __device__ __forceinline__ type ld(const uint16_t* p) { return ld8_nt(p); }
+};
+template <> struct GradVec<float> {
+  typedef f32x8 type;
+  static __device__ __forceinline__ type ld(const float* p) { return ld8f_nt(p); }
+};
+
+template <bool CLIP>
+__device__ __forceinline__ void master_elem(float& w, float g, float& m, float& v, const AdamScalars& s, float coef) {
+  if constexpr (CLIP) g = clip_grad(g, coef, false);
+  adam_elem_master(w, g, m, v, s);
+}
+
+// One launch over the list.  Seven or eight 16-byte loads and seven stores per chunk: ONE chunk
+// ahead (the bf16 kernel's two would need 3 x 32 data registers and drop the launch below four
+// blocks per CU); the next chunk's loads are issued before the current chunk's stores, so a wait
+// for a load never sits behind a store.  __launch_bounds__(256, 4): at most 128 VGPRs, the 1024
+// blocks of multi_grid are one resident round.
+template <typename GT, bool CLIP>
+__global__ __launch_bounds__(256, 4) void adamw_master_multi_kernel(const AdamMasterTensor* __restrict__ ts,
+                                                                    const int64_t* __restrict__ chunk_start, int nt,
+                                                                    int64_t per_block, AdamScalars s,
+                                                                    ClipArgs<CLIP> clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
+  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamMasterTensor& T, int64_t from, int64_t to) {
+    const GT* G = (const GT*)T.g;
+    const int64_t full = T.n >> 3;
+    const int64_t end = to < full ? to : full;   // this run's full chunks in tensor T
+    const int64_t bd = blockDim.x;
+    int64_t c = from + threadIdx.x;
+    f32x8 cw, cm, cv, nw, nm, nv;
+    typename GradVec<GT>::type cg, ng;
+    if (c < end) {
+      cw = ld8f_nt(T.w + c * 8); cg = GradVec<GT>::ld(G + c * 8); cm = ld8f_nt(T.m + c * 8); cv = ld8f_nt(T.v + c * 8);
+    }
+    for (; c < end; c += bd) {
+      const int64_t n1 = c + bd;
+      if (n1 < end) {
+        nw = ld8f_nt(T.w + n1 * 8); ng = GradVec<GT>::ld(G + n1 * 8); nm = ld8f_nt(T.m + n1 * 8);
+        nv = ld8f_nt(T.v + n1 * 8);
+      }
+      float w[8], g[8], m[8], v[8];
+      unpack8(cw, w); unpack8(cg, g); unpack8(cm, m); unpack8(cv, v);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) master_elem<CLIP>(w[j], g[j], m[j], v[j], s, coef);
+      st8f_nt(T.w + c * 8, pack8f(w));
+      st8_nt(T.p + c * 8, pack8(w));
+      st8f_nt(T.m + c * 8, pack8f(m));
+      st8f_nt(T.v + c * 8, pack8f(v));
+      cw = nw; cg = ng; cm = nm; cv = nv;
+    }
+    if (to > full && threadIdx.x == 0) {   // the ragged last chunk
+      for (int64_t i = full * 8; i < T.n; ++i) {
+        float w = T.w[i], m = T.m[i], v = T.v[i];
+        master_elem<CLIP>(w, ld_as_f(G, i), m, v, s, coef);
+        T.w[i] = w;
+        T.p[i] = f2bf(w);
+        T.m[i] = m;
+        T.v[i] = v;
+      }
+    }
+  });
+}
+
+// one tensor at any alignment (unaligned views, what the list form refuses): element by element
+template <typename GT, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_master_scalar_kernel(float* __restrict__ master, uint16_t* __restrict__ param,
+                                                                  const GT* __restrict__ grad, float* __restrict__ em,
+                                                                  float* __restrict__ ev, int64_t n, AdamScalars s,
+                                                                  ClipArgs<CLIP> clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float w = master[i], m = em[i], v = ev[i];
+    master_elem<CLIP>(w, ld_as_f(grad, i), m, v, s, coef);
+    master[i] = w;
+    param[i] = f2bf(w);
+    em[i] = m;
+    ev[i] = v;
+  }
+}
+
+__device__ __forceinline__ float sq8(const f32x8& x, float acc) {
+  float g[8];
+  unpack8(x, g);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc = fmaf(g[j], g[j], acc);
+  return acc;
+}
+
+// grad_sq_multi_kernel over the grad field of the master table, bf16 or f32 gradients: the same
+// walk, the same four accumulators, the same fixed order
+template <typename GT>
+__global__ __launch_bounds__(256) void grad_sq_master_multi_kernel(const AdamMasterTensor* __restrict__ ts,
+                                                                   const int64_t* __restrict__ chunk_start, int nt,
+                                                                   int64_t per_block, float* __restrict__ partial) {
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamMasterTensor& T, int64_t from, int64_t to) {
+    const GT* G = (const GT*)T.g;
+    const int64_t full = T.n >> 3;
+    const int64_t end = to < full ? to : full;
+    const int64_t bd = blockDim.x;
+    int64_t c = from + threadIdx.x;
+    for (; c + 3 * bd < end; c += 4 * bd) {
+      typename GradVec<GT>::type x[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[q] = GradVec<GT>::ld(G + (c + q * bd) * 8);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = sq8(x[q], acc[q]);
+    }
+    for (int q = 0; c < end; c += bd, ++q) acc[q & 3] = sq8(GradVec<GT>::ld(G + c * 8), acc[q & 3]);
+    if (to > full && threadIdx.x == 0) {   // the ragged last chunk
+      for (int64_t i = full * 8; i < T.n; ++i) {
+        const float g = ld_as_f(G, i);
+        acc[3] = fmaf(g, g, acc[3]);
+      }
+    }
+  });
+  const float sum = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
 int grid_for(int64_t work) {
   int64_t g = (work + 255) / 256;
   return (int)(g < PT_STREAM_GRID_CAP ? (g < 1 ? 1 : g) : PT_STREAM_GRID_CAP);
@@ -377,6 +561,38 @@ MultiGrid multi_grid(int64_t total_chunks, int64_t cap = 1024) {
   const int64_t want = (total_chunks + 511) / 512;
   const int64_t blocks = want < 1 ? 1 : (want < cap ? want : cap);
   return {(unsigned)blocks, (total_chunks + blocks - 1) / blocks};
+}
+
+
+// the master-weight launches, one body for the clipped and the unclipped entry point
+template <bool CLIP>
+int master_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks, int grad_dtype,
+                 const AdamScalars& s, const ClipArgs<CLIP>& clip, hipStream_t stream) {
+  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || (grad_dtype != 0 && grad_dtype != 1))
+    return PT_EINVAL;
+  if (total_chunks == 0) return PT_OK;
+  const MultiGrid g = multi_grid(total_chunks);
+  const auto* ts = (const AdamMasterTensor*)tensors;
+  if (grad_dtype == 0)
+    adamw_master_multi_kernel<uint16_t, CLIP><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, s, clip);
+  else
+    adamw_master_multi_kernel<float, CLIP><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, s, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+template <bool CLIP>
+int master_single(float* master, void* param, const void* grad, float* m, float* v, int64_t n, int grad_dtype,
+                  const AdamScalars& s, const ClipArgs<CLIP>& clip, hipStream_t stream) {
+  if (!master || !param || !grad || !m || !v || n < 0 || (grad_dtype != 0 && grad_dtype != 1)) return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  if (grad_dtype == 0)
+    adamw_master_scalar_kernel<uint16_t, CLIP><<<grid_for(n), 256, 0, stream>>>(master, (uint16_t*)param,
+                                                                                (const uint16_t*)grad, m, v, n, s, clip);
+  else
+    adamw_master_scalar_kernel<float, CLIP><<<grid_for(n), 256, 0, stream>>>(master, (uint16_t*)param,
+                                                                             (const float*)grad, m, v, n, s, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
 }
 
 }  // namespace
@@ -533,6 +749,63 @@ int pt_adamw_step_multi_clip(const void* tensors, const int64_t* chunk_start, in
   const MultiGrid g = multi_grid(total_chunks);
   adamw_multi_bf16_kernel<true><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
                                                              g.per_block, s, ClipArgs<true>{grad_sq, max_norm, status});
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+// ---- fp32 master weights --------------------------------------------------------------------
+int pt_adamw_master_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                               int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                               float step_size, hipStream_t stream) {
+  return master_multi<false>(tensors, chunk_start, ntensors, total_chunks, grad_dtype,
+                             AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, {}, stream);
+}
+
+int pt_adamw_master_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors,
+                                    int64_t total_chunks, int grad_dtype, float decay, float w1, float beta2, float c2,
+                                    float bc2_sqrt, float eps, float step_size, const float* grad_sq, float max_norm,
+                                    int* status, hipStream_t stream) {
+  if (!grad_sq || !(max_norm > 0.0f)) return PT_EINVAL;
+  return master_multi<true>(tensors, chunk_start, ntensors, total_chunks, grad_dtype,
+                            AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size},
+                            ClipArgs<true>{grad_sq, max_norm, status}, stream);
+}
+
+int pt_adamw_master_step(float* master, void* param, const void* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
+                         int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                         float step_size, hipStream_t stream) {
+  return master_single<false>(master, param, grad, exp_avg, exp_avg_sq, n, grad_dtype,
+                              AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, {}, stream);
+}
+
+int pt_adamw_master_step_clip(float* master, void* param, const void* grad, float* exp_avg, float* exp_avg_sq,
+                              int64_t n, int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt,
+                              float eps, float step_size, const float* grad_sq, float max_norm, int* status,
+                              hipStream_t stream) {
+  if (!grad_sq || !(max_norm > 0.0f)) return PT_EINVAL;
+  return master_single<true>(master, param, grad, exp_avg, exp_avg_sq, n, grad_dtype,
+                             AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size},
+                             ClipArgs<true>{grad_sq, max_norm, status}, stream);
+}
+
+int pt_grad_sq_master_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                            int grad_dtype, float weight, int accumulate, float* workspace, float* sq,
+                            hipStream_t stream) {
+  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !workspace || !sq ||
+      (grad_dtype != 0 && grad_dtype != 1))
+    return PT_EINVAL;
+  unsigned blocks = 0;
+  if (total_chunks) {
+    const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+    const auto* ts = (const AdamMasterTensor*)tensors;
+    blocks = g.blocks;
+    if (grad_dtype == 0)
+      grad_sq_master_multi_kernel<uint16_t><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
+    else
+      grad_sq_master_multi_kernel<float><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
+    PT_CHECK_LAUNCH();
+  }
+  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, (int)blocks, weight, accumulate, sq);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

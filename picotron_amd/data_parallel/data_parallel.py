@@ -85,6 +85,10 @@ class DataParallelBucket(nn.Module):
         self.register_backward_hook()
         _cp_averaged(module)
         self._post_backward_callback_set = False
+        # False: the averaged main_grad stays the only gradient (p.grad is left None) -- for
+        # optim.AdamW(master_weights=True, use_main_grad=True), which reads it unrounded and saves
+        # the cast pass over every parameter.  An attribute, so the constructor stays the reference's.
+        self.publish_grad = True
 
     def forward(self, *inputs, **kwargs):
         return self.module(*inputs, **kwargs)
@@ -135,6 +139,8 @@ class DataParallelBucket(nn.Module):
     def _post_backward(self):
         self.bucket_manager.wait()
         self._post_backward_callback_set = False
+        if not self.publish_grad:
+            return
         for p in self.module.parameters():
             if p.requires_grad:
                 p.grad = p.main_grad.to(p.dtype)

@@ -221,17 +221,17 @@ _ADAM_DESC = {}
 
 def _adam_desc(items):
     """(device pt_adam_tensor table, device chunk_start, total chunks) of a list of 4-tuples of
-    tensors, cached per pointer set (the tensors of a model stay put across steps; a re-allocated
+    tensors (5-tuples: the pt_adam_master_tensor table), cached per pointer set (the tensors of a model stay put across steps; a re-allocated
     gradient makes a new table).  A new table is staged in pinned host memory and copied on the
     current stream without a host sync (the caching host allocator keeps the staging buffer alive
     until that copy has run)."""
-    key = tuple((p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()) for p, g, m, v in items)
+    key = tuple(tuple(t.data_ptr() for t in it) + (it[0].numel(),) for it in items)
     ent = _ADAM_DESC.get(key)
     if ent is None:
         dev = items[0][0].device
         chunks = [0]
         for k in key:
-            chunks.append(chunks[-1] + (k[4] + 7) // 8)
+            chunks.append(chunks[-1] + (k[-1] + 7) // 8)
         desc_h = torch.tensor([list(k) for k in key], dtype=torch.int64).pin_memory()
         chunk_h = torch.tensor(chunks, dtype=torch.int64).pin_memory()
         ent = (desc_h.to(dev, non_blocking=True), chunk_h.to(dev, non_blocking=True), chunks[-1])
@@ -308,7 +308,8 @@ def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
     """out[0] (+)= weight * sum of g^2, in f32 and bit-reproducible (csrc/adamw.hip: per-workgroup
     partials, then one workgroup sums them in a fixed order).  items: bf16 (param, grad, exp_avg,
     exp_avg_sq) tuples as adamw_step_multi takes them -- one launch over the list on the SAME cached
-    table, of which only the grad field is read (gradients alone: (g, g, g, g)); tensors: single
+    table, of which only the grad field is read (gradients alone: (g, g, g, g)), or the (master, param,
+    grad, exp_avg, exp_avg_sq) tuples of adamw_master_step_multi, bf16 or f32 gradients; tensors: single
     gradients of what the list form does not take (f32, unaligned bf16).  Everything accumulates
     into the one device scalar in stream order; returns it (a [1] f32 tensor)."""
     items, tensors = list(items), list(tensors)
@@ -319,7 +320,14 @@ def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
         out = torch.empty(1, dtype=torch.float32, device=dev)
     _sq_ok(out, dev)
     ws, lib, acc = _grad_ws(dev), _C.lib(), bool(accumulate)
-    if items:
+    if items and len(items[0]) == 5:   # the master-weight list (adamw_master_step_multi's items)
+        gdt = _adam_master_items_ok(items)
+        desc, chunk_t, total = _adam_desc(items)
+        rc = lib.pt_grad_sq_master_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), gdt, float(weight),
+                                         int(acc), _ptr(ws), _ptr(out), _C.stream_ptr(dev))
+        _C.check(rc, "pt_grad_sq_master_multi")
+        acc = True
+    elif items:
         _adam_items_ok(items)
         desc, chunk_t, total = _adam_desc(items)
         rc = lib.pt_grad_sq_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(weight), int(acc),
@@ -385,6 +393,79 @@ def adamw_step_clip(p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2
                                          float(bc2_sqrt), float(eps), float(step_size), _ptr(sq), float(max_norm), st,
                                          _C.stream_ptr(p.device))
         _C.check(rc, "pt_adamw_step_clip")
+
+
+# ----------------------------------------------------- AdamW, fp32 master weights and moments
+def _adam_master_ok(w, p, g, m, v, what):
+    """One (master, param, grad, exp_avg, exp_avg_sq) entry; returns the gradient's dtype code."""
+    _req(p.dtype == BF16 and w.dtype == m.dtype == v.dtype == torch.float32,
+         f"{what}: a bf16 parameter with f32 master, exp_avg and exp_avg_sq")
+    _req(g.dtype in (BF16, torch.float32), f"{what}: bf16 or f32 gradients")
+    for t in (w, p, g, m, v):
+        _req(t.is_cuda and t.device == p.device and t.is_contiguous() and t.numel() == p.numel(),
+             f"{what}: contiguous device tensors of one length per parameter")
+    return 0 if g.dtype == BF16 else 1
+
+
+def _adam_master_items_ok(items):
+    _req(len(items) > 0, "adamw master multi: an empty tensor list")
+    gdt = None
+    for it in items:
+        d = _adam_master_ok(*it, "adamw master multi")
+        _req(gdt in (None, d), "adamw master multi: the gradients of one launch share a dtype")
+        gdt = d
+        _req(all(t.data_ptr() % 16 == 0 for t in it), "adamw master multi: 16-byte aligned tensors")
+    return gdt
+
+
+def adamw_master_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
+    """One launch of the AdamW update with f32 master weights and moments over a list of (master f32,
+    param bf16, grad bf16 | f32, exp_avg f32, exp_avg_sq f32) tuples (pt_adamw_master_step_multi):
+    torch's foreach f32 AdamW on the masters, then param = bf16(master).  The gradients of one list
+    share a dtype.  The descriptor table is cached as adamw_step_multi's."""
+    gdt = _adam_master_items_ok(items)
+    desc, chunk_t, total = _adam_desc(items)
+    rc = _C.lib().pt_adamw_master_step_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), gdt, float(decay),
+                                             float(w1), float(beta2), float(c2), float(bc2_sqrt), float(eps),
+                                             float(step_size), _C.stream_ptr(items[0][0].device))
+    _C.check(rc, "pt_adamw_master_step_multi")
+
+
+def adamw_master_step_multi_clip(items, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
+    """adamw_master_step_multi on float(grad) * coef, coef as in grad_scale_multi: one f32 product,
+    not rounded to bf16; the gradients are not modified.  A non-finite sq skips the update."""
+    gdt = _adam_master_items_ok(items)
+    dev = items[0][0].device
+    _sq_ok(sq, dev)
+    desc, chunk_t, total = _adam_desc(items)
+    with _clip_status(dev, status) as st:
+        rc = _C.lib().pt_adamw_master_step_multi_clip(_ptr(desc), _ptr(chunk_t), len(items), int(total), gdt,
+                                                      float(decay), float(w1), float(beta2), float(c2),
+                                                      float(bc2_sqrt), float(eps), float(step_size), _ptr(sq),
+                                                      float(max_norm), st, _C.stream_ptr(dev))
+        _C.check(rc, "pt_adamw_master_step_multi_clip")
+
+
+def adamw_master_step(master, p, grad, exp_avg, exp_avg_sq, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
+    """adamw_master_step_multi for one parameter at any alignment (element by element, the same math)."""
+    gdt = _adam_master_ok(master, p, grad, exp_avg, exp_avg_sq, "adamw master")
+    rc = _C.lib().pt_adamw_master_step(_ptr(master), _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(),
+                                       gdt, float(decay), float(w1), float(beta2), float(c2), float(bc2_sqrt),
+                                       float(eps), float(step_size), _C.stream_ptr(p.device))
+    _C.check(rc, "pt_adamw_master_step")
+
+
+def adamw_master_step_clip(master, p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps,
+                           step_size, status=None):
+    """adamw_master_step on the clipped gradient."""
+    gdt = _adam_master_ok(master, p, grad, exp_avg, exp_avg_sq, "adamw master")
+    _sq_ok(sq, p.device)
+    with _clip_status(p.device, status) as st:
+        rc = _C.lib().pt_adamw_master_step_clip(_ptr(master), _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                                p.numel(), gdt, float(decay), float(w1), float(beta2), float(c2),
+                                                float(bc2_sqrt), float(eps), float(step_size), _ptr(sq),
+                                                float(max_norm), st, _C.stream_ptr(p.device))
+        _C.check(rc, "pt_adamw_master_step_clip")
 
 
 # ------------------------------------------------------------------------------------ RoPE

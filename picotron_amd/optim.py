@@ -10,7 +10,12 @@ Global gradient-norm clipping (what a Llama recipe puts between the backward and
 torch.nn.utils.clip_grad_norm_) is part of the step: AdamW(..., max_grad_norm=M), or the stand-alone
 clip_grad_norm_ below.  Both compute ONE norm for the whole model -- over tensor- and pipeline-
 parallel ranks too -- in f32 on the device, and nothing of it is read on the host.
+
+AdamW(..., master_weights=True) is the mixed-precision recipe on top (opt-in; not torch's layout): an
+f32 `master_param` and f32 moments in the state of every bf16 parameter, one multi-tensor launch.
 """
+import itertools
+
 import torch
 import torch.distributed as dist
 
@@ -49,8 +54,9 @@ def _listable(*tensors):
 
 def _global_sq(batches):
     """batches: [(multi, [(param, x)])] -- multi: every x is a (param, grad, exp_avg, exp_avg_sq)
-    tuple and the batch is one multi-tensor list (summed on the descriptor table its AdamW launch
-    uses); else every x is a single gradient.  Returns the [1] f32 device scalar holding the squared
+    tuple (or a master-weight list's (master, param, grad, exp_avg, exp_avg_sq)) and the batch is one
+    multi-tensor list (summed on the descriptor table its AdamW launch uses); else every x is a
+    single gradient.  Returns the [1] f32 device scalar holding the squared
     L2 norm over all of them and over the model-parallel grid (grad_norm_plan), or None if there is
     no gradient."""
     m = pgm.current()
@@ -91,25 +97,41 @@ class AdamW(torch.optim.Optimizer):
     bit-unchanged and a status bit is set, which the next kernels.check_device_status /
     train.read_step_loss raises as HipKernelError.  (Deliberately not torch: clip_grad_norm_ with
     error_if_nonfinite=False would scale by NaN and the step would write NaN into every weight.)
-    The host cannot know of the skip without a synchronisation, so state['step'] still counts it."""
+    The host cannot know of the skip without a synchronisation, so state['step'] still counts it.
+
+    master_weights=True (opt-in; the default is the reference's recipe): every bf16 parameter gets an
+    f32 `master_param` in its state (from p.float() at the first step) and f32 `exp_avg` /
+    `exp_avg_sq`; the step is torch's foreach f32 AdamW on the masters and p = bf16(master), in one
+    launch over all such parameters that share a step count and a gradient dtype.  (In bf16 state
+    exp_avg_sq * 0.999 rounds back to itself and updates below half an ulp of a weight are lost.)
+    Gradients may be bf16 or f32; with max_grad_norm the coefficient multiplies the f32 gradient.
+    f32 parameters take the ordinary f32 path.  use_main_grad=True (needs master_weights): a
+    parameter with a `main_grad` attribute (DataParallelBucket's f32 accumulator, with
+    publish_grad=False the only gradient) is stepped on that tensor and its p.grad is ignored."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 maximize=False, max_grad_norm=None):
+                 maximize=False, max_grad_norm=None, master_weights=False, use_main_grad=False):
         if amsgrad or maximize:
             raise ValueError("picotron_amd.optim.AdamW: amsgrad / maximize are not used by picotron (train.py:209)")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"invalid AdamW hyper-parameters lr={lr} betas={betas} eps={eps}")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"invalid AdamW max_grad_norm={max_grad_norm}: a positive number or None")
+        if use_main_grad and not master_weights:
+            raise ValueError("AdamW(use_main_grad=True) needs master_weights=True: the bf16-state step takes the "
+                             "gradient in the parameter's dtype, p.grad")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.last_grad_norm = None
+        self.master_weights = bool(master_weights)
+        self.use_main_grad = bool(use_main_grad)
 
     @torch.no_grad()
     def step(self, closure=None):
         """torch.optim.AdamW.step (foreach, decoupled weight decay) on the HIP kernel: the bf16 tensors
         that share a step count go through ONE multi-tensor launch; anything else (f32, unaligned)
-        per tensor."""
+        per tensor.  master_weights: the bf16 tensors that share a step count and a gradient dtype
+        go through one master-weight launch."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -118,58 +140,150 @@ class AdamW(torch.optim.Optimizer):
             self._step_clipped()
             return loss
         for group in self.param_groups:
-            for sc, multi, items in self._batches(group):
-                if multi:
+            for sc, kind, items in self._batches(group):
+                if kind == MULTI:
                     K.adamw_step_multi(items, **sc)
-                else:
+                elif kind == SINGLE:
                     for p, g, m, v in items:
                         K.adamw_step(p, g, m, v, **sc)
+                elif kind == MASTER_MULTI:
+                    K.adamw_master_step_multi(items, **sc)
+                else:
+                    for it in items:
+                        _master_single(K.adamw_master_step, it, **sc)
         return loss
 
+    def _grad(self, p):
+        """The gradient step() consumes: p.main_grad (DataParallelBucket's averaged accumulator, bf16
+        or f32) with use_main_grad where the parameter has one, else p.grad."""
+        if self.use_main_grad and getattr(p, "main_grad", None) is not None:
+            return p.main_grad
+        return p.grad
+
     def _batches(self, group):
-        """[(kernel scalars, multi, [(param, grad, exp_avg, exp_avg_sq)])] of one param group; counts
-        the step."""
+        """[(kernel scalars, kind, items)] of one param group; counts the step.  kind MULTI / SINGLE:
+        items are (param, grad, exp_avg, exp_avg_sq), one list launch / one launch each.
+        MASTER_MULTI / MASTER_SINGLE (master_weights, bf16 parameters): items are (master_param,
+        param, grad, exp_avg, exp_avg_sq); a batch shares the step count and the gradient dtype."""
         lr, (beta1, beta2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
         batches = {}
         for p in group["params"]:
-            if p.grad is None:
+            grad = self._grad(p)
+            if grad is None:
                 continue
-            if p.grad.is_sparse:
+            if grad.is_sparse:
                 raise RuntimeError("AdamW does not support sparse gradients")
+            master = self.master_weights and p.dtype == torch.bfloat16
             st = self.state[p]
             if len(st) == 0:
                 st["step"] = torch.tensor(0.0, dtype=torch.float32)
-                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if master:
+                    st["exp_avg"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+                    st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.float32, device=p.device)
+                else:
+                    st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            if master and "master_param" not in st:   # the first step, or a state loaded without masters
+                st["master_param"] = p.detach().float().contiguous()
             st["step"] += 1
             t = st["step"].item()
-            item = (p, p.grad, st["exp_avg"], st["exp_avg_sq"])
-            multi = p.dtype == torch.bfloat16 and all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) \
-                and p.grad.dtype == p.dtype
-            batches.setdefault((t, multi), []).append(item)
+            if master:
+                item = (st["master_param"], p, grad, st["exp_avg"], st["exp_avg_sq"])
+                kind = MASTER_MULTI if all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) else MASTER_SINGLE
+                batches.setdefault((t, kind, grad.dtype), []).append(item)
+            else:
+                item = (p, grad, st["exp_avg"], st["exp_avg_sq"])
+                multi = p.dtype == torch.bfloat16 and all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) \
+                    and grad.dtype == p.dtype
+                batches.setdefault((t, MULTI if multi else SINGLE, None), []).append(item)
         out = []
-        for (t, multi), items in batches.items():
+        for (t, kind, _), items in batches.items():
             bc1 = 1 - beta1 ** t
             bc2 = 1 - beta2 ** t
             sc = dict(decay=1 - lr * wd, w1=1 - beta1, beta2=beta2, c2=1 - beta2, bc2_sqrt=bc2 ** 0.5, eps=eps,
                       step_size=(lr / bc1) * -1)
-            out.append((sc, multi, items))
+            out.append((sc, kind, items))
         return out
 
     def _step_clipped(self):
         work = [b for group in self.param_groups for b in self._batches(group)]
-        sq = _global_sq([(multi, [(it[0], it if multi else it[1]) for it in items]) for _, multi, items in work])
+        norm_batches = []
+        for _, kind, items in work:   # (param, what grad_sqnorm takes for it): see _global_sq
+            if kind in (MULTI, MASTER_MULTI):
+                norm_batches.append((True, [(it[0] if kind == MULTI else it[1], it) for it in items]))
+            else:
+                norm_batches.append((False, [(it[0], it[1]) if kind == SINGLE else (it[1], it[2].contiguous())
+                                             for it in items]))
+        sq = _global_sq(norm_batches)
         if sq is None:   # no gradients at all
             return
         self.last_grad_norm = sq.sqrt().reshape(())
         status = K.status_word(sq.device)   # one word, posted once: see kernels._clip_status
-        for sc, multi, items in work:
-            if multi:
+        for sc, kind, items in work:
+            if kind == MULTI:
                 K.adamw_step_multi_clip(items, sq, self.max_grad_norm, status=status, **sc)
-            else:
+            elif kind == SINGLE:
                 for p, g, m, v in items:
                     K.adamw_step_clip(p, g, m, v, sq, self.max_grad_norm, status=status, **sc)
+            elif kind == MASTER_MULTI:
+                K.adamw_master_step_multi_clip(items, sq, self.max_grad_norm, status=status, **sc)
+            else:
+                for it in items:
+                    _master_single(K.adamw_master_step_clip, it, sq, self.max_grad_norm, status=status, **sc)
         K._status_posted(sq.device)
+
+    @torch.no_grad()
+    def sync_master_from_params(self):
+        """Re-read every master weight from its bf16 parameter: for a caller that overwrites weights
+        (loads a checkpoint into the model, copies from another rank) after the first step()."""
+        for st_p, st in self.state.items():
+            if isinstance(st, dict) and "master_param" in st:
+                st["master_param"].copy_(st_p.detach().reshape(st["master_param"].shape))
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict, which casts every floating-point state tensor to the
+        parameter's dtype -- with master_weights the f32 `master_param`, `exp_avg` and `exp_avg_sq`
+        of a bf16 parameter are put back from the saved dict afterwards, bit for bit.  A bf16-state
+        dict (master_weights=False) loads into master_weights=True: the moments are widened and the
+        masters are taken from the parameters at the next step.  The other direction is refused."""
+        saved = list(itertools.chain.from_iterable(g["params"] for g in state_dict["param_groups"]))
+        mine = list(itertools.chain.from_iterable(g["params"] for g in self.param_groups))
+        pairs = [(state_dict["state"][k], p) for k, p in zip(saved, mine) if k in state_dict["state"]]
+        if not self.master_weights:
+            for s, p in pairs:
+                f32 = [k for k in ("exp_avg", "exp_avg_sq") if torch.is_tensor(s.get(k)) and s[k].dtype == torch.float32]
+                if p.dtype == torch.bfloat16 and ("master_param" in s or f32):
+                    raise ValueError("AdamW.load_state_dict: the state holds f32 master weights / moments of a bf16 "
+                                     "parameter (saved with master_weights=True); this optimizer has "
+                                     "master_weights=False and would round them to bf16 -- construct it with "
+                                     "master_weights=True")
+        super().load_state_dict(state_dict)
+        if self.master_weights:
+            for s, p in pairs:
+                if torch.is_tensor(self.state[p].get("step")):
+                    # torch hands the saved `step` tensor through as it is; a live optimizer's
+                    # state_dict() loaded here would share (and double-count) it
+                    self.state[p]["step"] = self.state[p]["step"].clone()
+                if p.dtype != torch.bfloat16:
+                    continue
+                for k in ("master_param", "exp_avg", "exp_avg_sq"):
+                    if torch.is_tensor(s.get(k)):
+                        self.state[p][k] = s[k].detach().to(device=p.device, dtype=torch.float32, copy=True).contiguous()
+
+
+MULTI, SINGLE, MASTER_MULTI, MASTER_SINGLE = "multi", "single", "master_multi", "master_single"
+
+
+def _master_single(fn, item, *args, **kw):
+    """One master-weight entry the list launch does not take: an unaligned view goes to the
+    single-tensor kernel as it is; a non-contiguous parameter or gradient through a dense copy."""
+    w, p, g, m, v = item
+    if p.is_contiguous():
+        fn(w, p, g.contiguous(), m, v, *args, **kw)
+    else:
+        dense = p.detach().contiguous()   # the current weights: a skipped (non-finite) step leaves them
+        fn(w, dense, g.contiguous(), m, v, *args, **kw)
+        p.copy_(dense)
 
 
 @torch.no_grad()

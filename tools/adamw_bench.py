@@ -4,8 +4,10 @@ pt_adamw_step_multi in the same process; --calib: beside it torch's fused AdamW 
 the HBM rate of torch's copy (1 read : 1 write) and add (2 : 1) over the same bytes, which bracket
 AdamW's 8 : 6 mix; --clip: global gradient-norm clipping -- (a) the plain step, (b) the norm pass alone
 (rate on 2 B per parameter, beside torch's x.sum() over the same bytes), (c) norm pass + clipped step,
-(c') the clipped step alone, (d) torch.nn.utils.clip_grad_norm_(foreach=True) + (a), alternating over three rounds in one call.
-python tools/adamw_bench.py [--old lib.so] [--calib] [--clip]"""
+(c') the clipped step alone, (d) torch.nn.utils.clip_grad_norm_(foreach=True) + (a), alternating over three rounds in one call;
+--master: fp32 master weights -- (a), the master step on bf16 / f32 gradients (28 / 30 B per parameter), the f32
+norm pass, and torch's fused f32 AdamW + a copy into the bf16 weights, alternating over three rounds in one call.
+python tools/adamw_bench.py [--old lib.so] [--calib] [--clip] [--master]"""
 import argparse
 import json
 import os
@@ -26,6 +28,7 @@ def main():
     ap.add_argument("--old", default="")
     ap.add_argument("--calib", action="store_true")
     ap.add_argument("--clip", action="store_true")
+    ap.add_argument("--master", action="store_true")
     a = ap.parse_args()
     H, I, V, L = 2048, 8192, 49152, 15
     shapes = [(V, H)] + [s for _ in range(L) for s in ((H,), (H, H), (H, H), (H, H), (H, H), (I, H), (I, H), (H, I), (H,))] + [(H,)]
@@ -50,6 +53,8 @@ def main():
         calib(items, n, args)
     if a.clip:
         clip(items, n, args)
+    if a.master:
+        master(items, n, args)
 
 
 def clip(items, n, args):
@@ -87,6 +92,46 @@ def clip(items, n, args):
     torch.cuda.synchronize()
     print(json.dumps({"clip": "grad norm", "value": round(float(sq.sqrt()), 4),
                       "status": K.device_status(dev)}), flush=True)
+
+
+def master(items, n, args):
+    """fp32 master weights: (a) today's bf16 step, (m16) / (m32) the master step on bf16 / f32 gradients
+    (28 / 30 B per parameter), (n32) the f32 norm pass alone (4 B), (t) what a user would do without the
+    kernel: torch._fused_adamw_ on f32 param / grad / moments, then _foreach_copy_ into the bf16 weights;
+    beside them torch's copy over the master step's bytes (1 read : 1 write, the step's own mix)."""
+    ps = [p for p, _, _, _ in items]
+    g16 = [g for _, g, _, _ in items]
+    ws = [p.float() for p in ps]
+    g32 = [g.float() for g in g16]
+    ms = [torch.zeros_like(w) for w in ws]
+    vs = [torch.zeros_like(w) for w in ws]
+    m16 = list(zip(ws, ps, g16, ms, vs))
+    m32 = list(zip(ws, ps, g32, ms, vs))
+    sq = torch.zeros(1, dtype=torch.float32, device=ps[0].device)
+    lr, wd, b1, b2, eps = args[6], 0.1, 0.9, args[2], args[5]
+    step = torch.tensor(3.0, device="cuda")
+
+    def torch_master():
+        torch._fused_adamw_(ws, g32, ms, vs, [], [step] * len(ws), lr=lr, beta1=b1, beta2=b2, weight_decay=wd, eps=eps,
+                            amsgrad=False, maximize=False)
+        torch._foreach_copy_(ps, ws)
+    x = torch.empty(7 * n, dtype=torch.bfloat16, device=ps[0].device).normal_()   # the master step's 14 B read,
+    y = torch.empty_like(x)                                                        # 14 B written, as one copy
+    variants = [("a: adamw_step_multi (bf16 state)", lambda: K.adamw_step_multi(items, *args), 14),
+                ("probe: torch copy 1r:1w over 28 B/param", lambda: y.copy_(x), 28),
+                ("m16: adamw_master_step_multi, bf16 grads", lambda: K.adamw_master_step_multi(m16, *args), 28),
+                ("m32: adamw_master_step_multi, f32 grads", lambda: K.adamw_master_step_multi(m32, *args), 30),
+                ("n32: grad_sqnorm, f32 grads", lambda: K.grad_sqnorm(items=m32, out=sq), 4),
+                ("t: torch._fused_adamw_ f32 + _foreach_copy_ to bf16", torch_master, None)]
+    for rnd in range(3):
+        for name, fn, bpp in variants:
+            us = graph_us(fn, 3)
+            rec = {"master": name, "round": rnd, "params": n, "us": round(us, 1)}
+            if bpp:
+                rec["TBps"] = round(bpp * n / us / 1e6, 2)
+            print(json.dumps(rec), flush=True)
+    torch.cuda.synchronize()
+    print(json.dumps({"master": "status", "value": K.device_status(ps[0].device)}), flush=True)
 
 
 def calib(items, n, args):

@@ -77,6 +77,8 @@ def listing(obj):
         m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
         if m:
             cur = code.setdefault(m.group(1), []) if m.group(1) in meta else None
+        elif cur is not None and line.strip() == "...":
+            pass   # zero padding up to the next symbol's alignment: depends on what follows the kernel
         elif cur is not None and line.startswith("\t"):
             cur.append(re.sub(r"\s*//.*$", "", line).strip())   # the comment: address, encoding, target symbol
     return {n: (code.get(n, []), meta[n]) for n in meta}
