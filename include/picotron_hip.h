@@ -418,6 +418,33 @@ int pt_attn_bwd_split(const void* q, const int64_t* q_str, const void* k, const 
                       const int64_t* dk_str, void* dv, const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV,
                       int64_t Sq, int64_t Sk, int64_t D, float scale, int causal, const void* rope_cos,
                       const void* rope_sin, int64_t rope_stride, void* ws, int64_t ws_bytes, hipStream_t stream);
+/* Band attention: document-masked ("varlen") and sliding-window causal attention, one mechanism.
+ * For batch row b, key j is visible to query i iff kv_lo[b, i] <= j <= i.  kv_lo: int32 [B, S],
+ * 0 <= kv_lo[b, i] <= i, non-decreasing in i -- the first token of i's document (documents packed
+ * back to back in one row), i - W + 1 for a window of W >= 1 keys, or the larger of the two.  q_hi:
+ * int32 [B, S], the key-side companion the dK/dV kernel walks: q_hi[b, j] = the first i with
+ * kv_lo[b, i] > j, or S (one past the last query that sees key j; non-decreasing, q_hi[b, j] > j).
+ * The two must describe the same mask; the kernels trust them (their tile ranges are clamped to the
+ * sequence, so a wrong bound gives a wrong mask, not a wrong address).  Positions for the fused RoPE
+ * inverse are sequence indices: RoPE scores depend on i - j only, so per-document position resets
+ * would give the same attention.
+ * pt_attn_fwd_band = pt_attn_fwd (causal, merge = 0, dense lse); pt_attn_bwd_band =
+ * pt_attn_bwd_fused_delta (causal, bf16 gradients, dense lse, optional RoPE inverse).  Sq == Sk,
+ * S % 128 == 0, D in {64, 128} (else PT_EUNSUPPORTED); a NULL bound is PT_EINVAL.  A refused call
+ * launches nothing.  With kv_lo = 0 everywhere (q_hi = S) the results are bit-identical to the causal
+ * kernels'.  The dK/dV kernel form follows "attn_split" as for causal calls; the few-head split forms
+ * are not used under a band. */
+int pt_attn_fwd_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H,
+                     int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, const int32_t* kv_lo,
+                     const int32_t* q_hi, hipStream_t stream);
+int pt_attn_bwd_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, const void* o, const int64_t* o_str, const void* dout,
+                     const int64_t* do_str, const float* lse, float* delta_out, void* dq, const int64_t* dq_str,
+                     void* dk, const int64_t* dk_str, void* dv, const int64_t* dv_str, int64_t B, int64_t H,
+                     int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, const void* rope_cos,
+                     const void* rope_sin, int64_t rope_stride, const int32_t* kv_lo, const int32_t* q_hi,
+                     hipStream_t stream);
 
 /* ---- measurement variants ------------------------------------------------------------------
  * Not a reference interface: selects between kernel forms with identical results, for A/B runs and

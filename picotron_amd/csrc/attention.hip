@@ -13,6 +13,16 @@
 // fused [T, (h + 2*hkv) * D] projection output -- no transposes, no copies.  lse is f32 [B, H, Sq]
 // with rows lse_ld apart (a slice of a longer sequence's LSE: the zig-zag ring's half blocks).
 // mask: 0 = full, 1 = causal (key j visible to query i iff j <= i; Sq == Sk).
+// Band kernels (pt_attn_fwd_band / pt_attn_bwd_band; the BAND instantiations of the block bodies):
+// document-masked and sliding-window causal attention as one mask, key j visible to query i of batch
+// row b iff kv_lo[b, i] <= j <= i.  kv_lo int32 [B, S], 0 <= kv_lo[b, i] <= i, non-decreasing in i:
+// the first token of i's document, i - W + 1 for a window of W keys, or the larger of the two.
+// q_hi int32 [B, S] is the same mask seen from the keys: q_hi[b, j] = the first i with kv_lo[b, i] > j,
+// else S (non-decreasing, > j).  The bounds are trusted (the host builds them); tile ranges derived
+// from them are clamped to the sequence.  Limits: causal, Sq == Sk, S % 128 == 0, D 64 / 128, bf16
+// gradients with D = rowsum(dO * O) formed in the dQ kernel, dense lse, no merge; never the few-head
+// split forms.  RoPE-inverse positions are sequence indices (RoPE scores
+// depend on i - j only: per-document positions would give the same attention).
 //
 // Fragment scheme (all v_mfma_f32_32x32x16_bf16): scores are computed "key on the row",
 // S^T = K . Q^T, so a lane owns one query column and softmax statistics are lane-local (plus one
@@ -89,6 +99,11 @@ struct AttnArgs {
   float* split_o;
   float* split_dv;
   float* split_lse;
+  // band kernels (pt_attn_fwd_band / pt_attn_bwd_band): key j is visible to query i of batch row b iff
+  // kv_lo[b, i] <= j <= i; q_hi[b, j] is one past the last query that sees key j.  Both int32 [B, S],
+  // non-decreasing along a row
+  const int32_t* kv_lo;
+  const int32_t* q_hi;
 };
 
 template <int D>
@@ -370,7 +385,10 @@ constexpr int dq_stages() { return D == 64 ? 4 : 2; }
 // ============================================================================ forward
 // NWK waves per workgroup (32 query rows each): 4, or 8 at d 128 (the K/V tiles staged once for
 // twice the queries; measured 7-8 % faster at S_local 4096, equal at d 64)
-template <int D, int NWK>
+// BAND (causal, no split items): the block's tiles start at the tile of kv_lo of its first row (the
+// block minimum: kv_lo is non-decreasing); a wave skips tiles wholly below the bound of its first row
+// and masks keys below a lane's own bound on tiles that reach under the bound of its last row.
+template <int D, int NWK, bool BAND = false>
 __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_or_hk, int b, int kt_lo = 0,
                                                int kt_hi = -1, int item = -1) {
   constexpr int DT = D / 32, KS = D / 16;
@@ -384,6 +402,16 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
   const int hk = h / (a.H / a.HKV);
   const int q0 = qb * NWK * 32 + wave * 32;
   const int myq = q0 + (lane & 31);
+  // band: this lane's lower bound, the wave's least (its first row) and greatest (its last row)
+  int mylo = 0, wlo_min = 0, wlo_max = 0;
+  if constexpr (BAND) {
+    const int32_t* lo_row = a.kv_lo + (int64_t)b * a.Sq;
+    mylo = lo_row[myq];
+    wlo_min = __builtin_amdgcn_readfirstlane(mylo);
+    wlo_max = __builtin_amdgcn_readlane(mylo, 31);
+    // the block's first tile (clamped: whatever the bound holds, the tile range stays inside K / V)
+    kt_lo = min(max(lo_row[qb * NWK * 32], 0), qb * NWK * 32) / KT;
+  }
 
   bf16x8_t qf[KS];
   if constexpr (D != 64) {
@@ -446,6 +474,8 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     const lds_u8* sv = sk + TILE_B;
     if constexpr (decltype(dg)::value == 3)
       if (a.causal && kv0 > q0 + 31) return;  // wave-uniform: skip tiles fully above the diagonal
+    if constexpr (BAND)
+      if (kv0 + KT - 1 < wlo_min) return;     // wave-uniform: every key is below every row's bound
     {
       f32x16_t s[2];
       // the tile's K operands in one batch of LDS reads ahead of the MFMAs (left to itself the
@@ -471,6 +501,16 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
           for (int r = 0; r < 16; ++r)
             if (32 * kh + (r & 3) + 8 * (r >> 2) > thr) s[kh][r] = -INFINITY;
       }
+      if constexpr (BAND) {
+        if (kv0 < wlo_max) {  // wave-uniform: some row's bound lies past the tile's first key
+          const int thr_lo = mylo - kv0 - 4 * (lane >> 5);   // key row visible iff >= thr_lo
+#pragma unroll
+          for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if (32 * kh + (r & 3) + 8 * (r >> 2) < thr_lo) s[kh][r] = -INFINITY;
+        }
+      }
       float mt = -INFINITY;
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh)
@@ -485,7 +525,11 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
       // slower
       if (D == 64 || __any(mt > m + kRescaleLog2)) {
         const float mn = __any(mt > m + kRescaleLog2) ? fmaxf(m, mt) : m;
-        const float alpha = __builtin_amdgcn_exp2f(m - mn);
+        // band: a row may have seen no key yet (its tiles so far lie below its bound): m = mn = -inf,
+        // and exp2(-inf + inf) is NaN; nothing is accumulated yet, so any finite factor is right.  (The
+        // exponent is what gets replaced: alpha itself stays a plain exp2 result, so l * alpha + sum
+        // contracts to the same fma as in the causal kernel and the two stay bit-identical.)
+        const float alpha = __builtin_amdgcn_exp2f((BAND && mn == -INFINITY) ? 0.f : m - mn);
         m = mn;
         l *= alpha;
 #pragma unroll
@@ -496,7 +540,9 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
       // P = exp2(S c2 - m), summed into l: the exponent arguments as packed pairs (v_pk_fma_f32) and
       // the row sum in four packed partial sums (v_pk_add_f32, a dependency chain of 8 instead of
       // 32 serial adds), combined once at the end of the tile
-      const f32x2_t c22 = {c2, c2}, nm2 = {-m, -m};
+      // (band: for a row still without a key every score is -inf; -m = +inf would make the fma NaN)
+      const float nm = (BAND && m == -INFINITY) ? 0.f : -m;
+      const f32x2_t c22 = {c2, c2}, nm2 = {nm, nm};
       f32x2_t ls[4];   // each partial starts as its first pair (= 0 + p: exp2 is never -0)
 #pragma unroll
       for (int kh = 0; kh < 2; ++kh)
@@ -540,7 +586,8 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     ring_wait<OPS, NS>(issued - (kt + 1));
     __syncthreads();
   };
-  if constexpr (D == 64) tile_loops(n_nd, n_c, nkt, step);
+  // (band: one loop with the skips and masks as wave-uniform runtime branches at both head dims)
+  if constexpr (D == 64 && !BAND) tile_loops(n_nd, n_c, nkt, step);
   else for (int kt = 0; kt < nkt; ++kt) step(std::integral_constant<int, 3>{}, kt);
 
   l = xor32_sum(l);
@@ -554,7 +601,9 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     return;
   }
   const float inv_l = 1.0f / l;
-  const float lse = m * kLn2 + __logf(l);
+  // (band d64: spelled as the fma this expression is contracted to in the causal d64 kernel -- the
+  // d128 kernels keep a multiply and an add -- so a band that masks nothing gives the causal bits)
+  const float lse = (BAND && D == 64) ? __builtin_fmaf(m, kLn2, __logf(l)) : m * kLn2 + __logf(l);
   float* lse_p = a.lse + ((int64_t)b * a.H + h) * a.lse_ld + myq;
   if (!a.merge) {
     uint16_t* orow = a.o.row<uint16_t>(b, myq, h);
@@ -592,6 +641,16 @@ __global__ __launch_bounds__(NWK * 64) void attn_fwd_kernel(AttnArgs a) {
   for (int pass = 0; pass <= a.pair; ++pass) {  // one inlined body: no register growth
     if (pass) __syncthreads();
     attn_fwd_block<D, NWK>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b);
+  }
+}
+
+template <int D, int NWK>
+__global__ __launch_bounds__(NWK * 64) void attn_fwd_band_kernel(AttnArgs a) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_fwd_block<D, NWK, true>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b);
   }
 }
 
@@ -725,7 +784,10 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(View4<const uint16_t> d
 }
 
 // ============================================================================ dK / dV
-template <int D>
+// BAND (causal, no split items): a head's q tiles end at the tile of q_hi of the block's last key (the
+// block maximum: q_hi is non-decreasing); every step runs the edge form, which skips half tiles
+// wholly past the wave's greatest q_hi and masks queries at or past a lane's own q_hi.
+template <int D, bool BAND = false>
 __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, int h_or_hk, int b, int it_lo = 0,
                                                     int it_hi = -1, int item = -1) {
   constexpr int DT = D / 32, KS = D / 16;
@@ -753,7 +815,17 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
 
   // q tiles: causal -> only those that can see this block's keys
   const int qt_begin = a.causal ? (kb * NW * 32) / KT : 0;
-  const int nqt = a.Sq / KT;
+  int nqt = a.Sq / KT;
+  // band: this lane's q_hi, the wave's least (its first key) and greatest (its last key)
+  int myhi = 0, whi_min = 0, whi_max = 0;
+  if constexpr (BAND) {
+    const int32_t* hi_row = a.q_hi + (int64_t)b * a.Sk;
+    myhi = hi_row[mykey];
+    whi_min = __builtin_amdgcn_readfirstlane(myhi);
+    whi_max = __builtin_amdgcn_readlane(myhi, 31);
+    // one past the block's last q tile (clamped: whatever the bound holds, the range stays inside Q)
+    nqt = min(nqt, max(qt_begin + 1, (hi_row[kb * NW * 32 + NW * 32 - 1] + KT - 1) / KT));
+  }
   const int nq = nqt - qt_begin;  // q tiles per query head
   // this call's (head, q tile) steps: all, or a split work item's [it_lo, it_hi)
   const int it0 = it_lo, n_iter = (it_hi < 0 ? nq * group : it_hi) - it_lo;
@@ -789,6 +861,8 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
     for (int qh = 0; qh < 2; ++qh) {
       const int qs = qt * KT + 32 * qh;
       if (decltype(edge)::value && a.causal && qs + 31 < k0) continue;  // wave-uniform: all these queries precede my keys
+      if constexpr (BAND)
+        if (qs >= whi_max) continue;   // wave-uniform: all these queries are past every key's q_hi
       // S = Q K^T and dP = dO V^T  (C layout: col = key = lane, row = query)
       f32x16_t s = zero16(), dp = zero16();
 #pragma unroll
@@ -801,6 +875,14 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if ((r & 3) + 8 * (r >> 2) < thr) s[r] = -INFINITY;
+      }
+      if constexpr (BAND) {
+        if (qs + 31 >= whi_min) {  // upper edge: query row crow(r) sees my key iff < thr_hi
+          const int thr_hi = myhi - qs - 4 * (lane >> 5);
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if ((r & 3) + 8 * (r >> 2) >= thr_hi) s[r] = -INFINITY;
+        }
       }
       // P = exp2(S c2 - lse log2e), dS = P (dP - D): packed pairs of rows (v_pk_fma / v_pk_add / v_pk_mul)
       const f32x2_t c22 = {c2, c2};
@@ -846,7 +928,8 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
     if (it + 1 < n_iter) put_lse(buf ^ 1);
     __syncthreads();
   };
-  const int n_edge = a.causal ? NW * 32 / KT : 0;   // q tiles of a head that reach the diagonal
+  // q tiles of a head that reach the diagonal (band: all of them, for the upper edge)
+  const int n_edge = BAND ? nq : (a.causal ? NW * 32 / KT : 0);
   for (int it = 0; it < n_iter;) {   // per query head: its edge steps, then its full ones
     const int h_end = min(n_iter, it + (nq - cur_t));   // this head's last step + 1
     const int e_end = min(h_end, it + max(0, n_edge - cur_t));
@@ -889,6 +972,17 @@ void attn_bwd_dkdv_kernel(AttnArgs a) {
   }
 }
 
+template <int D>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(D == 64 ? 2 : 1)))
+void attn_bwd_dkdv_band_kernel(AttnArgs a) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_bwd_dkdv_block<D, true>(a, pass ? a.Sk / (NW * 32) - 1 - bx : bx, hh, b);
+  }
+}
+
 // ================================================================ dK / dV, split over wave pairs
 // The same products as attn_bwd_dkdv_block, divided between the two waves of a pair so that one
 // SIMD holds a VALU-heavy and an MFMA-only wave side by side (8-wave workgroups; 128 keys = 4
@@ -906,7 +1000,10 @@ void attn_bwd_dkdv_kernel(AttnArgs a) {
 // bit-identical.
 constexpr int kXchB = 4 * 2 * 2 * 1024;  // one step's P|dS hand-off: 4 pairs x 2 k-steps x 2 kinds x 1 KiB
 
-template <int D>
+// BAND: as attn_bwd_dkdv_block's -- the q tiles end at the tile of q_hi of the block's last key, both
+// waves of a pair skip the half tiles wholly past the q_hi of the pair's last key (each reads that
+// bound itself: the skip must agree), and the score wave masks queries at or past a lane's own q_hi.
+template <int D, bool BAND = false>
 __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int bx, int hk, int b) {
   constexpr int DT = D / 32, KS = D / 16;
   constexpr int TILE_B = KT * D * 2;
@@ -926,7 +1023,16 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
   const float c2 = a.scale * kLog2e;
 
   const int qt_begin = a.causal ? (bx * 128) / KT : 0;
-  const int nq = a.Sq / KT - qt_begin;  // q tiles per query head
+  int nqt = a.Sq / KT;
+  int whi_min = 0, whi_max = 0;   // band: q_hi of the pair's first and last key (its least and greatest)
+  if constexpr (BAND) {
+    const int32_t* hi_row = a.q_hi + (int64_t)b * a.Sk;
+    whi_min = hi_row[k0];
+    whi_max = hi_row[k0 + 31];
+    // one past the block's last q tile (clamped: whatever the bound holds, the range stays inside Q)
+    nqt = min(nqt, max(qt_begin + 1, (hi_row[bx * 128 + 127] + KT - 1) / KT));
+  }
+  const int nq = nqt - qt_begin;  // q tiles per query head
   const int n_tiles = nq * group;
   const int n_steps = 2 * n_tiles;
 
@@ -982,7 +1088,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
       const int qs = qt * KT + 32 * qh;
       // causal: every query of the half tile precedes the pair's keys (wave-uniform; the partner
       // wave skips the same step)
-      if (j < n_steps && !(a.causal && qs + 31 < k0)) {
+      if (j < n_steps && !(a.causal && qs + 31 < k0) && !(BAND && qs >= whi_max)) {
         const lds_u8* sq = smem + buf * STAGE_B;
         const lds_u8* sdo = sq + TILE_B;
         const float* sl = (const float*)(sq + 2 * TILE_B);
@@ -1020,6 +1126,14 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
           for (int r = 0; r < 16; ++r)
             if ((r & 3) + 8 * (r >> 2) < thr) s[r] = -INFINITY;
         }
+        if constexpr (BAND) {
+          if (qs + 31 >= whi_min) {  // upper edge: query row crow(r) sees my key iff < thr_hi
+            const int thr_hi = a.q_hi[(int64_t)b * a.Sk + mykey] - qs - 4 * (lane >> 5);
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+              if ((r & 3) + 8 * (r >> 2) >= thr_hi) s[r] = -INFINITY;
+          }
+        }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -(lr[r] * kLog2e)));
@@ -1049,7 +1163,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
     for (int j = 0; j <= n_steps; ++j) {
       if (issue(j)) stage_next();
       const int h = j - 1, qh = h & 1;
-      if (j > 0 && !(a.causal && qt * KT + 32 * qh + 31 < k0)) {
+      if (j > 0 && !(a.causal && qt * KT + 32 * qh + 31 < k0) && !(BAND && qt * KT + 32 * qh >= whi_max)) {
         const lds_u8* sq = smem + buf * STAGE_B;
         const lds_u8* sdo = sq + TILE_B;
         const lds_u8* x = xch + (h & 1) * kXchB + pr * 4096 + lane * 16;
@@ -1096,8 +1210,19 @@ __global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_kernel(AttnArgs a) 
   }
 }
 
-// ============================================================================ dQ
 template <int D>
+__global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_band_kernel(AttnArgs a) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_bwd_dkdv_pair_block<D, true>(a, pass ? a.Sk / 128 - 1 - bx : bx, hh, b);
+  }
+}
+
+// ============================================================================ dQ
+// BAND: the forward's tile range, skip and lower-edge mask (attn_fwd_block)
+template <int D, bool BAND = false>
 __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int h_or_hk, int b, int kt_lo = 0,
                                                   int kt_hi = -1, int item = -1) {
   constexpr int DT = D / 32, KS = D / 16;
@@ -1111,6 +1236,14 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   const int hk = h / (a.H / a.HKV);
   const int q0 = qb * NW * 32 + wave * 32;
   const int myq = q0 + (lane & 31);
+  int mylo = 0, wlo_min = 0, wlo_max = 0;
+  if constexpr (BAND) {
+    const int32_t* lo_row = a.kv_lo + (int64_t)b * a.Sq;
+    mylo = lo_row[myq];
+    wlo_min = __builtin_amdgcn_readfirstlane(mylo);
+    wlo_max = __builtin_amdgcn_readlane(mylo, 31);
+    kt_lo = min(max(lo_row[qb * NW * 32], 0), qb * NW * 32) / KT;
+  }
 
   const uint16_t* qrow = a.q.row(b, myq, h);
   const uint16_t* dorow = a.dout.row(b, myq, h);
@@ -1162,7 +1295,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
       for (int j = 0; j < 8; ++j) part += (float)dof[ks][j] * (float)of[ks][j];
     del = xor32_sum(part);
     // (split work items: every item of the block forms D itself; the first one stores it)
-    if (lane < 32 && kt0 == 0) a.delta_w[ri] = del;
+    if (lane < 32 && (BAND || kt0 == 0)) a.delta_w[ri] = del;
   }
   __syncthreads();
 
@@ -1173,6 +1306,8 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
     const lds_u8* sv = sk + TILE_B;
     if constexpr (decltype(dg)::value == 3)
       if (a.causal && kv0 > q0 + 31) return;  // wave-uniform: every key of the tile is after my queries
+    if constexpr (BAND)
+      if (kv0 + KT - 1 < wlo_min) return;     // wave-uniform: every key is below every row's bound
     // each 32-key half's dS feeds its two dQ k-steps right away: one dS tile live, not two
     // (16 VGPRs: d128's dQ kernel fits 2 waves per SIMD)
 #pragma unroll
@@ -1189,6 +1324,22 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if ((r & 3) + 8 * (r >> 2) > thr) s[r] = -INFINITY;
+      }
+      if constexpr (BAND) {
+        if (kv0 + 32 * kh < wlo_max) {  // wave-uniform: some row's bound lies past the half's first key
+          // d128: the bound is re-read here, behind an opaque copy of the row index so the load is not
+          // hoisted out of the loop (held across it, that register spilled the 256-VGPR budget)
+          int lo = mylo;
+          if constexpr (D == 128) {
+            int myq_m = myq;
+            asm volatile("" : "+v"(myq_m));
+            lo = a.kv_lo[(int64_t)b * a.Sq + myq_m];
+          }
+          const int thr_lo = lo - kv0 - 32 * kh - 4 * (lane >> 5);   // key row visible iff >= thr_lo
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if ((r & 3) + 8 * (r >> 2) < thr_lo) s[r] = -INFINITY;
+        }
       }
       // dS = P (dP - D), P = exp2(S c2 - lse log2e): at d64 as packed pairs (v_pk_fma / v_pk_add /
       // v_pk_mul); d128 keeps the scalar form (its 256-VGPR budget spilled the packed one)
@@ -1230,7 +1381,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
     ring_wait<OPS, NS>(issued - (kt + 1));
     __syncthreads();
   };
-  if constexpr (D == 64) {
+  if constexpr (D == 64 && !BAND) {
     tile_loops(n_nd, n_c, nkt, step);
   } else {   // one loop: at d128 the three loops' extra copies of the body spilled (256-VGPR budget)
     for (int kt = 0; kt < nkt; ++kt) step(std::integral_constant<int, 3>{}, kt);
@@ -1269,6 +1420,17 @@ void attn_bwd_dq_kernel(AttnArgs a) {
   for (int pass = 0; pass <= a.pair; ++pass) {  // one inlined body: no register growth
     if (pass) __syncthreads();
     attn_bwd_dq_block<D>(a, pass ? a.Sq / (NW * 32) - 1 - bx : bx, hh, b);
+  }
+}
+
+template <int D>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(D == 128 ? 2 : 1)))
+void attn_bwd_dq_band_kernel(AttnArgs a) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_bwd_dq_block<D, true>(a, pass ? a.Sq / (NW * 32) - 1 - bx : bx, hh, b);
   }
 }
 
@@ -1402,7 +1564,8 @@ int fill_common(AttnArgs& a, const Problem& p) {
 template <int D, int NWK>
 void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
   // (d64: the Q image shares the last ring stage)
-  launch(attn_fwd_kernel<D, NWK>, grid, NWK * 64, fwd_stages<D, NWK>() * 2 * KT * D * 2, stream, a);
+  launch(a.kv_lo ? attn_fwd_band_kernel<D, NWK> : attn_fwd_kernel<D, NWK>, grid, NWK * 64,
+         fwd_stages<D, NWK>() * 2 * KT * D * 2, stream, a);
 }
 
 // the backward's operands beyond Problem; what an entry point does not have stays zero
@@ -1421,21 +1584,27 @@ struct BwdCall {
   const void* rope_cos; const void* rope_sin;
   int64_t rope_stride;
   int parts;                   // bit 0: dQ, bit 1: dK / dV
+  const int32_t* kv_lo; const int32_t* q_hi;   // pt_attn_bwd_band: the band kernels
 };
 
 // dQ first: with delta_w set it produces the D the dK/dV kernel reads (same stream, in order)
 template <int D>
 int launch_bwd(AttnArgs& a, int parts, dim3 gq, dim3 gk, bool wave_pairs, hipStream_t stream) {
   constexpr int stage_q = 2 * KT * D * 2 + 2 * KT * 4;   // Q tile, dO tile, lse [64], delta [64]
+  const bool band = a.kv_lo != nullptr;
   if (parts & 1) {
-    launch(attn_bwd_dq_kernel<D>, gq, NW * 64, dq_stages<D>() * 2 * KT * D * 2, stream, a);
+    launch(band ? attn_bwd_dq_band_kernel<D> : attn_bwd_dq_kernel<D>, gq, NW * 64, dq_stages<D>() * 2 * KT * D * 2,
+           stream, a);
     PT_CHECK_LAUNCH();
   }
   a.delta = a.delta_w ? a.delta_w : a.delta;
   a.delta_w = nullptr;
   if (!(parts & 2)) {
   } else if (wave_pairs) {
-    launch(attn_bwd_dkdv_pair_kernel<D>, gk, 8 * 64, 3 * stage_q + 2 * kXchB, stream, a);
+    launch(band ? attn_bwd_dkdv_pair_band_kernel<D> : attn_bwd_dkdv_pair_kernel<D>, gk, 8 * 64,
+           3 * stage_q + 2 * kXchB, stream, a);
+  } else if (band) {
+    launch(attn_bwd_dkdv_band_kernel<D>, gk, NW * 64, 2 * stage_q, stream, a);
   } else {
     launch(attn_bwd_dkdv_kernel<D>, gk, NW * 64, 2 * stage_q, stream, a);
   }
@@ -1469,6 +1638,7 @@ int attn_bwd(const BwdCall& c, hipStream_t stream) {
     a.o = view(c.o, c.o_str);
     a.delta_w = c.delta_w;
   }
+  a.kv_lo = c.kv_lo; a.q_hi = c.q_hi;
   int rc = fill_common(a, p);
   if (rc) return rc;
   if (p.Sk % (NW * 32)) return PT_EUNSUPPORTED;
@@ -1503,6 +1673,9 @@ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 // bytes of `items` f32 partial tiles of NW * 32 rows x `width`, as the workspace lays them out
 inline int64_t split_tile_bytes(int64_t items, int64_t width) { return align256(items * NW * 32 * width * 4); }
 
+// the forward's launch (pt_attn_fwd, pt_attn_fwd_band): fills and checks the common part, picks the form
+int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream);
+
 }  // namespace
 
 extern "C" {
@@ -1521,7 +1694,52 @@ int pt_attn_fwd(const void* q, const int64_t* q_str, const void* k, const int64_
   a.o = view(o, o_str);
   a.lse = lse;
   a.merge = merge;
-  int rc = fill_common(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal});
+  return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal}, stream);
+}
+
+// Band attention forward: key j visible to query i of batch row b iff kv_lo[b, i] <= j <= i (document
+// masking, a sliding window, or both; see the header).  o bf16, lse f32 [B, H, S] dense.
+int pt_attn_fwd_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H,
+                     int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, const int32_t* kv_lo,
+                     const int32_t* q_hi, hipStream_t stream) {
+  if (!q || !k || !v || !o || !lse || !kv_lo || !q_hi) return PT_EINVAL;
+  if (Sq != Sk) return PT_EUNSUPPORTED;
+  AttnArgs a{};
+  a.lse_ld = Sq;
+  a.o = view(o, o_str);
+  a.lse = lse;
+  a.kv_lo = kv_lo; a.q_hi = q_hi;
+  return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1}, stream);
+}
+
+// pt_attn_bwd_fused_delta under a band (bf16 gradients, dense lse; the optional fused RoPE inverse)
+int pt_attn_bwd_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, const void* o, const int64_t* o_str, const void* dout,
+                     const int64_t* do_str, const float* lse, float* delta_out, void* dq, const int64_t* dq_str,
+                     void* dk, const int64_t* dk_str, void* dv, const int64_t* dv_str, int64_t B, int64_t H,
+                     int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, const void* rope_cos,
+                     const void* rope_sin, int64_t rope_stride, const int32_t* kv_lo, const int32_t* q_hi,
+                     hipStream_t stream) {
+  if (!o || !delta_out || !o_str || !kv_lo || !q_hi) return PT_EINVAL;
+  if (Sq != Sk) return PT_EUNSUPPORTED;
+  if (!view_aligned(o, o_str)) return PT_EALIGN;
+  BwdCall c{{q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1},
+            dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, 0, nullptr, o, o_str, delta_out};
+  c.rope_cos = rope_cos; c.rope_sin = rope_sin; c.rope_stride = rope_stride;
+  c.parts = 3;
+  c.kv_lo = kv_lo; c.q_hi = q_hi;
+  return attn_bwd(c, stream);
+}
+
+}  // extern "C"
+
+namespace {
+
+int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream) {
+  const int64_t B = p.B, H = p.H, Sq = p.Sq, D = p.D;
+  const int causal = p.causal;
+  int rc = fill_common(a, p);
   if (rc) return rc;
   // 8-wave workgroups (the K|V tiles staged once for 256 queries) at d128; at d64 measured equal or
   // slower (round 5: 35.6 vs 34.8 us, bit-identical), so 4
@@ -1535,6 +1753,10 @@ int pt_attn_fwd(const void* q, const int64_t* q_str, const void* k, const int64_
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
+
+}  // namespace
+
+extern "C" {
 
 // delta[b, h, q] = sum_d dO * O   (f32, [B, H, Sq])
 int pt_attn_bwd_delta(const void* dout, const int64_t* do_str, const void* o, const int64_t* o_str, float* delta,

@@ -732,11 +732,16 @@ def ring_enabled():
 class AttnShape:
     """Views of the fused [T, q | k | v] projection as token-major [B, S, heads, d] tensors."""
 
-    def __init__(self, B, S, nh, nkv, d, zz=False):
+    def __init__(self, B, S, nh, nkv, d, zz=False, band=None):
         self.B, self.S, self.nh, self.nkv, self.d = B, S, nh, nkv, d
         self.T = B * S
         self.wq, self.wkv = nh * d, nkv * d
         self.zz = zz    # the tokens are a zig-zag CP shard (context_parallel.apply_context_parallel)
+        # a kernels.AttnBand: document-masked / sliding-window causal attention (None: plain causal)
+        self.band = band
+        if band is not None and ring_enabled():
+            raise NotImplementedError("document masking / sliding-window attention under context parallelism "
+                                      "(the ring's blocks take no band)")
 
     def q(self, t):
         return t[:, :self.wq].view(self.B, self.S, self.nh, self.d)
@@ -746,6 +751,27 @@ class AttnShape:
 
     def v(self, t):
         return t[:, self.wq + self.wkv:].view(self.B, self.S, self.nkv, self.d)
+
+
+def document_ids_from_eos(input_ids, eos_token_id):
+    """Document ids [B, S] (int32, counting from 0 in every row) of rows of documents packed back to
+    back and ended by `eos_token_id`: the EOS token belongs to the document it ends, the next token
+    starts a new one."""
+    if input_ids.dim() != 2:
+        raise ValueError("document_ids_from_eos: input_ids must be [B, S]")
+    ends = (input_ids == int(eos_token_id)).to(torch.int32)
+    return torch.cumsum(ends, dim=1, dtype=torch.int32) - ends
+
+
+def make_band(B, S, device, document_ids=None, window=None):
+    """The kernels.AttnBand of a forward: `document_ids` a [B, S] integer tensor or a ready AttnBand
+    (then `window` must already be part of it), `window` a sliding-window width; None when neither
+    is given (plain causal attention)."""
+    if isinstance(document_ids, K.AttnBand):
+        return document_ids
+    if document_ids is None and window is None:
+        return None
+    return K.attn_band(B, S, device, document_ids=document_ids, window=None if window is None else int(window))
 
 
 # head dims the attention kernels do not take (64 / 128; e.g. 60 = SmolLM-360M with 16 heads, as
@@ -788,7 +814,7 @@ def _attention_core_fwd_padded(qkv, sh, cos, sin, scale):
     # the rotated q|k back into qkv (in place, as the kernel-width path leaves them for the backward)
     qkv[:, :sh.wq + sh.wkv].copy_(_unpad_heads(x.view(sh.T, heads, dp)[:, :sh.nh + sh.nkv], d))
     shp = AttnShape(sh.B, sh.S, sh.nh, sh.nkv, dp)
-    o, lse = K.attn_fwd(shp.q(x), shp.k(x), shp.v(x), scale, True)
+    o, lse = K.attn_fwd(shp.q(x), shp.k(x), shp.v(x), scale, True, band=sh.band)
     return _unpad_heads(o.view(sh.T, sh.nh, dp), d).view(sh.B, sh.S, sh.nh, d), lse
 
 
@@ -800,7 +826,8 @@ def _attention_core_bwd_padded(do, qkv, o, lse, sh, cos, sin, scale):
     dop = _pad_heads(do.reshape(sh.T, sh.wq), sh.nh, d, dp).view(sh.B, sh.S, sh.nh, dp)
     op = _pad_heads(o.reshape(sh.T, sh.wq), sh.nh, d, dp).view(sh.B, sh.S, sh.nh, dp)
     dxp = torch.empty_like(x)
-    K.attn_bwd(dop, shp.q(x), shp.k(x), shp.v(x), op, lse, scale, True, dq=shp.q(dxp), dk=shp.k(dxp), dv=shp.v(dxp))
+    K.attn_bwd(dop, shp.q(x), shp.k(x), shp.v(x), op, lse, scale, True, dq=shp.q(dxp), dk=shp.k(dxp), dv=shp.v(dxp),
+               band=sh.band)
     K.rope_(dxp, sh.nh + sh.nkv, dp, _pad_rope_table(cos, d, dp), _pad_rope_table(sin, d, dp), sh.S, inverse=True)
     return _unpad_heads(dxp.view(sh.T, heads, dp), d)
 
@@ -822,7 +849,7 @@ def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False):
     if ring_enabled():
         from .context_parallel.context_parallel import ring_attention_tokens
         return ring_attention_tokens(qkv, sh, scale, True, resident=sh.zz)
-    return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True)
+    return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True, band=sh.band)
 
 
 def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale):
@@ -836,10 +863,10 @@ def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale):
         K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
     elif _fuse():  # the RoPE backward is fused into the dq / dk stores
         K.attn_bwd(do, sh.q(qkv), sh.k(qkv), sh.v(qkv), o, lse, scale, True,
-                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=(cos, sin))
+                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=(cos, sin), band=sh.band)
     else:
         K.attn_bwd(do, sh.q(qkv), sh.k(qkv), sh.v(qkv), o, lse, scale, True,
-                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv))
+                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), band=sh.band)
         K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
     return dqkv
 
@@ -908,9 +935,9 @@ class AttentionFunction(torch.autograd.Function):
     attention, out_proj, with the Column/Row TP reductions."""
 
     @staticmethod
-    def forward(ctx, x, wq, wk, wv, wo, cos, sin, nh, nkv, d):
+    def forward(ctx, x, wq, wk, wv, wo, cos, sin, nh, nkv, d, band=None):
         B, S, _ = x.shape
-        sh = AttnShape(B, S, nh, nkv, d)
+        sh = AttnShape(B, S, nh, nkv, d, band=band)
         h2 = _contig2d(x)
         a, saved = attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, TPContext.current())
         ctx.save_for_backward(h2, *saved, wq, wk, wv, wo, cos, sin)
@@ -923,7 +950,7 @@ class AttentionFunction(torch.autograd.Function):
         sh = ctx.sh
         dh = attn_block_bwd(_contig2d(da), h2, (qkv, o, lse), wq, wk, wv, wo, cos, sin, sh, TPContext.current(),
                             need_dx=ctx.needs_input_grad[0])
-        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 9
+        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 10
 
 
 # ------------------------------------------------------------------------ MLP block
@@ -1028,13 +1055,17 @@ class DecoderLayerFunction(torch.autograd.Function):
     shard (cos / sin its positions' tables): the ring runs on it with no re-lay."""
 
     @staticmethod
-    def forward(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode, nh, nkv, d, zz=False, sp=0):
+    def forward(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode, nh, nkv, d, zz=False, sp=0,
+                band=None):
+        if sp and band is not None:
+            raise NotImplementedError("document masking / sliding-window attention in the sequence-parallel TP "
+                                      "layout (its chunks re-batch the rows the band describes)")
         if sp:   # sp = the chunk count of the sequence-parallel layout (0: the replicated stream)
             return DecoderLayerFunction._forward_sp(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode,
                                                     nh, nkv, d, int(sp))
         ctx.sp = False
         B, S, H = x.shape
-        sh = AttnShape(B, S, nh, nkv, d, zz)
+        sh = AttnShape(B, S, nh, nkv, d, zz, band)
         tp = TPContext.current()
         x2 = _contig2d(x)
         h1, rstd1, _ = K.rmsnorm_fwd(x2, w1, eps, mode)
@@ -1133,7 +1164,7 @@ class DecoderLayerFunction(torch.autograd.Function):
                                      rs_out=dh1[j * n:(j + 1) * n], notify=j == c - 1))
         wait_all(rs)
         dx = norm_bwd(dh1, x2, w1, rstd1, mode, dres=dz, sp=tp)
-        return (dx.view(dout.shape),) + (None,) * 18
+        return (dx.view(dout.shape),) + (None,) * 19
 
     @staticmethod
     def backward(ctx, dout):
@@ -1149,7 +1180,7 @@ class DecoderLayerFunction(torch.autograd.Function):
         dz = norm_bwd(dh2, z, w2, rstd2, mode, dres=dout2)
         dh1 = attn_block_bwd(dz, h1, (qkv, o, lse), wq, wk, wv, wo, cos, sin, sh, tp, keep_parts=K.norm_splitk_enabled())
         dx = norm_bwd(dh1, x2, w1, rstd1, mode, dres=dz)   # (norm_bwd skips dW of frozen weights)
-        return (dx.view(sh.B, sh.S, -1),) + (None,) * 18
+        return (dx.view(sh.B, sh.S, -1),) + (None,) * 19
 
 
 # ------------------------------------------------------------------------ cross entropy

@@ -1700,12 +1700,117 @@ def _attn_off_block(causal, Sq, Sk, lse, B, H):
     return causal and Sq == Sk and Sq % ATTN_Q_BLOCK != 0 and (lse is None or _lse_ld(lse, B, H, Sq) == Sq)
 
 
-def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False):
+# Band attention (document masking and sliding windows; include/picotron_hip.h pt_attn_fwd_band): key j
+# is visible to query i of batch row b iff kv_lo[b, i] <= j <= i.
+_BAND_KEY = object()
+
+
+class AttnBand:
+    """The two bound arrays of a band, int32 [B, S] on the device: kv_lo[b, i] = the first key query i
+    sees, q_hi[b, j] = one past the last query that sees key j.  Built only by attn_band(), so the
+    kernels never see an invalid bound and nothing has to be read back to validate one."""
+
+    def __init__(self, key, kv_lo, q_hi):
+        if key is not _BAND_KEY:
+            raise TypeError("AttnBand is built by attn_band()")
+        self.kv_lo, self.q_hi = kv_lo, q_hi
+        self.B, self.S = kv_lo.shape
+        self._padded = {}
+
+    @property
+    def device(self):
+        return self.kv_lo.device
+
+    def padded(self, Sp):
+        """The band over Sp >= S rows: every row past S is a one-token document of its own."""
+        if Sp == self.S:
+            return self
+        _req(Sp > self.S, "AttnBand.padded: a shorter sequence")
+        if Sp not in self._padded:
+            tail = torch.arange(self.S, Sp, dtype=torch.int32, device=self.device).expand(self.B, -1)
+            self._padded[Sp] = AttnBand(_BAND_KEY, torch.cat([self.kv_lo, tail], 1).contiguous(),
+                                        torch.cat([self.q_hi, tail + 1], 1).contiguous())
+        return self._padded[Sp]
+
+    def mask(self):
+        """The boolean [B, 1, S, S] mask (query on dim 2), from kv_lo; for tests and references."""
+        i = torch.arange(self.S, device=self.device)
+        return ((i[None, None, :] >= self.kv_lo[:, :, None]) & (i[None, None, :] <= i[None, :, None]))[:, None]
+
+
+def attn_band(B, S, device, document_ids=None, window=None):
+    """The AttnBand of B rows of S tokens.  document_ids: integer [B, S]; a document boundary falls
+    wherever the value changes along a row, and a token sees only its own document's earlier tokens.
+    window: W >= 1, a token sees the last W keys (itself included).  Both: the intersection.  Neither:
+    plain causal attention.  Runs on `device` without a host synchronisation."""
+    B, S = int(B), int(S)
+    _req(B > 0 and S > 0, "attn_band: B and S must be positive")
+    device = torch.device(device)
+    idx = torch.arange(S, dtype=torch.int32, device=device)
+    kv_lo = torch.zeros(B, S, dtype=torch.int32, device=device)
+    if document_ids is not None:
+        _req(isinstance(document_ids, torch.Tensor) and tuple(document_ids.shape) == (B, S),
+             f"attn_band: document_ids must be a [B, S] = [{B}, {S}] tensor")
+        _req(not document_ids.dtype.is_floating_point and not document_ids.dtype.is_complex
+             and document_ids.dtype != torch.bool, "attn_band: document_ids must be an integer tensor")
+        ids = document_ids.to(device)
+        first = torch.ones(B, S, dtype=torch.bool, device=device)
+        first[:, 1:] = ids[:, 1:] != ids[:, :-1]
+        kv_lo = torch.cummax(torch.where(first, idx, torch.zeros_like(idx)), dim=1).values.to(torch.int32)
+    if window is not None:
+        _req(isinstance(window, int) and not isinstance(window, bool) and window >= 1,
+             "attn_band: window must be an integer >= 1")
+        if window < S:
+            kv_lo = torch.maximum(kv_lo, (idx - (window - 1)).clamp_(min=0))
+    kv_lo = kv_lo.contiguous()
+    # the first i with kv_lo[b, i] > j (kv_lo is non-decreasing along a row), S when there is none
+    q_hi = torch.searchsorted(kv_lo, idx.expand(B, S).contiguous(), right=True).to(torch.int32).contiguous()
+    return AttnBand(_BAND_KEY, kv_lo, q_hi)
+
+
+def _band_for(band, q, k, causal, what):
+    """The checks every band call shares; returns the band padded to the kernels' 128-row blocks."""
+    B, Sq = q.shape[0], q.shape[1]
+    _req(isinstance(band, AttnBand), f"{what}: band must be an AttnBand (attn_band())")
+    _req(bool(causal), f"{what}: a band is a causal mask (causal=False given)")
+    _req(Sq == k.shape[1], f"{what}: a band needs Sq == Sk")
+    _req((band.B, band.S) == (B, Sq) and band.device == q.device,
+         f"{what}: the band is [{band.B}, {band.S}] on {band.device}, the queries [{B}, {Sq}] on {q.device}")
+    return band.padded(_attn_padded_len(Sq))
+
+
+def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None):
     """q [B,Sq,H,D], k/v [B,Sk,Hkv,D] (token-major views).  Returns (out, lse[B,H,Sq] f32).
     merge=True: `out` is an f32 accumulator and `lse` the running LSE; this block is merged in.
-    lse may be the Sq-column slice of a longer [B, H, S] LSE (rows evenly spaced)."""
+    lse may be the Sq-column slice of a longer [B, H, S] LSE (rows evenly spaced).
+    band (an AttnBand): document-masked / sliding-window causal attention; causal only, no merge,
+    dense lse; the few-head split forms are not taken."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if band is not None:
+        _req(not merge, "attn_fwd: a band does not combine with merge=True")
+        bp = _band_for(band, q, k, causal, "attn_fwd")
+        _req(lse is None or _lse_ld(lse, B, H, Sq) == Sq, "attn_fwd: a band takes a dense lse")
+        if bp is not band:   # S off the 128-row blocks: the padded path below, pad rows their own documents
+            op, lp = attn_fwd(_pad_seq(q, bp.S), _pad_seq(k, bp.S), _pad_seq(v, bp.S), scale, True, band=bp)
+            if out is None:
+                out = op[:, :Sq].contiguous()
+            else:
+                out.copy_(op[:, :Sq])
+            if lse is None:
+                lse = lp[:, :, :Sq].contiguous()
+            else:
+                lse.copy_(lp[:, :, :Sq])
+            return out, lse
+        if out is None:
+            out = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device)
+        if lse is None:
+            lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+        rc = _C.lib().pt_attn_fwd_band(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                       _ptr(lse), B, H, HKV, Sq, Sk, D, float(scale), _ptr(band.kv_lo),
+                                       _ptr(band.q_hi), _C.stream_ptr(q.device))
+        _C.check(rc, "pt_attn_fwd_band")
+        return out, lse
     if not merge and _attn_off_block(causal, Sq, Sk, lse, B, H):
         Sp = _attn_padded_len(Sq)
         op, lp = attn_fwd(_pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp), scale, True)
@@ -1778,11 +1883,15 @@ def attn_bwd_part(dout, q, k, v, lse, delta, scale, causal, dq=None, dk=None, dv
 
 
 def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, grad_f32=False, delta=None,
-             rope=None):
+             rope=None, band=None):
     """rope = (cos, sin) [S, d] bf16 tables: dq / dk are stored rotated back by -theta (the RoPE
-    backward fused into the attention backward; positions = sequence index)."""
+    backward fused into the attention backward; positions = sequence index).
+    band (an AttnBand): the backward of attn_fwd(band=); bf16 gradients, dense lse, D = rowsum(dO * O)
+    always formed inside the dQ kernel (no `delta` argument)."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if band is not None:
+        return _attn_bwd_band(dout, q, k, v, out, lse, scale, causal, dq, dk, dv, grad_f32, delta, rope, band)
     if not grad_f32 and _attn_off_block(causal, Sq, Sk, lse, B, H) and \
             (delta is None or _lse_ld(delta, B, H, Sq, "delta") == Sq):
         Sp = _attn_padded_len(Sq)
@@ -1854,4 +1963,53 @@ def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, 
                          B, H, HKV, Sq, Sk, D, float(scale), int(bool(causal)), int(bool(grad_f32)),
                          _ptr(rc_cos), _ptr(rc_sin), rstride, ld, _C.stream_ptr(q.device))
     _C.check(rc, "pt_attn_bwd")
+    return dq, dk, dv, delta
+
+
+def _attn_bwd_band(dout, q, k, v, out, lse, scale, causal, dq, dk, dv, grad_f32, delta, rope, band):
+    B, Sq, H, D = q.shape
+    Sk, HKV = k.shape[1], k.shape[2]
+    _req(not grad_f32, "attn_bwd: a band writes bf16 gradients (grad_f32=True given)")
+    _req(delta is None, "attn_bwd: under a band D is formed inside the dQ kernel (no delta argument)")
+    bp = _band_for(band, q, k, causal, "attn_bwd")
+    _req(_lse_ld(lse, B, H, Sq) == Sq, "attn_bwd: a band takes a dense lse")
+    _req(out.dtype == BF16 and out.shape == q.shape, "attn_bwd: out must be bf16 [B, Sq, H, D]")
+    if bp is not band:   # S off the 128-row blocks: as the causal padded path, pad rows their own documents
+        Sp = bp.S
+        lsep = torch.full((B, H, Sp), float("inf"), dtype=torch.float32, device=q.device)
+        lsep[:, :, :Sq] = lse
+        rp = None
+        if rope is not None:
+            rp = tuple(t if t.shape[0] >= Sp else _pad_seq(t.unsqueeze(0), Sp)[0] for t in rope)
+        dqp, dkp, dvp, dlt = attn_bwd(_pad_seq(dout, Sp), _pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp),
+                                      _pad_seq(out, Sp), lsep, scale, True, rope=rp, band=bp)
+        res = []
+        for given, got in ((dq, dqp), (dk, dkp), (dv, dvp)):
+            if given is None:
+                res.append(got[:, :Sq].contiguous())
+            else:
+                given.copy_(got[:, :Sq])
+                res.append(given)
+        return res[0], res[1], res[2], dlt[:, :, :Sq]
+    if dq is None:
+        dq = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device)
+    if dk is None:
+        dk = torch.empty(B, Sk, HKV, D, dtype=BF16, device=q.device)
+    if dv is None:
+        dv = torch.empty(B, Sk, HKV, D, dtype=BF16, device=q.device)
+    rc_cos = rc_sin = None
+    rstride = 0
+    if rope is not None:
+        rc_cos, rc_sin = rope
+        _req(rc_cos.dtype == BF16 and rc_sin.dtype == BF16 and rc_cos.stride(-1) == 1 and rc_cos.shape[0] >= Sq,
+             "attn_bwd rope tables: bf16 [S, d]")
+        _req(rc_sin.stride(0) == rc_cos.stride(0), "attn_bwd rope tables share a stride")
+        rstride = rc_cos.stride(0)
+    delta = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+    rc = _C.lib().pt_attn_bwd_band(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                   _ptr(dout), _str3(dout), _ptr(lse), _ptr(delta), _ptr(dq), _str3(dq), _ptr(dk),
+                                   _str3(dk), _ptr(dv), _str3(dv), B, H, HKV, Sq, Sk, D, float(scale),
+                                   _ptr(rc_cos), _ptr(rc_sin), rstride, _ptr(band.kv_lo), _ptr(band.q_hi),
+                                   _C.stream_ptr(q.device))
+    _C.check(rc, "pt_attn_bwd_band")
     return dq, dk, dv, delta

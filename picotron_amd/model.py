@@ -227,6 +227,8 @@ class Attention(nn.Module):
         self.v_proj = Linear(config.hidden_size, self.num_key_values * self.head_dim, bias=False)
         self.out_proj = Linear(config.hidden_size, config.hidden_size, bias=False)
         self.layer_idx = layer_idx
+        # Mistral-style sliding-window attention: a token sees the last `sliding_window` keys (None: all)
+        self.sliding_window = getattr(config, "sliding_window", None)
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -236,9 +238,18 @@ class Attention(nn.Module):
     def weights(self):
         return self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.out_proj.weight
 
-    def forward(self, x, cos, sin, attention_mask=None, position_ids=None):
+    def band(self, x, document_ids):
+        """The kernels.AttnBand of this forward (None: plain causal): document_ids a [B, S] integer
+        tensor (a boundary wherever the value changes along a row), combined with the config's
+        sliding_window -- or an AttnBand built once by the caller, taken as it is."""
+        return FN.make_band(x.shape[0], x.shape[1], x.device, document_ids, self.sliding_window)
+
+    def forward(self, x, cos, sin, attention_mask=None, position_ids=None, document_ids=None):
+        """document_ids: tokens attend within their own document only (intra-document causal masking of
+        packed rows).  RoPE positions stay sequence indices: RoPE scores depend on i - j only, so
+        positions reset per document would give the same attention; position_ids stays unused."""
         return FN.AttentionFunction.apply(x, *self.weights(), cos, sin, self.num_local_heads,
-                                          self.num_local_kv_heads, self.head_dim)
+                                          self.num_local_kv_heads, self.head_dim, self.band(x, document_ids))
 
 
 class MLP(nn.Module):
@@ -297,7 +308,7 @@ class DecoderLayer(nn.Module):
             self.cos, self.sin = cos, sin
         return cos, sin
 
-    def forward(self, x, attention_mask=None, position_ids=None):
+    def forward(self, x, attention_mask=None, position_ids=None, document_ids=None):
         zz = self.cp_zigzag_residual and context_parallel.zigzag_enabled(x.shape[1], True)
         cos, sin = self._tables(x.device, x.shape[1] if zz else 0)
         n1, n2, at, mlp = self.input_layernorm, self.post_attention_layernorm, self.attention, self.mlp
@@ -308,9 +319,16 @@ class DecoderLayer(nn.Module):
         st = getattr(self, "_pt_sp_state", None)
         sp = st.chunks if (self.tp_sequence_parallel and st is not None and st.local_len and
                            st.local_len == x.shape[1]) else 0
+        band = document_ids if isinstance(document_ids, K.AttnBand) else None
+        if band is None and (document_ids is not None or at.sliding_window is not None):
+            if sp or zz:
+                raise NotImplementedError("document masking / sliding-window attention on a sharded residual "
+                                          "stream (sequence-parallel TP, zig-zag context parallelism)")
+            band = at.band(x, document_ids)
         return FN.DecoderLayerFunction.apply(
             x, n1.weight, n2.weight, *at.weights(), mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
-            cos, sin, _norm_eps(n1), _norm_mode(n1), at.num_local_heads, at.num_local_kv_heads, at.head_dim, zz, sp)
+            cos, sin, _norm_eps(n1), _norm_mode(n1), at.num_local_heads, at.num_local_kv_heads, at.head_dim, zz, sp,
+            band)
 
 
 class Embedding(nn.Module):
@@ -366,10 +384,21 @@ class Llama(nn.Module):
         self.final_norm.reset_parameters()
         self.final_proj.reset_parameters()
 
-    def forward(self, input_ids, attention_mask=None, position_ids: torch.Tensor = None):
+    def forward(self, input_ids, attention_mask=None, position_ids: torch.Tensor = None, document_ids=None):
+        """document_ids ([B, S] integer tensor, or a kernels.AttnBand): intra-document causal masking
+        of packed rows; with the config's `sliding_window`, both.  The band is built once per forward
+        and shared by the layers.  position_ids stays unused: RoPE positions are sequence indices, and
+        RoPE scores depend on i - j only, so per-document positions would give the same attention."""
         x = self.embedding(input_ids)
+        band = None
+        if document_ids is not None or getattr(self.model_config, "sliding_window", None) is not None:
+            if FN.ring_enabled():
+                raise NotImplementedError("document masking / sliding-window attention under context parallelism")
+            # (ids of the full rows: a token-row shard of the stream has no band of its own)
+            band = FN.make_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids,
+                                getattr(self.model_config, "sliding_window", None))
         for layer in self.decoder_layers:
-            x = layer(x)
+            x = layer(x) if band is None else layer(x, document_ids=band)
         x = self.final_norm(x)
         return lm_head(self.final_proj, x)
 

@@ -68,7 +68,11 @@ class PipelineParallel(nn.Module):
         m = pgm.process_group_manager
         return stage_layers(num_layers, m.pp_world_size, m.pp_rank)
 
-    def forward(self, input_ids, position_ids, hidden_states):
+    def forward(self, input_ids, position_ids, hidden_states, document_ids=None):
+        if document_ids is not None or any(getattr(layer.attention, "sliding_window", None) is not None
+                                           for layer in self.decoder_layers.values()):
+            raise NotImplementedError("document masking / sliding-window attention in the pipeline engine "
+                                      "(the stages exchange hidden states only)")
         x = self.embedding(input_ids if hidden_states is None else hidden_states)
         for layer in self.decoder_layers.values():
             x = layer(x, position_ids=position_ids)
@@ -128,6 +132,9 @@ def _run_schedule(kind, model, data_loader, tensor_shapes, device, dtype):
         if op == "F":
             x = pipeline_communicate("recv_forward", device, dtype, shapes=tensor_shapes) if recv else carry
             batch = next(data_loader)
+            if "document_ids" in batch:
+                raise NotImplementedError("the pipeline engine does not carry document_ids (document-masked "
+                                          "attention) to its stages")
             out = model.forward(input_ids=batch["input_ids"].to(device), position_ids=batch["position_ids"].to(device),
                                 hidden_states=None if x is None else x.to(device))
             if m.pp_is_last_stage:

@@ -108,7 +108,10 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True):
             target_ids = batch["target_ids"].to(device)
             if requires_grad_sync:
                 model.require_backward_grad_sync = (i == ga - 1)
-            outputs = model(input_ids=input_ids)
+            if "document_ids" in batch:   # packed rows: tokens attend within their own document
+                outputs = model(input_ids=input_ids, document_ids=batch["document_ids"].to(device))
+            else:
+                outputs = model(input_ids=input_ids)
             batch_size, seq_len = input_ids.shape
             target_ids = target_ids.reshape(-1)
             outputs = outputs.view(seq_len * batch_size, -1)
@@ -237,6 +240,8 @@ class GraphedTrainStep:
             if on_microbatch is not None:
                 on_microbatch(i)
             batch = next(self.loader)
+            if "document_ids" in batch:   # the band is rebuilt from each batch's ids: not a replayed launch
+                raise NotImplementedError("GraphedTrainStep: document-masked batches (document_ids) are not captured")
             if self.graph is None and i < self.warmup:
                 side = torch.cuda.Stream(self.device)
                 side.wait_stream(torch.cuda.current_stream(self.device))

@@ -6,6 +6,11 @@ each 2 B h S^2 d / 2).
 
     python tools/attn_bench.py [--reps 20] [--B 4 --S 1024 --H 32 --D 64] [--old lib.so]
 
+--docs N / --window W: a further arm "band" on this build -- document-masked (N equal documents per row)
+and / or sliding-window (W keys) causal attention through pt_attn_fwd_band / pt_attn_bwd_band, timed
+beside the causal arm in the same rounds (the backward as the layer calls it: delta inside).  Its
+TF/s are in causal FLOP, so they read as speed relative to the causal kernels, not as MFMA rate.
+
 --old: libraries (comma-separated) holding other builds of the pt_attn_* entry points, timed in the
 same process (rounds interleaved, first one rotated) and compared element-wise with this build's outputs.
 """
@@ -62,6 +67,8 @@ def main():
     ap.add_argument("--full", action="store_true",
                     help="the CP ring's visiting block: no causal mask, f32 dq/dk/dv accumulators (grad_f32)")
     ap.add_argument("--rounds", type=int, default=2, help="interleaved rounds; medians are printed at the end")
+    ap.add_argument("--docs", type=int, default=0, help="band arm: N equal documents per row (S %% N == 0)")
+    ap.add_argument("--window", type=int, default=0, help="band arm: sliding window of W keys")
     a = ap.parse_args()
     B, S, H, D = a.B, a.S, a.H, a.D
     g = torch.Generator(device="cuda").manual_seed(0)
@@ -84,6 +91,14 @@ def main():
         for val in vals[1:]:
             libs[f"{var}={val}"] = libs["new"]
             variants[f"{var}={val}"] = {var: val}
+    bands = {}
+    if a.docs or a.window:
+        if a.full or (a.docs and S % a.docs):
+            ap.error("--docs / --window: causal only, S a multiple of --docs")
+        ids = (torch.arange(S, device="cuda") // (S // a.docs)).expand(B, S) if a.docs else None
+        bands["band"] = K.attn_band(B, S, "cuda", document_ids=ids, window=a.window or None)
+        libs["band"] = libs["new"]
+        variants["band"] = dict(variants["new"])
     defaults = {}
     outs = {}
     split_ws = K._attn_split_ws
@@ -99,9 +114,15 @@ def main():
                 if var not in defaults:
                     defaults[var] = lib.pt_get_variant(var.encode())
                 lib.pt_set_variant(var.encode(), int(val))
-            o, lse = K.attn_fwd(q, k, v, scale, causal)
+            band = bands.get(name)
+            o, lse = K.attn_fwd(q, k, v, scale, causal, band=band)
             delta = K.attn_delta(do, o)
-            if a.full:
+            if band is not None:
+                dq, dk, dv, _ = K.attn_bwd(do, q, k, v, o, lse, scale, True, band=band)
+
+                def bwd():
+                    K.attn_bwd(do, q, k, v, o, lse, scale, True, band=band)
+            elif a.full:
                 for t in acc:
                     t.zero_()
                 K.attn_bwd(do, q, k, v, o, lse, scale, False, dq=acc[0], dk=acc[1], dv=acc[2], grad_f32=True,
@@ -118,7 +139,7 @@ def main():
                 def bwd():
                     K.attn_bwd(do, q, k, v, o, lse, scale, True, delta=dl)
             outs[name] = [t.clone() for t in (o, lse, dq, dk, dv)]
-            t_fwd = graph_us(lambda: K.attn_fwd(q, k, v, scale, causal, out=o, lse=lse), a.reps)
+            t_fwd = graph_us(lambda: K.attn_fwd(q, k, v, scale, causal, out=o, lse=lse, band=band), a.reps)
             t_bwd = graph_us(bwd, a.reps)
             for var, val in defaults.items():
                 lib.pt_set_variant(var.encode(), int(val))
@@ -134,7 +155,7 @@ def main():
         f, b = sorted(m["fwd"])[len(m["fwd"]) // 2], sorted(m["bwd"])[len(m["bwd"]) // 2]
         print(json.dumps({"median": name, "fwd_us": round(f, 1), "bwd_us": round(b, 1)}), flush=True)
     for name in outs:
-        if name == "new":
+        if name in ("new", "band"):
             continue
         rel = [((x.float() - y.float()).norm() / y.float().norm()).item() for x, y in zip(outs["new"], outs[name])]
         print(json.dumps({f"new_vs_{name}_rel_o_lse_dq_dk_dv": rel}), flush=True)
