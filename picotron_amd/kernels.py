@@ -165,6 +165,8 @@ def embedding_fwd(ids, weight, vocab_lo=0, vocab_hi=None):
     flat = ids.reshape(-1).contiguous().to(torch.int64)
     H = weight.shape[1]
     out = torch.empty(flat.numel(), H, dtype=BF16, device=weight.device)
+    if flat.numel() == 0:   # an empty tensor has no address to hand to the kernel's argument check
+        return out.view(*ids.shape, H)
     rc = _C.lib().pt_embedding_fwd(_ptr(flat), flat.numel(), _ptr(weight), weight.stride(0), int(vocab_lo),
                                    int(vocab_hi), _ptr(out), out.stride(0), H, _C.stream_ptr(weight.device))
     _C.check(rc, "pt_embedding_fwd")
@@ -178,6 +180,8 @@ def embedding_bwd(ids, dy2d, dweight, sink, vocab_lo=0, vocab_hi=None, padding_i
     flat = ids.reshape(-1).to(torch.int64).contiguous()
     vocab_hi = vocab_lo + dweight.shape[0] if vocab_hi is None else vocab_hi
     T = flat.numel()
+    if T == 0:   # no token: nothing to add (and no address to hand to the kernels' argument checks)
+        return
     sorted_ids = torch.empty(T, dtype=torch.int64, device=flat.device)
     perm = torch.empty(T, dtype=torch.int64, device=flat.device)
     rc = _C.lib().pt_embedding_sort(_ptr(flat), T, int(vocab_lo), int(vocab_hi), int(padding_idx is not None),
