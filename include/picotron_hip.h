@@ -130,6 +130,44 @@ int pt_cross_entropy_bwd_lse_shard(const void* logits, int64_t logits_stride, co
                                    int64_t vocab_shard, int64_t vocab_lo, const float* scale, int64_t scale_stride,
                                    int64_t ignore_index, hipStream_t stream);
 
+/* ---- auxiliary z-loss (PaLM / OLMo-2 / Chameleon): z_coef * lse^2 per valid row ----------------
+ * Each _z function is its namesake with the z term, formed from the row LSE the forward already
+ * holds (no further pass over the logits):
+ *   row_z[r] = z_coef * lse^2 (optional output [rows] f32, NULL: not written; 0 on ignore_index
+ *   rows, NaN for a bad target);  row_loss[r] = (lse - logit[target]) + row_z[r];
+ *   dlogits = (exp(x - lse) * (1 + 2 z_coef lse) - onehot) * scale[...]  (ignored rows: +0).
+ * z_coef is a finite f32 >= 0 (else PT_EINVAL before any launch); z_coef == 0 writes the bits of
+ * the plain function and row_z = 0.  pt_cross_entropy_mean over row_z gives the reported z part. */
+/* pt_cross_entropy_fwd_bwd with the z term in row_loss, row_z and dlogits (both kernels). */
+int pt_cross_entropy_fwd_bwd_z(const void* logits, int64_t logits_stride, const int64_t* targets, void* dlogits,
+                               int64_t dlogits_stride, float* row_loss, int64_t rows, int64_t vocab, float scale,
+                               const float* inv_count, int64_t ignore_index, int* status, float z_coef, float* row_z,
+                               hipStream_t stream);
+/* pt_cross_entropy_fwd_lse with the z term; row_lse is the plain LSE, saved for the backward. */
+int pt_cross_entropy_fwd_lse_z(const void* logits, int64_t logits_stride, const int64_t* targets, float* row_loss,
+                               float* row_lse, int64_t rows, int64_t vocab, int64_t ignore_index, int* status,
+                               float z_coef, float* row_z, hipStream_t stream);
+/* pt_cross_entropy_bwd_lse with the factor 1 + 2 z_coef row_lse on the softmax. */
+int pt_cross_entropy_bwd_lse_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                               const float* row_lse, void* dlogits, int64_t dlogits_stride, int64_t rows,
+                               int64_t vocab, const float* scale, int64_t scale_stride, int64_t ignore_index,
+                               float z_coef, hipStream_t stream);
+/* pt_cross_entropy_fwd_stats with the z term (the GEMM statistics are unchanged). */
+int pt_cross_entropy_fwd_stats_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                 const float* stats, int64_t nblk, float* row_loss, float* row_lse, int64_t rows,
+                                 int64_t vocab, int64_t ignore_index, int* status, float z_coef, float* row_z,
+                                 hipStream_t stream);
+/* pt_cross_entropy_vp_combine with the z term from the combined LSE (the 16-byte parts of
+ * pt_cross_entropy_vp_partial are unchanged). */
+int pt_cross_entropy_vp_combine_z(const float* parts, int64_t tp, const int64_t* targets, float* row_loss,
+                                  float* row_lse, int64_t rows, int64_t vocab, int64_t ignore_index, int* status,
+                                  float z_coef, float* row_z, hipStream_t stream);
+/* pt_cross_entropy_bwd_lse_shard with the factor 1 + 2 z_coef row_lse on the shard's softmax. */
+int pt_cross_entropy_bwd_lse_shard_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                     const float* row_lse, void* dlogits, int64_t dlogits_stride, int64_t rows,
+                                     int64_t vocab_shard, int64_t vocab_lo, const float* scale, int64_t scale_stride,
+                                     int64_t ignore_index, float z_coef, hipStream_t stream);
+
 /* train.py:49's reduction='mean' over the per-row losses: loss = sum(row_loss) / #(target !=
  * ignore_index) in one deterministic launch; inv_count = 1 / #valid (the backward's scale);
  * reduce_sum != 0: reduction='sum' (loss = sum(row_loss), inv_count = 1);

@@ -15,6 +15,15 @@
 // PT_STATUS_BAD_TARGET of *status (when given) -- torch's device-side assert, made observable
 // without a trap (kernels.device_status / functional.check_device_status read it).
 //
+// Auxiliary z-loss (PaLM, OLMo-2, Chameleon): the _z entry points add z lse^2 per valid row,
+//   row_z[r]    = z * lse_r^2                  (0 for ignored rows, NaN for a bad target)
+//   row_loss[r] = (lse_r - x[r, t_r]) + row_z[r]
+//   dlogits[r,:] = (softmax(x[r,:]) * (1 + 2 z lse_r) - onehot(t_r)) * scale ...
+// from the LSE every forward already holds and every backward already reads: no further pass over
+// the logits.  Each kernel is one body with a compile-time switch Z; the plain entry points and
+// z == 0 run Z = false, which is the arithmetic above without the z terms (z lse^2 is never formed
+// there: 0 * inf would be NaN), so a _z call with z == 0 writes its namesake's bits.
+//
 // One 256-thread workgroup per row; the row is held in registers (NC 16-byte chunks per
 // thread) so HBM sees exactly one read and one write of the logits: 4*V bytes per row, the
 // roofline figure in DESIGN.md.  Rows longer than 256*8*32 elements take the two-pass variant.
@@ -36,12 +45,33 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
   return r;
 }
 
-template <int NC>
+// z lse^2: two f32 multiplies, and the loss's sum kept a separate rounding (no contraction)
+template <bool Z>
+__device__ __forceinline__ void store_row_loss(float* __restrict__ row_loss, float* __restrict__ row_z, int64_t row,
+                                               bool valid, float lse, float xt, float z) {
+#pragma clang fp contract(off)
+  float loss = valid ? lse - xt : 0.f, rz = 0.f;
+  if (Z && valid) {
+    rz = z * (lse * lse);
+    loss = loss + rz;
+  }
+  row_loss[row] = loss;
+  if (row_z) row_z[row] = rz;
+}
+
+// d(lse + z lse^2) / dx_j = p_j (1 + 2 z lse); 1 on ignored rows, whose gradient stays +0 by bits
+template <bool Z>
+__device__ __forceinline__ float z_factor(bool valid, float lse, float z) {
+  return (Z && valid) ? fmaf(2.f * z, lse, 1.f) : 1.f;
+}
+
+template <int NC, bool Z>
 __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict__ logits, int64_t ls,
                                                       const int64_t* __restrict__ tgt, uint16_t* dlogits,
                                                       int64_t ds, float* __restrict__ row_loss, int V,
                                                       float scale, const float* __restrict__ inv_count,
-                                                      int64_t ignore_index, int* __restrict__ status) {
+                                                      int64_t ignore_index, int* __restrict__ status, float z,
+                                                      float* __restrict__ row_z) {
   __shared__ float red[kThreads / 64];
   const int64_t row = blockIdx.x;
   const uint16_t* x = logits + row * ls;
@@ -80,8 +110,9 @@ __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict
   se = block_reduce(se, red, false);
   const float lse = bad ? __builtin_nanf("") : mx + __logf(se);
   const float g = valid ? scale * (inv_count ? *inv_count : 1.0f) : 0.f;
-  if (threadIdx.x == 0) row_loss[row] = valid ? lse - xt : 0.f;
+  if (threadIdx.x == 0) store_row_loss<Z>(row_loss, row_z, row, valid, lse, xt, z);
   if (!dlogits) return;  // loss-only (forward) launch
+  const float cz = z_factor<Z>(valid, lse, z);
   uint16_t* d = dlogits + row * ds;
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
@@ -91,7 +122,8 @@ __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict
       unpack8(v[i], f);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float p = __expf(f[j] - lse);
+        float p = __expf(f[j] - lse);
+        if (Z) p *= cz;
         f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
       }
       st8(d + c * 8, pack8(f));
@@ -100,11 +132,13 @@ __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict
 }
 
 // long rows: online max/sum in one read, gradient in a second read
+template <bool Z>
 __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __restrict__ logits, int64_t ls,
                                                             const int64_t* __restrict__ tgt, uint16_t* dlogits,
                                                             int64_t ds, float* __restrict__ row_loss, int V,
                                                             float scale, const float* __restrict__ inv_count,
-                                                            int64_t ignore_index, int* __restrict__ status) {
+                                                            int64_t ignore_index, int* __restrict__ status, float z,
+                                                            float* __restrict__ row_z) {
   __shared__ float red[kThreads / 64];
   __shared__ float red2[kThreads / 64];
   const int64_t row = blockIdx.x;
@@ -143,16 +177,22 @@ __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __re
   const bool bad = valid && (t < 0 || t >= V);
   const float lse = bad ? __builtin_nanf("") : M + __logf(S);
   const float g = valid ? scale * (inv_count ? *inv_count : 1.0f) : 0.f;
-  if (threadIdx.x == 0) row_loss[row] = valid ? lse - (bad ? 0.f : bf2f(x[t])) : 0.f;
+  if (threadIdx.x == 0)
+    store_row_loss<Z>(row_loss, row_z, row, valid, lse, (valid && !bad) ? bf2f(x[t]) : 0.f, z);
   if (bad && threadIdx.x == 0 && status) status[0] = PT_STATUS_BAD_TARGET;
   __syncthreads();  // x[t] read before any in-place write
   if (!dlogits) return;
+  const float cz = z_factor<Z>(valid, lse, z);
   uint16_t* d = dlogits + row * ds;
   for (int c = threadIdx.x; c < nch; c += kThreads) {
     float f[8];
     unpack8(ld8(x + c * 8), f);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (__expf(f[j] - lse) - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
+    for (int j = 0; j < 8; ++j) {
+      float p = __expf(f[j] - lse);
+      if (Z) p *= cz;
+      f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
+    }
     st8(d + c * 8, pack8(f));
   }
 }
@@ -166,11 +206,13 @@ __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __re
 constexpr int kUnroll = 4;
 constexpr float kLog2e = 1.4426950408889634f;
 
+template <bool Z>
 __global__ __launch_bounds__(kThreads) void ce_fwd_stream_kernel(const uint16_t* __restrict__ logits, int64_t ls,
                                                                  const int64_t* __restrict__ tgt,
                                                                  float* __restrict__ row_loss,
                                                                  float* __restrict__ row_lse, int V,
-                                                                 int64_t ignore_index, int* __restrict__ status) {
+                                                                 int64_t ignore_index, int* __restrict__ status,
+                                                                 float z, float* __restrict__ row_z) {
   __shared__ float red[kThreads / 64];
   __shared__ float red2[kThreads / 64];
   const int64_t row = blockIdx.x;
@@ -229,7 +271,7 @@ __global__ __launch_bounds__(kThreads) void ce_fwd_stream_kernel(const uint16_t*
     const bool bad = valid && (t < 0 || t >= V);
     const float lse = bad ? __builtin_nanf("") : M + __logf(S);
     row_lse[row] = lse;
-    row_loss[row] = valid ? lse - (bad ? 0.f : bf2f(x[t])) : 0.f;
+    store_row_loss<Z>(row_loss, row_z, row, valid, lse, (valid && !bad) ? bf2f(x[t]) : 0.f, z);
     if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
   }
 }
@@ -241,10 +283,11 @@ __global__ __launch_bounds__(kThreads) void ce_fwd_stream_kernel(const uint16_t*
 // partial merges of a row are combined in a fixed order.  The [rows, V] logits are not read again
 // (only x[t]).
 constexpr int kStatRows = 32, kStatGroups = 8;
+template <bool Z>
 __global__ __launch_bounds__(kStatRows * kStatGroups) void ce_fwd_stats_kernel(
     const uint16_t* __restrict__ logits, int64_t ls, const int64_t* __restrict__ tgt,
     const float2* __restrict__ stats, int nblk, float* __restrict__ row_loss, float* __restrict__ row_lse,
-    int64_t rows, int V, int64_t ignore_index, int* __restrict__ status) {
+    int64_t rows, int V, int64_t ignore_index, int* __restrict__ status, float z, float* __restrict__ row_z) {
   __shared__ float2 part[kStatGroups][kStatRows];
   const int r = threadIdx.x % kStatRows, grp = threadIdx.x / kStatRows;
   const int64_t row = (int64_t)blockIdx.x * kStatRows + r;
@@ -271,7 +314,7 @@ __global__ __launch_bounds__(kStatRows * kStatGroups) void ce_fwd_stats_kernel(
     const bool bad = valid && (t < 0 || t >= V);
     const float lse = bad ? __builtin_nanf("") : m + __logf(s);
     row_lse[row] = lse;
-    row_loss[row] = valid ? lse - (bad ? 0.f : bf2f(logits[row * ls + t])) : 0.f;
+    store_row_loss<Z>(row_loss, row_z, row, valid, lse, (valid && !bad) ? bf2f(logits[row * ls + t]) : 0.f, z);
     if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
   }
 }
@@ -315,13 +358,14 @@ __global__ __launch_bounds__(kMeanThreads) void ce_mean_kernel(const float* __re
   }
 }
 
+template <bool Z>
 __global__ __launch_bounds__(kThreads) void ce_bwd_stream_kernel(const uint16_t* __restrict__ logits, int64_t ls,
                                                                  const int64_t* __restrict__ tgt,
                                                                  const float* __restrict__ row_lse,
                                                                  uint16_t* __restrict__ dl, int64_t ds, int V,
                                                                  const float* __restrict__ scale_dev,
                                                                  int64_t scale_stride, int64_t ignore_index,
-                                                                 int64_t vocab_lo) {
+                                                                 int64_t vocab_lo, float z) {
   const int64_t row = blockIdx.x;
   const uint16_t* x = logits + row * ls;
   uint16_t* d = dl + row * ds;
@@ -329,6 +373,7 @@ __global__ __launch_bounds__(kThreads) void ce_bwd_stream_kernel(const uint16_t*
   const int64_t t = tgt[row] - vocab_lo;   // a vocab shard [vocab_lo, vocab_lo + V): its own columns
   const float nl2 = -row_lse[row] * kLog2e;   // exp(x - lse) = exp2(x log2e - lse log2e)
   const float g = tgt[row] != ignore_index ? scale_dev[row * scale_stride] : 0.f;
+  const float cz = z_factor<Z>(tgt[row] != ignore_index, row_lse[row], z);
   for (int c0 = threadIdx.x; c0 < nch; c0 += kThreads * kUnroll) {
     bf16x8 v[kUnroll];
 #pragma unroll
@@ -343,8 +388,11 @@ __global__ __launch_bounds__(kThreads) void ce_bwd_stream_kernel(const uint16_t*
         float f[8];
         unpack8(v[u], f);
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          f[j] = (__builtin_amdgcn_exp2f(fmaf(f[j], kLog2e, nl2)) - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
+        for (int j = 0; j < 8; ++j) {
+          float p = __builtin_amdgcn_exp2f(fmaf(f[j], kLog2e, nl2));
+          if (Z) p *= cz;
+          f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
+        }
         st8(d + c * 8, pack8(f));
       }
     }
@@ -389,10 +437,12 @@ __global__ __launch_bounds__(kStatRows * kStatGroups) void ce_vp_partial_kernel(
 
 // every rank's partials [tp][rows] -> row_lse, row_loss (lse - x[target]); the range check of
 // ce_fwd_stats_kernel against the global vocab (NaN row + PT_STATUS_BAD_TARGET)
+template <bool Z>
 __global__ __launch_bounds__(256) void ce_vp_combine_kernel(const float4* __restrict__ parts, int tp,
                                                             const int64_t* __restrict__ tgt, float* __restrict__ row_loss,
                                                             float* __restrict__ row_lse, int64_t rows, int64_t V,
-                                                            int64_t ignore_index, int* __restrict__ status) {
+                                                            int64_t ignore_index, int* __restrict__ status, float z,
+                                                            float* __restrict__ row_z) {
   const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= rows) return;
   float m = -INFINITY, s = 0.f, xt = 0.f;
@@ -408,7 +458,7 @@ __global__ __launch_bounds__(256) void ce_vp_combine_kernel(const float4* __rest
   const bool bad = valid && (t < 0 || t >= V);
   const float lse = bad ? __builtin_nanf("") : m + __logf(s);
   row_lse[row] = lse;
-  row_loss[row] = valid ? lse - xt : 0.f;
+  store_row_loss<Z>(row_loss, row_z, row, valid, lse, xt, z);
   if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
 }
 
@@ -428,14 +478,48 @@ extern "C" int pt_cross_entropy_vp_partial(const void* logits, int64_t logits_st
   return PT_OK;
 }
 
+// z_coef of the _z entry points: finite and >= 0 (NaN fails the comparison)
+static bool z_ok(float z) { return z >= 0.f && z < __builtin_inff(); }
+
+// Every rank's parts -> row_loss / row_lse (+ z lse^2 in row_loss and, optionally, row_z [rows]).
+extern "C" int pt_cross_entropy_vp_combine_z(const float* parts, int64_t tp, const int64_t* targets, float* row_loss,
+                                             float* row_lse, int64_t rows, int64_t vocab, int64_t ignore_index,
+                                             int* status, float z_coef, float* row_z, hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
+  if (!parts || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0 || tp <= 0) return PT_EINVAL;
+  if (!pt_aligned16(parts)) return PT_EALIGN;
+  const unsigned grid = (unsigned)((rows + 255) / 256);
+#define PT_CE(Z) ce_vp_combine_kernel<Z><<<grid, 256, 0, stream>>>((const float4*)parts, (int)tp, targets, row_loss, row_lse, rows, vocab, ignore_index, status, z_coef, row_z)
+  if (z_coef > 0.f) PT_CE(true);
+  else PT_CE(false);
+#undef PT_CE
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
 extern "C" int pt_cross_entropy_vp_combine(const float* parts, int64_t tp, const int64_t* targets, float* row_loss,
                                            float* row_lse, int64_t rows, int64_t vocab, int64_t ignore_index,
                                            int* status, hipStream_t stream) {
-  if (!parts || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0 || tp <= 0) return PT_EINVAL;
-  if (!pt_aligned16(parts)) return PT_EALIGN;
-  ce_vp_combine_kernel<<<(unsigned)((rows + 255) / 256), 256, 0, stream>>>((const float4*)parts, (int)tp, targets,
-                                                                          row_loss, row_lse, rows, vocab,
-                                                                          ignore_index, status);
+  return pt_cross_entropy_vp_combine_z(parts, tp, targets, row_loss, row_lse, rows, vocab, ignore_index, status, 0.f,
+                                       nullptr, stream);
+}
+
+// dlogits = (exp(x - lse) (1 + 2 z lse) - onehot) scale on a vocab shard.
+extern "C" int pt_cross_entropy_bwd_lse_shard_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                                const float* row_lse, void* dlogits, int64_t dlogits_stride,
+                                                int64_t rows, int64_t vocab_shard, int64_t vocab_lo,
+                                                const float* scale, int64_t scale_stride, int64_t ignore_index,
+                                                float z_coef, hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
+  if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab_shard <= 0) return PT_EINVAL;
+  if (scale_stride != 0 && scale_stride != 1) return PT_EINVAL;
+  if ((vocab_shard & 7) || (logits_stride & 7) || (dlogits_stride & 7)) return PT_EALIGN;
+  if (!pt_aligned16(logits) || !pt_aligned16(dlogits)) return PT_EALIGN;
+  if (rows > INT32_MAX || vocab_shard > INT32_MAX) return PT_EUNSUPPORTED;
+#define PT_CE(Z) ce_bwd_stream_kernel<Z><<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, row_lse, (uint16_t*)dlogits, dlogits_stride, (int)vocab_shard, scale, scale_stride, ignore_index, vocab_lo, z_coef)
+  if (z_coef > 0.f) PT_CE(true);
+  else PT_CE(false);
+#undef PT_CE
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -444,15 +528,23 @@ extern "C" int pt_cross_entropy_bwd_lse_shard(const void* logits, int64_t logits
                                               const float* row_lse, void* dlogits, int64_t dlogits_stride,
                                               int64_t rows, int64_t vocab_shard, int64_t vocab_lo, const float* scale,
                                               int64_t scale_stride, int64_t ignore_index, hipStream_t stream) {
-  if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab_shard <= 0) return PT_EINVAL;
-  if (scale_stride != 0 && scale_stride != 1) return PT_EINVAL;
-  if ((vocab_shard & 7) || (logits_stride & 7) || (dlogits_stride & 7)) return PT_EALIGN;
-  if (!pt_aligned16(logits) || !pt_aligned16(dlogits)) return PT_EALIGN;
-  if (rows > INT32_MAX || vocab_shard > INT32_MAX) return PT_EUNSUPPORTED;
-  ce_bwd_stream_kernel<<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets,
-                                                               row_lse, (uint16_t*)dlogits, dlogits_stride,
-                                                               (int)vocab_shard, scale, scale_stride, ignore_index,
-                                                               vocab_lo);
+  return pt_cross_entropy_bwd_lse_shard_z(logits, logits_stride, targets, row_lse, dlogits, dlogits_stride, rows,
+                                          vocab_shard, vocab_lo, scale, scale_stride, ignore_index, 0.f, stream);
+}
+
+// The streaming forward with the z term: row_loss = (lse - x_t) + z lse^2, row_z (optional) = z lse^2.
+extern "C" int pt_cross_entropy_fwd_lse_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                          float* row_loss, float* row_lse, int64_t rows, int64_t vocab,
+                                          int64_t ignore_index, int* status, float z_coef, float* row_z,
+                                          hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
+  if (!logits || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0) return PT_EINVAL;
+  if ((vocab & 7) || (logits_stride & 7) || !pt_aligned16(logits)) return PT_EALIGN;
+  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
+#define PT_CE(Z) ce_fwd_stream_kernel<Z><<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, row_loss, row_lse, (int)vocab, ignore_index, status, z_coef, row_z)
+  if (z_coef > 0.f) PT_CE(true);
+  else PT_CE(false);
+#undef PT_CE
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -460,35 +552,33 @@ extern "C" int pt_cross_entropy_bwd_lse_shard(const void* logits, int64_t logits
 extern "C" int pt_cross_entropy_fwd_lse(const void* logits, int64_t logits_stride, const int64_t* targets,
                                         float* row_loss, float* row_lse, int64_t rows, int64_t vocab,
                                         int64_t ignore_index, int* status, hipStream_t stream) {
-  if (!logits || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0) return PT_EINVAL;
-  if ((vocab & 7) || (logits_stride & 7) || !pt_aligned16(logits)) return PT_EALIGN;
-  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
-  ce_fwd_stream_kernel<<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets,
-                                                               row_loss, row_lse, (int)vocab, ignore_index, status);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  return pt_cross_entropy_fwd_lse_z(logits, logits_stride, targets, row_loss, row_lse, rows, vocab, ignore_index,
+                                    status, 0.f, nullptr, stream);
+}
+
+// The elementwise backward from the saved LSE with the z factor on the softmax.
+extern "C" int pt_cross_entropy_bwd_lse_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                          const float* row_lse, void* dlogits, int64_t dlogits_stride, int64_t rows,
+                                          int64_t vocab, const float* scale, int64_t scale_stride,
+                                          int64_t ignore_index, float z_coef, hipStream_t stream) {
+  return pt_cross_entropy_bwd_lse_shard_z(logits, logits_stride, targets, row_lse, dlogits, dlogits_stride, rows,
+                                          vocab, 0, scale, scale_stride, ignore_index, z_coef, stream);
 }
 
 extern "C" int pt_cross_entropy_bwd_lse(const void* logits, int64_t logits_stride, const int64_t* targets,
                                         const float* row_lse, void* dlogits, int64_t dlogits_stride, int64_t rows,
                                         int64_t vocab, const float* scale, int64_t scale_stride,
                                         int64_t ignore_index, hipStream_t stream) {
-  if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab <= 0) return PT_EINVAL;
-  if (scale_stride != 0 && scale_stride != 1) return PT_EINVAL;
-  if ((vocab & 7) || (logits_stride & 7) || (dlogits_stride & 7)) return PT_EALIGN;
-  if (!pt_aligned16(logits) || !pt_aligned16(dlogits)) return PT_EALIGN;
-  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
-  ce_bwd_stream_kernel<<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets,
-                                                               row_lse, (uint16_t*)dlogits, dlogits_stride,
-                                                               (int)vocab, scale, scale_stride, ignore_index, 0);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  return pt_cross_entropy_bwd_lse_shard_z(logits, logits_stride, targets, row_lse, dlogits, dlogits_stride, rows,
+                                          vocab, 0, scale, scale_stride, ignore_index, 0.f, stream);
 }
 
-extern "C" int pt_cross_entropy_fwd_bwd(const void* logits, int64_t logits_stride, const int64_t* targets,
-                                        void* dlogits, int64_t dlogits_stride, float* row_loss, int64_t rows,
-                                        int64_t vocab, float scale, const float* inv_count, int64_t ignore_index,
-                                        int* status, hipStream_t stream) {
+// The one-read fused form with the z term in row_loss (and row_z, optional) and in dlogits.
+extern "C" int pt_cross_entropy_fwd_bwd_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                          void* dlogits, int64_t dlogits_stride, float* row_loss, int64_t rows,
+                                          int64_t vocab, float scale, const float* inv_count, int64_t ignore_index,
+                                          int* status, float z_coef, float* row_z, hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
   if (!logits || !targets || !row_loss || rows <= 0 || vocab <= 0) return PT_EINVAL;
   if ((vocab & 7) || (logits_stride & 7) || (dlogits && (dlogits_stride & 7))) return PT_EALIGN;
   if (!pt_aligned16(logits) || (dlogits && !pt_aligned16(dlogits))) return PT_EALIGN;
@@ -497,33 +587,55 @@ extern "C" int pt_cross_entropy_fwd_bwd(const void* logits, int64_t logits_strid
   auto* D = (uint16_t*)dlogits;
   const int nc = (int)((vocab / 8 + kThreads - 1) / kThreads);
   const dim3 grid((unsigned)rows);
-#define PT_CE(N) ce_kernel<N><<<grid, kThreads, 0, stream>>>(L, logits_stride, targets, D, dlogits_stride, row_loss, (int)vocab, scale, inv_count, ignore_index, status)
+  const bool zon = z_coef > 0.f;
+#define PT_CE_ARGS <<<grid, kThreads, 0, stream>>>(L, logits_stride, targets, D, dlogits_stride, row_loss, (int)vocab, scale, inv_count, ignore_index, status, z_coef, row_z)
+#define PT_CE(N) do { if (zon) ce_kernel<N, true> PT_CE_ARGS; else ce_kernel<N, false> PT_CE_ARGS; } while (0)
   if (nc <= 4) PT_CE(4);
   else if (nc <= 8) PT_CE(8);
   else if (nc <= 16) PT_CE(16);
   else if (nc <= 24) PT_CE(24);
   else if (nc <= 32) PT_CE(32);
-  else ce_kernel_2pass<<<grid, kThreads, 0, stream>>>(L, logits_stride, targets, D, dlogits_stride, row_loss,
-                                                      (int)vocab, scale, inv_count, ignore_index, status);
+  else if (zon) ce_kernel_2pass<true> PT_CE_ARGS;
+  else ce_kernel_2pass<false> PT_CE_ARGS;
+#undef PT_CE
+#undef PT_CE_ARGS
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+extern "C" int pt_cross_entropy_fwd_bwd(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                        void* dlogits, int64_t dlogits_stride, float* row_loss, int64_t rows,
+                                        int64_t vocab, float scale, const float* inv_count, int64_t ignore_index,
+                                        int* status, hipStream_t stream) {
+  return pt_cross_entropy_fwd_bwd_z(logits, logits_stride, targets, dlogits, dlogits_stride, row_loss, rows, vocab,
+                                    scale, inv_count, ignore_index, status, 0.f, nullptr, stream);
+}
+
+// Forward (per-row loss + LSE) from the lm_head GEMM's statistics (pt_gemm_ce_stats): float2
+// stats[b * rows + row] = (max, sum exp(x - max)) of the row's logits in column tile b < nblk;
+// the z term as in pt_cross_entropy_fwd_lse_z.
+extern "C" int pt_cross_entropy_fwd_stats_z(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                            const float* stats, int64_t nblk, float* row_loss, float* row_lse,
+                                            int64_t rows, int64_t vocab, int64_t ignore_index, int* status,
+                                            float z_coef, float* row_z, hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
+  if (!logits || !targets || !stats || !row_loss || !row_lse || rows <= 0 || vocab <= 0 || nblk <= 0) return PT_EINVAL;
+  if (vocab % nblk || !pt_aligned16(stats)) return PT_EINVAL;
+  const unsigned grid = (unsigned)((rows + kStatRows - 1) / kStatRows);
+#define PT_CE(Z) ce_fwd_stats_kernel<Z><<<grid, kStatRows * kStatGroups, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, (const float2*)stats, (int)nblk, row_loss, row_lse, rows, (int)vocab, ignore_index, status, z_coef, row_z)
+  if (z_coef > 0.f) PT_CE(true);
+  else PT_CE(false);
 #undef PT_CE
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
 
-// Forward (per-row loss + LSE) from the lm_head GEMM's statistics (pt_gemm_ce_stats): float2
-// stats[b * rows + row] = (max, sum exp(x - max)) of the row's logits in column tile b < nblk.
 extern "C" int pt_cross_entropy_fwd_stats(const void* logits, int64_t logits_stride, const int64_t* targets,
                                           const float* stats, int64_t nblk, float* row_loss, float* row_lse,
                                           int64_t rows, int64_t vocab, int64_t ignore_index, int* status,
                                           hipStream_t stream) {
-  if (!logits || !targets || !stats || !row_loss || !row_lse || rows <= 0 || vocab <= 0 || nblk <= 0) return PT_EINVAL;
-  if (vocab % nblk || !pt_aligned16(stats)) return PT_EINVAL;
-  const unsigned grid = (unsigned)((rows + kStatRows - 1) / kStatRows);
-  ce_fwd_stats_kernel<<<grid, kStatRows * kStatGroups, 0, stream>>>((const uint16_t*)logits, logits_stride, targets,
-                                                                  (const float2*)stats, (int)nblk, row_loss, row_lse,
-                                                                  rows, (int)vocab, ignore_index, status);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  return pt_cross_entropy_fwd_stats_z(logits, logits_stride, targets, stats, nblk, row_loss, row_lse, rows, vocab,
+                                      ignore_index, status, 0.f, nullptr, stream);
 }
 
 // loss = mean of row_loss over the rows whose target is not ignore_index; inv_count = 1 / #valid

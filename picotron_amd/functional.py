@@ -644,24 +644,31 @@ class VocabParallelCEFunction(torch.autograd.Function):
     statistics), all-gathered over tp (16 B per row), combined in rank order
     (pt_cross_entropy_vp_combine) -- the same loss on every rank.  Backward: the shard's
     (exp(x - lse) - onehot) * scale, the columns of the gathered logits' gradient this rank's
-    GatherFromModelParallelRegion backward (tp_communications.py:69-72) would keep."""
+    GatherFromModelParallelRegion backward (tp_communications.py:69-72) would keep.
+    z > 0 (the auxiliary z-loss): the z term comes from the combined LSE -- the gathered parts are the
+    same 16 bytes per row -- and the outputs are (loss, z_part), z_part f32 and not differentiable."""
 
     @staticmethod
-    def forward(ctx, shard, targets, stats, vocab_lo, vocab, ignore_index, reduction):
+    def forward(ctx, shard, targets, stats, vocab_lo, vocab, ignore_index, reduction, z=0.0):
         lg = _contig2d(shard)
         tg = targets.reshape(-1)
         tp = TPContext.current()
         part = K.cross_entropy_vp_partial(lg, tg, stats, vocab_lo)
         parts = tp.all_gather_rows(part).view(tp.world_size, lg.shape[0], 4)
         odt = shard.dtype if shard.dtype in (torch.bfloat16, torch.float32) else torch.float32
-        loss, inv_count, row_lse = K.cross_entropy_vp_combine(parts, tg, vocab, ignore_index, out_dtype=odt,
-                                                              reduction=reduction)
+        loss, inv_count, row_lse, *zp = K.cross_entropy_vp_combine(parts, tg, vocab, ignore_index, out_dtype=odt,
+                                                                   reduction=reduction, z_loss=z)
         ctx.save_for_backward(lg, tg, row_lse, *([inv_count] if inv_count is not None else []))
         ctx.vocab_lo, ctx.ignore_index, ctx.shape, ctx.reduction = vocab_lo, ignore_index, shard.shape, reduction
-        return loss if loss.dtype == shard.dtype else loss.to(shard.dtype)
+        ctx.z = z
+        loss = loss if loss.dtype == shard.dtype else loss.to(shard.dtype)
+        if not zp:
+            return loss
+        ctx.mark_non_differentiable(zp[0])
+        return loss, zp[0]
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         lg, tg, row_lse, *inv = ctx.saved_tensors
         if ctx.reduction == "none":
             scale = g.float().reshape(-1).contiguous()
@@ -669,8 +676,8 @@ class VocabParallelCEFunction(torch.autograd.Function):
             scale = g.float().reshape(1)
         else:
             scale = g.float().reshape(1) * inv[0]
-        dl = K.cross_entropy_grad_lse_shard(lg, tg, row_lse, scale, ctx.vocab_lo, ctx.ignore_index)
-        return dl.view(ctx.shape), None, None, None, None, None, None
+        dl = K.cross_entropy_grad_lse_shard(lg, tg, row_lse, scale, ctx.vocab_lo, ctx.ignore_index, z_loss=ctx.z)
+        return dl.view(ctx.shape), None, None, None, None, None, None, None
 
 
 _ROW_VIEWS = (torch.Tensor.view, torch.Tensor.reshape, torch.Tensor.flatten)
@@ -701,9 +708,10 @@ def _vp_path_form(path, ndim):
     return None
 
 
-def _vp_cross_entropy(input, target, reduction, ignore_index):
+def _vp_cross_entropy(input, target, reduction, ignore_index, z=0.0):
     """cross_entropy on a stand-in in one of the reference's two forms -- [N, V] rows (train.py:49)
-    or [B, V, S] = transpose(1, 2) of [B, S, V] (pipeline_parallel.py:103,153) -- else None."""
+    or [B, V, S] = transpose(1, 2) of [B, S, V] (pipeline_parallel.py:103,153) -- else None.
+    z > 0: (loss, z_part)."""
     info = input._pt_vp
     shard, V = info.shard, info.vocab
     lead = tuple(shard.shape[:-1])
@@ -719,7 +727,9 @@ def _vp_cross_entropy(input, target, reduction, ignore_index):
     else:
         return None
     out = VocabParallelCEFunction.apply(shard, target.reshape(-1), info.stats, info.vocab_lo, V, ignore_index,
-                                        reduction)
+                                        reduction, z)
+    if z > 0:
+        return tuple(o.view(out_shape) for o in out) if reduction == "none" else out
     return out.view(out_shape) if reduction == "none" else out
 
 
@@ -1224,10 +1234,14 @@ class CrossEntropyFunction(torch.autograd.Function):
     loss and LSE (saved, 16 KiB at 4096 rows) -- or takes both from the lm_head GEMM's statistics;
     backward writes (exp(x - lse) - onehot) * scale elementwise in one more read + write, with the
     scale (the incoming gradient, the reference's `/ grad_acc_steps`, times 1 / #valid for 'mean';
-    per row for 'none') taken from device memory -- no host synchronisation."""
+    per row for 'none') taken from device memory -- no host synchronisation.
+    z > 0 (the auxiliary z-loss, z lse^2 per valid row): the same two launches through the _z kernels --
+    the forward adds the term from the LSE it already holds, the backward multiplies the softmax by
+    1 + 2 z lse -- and the outputs are (loss, z_part), z_part f32, reduced like the loss, not
+    differentiable."""
 
     @staticmethod
-    def forward(ctx, logits, targets, ignore_index, reduction):
+    def forward(ctx, logits, targets, ignore_index, reduction, z=0.0):
         lg = _contig2d(logits)
         tg = targets.reshape(-1)
         stats = _take_ce_stats(lg)   # the lm_head GEMM's statistics of exactly these logits, if any
@@ -1242,17 +1256,21 @@ class CrossEntropyFunction(torch.autograd.Function):
         ctx.vocab = V
         odt = logits.dtype if logits.dtype in (torch.bfloat16, torch.float32) else torch.float32
         if stats is not None:
-            loss, inv_count, row_lse = K.cross_entropy_loss_lse_stats(lg, tg, stats, ignore_index, out_dtype=odt,
-                                                                      reduction=reduction)
+            loss, inv_count, row_lse, *zp = K.cross_entropy_loss_lse_stats(lg, tg, stats, ignore_index, out_dtype=odt,
+                                                                           reduction=reduction, z_loss=z)
         else:
-            loss, inv_count, row_lse = K.cross_entropy_loss_lse(lg, tg, ignore_index, out_dtype=odt,
-                                                                reduction=reduction)
+            loss, inv_count, row_lse, *zp = K.cross_entropy_loss_lse(lg, tg, ignore_index, out_dtype=odt,
+                                                                     reduction=reduction, z_loss=z)
         ctx.save_for_backward(lg, tg, row_lse, *([inv_count] if inv_count is not None else []))
-        ctx.ignore_index, ctx.shape, ctx.reduction = ignore_index, logits.shape, reduction
-        return loss if loss.dtype == logits.dtype else loss.to(logits.dtype)
+        ctx.ignore_index, ctx.shape, ctx.reduction, ctx.z = ignore_index, logits.shape, reduction, z
+        loss = loss if loss.dtype == logits.dtype else loss.to(logits.dtype)
+        if not zp:
+            return loss
+        ctx.mark_non_differentiable(zp[0])
+        return loss, zp[0]
 
     @staticmethod
-    def backward(ctx, g):
+    def backward(ctx, g, *_):
         lg, tg, row_lse, *inv = ctx.saved_tensors
         if ctx.reduction == "none":
             scale = g.float().reshape(-1).contiguous()
@@ -1260,10 +1278,10 @@ class CrossEntropyFunction(torch.autograd.Function):
             scale = g.float().reshape(1)
         else:
             scale = g.float().reshape(1) * inv[0]
-        dl = K.cross_entropy_grad_lse(lg, tg, row_lse, scale, ctx.ignore_index)
+        dl = K.cross_entropy_grad_lse(lg, tg, row_lse, scale, ctx.ignore_index, z_loss=ctx.z)
         if dl.shape[1] != ctx.vocab:
             dl = dl[:, :ctx.vocab]
-        return dl.reshape(ctx.shape), None, None, None
+        return dl.reshape(ctx.shape), None, None, None, None
 
 
 def _plain(t):
@@ -1368,7 +1386,7 @@ def as_logits(t):
     return t if isinstance(t, HipLogits) else t.as_subclass(HipLogits)
 
 
-def cross_entropy(input, target, reduction="mean", ignore_index=-100):
+def cross_entropy(input, target, reduction="mean", ignore_index=-100, z_loss=0.0, return_z_loss=False):
     """Drop-in for F.cross_entropy(input, target, reduction=..., ignore_index=...) at the reference's
     two call sites (reduction='mean'):
       * train.py:49                     input [N, V], target [N];
@@ -1376,11 +1394,29 @@ def cross_entropy(input, target, reduction="mean", ignore_index=-100):
         dim 1 (a view of the [B, S, V] stage output), target [B, S].
     The [B, V, S] form is read as the [B*S, V] rows it views (no copy when the underlying [B, S, V]
     is contiguous); the gradient flows back through the same views.  reduction 'sum' and 'none'
-    (per-row losses shaped like target, 0 at ignored rows) follow torch."""
+    (per-row losses shaped like target, 0 at ignored rows) follow torch.
+
+    z_loss (a finite Python float >= 0, else ValueError; torch has no such keyword) adds the auxiliary
+    z-loss  z_loss * logsumexp(logits)^2  per valid row before the reduction, on every path (plain
+    logits, the lm_head's statistics, a vocabulary off the 8-column grid, [B, V, S], the vocab-parallel
+    stand-in): the returned loss includes it, in the dtype it has without it.  return_z_loss=True
+    returns (loss, z_part): z_part the z term alone, a detached f32 device tensor reduced like the loss
+    (per row, shaped like target, under 'none'; zeros when z_loss == 0).  Nothing is read on the host."""
     if reduction not in ("mean", "sum", "none"):
         raise ValueError(f"cross_entropy: reduction must be 'mean', 'sum' or 'none', got {reduction!r}")
+    z = K.z_coef(z_loss)
+    out = _cross_entropy(input, target, reduction, ignore_index, z)
+    if z > 0:
+        return (out[0], out[1].detach()) if return_z_loss else out[0]
+    if return_z_loss:
+        return out, torch.zeros(out.shape if reduction == "none" else (), dtype=torch.float32, device=out.device)
+    return out
+
+
+def _cross_entropy(input, target, reduction, ignore_index, z):
+    """cross_entropy's paths: the loss, or (loss, z part) when z > 0."""
     if _is_vp(input):   # the TP lm_head's stand-in: on the vocab shards, else on the gathered logits
-        out = _vp_cross_entropy(input, target, reduction, ignore_index)
+        out = _vp_cross_entropy(input, target, reduction, ignore_index, z)
         if out is not None:
             return out
         input = _vp_real(input)
@@ -1391,9 +1427,11 @@ def cross_entropy(input, target, reduction="mean", ignore_index=-100):
             raise ValueError(f"cross_entropy: input [B, V, S] = {tuple(input.shape)} needs target [B, S], got "
                              f"{tuple(target.shape)}")
         rows = input.transpose(1, 2).reshape(B * S, V)
-        out = CrossEntropyFunction.apply(rows, target.reshape(-1), ignore_index, reduction)
-        return out.view(B, S) if reduction == "none" else out
+        out = CrossEntropyFunction.apply(rows, target.reshape(-1), ignore_index, reduction, z)
+        if reduction != "none":
+            return out
+        return tuple(o.view(B, S) for o in out) if z > 0 else out.view(B, S)
     if input.dim() != 2 or target.dim() != 1 or target.shape[0] != input.shape[0]:
         raise ValueError(f"cross_entropy: expected input [N, V] and target [N] (or [B, V, S] / [B, S]), got "
                          f"{tuple(input.shape)} / {tuple(target.shape)}")
-    return CrossEntropyFunction.apply(input, target, ignore_index, reduction)
+    return CrossEntropyFunction.apply(input, target, ignore_index, reduction, z)

@@ -589,9 +589,28 @@ def check_device_status(device=None):
 
 
 # ---------------------------------------------------------------------------- cross entropy
-def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace=True):
+# Auxiliary z-loss: every wrapper below takes z_loss (a finite Python float >= 0; the kernels get it as
+# an f32).  With z_loss == 0 a wrapper calls and returns exactly what it did without the keyword; with
+# z_loss > 0 it calls the _z entry point, the loss includes z_loss * lse^2 per valid row, and the
+# wrappers that produce a loss return one more element: the z part, f32, reduced like the loss.
+def z_coef(z_loss):
+    """z_loss as the float the kernels receive (its f32 value); ValueError unless finite and >= 0."""
+    if isinstance(z_loss, bool) or not isinstance(z_loss, (int, float)):
+        raise ValueError(f"cross_entropy: z_loss must be a Python float (float(x) of a numpy scalar or a tensor), got "
+                         f"{type(z_loss).__name__} {z_loss!r}")
+    if not math.isfinite(z_loss) or z_loss < 0:
+        raise ValueError(f"cross_entropy: z_loss must be a finite float >= 0, got {z_loss!r}")
+    z = ctypes.c_float(z_loss).value
+    if not math.isfinite(z):
+        raise ValueError(f"cross_entropy: z_loss {z_loss!r} is not finite in f32")
+    return z
+
+
+def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace=True, z_loss=0.0):
     """logits [rows, V] bf16, targets [rows] int64.  Returns (loss (f32 scalar tensor, mean over
-    valid rows, *not* multiplied by scale), dlogits (aliases logits when inplace), inv_count)."""
+    valid rows, *not* multiplied by scale), dlogits (aliases logits when inplace), inv_count); with
+    z_loss > 0 the loss and dlogits carry the z term and a fourth element is the mean z part."""
+    z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     targets = targets.contiguous().to(torch.int64)
     rows, vocab = logits.shape
@@ -599,6 +618,15 @@ def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace
     inv_count = (1.0 / valid.sum().clamp_min(1).to(torch.float32)).reshape(1)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     dlogits = logits if inplace else torch.empty_like(logits)
+    if z > 0:
+        row_z = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        rc = _C.lib().pt_cross_entropy_fwd_bwd_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits),
+                                                 dlogits.stride(0), _ptr(row_loss), rows, vocab, float(scale),
+                                                 _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device)),
+                                                 z, _ptr(row_z), _C.stream_ptr(logits.device))
+        _C.check(rc, "pt_cross_entropy_fwd_bwd_z")
+        _status_posted(logits.device)
+        return row_loss.sum() * inv_count[0], dlogits, inv_count, row_z.sum() * inv_count[0]
     rc = _C.lib().pt_cross_entropy_fwd_bwd(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits),
                                            dlogits.stride(0), _ptr(row_loss), rows, vocab, float(scale),
                                            _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device)), _C.stream_ptr(logits.device))
@@ -646,15 +674,33 @@ def _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction):
     return _ce_mean(row_loss, targets, ignore_index, out_dtype, reduce_sum=reduction == "sum")
 
 
-def cross_entropy_loss_lse(logits, targets, ignore_index=-100, out_dtype=torch.float32, reduction="mean"):
+def _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction):
+    """_ce_reduce of the row losses and, in f32, of their z parts: (loss, inv_count, z_part)."""
+    loss, inv_count = _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction)
+    return loss, inv_count, _ce_reduce(row_z, targets, ignore_index, torch.float32, reduction)[0]
+
+
+def cross_entropy_loss_lse(logits, targets, ignore_index=-100, out_dtype=torch.float32, reduction="mean", z_loss=0.0):
     """Forward of the autograd pair: (mean loss f32 scalar tensor, inv_count [1] f32, row_lse [rows]
-    f32) from one streaming read of the logits (online max / sum-exp)."""
+    f32) from one streaming read of the logits (online max / sum-exp); z_loss > 0: (loss with the z
+    term, inv_count, row_lse, z_part)."""
+    z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
     _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
     targets = targets.contiguous()
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     row_lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if z > 0:
+        row_z = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        rc = _C.lib().pt_cross_entropy_fwd_lse_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_loss),
+                                                 _ptr(row_lse), rows, vocab, int(ignore_index),
+                                                 _ptr(status_word(logits.device)), z, _ptr(row_z),
+                                                 _C.stream_ptr(logits.device))
+        _C.check(rc, "pt_cross_entropy_fwd_lse_z")
+        _status_posted(logits.device)
+        loss, inv_count, z_part = _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction)
+        return loss, inv_count, row_lse, z_part
     rc = _C.lib().pt_cross_entropy_fwd_lse(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_loss),
                                            _ptr(row_lse), rows, vocab, int(ignore_index), _ptr(status_word(logits.device)), _C.stream_ptr(logits.device))
     _C.check(rc, "pt_cross_entropy_fwd_lse")
@@ -664,9 +710,11 @@ def cross_entropy_loss_lse(logits, targets, ignore_index=-100, out_dtype=torch.f
     return loss, inv_count, row_lse
 
 
-def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-100):
+def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-100, z_loss=0.0):
     """dlogits = (exp(x - row_lse) - onehot) * scale_dev[0] (one f32 device scalar) or
-    * scale_dev[row] (f32 [rows]: reduction='none'): elementwise, no row reduction."""
+    * scale_dev[row] (f32 [rows]: reduction='none'): elementwise, no row reduction.  z_loss > 0: the
+    softmax term times 1 + 2 z_loss row_lse."""
+    z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
     targets = targets.contiguous()
@@ -674,6 +722,13 @@ def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-10
     _req(row_lse.dtype == torch.float32 and row_lse.is_contiguous() and row_lse.numel() == rows, "row_lse: f32 [rows]")
     scale_dev = scale_dev.contiguous()
     dl = torch.empty(rows, vocab, dtype=BF16, device=logits.device)
+    if z > 0:
+        rc = _C.lib().pt_cross_entropy_bwd_lse_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse),
+                                                 _ptr(dl), dl.stride(0), rows, vocab, _ptr(scale_dev),
+                                                 int(scale_dev.numel() != 1), int(ignore_index), z,
+                                                 _C.stream_ptr(logits.device))
+        _C.check(rc, "pt_cross_entropy_bwd_lse_z")
+        return dl
     rc = _C.lib().pt_cross_entropy_bwd_lse(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse), _ptr(dl),
                                            dl.stride(0), rows, vocab, _ptr(scale_dev), int(scale_dev.numel() != 1),
                                            int(ignore_index), _C.stream_ptr(logits.device))
@@ -1262,9 +1317,10 @@ def linear_ce_stats(x2d, weight):
 
 
 def cross_entropy_loss_lse_stats(logits, targets, stats, ignore_index=-100, out_dtype=torch.float32,
-                                 reduction="mean"):
+                                 reduction="mean", z_loss=0.0):
     """cross_entropy_loss_lse from the lm_head GEMM's statistics (linear_ce_stats): same outputs,
     the logits are not streamed again (only x[row, target] is read)."""
+    z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
     _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
@@ -1273,6 +1329,16 @@ def cross_entropy_loss_lse_stats(logits, targets, stats, ignore_index=-100, out_
     targets = targets.contiguous()
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     row_lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
+    if z > 0:
+        row_z = torch.empty(rows, dtype=torch.float32, device=logits.device)
+        rc = _C.lib().pt_cross_entropy_fwd_stats_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(stats),
+                                                   stats.shape[0], _ptr(row_loss), _ptr(row_lse), rows, vocab,
+                                                   int(ignore_index), _ptr(status_word(logits.device)), z,
+                                                   _ptr(row_z), _C.stream_ptr(logits.device))
+        _C.check(rc, "pt_cross_entropy_fwd_stats_z")
+        _status_posted(logits.device)
+        loss, inv_count, z_part = _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction)
+        return loss, inv_count, row_lse, z_part
     rc = _C.lib().pt_cross_entropy_fwd_stats(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(stats),
                                              stats.shape[0], _ptr(row_loss), _ptr(row_lse), rows, vocab,
                                              int(ignore_index), _ptr(status_word(logits.device)),
@@ -1301,9 +1367,12 @@ def cross_entropy_vp_partial(logits_shard, targets, stats, vocab_lo):
     return part
 
 
-def cross_entropy_vp_combine(parts, targets, vocab, ignore_index=-100, out_dtype=torch.float32, reduction="mean"):
+def cross_entropy_vp_combine(parts, targets, vocab, ignore_index=-100, out_dtype=torch.float32, reduction="mean",
+                             z_loss=0.0):
     """Every tp rank's partials [tp, rows, 4] (rank order) -> (loss, inv_count, row_lse) as
-    cross_entropy_loss_lse_stats returns them for the whole [rows, vocab] logits."""
+    cross_entropy_loss_lse_stats returns them for the whole [rows, vocab] logits (z_loss > 0: the z
+    term from the combined LSE, and z_part as a fourth element)."""
+    z = z_coef(z_loss)
     _req(parts.dtype == torch.float32 and parts.is_contiguous() and parts.dim() == 3 and parts.shape[2] == 4,
          "parts: f32 [tp, rows, 4]")
     tp, rows = parts.shape[0], parts.shape[1]
@@ -1311,6 +1380,15 @@ def cross_entropy_vp_combine(parts, targets, vocab, ignore_index=-100, out_dtype
     targets = targets.contiguous()
     row_loss = torch.empty(rows, dtype=torch.float32, device=parts.device)
     row_lse = torch.empty(rows, dtype=torch.float32, device=parts.device)
+    if z > 0:
+        row_z = torch.empty(rows, dtype=torch.float32, device=parts.device)
+        rc = _C.lib().pt_cross_entropy_vp_combine_z(_ptr(parts), tp, _ptr(targets), _ptr(row_loss), _ptr(row_lse), rows,
+                                                    int(vocab), int(ignore_index), _ptr(status_word(parts.device)), z,
+                                                    _ptr(row_z), _C.stream_ptr(parts.device))
+        _C.check(rc, "pt_cross_entropy_vp_combine_z")
+        _status_posted(parts.device)
+        loss, inv_count, z_part = _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction)
+        return loss, inv_count, row_lse, z_part
     rc = _C.lib().pt_cross_entropy_vp_combine(_ptr(parts), tp, _ptr(targets), _ptr(row_loss), _ptr(row_lse), rows,
                                               int(vocab), int(ignore_index), _ptr(status_word(parts.device)),
                                               _C.stream_ptr(parts.device))
@@ -1320,9 +1398,10 @@ def cross_entropy_vp_combine(parts, targets, vocab, ignore_index=-100, out_dtype
     return loss, inv_count, row_lse
 
 
-def cross_entropy_grad_lse_shard(logits_shard, targets, row_lse, scale_dev, vocab_lo, ignore_index=-100):
+def cross_entropy_grad_lse_shard(logits_shard, targets, row_lse, scale_dev, vocab_lo, ignore_index=-100, z_loss=0.0):
     """cross_entropy_grad_lse on a vocab shard (columns vocab_lo ..): the one-hot only where the
     target falls in the shard; row_lse is the whole vocabulary's."""
+    z = z_coef(z_loss)
     _bf16_rowmajor(logits_shard, "logits")
     rows, vs = logits_shard.shape
     targets = targets.contiguous()
@@ -1330,6 +1409,13 @@ def cross_entropy_grad_lse_shard(logits_shard, targets, row_lse, scale_dev, voca
     _req(row_lse.dtype == torch.float32 and row_lse.is_contiguous() and row_lse.numel() == rows, "row_lse: f32 [rows]")
     scale_dev = scale_dev.contiguous()
     dl = torch.empty(rows, vs, dtype=BF16, device=logits_shard.device)
+    if z > 0:
+        rc = _C.lib().pt_cross_entropy_bwd_lse_shard_z(_ptr(logits_shard), logits_shard.stride(0), _ptr(targets),
+                                                       _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vs, int(vocab_lo),
+                                                       _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index),
+                                                       z, _C.stream_ptr(logits_shard.device))
+        _C.check(rc, "pt_cross_entropy_bwd_lse_shard_z")
+        return dl
     rc = _C.lib().pt_cross_entropy_bwd_lse_shard(_ptr(logits_shard), logits_shard.stride(0), _ptr(targets),
                                                  _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vs, int(vocab_lo),
                                                  _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index),

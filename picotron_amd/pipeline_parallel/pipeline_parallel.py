@@ -119,9 +119,13 @@ def pipeline_schedule(kind, pp_size, pp_rank, n_micro):
     return acts
 
 
-def _run_schedule(kind, model, data_loader, tensor_shapes, device, dtype):
+def _run_schedule(kind, model, data_loader, tensor_shapes, device, dtype, z_loss=0.0):
+    from .. import functional as FN
+    from .. import kernels as K
     m = pgm.process_group_manager
     n = data_loader.grad_acc_steps
+    z_on = K.z_coef(z_loss) > 0     # validated once, on every stage, before any work
+    z_sum = torch.zeros((), dtype=torch.float32, device=device) if z_on and m.pp_is_last_stage else None
     sync = m.cp_dp_world_size > 1
     acts = pipeline_schedule(kind, m.pp_world_size, m.pp_rank, n)
     last_b = max(k for k, a in enumerate(acts) if a[0] == "B")
@@ -138,7 +142,12 @@ def _run_schedule(kind, model, data_loader, tensor_shapes, device, dtype):
             out = model.forward(input_ids=batch["input_ids"].to(device), position_ids=batch["position_ids"].to(device),
                                 hidden_states=None if x is None else x.to(device))
             if m.pp_is_last_stage:
-                out = F.cross_entropy(out.transpose(1, 2), batch["target_ids"].to(device), reduction="mean")
+                if z_on:   # torch's F.cross_entropy has no such keyword: the same kernels, called by name
+                    out, z_part = FN.cross_entropy(out.transpose(1, 2), batch["target_ids"].to(device), reduction="mean",
+                                                   z_loss=z_loss, return_z_loss=True)
+                    z_sum += z_part
+                else:
+                    out = F.cross_entropy(out.transpose(1, 2), batch["target_ids"].to(device), reduction="mean")
                 loss_sum += out.detach().double()
             saved[i] = (x, out)
             if send == "fwd":
@@ -157,15 +166,19 @@ def _run_schedule(kind, model, data_loader, tensor_shapes, device, dtype):
                 carry = None
             else:   # "bwd+fwd": the next forward's activation comes back here
                 carry = bidirectional_pipeline_communicate("send_bwd_recv_fwd", dx, tensor_shapes, device, dtype)
+    model.z_loss_part = z_sum / n if z_sum is not None else None
     return (loss_sum / n).item() if m.pp_is_last_stage else 0.0
 
 
-def train_step_pipeline_afab(model, data_loader, tensor_shapes, device, dtype):
+def train_step_pipeline_afab(model, data_loader, tensor_shapes, device, dtype, z_loss=0.0):
     """All forwards, then all backwards (pipeline_parallel.py:77-122).  Returns the step's logging
-    loss on the last stage (0.0 elsewhere, as the reference)."""
-    return _run_schedule("afab", model, data_loader, tensor_shapes, device, dtype)
+    loss on the last stage (0.0 elsewhere, as the reference).  z_loss > 0: the last stage's loss is
+    functional.cross_entropy(..., z_loss=z_loss), the auxiliary z-loss included, and the step's z part
+    (the mean over the micro-batches, like the logging loss) is left as an f32 device scalar in
+    `model.z_loss_part` on the last stage; None on the other stages and when z_loss == 0."""
+    return _run_schedule("afab", model, data_loader, tensor_shapes, device, dtype, z_loss)
 
 
-def train_step_pipeline_1f1b(model, data_loader, tensor_shapes, device, dtype):
-    """One-forward-one-backward (pipeline_parallel.py:124-214)."""
-    return _run_schedule("1f1b", model, data_loader, tensor_shapes, device, dtype)
+def train_step_pipeline_1f1b(model, data_loader, tensor_shapes, device, dtype, z_loss=0.0):
+    """One-forward-one-backward (pipeline_parallel.py:124-214); z_loss as in train_step_pipeline_afab."""
+    return _run_schedule("1f1b", model, data_loader, tensor_shapes, device, dtype, z_loss)

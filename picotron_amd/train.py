@@ -83,7 +83,7 @@ class SyntheticMicroBatchDataLoader:
                 "hidden_states": None}
 
 
-def train_step(model, data_loader, device, on_microbatch=None, read_loss=True):
+def train_step(model, data_loader, device, on_microbatch=None, read_loss=True, z_loss=0.0):
     """train.py:29-55 with the fused HIP cross-entropy; returns the accumulated loss (float).
     on_microbatch(i): optional hook called before micro-batch i (bench.py samples its GEMM timing).
     read_loss=False: return the loss as a device scalar instead, so that the caller can enqueue the
@@ -93,8 +93,14 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True):
     read_loss=False also postpones the device-status check (a bad cross-entropy target: NaN rows and
     gradients) to `read_step_loss`, i.e. after an optimizer step enqueued in between has already
     applied those gradients -- bench.py's ordering; a training loop that must not update weights
-    from a flagged step reads the loss (read_loss=True) before its optimizer step."""
+    from a flagged step reads the loss (read_loss=True) before its optimizer step.
+    z_loss > 0: the auxiliary z-loss  z_loss * logsumexp(logits)^2  per token is part of every
+    micro-batch's loss (functional.cross_entropy's keyword) and of the returned loss; the step's z
+    part, sum_i z_part_i / grad_acc, is left as an f32 device scalar in `model.z_loss_part` (None when
+    z_loss == 0) -- reading it is the caller's synchronisation, not this function's."""
     acc_loss = torch.zeros((), dtype=torch.float32, device=device)
+    z_on = K.z_coef(z_loss) > 0
+    acc_z = torch.zeros((), dtype=torch.float32, device=device) if z_on else None
     # (bench.py --dp-bucket: a 1-rank DataParallelBucket syncs like N > 1 would)
     requires_grad_sync = pgm.current().cp_dp_world_size > 1 or getattr(model, "_force_grad_sync", False)
     ga = data_loader.grad_acc_steps
@@ -115,7 +121,12 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True):
             batch_size, seq_len = input_ids.shape
             target_ids = target_ids.reshape(-1)
             outputs = outputs.view(seq_len * batch_size, -1)
-            loss = FN.cross_entropy(outputs, target_ids, reduction="mean") / ga
+            if z_on:
+                loss, z_part = FN.cross_entropy(outputs, target_ids, reduction="mean", z_loss=z_loss, return_z_loss=True)
+                loss = loss / ga
+                acc_z += z_part / ga
+            else:
+                loss = FN.cross_entropy(outputs, target_ids, reduction="mean") / ga
             # micro-batches (2 j, 2 j + 1) share their weight-gradient launches (functional.WgradPairing):
             # the first defers, the second launches K = 2 T GEMMs; an odd last micro-batch on its own
             if pairing:
@@ -126,6 +137,7 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True):
         if pairing:
             FN.wgrad_pairing(None)
             FN.flush_wgrad_pairs()
+    model.z_loss_part = acc_z
     return read_step_loss(acc_loss, device) if read_loss else acc_loss
 
 
@@ -186,9 +198,11 @@ class GraphedTrainStep:
         before this wait).
     The first call runs its first `warmup` micro-batches eagerly on a side stream (they are real
     micro-batches: their gradients count), captures the next, replays it, and replays the rest;
-    later calls only replay."""
+    later calls only replay.
+    z_loss > 0: as train_step's keyword; the step's z part accumulates in the static buffer
+    `self.z_acc` (like `acc`), which `model.z_loss_part` names after each call (None when z_loss == 0)."""
 
-    def __init__(self, model, data_loader, device, warmup=2):
+    def __init__(self, model, data_loader, device, warmup=2, z_loss=0.0):
         if not GraphedTrainStep.supported(model):
             raise ValueError("GraphedTrainStep: data-parallel wrappers, CP and PP are not captured")
         self.model, self.loader, self.device = model, data_loader, torch.device(device)
@@ -197,6 +211,8 @@ class GraphedTrainStep:
         self.params = [p for p in model.parameters() if p.requires_grad]
         self.grads = None
         self.acc = torch.zeros((), dtype=torch.float32, device=self.device)
+        self.z_loss = z_loss
+        self.z_acc = torch.zeros((), dtype=torch.float32, device=self.device) if K.z_coef(z_loss) > 0 else None
 
     @staticmethod
     def supported(model):
@@ -208,7 +224,14 @@ class GraphedTrainStep:
         outputs = self.model(input_ids=input_ids)
         batch_size, seq_len = input_ids.shape
         outputs = outputs.view(seq_len * batch_size, -1)
-        loss = FN.cross_entropy(outputs, target_ids.reshape(-1), reduction="mean") / self.loader.grad_acc_steps
+        ga = self.loader.grad_acc_steps
+        if self.z_acc is not None:
+            loss, z_part = FN.cross_entropy(outputs, target_ids.reshape(-1), reduction="mean", z_loss=self.z_loss,
+                                            return_z_loss=True)
+            loss = loss / ga
+            self.z_acc += z_part / ga
+        else:
+            loss = FN.cross_entropy(outputs, target_ids.reshape(-1), reduction="mean") / ga
         loss.backward()
         self.acc += loss.detach().float()
 
@@ -231,6 +254,9 @@ class GraphedTrainStep:
         device scalar with read_loss=False: see train_step)."""
         ga = self.loader.grad_acc_steps
         self.acc.zero_()
+        if self.z_acc is not None:
+            self.z_acc.zero_()
+        self.model.z_loss_part = self.z_acc
         if self.grads is not None:
             for p, g in zip(self.params, self.grads):
                 if p.grad is not g:
