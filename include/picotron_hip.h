@@ -71,6 +71,33 @@ int pt_rmsnorm_colsum_batch(const float* const* partials, const int* nparts, voi
 int pt_rope(void* x, int64_t rows, int64_t row_stride, int64_t nheads, int64_t head_dim, const void* cos_table,
             const void* sin_table, int64_t seq_len, int64_t table_stride, int inverse, hipStream_t stream);
 
+/* ---- per-head QK-norm fused with RoPE ---------------------------------------------------------
+ * Not in the reference: the q_norm / k_norm of Qwen3 / OLMo-2 / Gemma-3 / Chameleon between the
+ * q|k|v projection (model.py:124-126) and the rotation (model.py:136-137).  An RMSNorm over the
+ * head_dim values of every q head (weight wq [head_dim] bf16) and every k head (wk), in
+ * pt_rmsnorm_fwd's two modes, the bf16 result then rotated as pt_rope rotates it (position =
+ * row % seq_len; cos_table = sin_table = NULL: norm only) -- bit-identical to the norm-only call
+ * followed by pt_rope.  x, y: [rows, stride] bf16 whose first nheads_q + nheads_k heads are q|k;
+ * later columns (v) are neither read nor written; y may be x.  rstd [rows, nheads_q + nheads_k] f32.
+ * Checked in this order, before any launch: head_dim not 64 / 128 PT_EUNSUPPORTED; a NULL required
+ * pointer, a count <= 0, mode not 0 / 1, exactly one of cos / sin NULL PT_EINVAL; rows, a row's
+ * width, a stride or a table size past 32 bits PT_EUNSUPPORTED; a stride below the q|k width
+ * PT_EINVAL; a stride not a multiple of 8 or a pointer not 16-byte aligned PT_EALIGN. */
+int pt_qk_norm_rope_fwd(const void* x, int64_t x_stride, void* y, int64_t y_stride, const void* wq, const void* wk,
+                        float* rstd, int64_t rows, int64_t nheads_q, int64_t nheads_k, int64_t head_dim, float eps,
+                        int mode, const void* cos_table, const void* sin_table, int64_t seq_len, int64_t table_stride,
+                        hipStream_t stream);
+/* number of f32 rows of head_dim the backward writes into each partial buffer (negative: refused) */
+int pt_qk_norm_bwd_partials(int64_t rows, int64_t nheads_q, int64_t nheads_k, int64_t head_dim);
+/* Backward of the norm, from the saved pre-norm x and rstd, on dy = the gradient with respect to
+ * the normed (un-rotated) y: dx = bf16(rstd * (dy w - xh mean_d(dy w xh))), xh = x rstd; dx may be
+ * dy.  dwq_partial / dwk_partial [pt_qk_norm_bwd_partials, head_dim] f32: every row is written (one
+ * per workgroup, summed in a fixed order: deterministic); pt_rmsnorm_colsum_batch(cols = head_dim)
+ * finishes the weight gradient into its sink.  NULL: that weight's gradient is not formed. */
+int pt_qk_norm_bwd(const void* dy, int64_t dy_stride, const void* x, int64_t x_stride, const void* wq, const void* wk,
+                   const float* rstd, void* dx, int64_t dx_stride, float* dwq_partial, float* dwk_partial,
+                   int64_t rows, int64_t nheads_q, int64_t nheads_k, int64_t head_dim, int mode, hipStream_t stream);
+
 /* ---- SwiGLU: h = silu(g) * u --------------------------------------------------------------
  * replaces picotron/model.py:186 F.silu(gate_proj(x)) * up_proj(x) (fwd and autograd bwd). */
 int pt_swiglu_fwd(const void* g, int64_t g_stride, const void* u, int64_t u_stride, void* h, int64_t h_stride,

@@ -283,6 +283,45 @@ def _flush_norm_dw(task):
         _grad_ready(w)
 
 
+def _dw_waiting(weight):
+    """An owner of weight's gradient (a data-parallel wrapper outside no_sync) all-reduces during this
+    backward and waits for it at its end: the sum cannot wait for the end of the backward."""
+    sync = getattr(weight, "_pt_grad_sync", None)
+    return getattr(weight, "_pt_grad_ready", None) is not None and (sync is None or sync())
+
+
+def _defer_dw(task, entry):
+    """Queue one _PENDING_DW entry (partial, weight, stream, tp context or None) of autograd graph task
+    `task`; the first entry of a task registers the flush at the end of its backward."""
+    if task not in _PENDING_DW:
+        _PENDING_DW[task] = []
+        torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_norm_dw(task))
+    _PENDING_DW[task].append(entry)
+
+
+def _dw_defer_task(weight, t):
+    """The autograd graph task whose end the column sum of weight's gradient may wait for, or None:
+    the sum runs at once when an owner waits for it, outside an autograd backward, or with the
+    deferral switched off."""
+    task = torch._C._current_graph_task_id()   # -1 outside an autograd backward
+    if not _dw_waiting(weight) and t.is_cuda and task != -1 and _norm_defer_enabled():
+        return task
+    return None
+
+
+def norm_dw_from_partial(partial, weight):
+    """The weight gradient of a norm whose backward kernel left only its f32 partial rows (the QK-norm):
+    deferred to the end of the backward with the layer norms' sums, or -- an owner is waiting -- summed
+    into the sink now and the owner told, exactly as norm_bwd settles a layer norm's."""
+    task = _dw_defer_task(weight, partial)
+    if task is not None:
+        _defer_dw(task, (partial, weight, torch.cuda.current_stream(partial.device), None))
+        return
+    buf, sink = _norm_dw_sink(weight)
+    K.rmsnorm_colsum_batch([(partial, buf, sink)])
+    _grad_ready(weight)
+
+
 def norm_bwd(dy2, z, weight, rstd, mode, dres=None, need_dw=True, sp=None):
     """RMSNorm backward with the weight gradient summed straight into p's sink (bf16 .grad store or
     accumulate -- autograd's AccumulateGrad -- or the f32 main_grad of DataParallelBucket).  A frozen
@@ -292,13 +331,11 @@ def norm_bwd(dy2, z, weight, rstd, mode, dres=None, need_dw=True, sp=None):
     if not (need_dw and weight.requires_grad):
         dx, _ = K.rmsnorm_bwd(dy2, z, weight, rstd, mode, dres=dres)
         return dx
-    task = torch._C._current_graph_task_id()   # -1 outside an autograd backward
     if sp is not None and sp.world_size > 1:
+        task = torch._C._current_graph_task_id()   # -1 outside an autograd backward
         dx, partial = K.rmsnorm_bwd(dy2, z, weight, rstd, mode, dres=dres, defer_dw=True)
         entry = (partial, weight, torch.cuda.current_stream(z.device), sp)
-        sync = getattr(weight, "_pt_grad_sync", None)
-        waiting = getattr(weight, "_pt_grad_ready", None) is not None and (sync is None or sync())
-        if task == -1 or waiting:
+        if task == -1 or _dw_waiting(weight):
             # not inside an autograd backward, or an owner (a data-parallel wrapper) all-reduces this
             # backward and waits for it at its end: sum over tp and store now (one [1, H] all-reduce)
             for part, w, st, *_ in _sp_sum_partials([entry]):
@@ -306,20 +343,13 @@ def norm_bwd(dy2, z, weight, rstd, mode, dres=None, need_dw=True, sp=None):
                 K.rmsnorm_colsum_batch([(part, buf, sink)])
                 _grad_ready(w)
             return dx
-        if task not in _PENDING_DW:
-            _PENDING_DW[task] = []
-            torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_norm_dw(task))
-        _PENDING_DW[task].append(entry)
+        _defer_dw(task, entry)
         return dx
     # an owner that all-reduces this backward (a data-parallel wrapper outside no_sync) is told at once
-    sync = getattr(weight, "_pt_grad_sync", None)
-    waiting = getattr(weight, "_pt_grad_ready", None) is not None and (sync is None or sync())
-    if not waiting and z.is_cuda and task != -1 and _norm_defer_enabled():
+    task = _dw_defer_task(weight, z)
+    if task is not None:
         dx, partial = K.rmsnorm_bwd(dy2, z, weight, rstd, mode, dres=dres, defer_dw=True)
-        if task not in _PENDING_DW:
-            _PENDING_DW[task] = []
-            torch.autograd.Variable._execution_engine.queue_callback(lambda: _flush_norm_dw(task))
-        _PENDING_DW[task].append((partial, weight, torch.cuda.current_stream(z.device), None))
+        _defer_dw(task, (partial, weight, torch.cuda.current_stream(z.device), None))
         return dx
     buf, sink = _norm_dw_sink(weight)
     dx, _ = K.rmsnorm_bwd(dy2, z, weight, rstd, mode, dres=dres, dw_out=buf, dw_sink=sink)
@@ -847,10 +877,44 @@ def _req_head_dim(d, roped):
         raise RuntimeError(f"attention: head_dim {d} -- the kernels take 64 / 128 and pad even dims below 128")
 
 
-def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False):
+class QKNorm:
+    """The per-head q_norm / k_norm of a layer (Qwen3 / OLMo-2 / Gemma-3 / Chameleon): an RMSNorm over
+    the head_dim values of every q head (weight wq [d]) and every k head (wk [d]) between the q|k|v
+    projection and RoPE, in the layer norms' flavour (eps, mode)."""
+
+    def __init__(self, wq, wk, eps, mode):
+        self.wq, self.wk, self.eps, self.mode = wq, wk, eps, mode
+
+    @staticmethod
+    def of(wqn, wkn, eps, mode):
+        """The Functions' trailing arguments -> a QKNorm, or None when the layer has no QK-norm."""
+        return None if wqn is None else QKNorm(wqn, wkn, eps, mode)
+
+    def require(self, sh, tp, sp=False):
+        """Refuse, before any launch, what this path does not do."""
+        if tp.world_size > 1 or sp:
+            raise NotImplementedError("QK-norm under tensor parallelism (tp > 1, the sequence-parallel layout "
+                                      "included): the per-head weight gradients need a sum over the tp group, and "
+                                      "the chunked layer's saved tensors are three per chunk")
+        if ring_enabled():
+            raise NotImplementedError("QK-norm under context parallelism (the ring takes one q|k|v tensor)")
+        if sh.d not in ATTN_HEAD_DIMS:
+            raise NotImplementedError(f"QK-norm with head_dim {sh.d}: the kernels take 64 / 128, and the "
+                                      "zero-padding path would have to norm over the real head_dim")
+
+
+def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None):
     """RoPE on q|k in place (model.py:136-137; skipped when the projection epilogue already
     rotated them: roped), then causal flash attention (model.py:154) or the ring
-    (model.py:148-151).  Returns (o [B,S,nh,d] bf16, lse f32 [B,nh,S])."""
+    (model.py:148-151).  Returns (o [B,S,nh,d] bf16, lse f32 [B,nh,S]).
+    qkn (a QKNorm): q|k are normed per head and rotated by one kernel into their own [T, q|k] buffer
+    -- qkv keeps the raw projection, which the norm's backward needs -- and attention reads q, k from
+    that buffer and v from qkv; returns (o, lse, qk, rstd [T, nh + nkv] f32)."""
+    if qkn is not None:
+        qkn.require(sh, TPContext.current())
+        qk, rstd = K.qk_norm_rope_fwd(qkv, sh.nh, sh.nkv, sh.d, qkn.wq, qkn.wk, qkn.eps, qkn.mode, cos, sin, sh.S)
+        o, lse = K.attn_fwd(sh.q(qk), sh.k(qk), sh.v(qkv), scale, True, band=sh.band)
+        return o, lse, qk, rstd
     if sh.d not in ATTN_HEAD_DIMS and not ring_enabled():
         _req_head_dim(sh.d, roped)
         return _attention_core_fwd_padded(qkv, sh, cos, sin, scale)
@@ -862,8 +926,26 @@ def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False):
     return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True, band=sh.band)
 
 
-def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale):
-    """dq|dk|dv written into one [T, q|k|v] buffer, then the inverse rotation of dq|dk."""
+def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=None):
+    """dq|dk|dv written into one [T, q|k|v] buffer, then the inverse rotation of dq|dk.
+    qkn / normed = (qk, rstd) of attention_core_fwd: attention ran on the normed, rotated qk (v from
+    qkv); after the inverse rotation dq|dk are the gradient of the norm's output, and its backward
+    runs in place on those columns from the raw q|k in qkv.  The two [d] weight gradients go the
+    layer norms' way (norm_dw_from_partial); a frozen weight gets none."""
+    if qkn is not None:
+        qk, rstd = normed
+        dqkv = torch.empty_like(qkv)
+        rope = (cos, sin) if _fuse() else None   # the RoPE backward fused into the dq / dk stores, or after
+        K.attn_bwd(do, sh.q(qk), sh.k(qk), sh.v(qkv), o, lse, scale, True,
+                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band)
+        if rope is None:
+            K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
+        need = (qkn.wq.requires_grad, qkn.wk.requires_grad)
+        _, pq, pk = K.qk_norm_bwd(dqkv, qkv, qkn.wq, qkn.wk, rstd, sh.nh, sh.nkv, sh.d, qkn.mode, dx=dqkv, need_dw=need)
+        for part, w in ((pq, qkn.wq), (pk, qkn.wk)):
+            if part is not None:
+                norm_dw_from_partial(part, w)
+        return dqkv
     if sh.d not in ATTN_HEAD_DIMS and not ring_enabled():
         return _attention_core_bwd_padded(do, qkv, o, lse, sh, cos, sin, scale)
     dqkv = torch.empty_like(qkv)
@@ -881,10 +963,19 @@ def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale):
     return dqkv
 
 
-def attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, tp, reduce=True):
+def attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, tp, reduce=True, qkn=None):
     """h2 [T,H] -> (a [T,H], saved).  Row-parallel out_proj: a = sum over tp of o W_o^T (reduce=False:
-    this rank's partial, for the sequence-parallel reduce-scatter)."""
+    this rank's partial, for the sequence-parallel reduce-scatter).
+    qkn (a QKNorm): the plain q|k|v GEMM (the norm sits between the projection and the rotation, so
+    the RoPE-epilogue GEMM cannot run), then the fused norm + RoPE kernel; saved grows by the normed,
+    rotated [T, q|k] and rstd [T, nh + nkv] f32."""
     scale = 1.0 / math.sqrt(sh.d)
+    if qkn is not None:
+        qkn.require(sh, tp, not reduce)
+        qkv = K.linear_fwd(h2, [wq, wk, wv])
+        o, lse, qk, rstd = attention_core_fwd(qkv, sh, cos, sin, scale, qkn=qkn)
+        a = K.linear_fwd(o.view(sh.T, sh.wq), [wo])
+        return a, (qkv, o, lse, qk, rstd)
     if _fuse() and K.rope_fusable(h2.shape[0], sh.d, sh.S, (wq.shape[0], wk.shape[0], wv.shape[0])):   # RoPE of q|k in the projection's epilogue
         qkv = K.linear_fwd_rope(h2, [wq, wk, wv], cos, sin, sh.S, sh.nh + sh.nkv, sh.d)
         o, lse = attention_core_fwd(qkv, sh, cos, sin, scale, roped=True)
@@ -902,17 +993,17 @@ def _dual_qkv_enabled():
 
 
 def attn_block_bwd(da, h2, saved, wq, wk, wv, wo, cos, sin, sh, tp, need_dx=True, keep_parts=False, sp=False,
-                   rs_out=None, notify=True):
+                   rs_out=None, notify=True, qkn=None):
     """keep_parts: the q|k|v dX may come back as K.SplitKParts (two f32 K halves) for a following
     rmsnorm backward to sum.  sp: the column-parallel dX is reduce-scattered onto this rank's token
     rows (sequence parallelism) instead of all-reduced.  rs_out: one token chunk of the chunked
     sequence-parallel layer -- the dX reduce-scatter writes rs_out and is NOT waited for: its handle
     is returned (the next chunk's work runs under it); notify=False: this chunk's weight gradients
     are partial sums (wgrad)."""
-    qkv, o, lse = saved
+    qkv, o, lse, *normed = saved   # normed: (qk, rstd) of a QK-norm forward, else nothing
     scale = 1.0 / math.sqrt(sh.d)
     do2 = K.linear_dgrad(da, [wo])
-    dqkv = attention_core_bwd(do2.view(sh.B, sh.S, sh.nh, sh.d), qkv, o, lse, sh, cos, sin, scale)
+    dqkv = attention_core_bwd(do2.view(sh.B, sh.S, sh.nh, sh.d), qkv, o, lse, sh, cos, sin, scale, qkn, normed)
     if need_dx and tp.world_size == 1 and _dual_qkv_enabled():
         # tp = 1 (no all-reduce to overlap): the q|k|v dX as two split-K halves (128 + 128 tiles of
         # 256x256, summed by the input norm's backward -- or by the sum pass without keep_parts) in
@@ -945,22 +1036,28 @@ class AttentionFunction(torch.autograd.Function):
     attention, out_proj, with the Column/Row TP reductions."""
 
     @staticmethod
-    def forward(ctx, x, wq, wk, wv, wo, cos, sin, nh, nkv, d, band=None):
+    def forward(ctx, x, wq, wk, wv, wo, cos, sin, nh, nkv, d, band=None, wqn=None, wkn=None, qk_eps=None,
+                qk_mode=None):
         B, S, _ = x.shape
         sh = AttnShape(B, S, nh, nkv, d, band=band)
+        qkn = QKNorm.of(wqn, wkn, qk_eps, qk_mode)
+        if qkn is not None:
+            qkn.require(sh, TPContext.current())
         h2 = _contig2d(x)
-        a, saved = attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, TPContext.current())
-        ctx.save_for_backward(h2, *saved, wq, wk, wv, wo, cos, sin)
-        ctx.sh = sh
+        a, saved = attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, TPContext.current(), qkn=qkn)
+        ctx.save_for_backward(h2, *saved[:3], wq, wk, wv, wo, cos, sin,
+                              *((*saved[3:], wqn, wkn) if qkn is not None else ()))
+        ctx.sh, ctx.qk = sh, (qk_eps, qk_mode)
         return a.view(B, S, -1)
 
     @staticmethod
     def backward(ctx, da):
-        h2, qkv, o, lse, wq, wk, wv, wo, cos, sin = ctx.saved_tensors
+        h2, qkv, o, lse, wq, wk, wv, wo, cos, sin, *rest = ctx.saved_tensors
         sh = ctx.sh
-        dh = attn_block_bwd(_contig2d(da), h2, (qkv, o, lse), wq, wk, wv, wo, cos, sin, sh, TPContext.current(),
-                            need_dx=ctx.needs_input_grad[0])
-        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 10
+        qkn = QKNorm(rest[2], rest[3], *ctx.qk) if rest else None   # rest: qk, rstd, q_norm, k_norm weights
+        dh = attn_block_bwd(_contig2d(da), h2, (qkv, o, lse, *rest[:2]), wq, wk, wv, wo, cos, sin, sh,
+                            TPContext.current(), need_dx=ctx.needs_input_grad[0], qkn=qkn)
+        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 14
 
 
 # ------------------------------------------------------------------------ MLP block
@@ -1066,7 +1163,10 @@ class DecoderLayerFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode, nh, nkv, d, zz=False, sp=0,
-                band=None):
+                band=None, wqn=None, wkn=None):
+        qkn = QKNorm.of(wqn, wkn, eps, mode)   # the q_norm / k_norm weights: the layer norms' flavour
+        if qkn is not None:
+            qkn.require(AttnShape(1, x.shape[1], nh, nkv, d), TPContext.current(), bool(sp))
         if sp and band is not None:
             raise NotImplementedError("document masking / sliding-window attention in the sequence-parallel TP "
                                       "layout (its chunks re-batch the rows the band describes)")
@@ -1079,12 +1179,13 @@ class DecoderLayerFunction(torch.autograd.Function):
         tp = TPContext.current()
         x2 = _contig2d(x)
         h1, rstd1, _ = K.rmsnorm_fwd(x2, w1, eps, mode)
-        a, asaved = attn_block_fwd(h1, wq, wk, wv, wo, cos, sin, sh, tp)
+        a, asaved = attn_block_fwd(h1, wq, wk, wv, wo, cos, sin, sh, tp, qkn=qkn)
         h2, rstd2, z = K.rmsnorm_fwd(a, w2, eps, mode, residual=x2)
         out, msaved = mlp_block_fwd(h2, wg, wu, wd, tp, residual=z)
-        ctx.save_for_backward(x2, h1, rstd1, *asaved, z, h2, rstd2, *msaved,
-                              w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin)
-        ctx.sh, ctx.mode = sh, mode
+        ctx.save_for_backward(x2, h1, rstd1, *asaved[:3], z, h2, rstd2, *msaved,
+                              w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin,
+                              *((*asaved[3:], wqn, wkn) if qkn is not None else ()))
+        ctx.sh, ctx.mode, ctx.eps = sh, mode, eps
         return out.view(B, S, H)
 
     @staticmethod
@@ -1174,23 +1275,25 @@ class DecoderLayerFunction(torch.autograd.Function):
                                      rs_out=dh1[j * n:(j + 1) * n], notify=j == c - 1))
         wait_all(rs)
         dx = norm_bwd(dh1, x2, w1, rstd1, mode, dres=dz, sp=tp)
-        return (dx.view(dout.shape),) + (None,) * 19
+        return (dx.view(dout.shape),) + (None,) * 21
 
     @staticmethod
     def backward(ctx, dout):
         if ctx.sp:
             return DecoderLayerFunction._backward_sp(ctx, dout)
         (x2, h1, rstd1, qkv, o, lse, z, h2, rstd2, gu, hh,
-         w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin) = ctx.saved_tensors
+         w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, *rest) = ctx.saved_tensors
         sh, mode = ctx.sh, ctx.mode
+        qkn = QKNorm(rest[2], rest[3], ctx.eps, mode) if rest else None   # rest: qk, rstd, q_norm, k_norm weights
         tp = TPContext.current()
         dout2 = _contig2d(dout)
         # the gate|up dX's split-K halves go straight into the norm backward (summed there)
         dh2 = mlp_block_bwd(dout2, h2, (gu, hh), wg, wu, wd, tp, keep_parts=K.norm_splitk_enabled())
         dz = norm_bwd(dh2, z, w2, rstd2, mode, dres=dout2)
-        dh1 = attn_block_bwd(dz, h1, (qkv, o, lse), wq, wk, wv, wo, cos, sin, sh, tp, keep_parts=K.norm_splitk_enabled())
+        dh1 = attn_block_bwd(dz, h1, (qkv, o, lse, *rest[:2]), wq, wk, wv, wo, cos, sin, sh, tp,
+                             keep_parts=K.norm_splitk_enabled(), qkn=qkn)
         dx = norm_bwd(dh1, x2, w1, rstd1, mode, dres=dz)   # (norm_bwd skips dW of frozen weights)
-        return (dx.view(sh.B, sh.S, -1),) + (None,) * 19
+        return (dx.view(sh.B, sh.S, -1),) + (None,) * 21
 
 
 # ------------------------------------------------------------------------ cross entropy

@@ -485,6 +485,69 @@ def rope_(x2d, nheads, head_dim, cos, sin, seq_len, inverse=False):
     return x2d
 
 
+# ------------------------------------------------------------------------- QK-norm (+ RoPE)
+def _qk_rows(t, nq, nk, d, name):
+    _req(t.dtype == BF16 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1, f"{name}: bf16 row-major device view")
+    _req(t.shape[1] >= (nq + nk) * d, f"{name}: rows narrower than {nq} + {nk} heads of {d}")
+
+
+def _qk_weight(w, d, name):
+    _req(w.dtype == BF16 and w.is_contiguous() and w.numel() == d, f"{name}: contiguous bf16 [{d}]")
+
+
+def qk_norm_rope_fwd(qkv, nq, nk, d, wq, wk, eps, mode, cos, sin, seq_len, out=None):
+    """Per-head RMSNorm of the first nq + nk heads of every row of qkv ([T, >= (nq + nk) d] bf16 view;
+    wq / wk [d]: the q heads' and the k heads' weight), then RoPE on the bf16 result (cos = sin = None:
+    norm only).  Later columns (v) are neither read nor written.  out: where y goes -- a new
+    [T, (nq + nk) d] tensor when None; may be qkv itself.  Returns (y, rstd [T, nq + nk] f32)."""
+    _qk_rows(qkv, nq, nk, d, "qkv")
+    _qk_weight(wq, d, "q_norm weight")
+    _qk_weight(wk, d, "k_norm weight")
+    T = qkv.shape[0]
+    if out is None:
+        out = torch.empty(T, (nq + nk) * d, dtype=BF16, device=qkv.device)
+    _qk_rows(out, nq, nk, d, "out")
+    _req(out.shape[0] == T, "out: one row per row of qkv")
+    _req((cos is None) == (sin is None), "qk_norm_rope_fwd: cos and sin together, or neither")
+    if cos is not None:
+        _req(cos.dtype == BF16 and sin.dtype == BF16 and cos.stride(-1) == 1 and sin.stride() == cos.stride(),
+             "qk_norm_rope_fwd: bf16 cos/sin tables of one layout")
+        _req(cos.shape[0] >= seq_len, "qk_norm_rope_fwd: table shorter than the sequence")
+    rstd = torch.empty(T, nq + nk, dtype=torch.float32, device=qkv.device)
+    rc = _C.lib().pt_qk_norm_rope_fwd(_ptr(qkv), qkv.stride(0), _ptr(out), out.stride(0), _ptr(wq), _ptr(wk), _ptr(rstd),
+                                      T, nq, nk, d, float(eps), int(mode), _ptr(cos), _ptr(sin), seq_len,
+                                      cos.stride(0) if cos is not None else 0, _C.stream_ptr(qkv.device))
+    _C.check(rc, "pt_qk_norm_rope_fwd")
+    return out, rstd
+
+
+def qk_norm_bwd(dy, x, wq, wk, rstd, nq, nk, d, mode, dx=None, need_dw=(True, True)):
+    """Backward of the norm of qk_norm_rope_fwd on dy = the gradient with respect to the normed,
+    un-rotated y (the first nq + nk heads of every row of dy), from the pre-norm x and the saved rstd.
+    dx: where the input gradient goes (new [T, (nq + nk) d] when None; may be dy itself).  Returns
+    (dx, partial_q, partial_k): the f32 per-workgroup partial rows of the two weight gradients, to be
+    summed into their sinks by rmsnorm_colsum_batch (None where need_dw says the weight takes none)."""
+    _qk_rows(dy, nq, nk, d, "dy")
+    _qk_rows(x, nq, nk, d, "x")
+    _qk_weight(wq, d, "q_norm weight")
+    _qk_weight(wk, d, "k_norm weight")
+    T = x.shape[0]
+    _req(dy.shape[0] == T, "dy: one row per row of x")
+    _req(rstd.dtype == torch.float32 and rstd.is_contiguous() and tuple(rstd.shape) == (T, nq + nk), "rstd [T, nq + nk] f32")
+    if dx is None:
+        dx = torch.empty(T, (nq + nk) * d, dtype=BF16, device=x.device)
+    _qk_rows(dx, nq, nk, d, "dx")
+    _req(dx.shape[0] == T, "dx: one row per row of x")
+    lib = _C.lib()
+    nparts = lib.pt_qk_norm_bwd_partials(T, nq, nk, d)
+    _C.check(0 if nparts > 0 else nparts, "pt_qk_norm_bwd_partials")
+    pq, pk = (torch.empty(nparts, d, dtype=torch.float32, device=x.device) if need else None for need in need_dw)
+    rc = lib.pt_qk_norm_bwd(_ptr(dy), dy.stride(0), _ptr(x), x.stride(0), _ptr(wq), _ptr(wk), _ptr(rstd), _ptr(dx),
+                            dx.stride(0), _ptr(pq), _ptr(pk), T, nq, nk, d, int(mode), _C.stream_ptr(x.device))
+    _C.check(rc, "pt_qk_norm_bwd")
+    return dx, pq, pk
+
+
 # ---------------------------------------------------------------------------------- SwiGLU
 def swiglu_fwd(g, u, out=None):
     rows, cols = g.shape

@@ -229,14 +229,39 @@ class Attention(nn.Module):
         self.layer_idx = layer_idx
         # Mistral-style sliding-window attention: a token sees the last `sliding_window` keys (None: all)
         self.sliding_window = getattr(config, "sliding_window", None)
+        # QK-norm (config.qk_norm; Qwen3 / OLMo-2 / Gemma-3 / Chameleon): an RMSNorm of the layer norms'
+        # flavour over each q head's and each k head's head_dim values, between the projection and
+        # RoPE; one [head_dim] weight for the q heads, one for the k heads (Qwen3's layout)
+        self.qk_norm = bool(getattr(config, "qk_norm", False))
+        if self.qk_norm:
+            if m.tp_world_size > 1:
+                raise NotImplementedError("qk_norm under tensor parallelism (tp > 1): the per-head weight gradients "
+                                          "need a sum over the tp group")
+            if self.head_dim not in FN.ATTN_HEAD_DIMS:
+                raise NotImplementedError(f"qk_norm with head_dim {self.head_dim}: the kernels take 64 / 128, and "
+                                          "the zero-padding path would have to norm over the real head_dim")
+            RMSNorm = TritonRMSNorm if _flash() else LlamaRMSNorm
+            self.q_norm = RMSNorm(self.head_dim, eps=config.rms_norm_eps)
+            self.k_norm = RMSNorm(self.head_dim, eps=config.rms_norm_eps)
         self.reset_parameters()
 
     def reset_parameters(self):
         for t in (self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.out_proj.weight):
             _init_uniform_fan_in(t)
+        if self.qk_norm:
+            self.q_norm.reset_parameters()
+            self.k_norm.reset_parameters()
 
     def weights(self):
         return self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.out_proj.weight
+
+    def qk_norm_args(self):
+        """AttentionFunction's trailing arguments: the q_norm / k_norm weights, eps and mode, or nothing."""
+        if not self.qk_norm:
+            return ()
+        if _norm_mode(self.q_norm) != _norm_mode(self.k_norm) or _norm_eps(self.q_norm) != _norm_eps(self.k_norm):
+            raise ValueError("Attention: q_norm and k_norm must be the same flavour")
+        return self.q_norm.weight, self.k_norm.weight, _norm_eps(self.q_norm), _norm_mode(self.q_norm)
 
     def band(self, x, document_ids):
         """The kernels.AttnBand of this forward (None: plain causal): document_ids a [B, S] integer
@@ -249,7 +274,8 @@ class Attention(nn.Module):
         packed rows).  RoPE positions stay sequence indices: RoPE scores depend on i - j only, so
         positions reset per document would give the same attention; position_ids stays unused."""
         return FN.AttentionFunction.apply(x, *self.weights(), cos, sin, self.num_local_heads,
-                                          self.num_local_kv_heads, self.head_dim, self.band(x, document_ids))
+                                          self.num_local_kv_heads, self.head_dim, self.band(x, document_ids),
+                                          *self.qk_norm_args())
 
 
 class MLP(nn.Module):
@@ -325,10 +351,13 @@ class DecoderLayer(nn.Module):
                 raise NotImplementedError("document masking / sliding-window attention on a sharded residual "
                                           "stream (sequence-parallel TP, zig-zag context parallelism)")
             band = at.band(x, document_ids)
+        qk = at.qk_norm_args()   # (): no QK-norm; else its two weights, in the layer norms' flavour
+        if qk and qk[2:] != (_norm_eps(n1), _norm_mode(n1)):
+            raise ValueError("DecoderLayer: q_norm / k_norm must be the layer norms' flavour")
         return FN.DecoderLayerFunction.apply(
             x, n1.weight, n2.weight, *at.weights(), mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
             cos, sin, _norm_eps(n1), _norm_mode(n1), at.num_local_heads, at.num_local_kv_heads, at.head_dim, zz, sp,
-            band)
+            band, *qk[:2])
 
 
 class Embedding(nn.Module):
