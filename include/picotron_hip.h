@@ -225,7 +225,10 @@ int pt_embedding_sort(const int64_t* ids, int64_t T, int64_t vocab_lo, int64_t v
  * replaces train.py:209 torch.optim.AdamW(...).step() for one tensor: the eight foreach passes of
  * torch's multi-tensor Adam (decoupled weight decay) in one, same per-op rounding to the storage
  * dtype (dtype 0 bf16, 1 f32).  Scalars as torch casts them: decay = 1 - lr*wd, w1 = 1 - beta1,
- * c2 = 1 - beta2, bc2_sqrt = sqrt(1 - beta2^t), step_size = -lr / (1 - beta1^t). */
+ * c2 = 1 - beta2, bc2_sqrt = sqrt(1 - beta2^t), step_size = -lr / (1 - beta1^t).
+ * Like every entry of this family it checks all of its arguments before it looks at whether there
+ * is anything to do: a dtype outside {0, 1} is PT_EINVAL at n == 0 too (it used to be PT_OK here,
+ * and only here). */
 int pt_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
                   float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
                   hipStream_t stream);

@@ -1,29 +1,36 @@
 // Fused AdamW step for gfx950: one pass over (param, grad, exp_avg, exp_avg_sq) per tensor.
 //
-// Replaces (reference, /root/reference): picotron/train.py:205-209 -- `torch.optim.AdamW(
-// model.parameters(), lr=learning_rate)` (the reference's own fused switch at :205-207 is dead
-// code), i.e. torch's multi-tensor Adam with decoupled weight decay, which on bf16 tensors runs
-// eight foreach passes, each computing in f32 and rounding its result to the tensor dtype:
+// Replaces (reference): picotron/train.py:205-209 -- `torch.optim.AdamW(model.parameters(),
+// lr=learning_rate)` (the reference's own fused switch at :205-207 is dead code), i.e. torch's
+// multi-tensor Adam with decoupled weight decay, which on bf16 tensors runs eight foreach passes,
+// each computing in f32 and rounding its result to the tensor dtype:
 //   p  = r(p * decay)                       _foreach_mul_      decay = 1 - lr * wd
 //   m  = r(m + w1 * (g - m))                _foreach_lerp_     w1 = 1 - beta1 (|w| < .5 form)
 //   v  = r(v * beta2)                       _foreach_mul_
 //   v  = r(v + c2 * (g * g))                _foreach_addcmul_  c2 = 1 - beta2
 //   s  = r(sqrt(v)); s = r(s / bc2s); s = r(s + eps)   _foreach_sqrt / div_ / add_
 //   p  = r(p + step * (m / s))              _foreach_addcdiv_  step = -lr / (1 - beta1^t)
-// r() = round to the storage dtype.  This kernel performs exactly that sequence per element, with
-// the roundings, so its result matches torch's bit for bit up to f32 contraction differences --
-// but reads each of the four tensors once and writes three (14 bytes per bf16 parameter instead
+// r() = round to the storage dtype.  The kernels perform exactly that sequence per element, with
+// the roundings, so the result matches torch's bit for bit up to f32 contraction differences --
+// but read each of the four tensors once and write three (14 bytes per bf16 parameter instead
 // of ~44 over the eight passes).  Scalars arrive as f32, as torch's foreach kernels cast them.
 //
-// Also here, because they walk the same tensor table: global gradient-norm clipping
+// Also here, because they walk the same tensor tables: global gradient-norm clipping
 // (torch.nn.utils.clip_grad_norm_ in front of the step) -- the f32 sum of squares of every
 // gradient, and the clip coefficient applied where the AdamW kernels load the gradient (a
 // compile-time variant of each) or in place.  And the opt-in mixed-precision form of the step: f32
-// master weights and moments behind the bf16 parameters (adamw_master_* below).
+// master weights and moments behind the bf16 parameters.
+//
+// Top to bottom: element functions (adam_elem, adam_elem_master, the clip coefficient); the table
+// walk (the two descriptor structs and for_each_run, a workgroup's run of 8-element chunks tensor
+// by tensor); the kernels (step, sum of squares, in-place scale); the host launch helpers (geometry,
+// the shared argument checks, one body per form with the clipping as a template argument:
+// step_single / step_multi, master_single / master_multi, grad_sq_sum); the extern "C" forwards.
 #include "common.h"
 
 namespace {
 
+// ---- element functions ------------------------------------------------------------------------
 struct AdamScalars {
   float decay, w1, beta2, c2, bc2s, eps, step;
 };
@@ -47,12 +54,12 @@ __device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v,
   p = r(p + s.step * (m / d));
 }
 
-// ---- global gradient-norm clipping ---------------------------------------------------------
-// torch.nn.utils.clip_grad_norm_'s coefficient, clip_coef = max_norm / (total_norm + 1e-6) clamped
-// to 1, from the device scalar sq = sum g^2 (IEEE sqrt and division: every consumer computes the
-// same bits).  false: sq is inf or NaN -- the consumer does nothing and posts the status bit.
-// The kernels take the scale as a compile-time variant: the unclipped instantiation's ClipArgs is
-// empty and its code is what it was before there was a variant.
+// Global gradient-norm clipping: torch.nn.utils.clip_grad_norm_'s coefficient, clip_coef =
+// max_norm / (total_norm + 1e-6) clamped to 1, from the device scalar sq = sum g^2 (IEEE sqrt and
+// division: every consumer computes the same bits).  false: sq is inf or NaN -- the consumer does
+// nothing and posts the status bit.  The kernels take the scale as a compile-time variant: the
+// unclipped instantiation's ClipArgs is empty and its code is what it was before there was a
+// variant.
 template <bool CLIP>
 struct ClipArgs {};
 template <>
@@ -80,6 +87,111 @@ __device__ __forceinline__ float clip_grad(float g, float coef, bool bf) {
   return bf ? round_bf(x) : x;
 }
 
+// fp32 master weights and moments (optim.AdamW(master_weights=True)), the mixed-precision recipe
+// on top of the bf16 one above: the optimizer owns an f32 copy of every bf16 weight and both
+// moments in f32, updates them with torch's foreach *f32* AdamW sequence (no rounding between the
+// ops) and publishes param = bf16(master), round to nearest even.  In bf16 state v * 0.999 rounds
+// back to v (1 - beta2 is below half an ulp) and an update below half an ulp of the weight is
+// lost; here neither happens.  The gradient is bf16 or f32 (a property of the launch); with
+// clipping it is scaled in f32 as it is loaded and never rounded to bf16.
+// Traffic per parameter: master, grad, m, v read (14 / 16 B), master, param, m, v written (14 B).
+//
+// The f32 sequence (adam_elem with bf = false) with its contraction spelled out: a fused
+// multiply-add where torch's lerp / addcmul / addcdiv kernels have one, everything else rounded on
+// its own.  Nothing is left to the compiler, so the bf16- and the f32-gradient instantiations,
+// clipped or not, list or single tensor, are the same arithmetic on the same f32 inputs and give
+// the same bits.
+__device__ __forceinline__ void adam_elem_master(float& p, float g, float& m, float& v, const AdamScalars& s) {
+#pragma clang fp contract(off)
+  p = p * s.decay;
+  m = fmaf(s.w1, g - m, m);
+  v = v * s.beta2;
+  v = fmaf(s.c2, g * g, v);
+  float d = sqrtf(v);
+  d = d / s.bc2s;
+  d = d + s.eps;
+  p = fmaf(s.step, m / d, p);
+}
+
+template <bool CLIP>
+__device__ __forceinline__ void master_elem(float& w, float g, float& m, float& v, const AdamScalars& s, float coef) {
+  if constexpr (CLIP) g = clip_grad(g, coef, false);
+  adam_elem_master(w, g, m, v, s);
+}
+
+// 8 x f32 as two 16-byte vectors, non-temporal
+typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(1))) pt_f32x4 pt_g_f32x4;
+struct f32x8 { pt_f32x4 lo, hi; };
+__device__ __forceinline__ f32x8 ld8f_nt(const float* p) {
+  return f32x8{__builtin_nontemporal_load((const pt_g_f32x4*)(p)), __builtin_nontemporal_load((const pt_g_f32x4*)(p + 4))};
+}
+__device__ __forceinline__ void st8f_nt(float* p, const f32x8& x) {
+  __builtin_nontemporal_store(x.lo, (pt_g_f32x4*)(p));
+  __builtin_nontemporal_store(x.hi, (pt_g_f32x4*)(p + 4));
+}
+__device__ __forceinline__ void unpack8(const f32x8& x, float* f) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { f[j] = x.lo[j]; f[4 + j] = x.hi[j]; }
+}
+__device__ __forceinline__ f32x8 pack8f(const float* f) {
+  return f32x8{pt_f32x4{f[0], f[1], f[2], f[3]}, pt_f32x4{f[4], f[5], f[6], f[7]}};
+}
+// a chunk of the gradient stream in its storage type
+template <typename GT> struct GradVec;
+template <> struct GradVec<uint16_t> {
+  typedef bf16x8 type;
+  static __device__ __forceinline__ type ld(const uint16_t* p) { return ld8_nt(p); }
+};
+template <> struct GradVec<float> {
+  typedef f32x8 type;
+  static __device__ __forceinline__ type ld(const float* p) { return ld8f_nt(p); }
+};
+
+// ---- table walk -------------------------------------------------------------------------------
+// Multi-tensor form: ONE launch per step over every listed parameter (torch's foreach AdamW works
+// on the whole list too).  The tensors are a virtual concatenation of 8-element chunks; workgroup b
+// owns a contiguous run of chunks, finds the tensor its run starts in by binary search over the
+// chunk prefix sums (read from the caller's descriptor table), then walks forward.  A tensor whose
+// length is not a multiple of 8 finishes its last chunk element by element.
+struct AdamTensor {   // pt_adam_tensor (include/picotron_hip.h)
+  uint16_t* p;
+  const uint16_t* g;
+  uint16_t* m;
+  uint16_t* v;
+  int64_t n;
+};
+struct AdamMasterTensor {   // pt_adam_master_tensor (include/picotron_hip.h)
+  float* w;
+  uint16_t* p;
+  const void* g;
+  float* m;
+  float* v;
+  int64_t n;
+};
+
+// workgroup b's run of chunks, tensor by tensor; fn(T, from, to) gets the run's chunk range inside
+// tensor T
+template <typename TT, typename F>
+__device__ __forceinline__ void for_each_run(const TT* __restrict__ ts, const int64_t* __restrict__ chunk_start,
+                                             int nt, int64_t per_block, F fn) {
+  const int64_t total = chunk_start[nt];
+  const int64_t lo = (int64_t)blockIdx.x * per_block;
+  const int64_t hi = lo + per_block < total ? lo + per_block : total;
+  if (lo >= hi) return;
+  // the tensor holding chunk lo: largest t with chunk_start[t] <= lo
+  int a = 0, b = nt - 1;
+  while (a < b) {
+    const int mid = (a + b + 1) >> 1;
+    if (chunk_start[mid] <= lo) a = mid; else b = mid - 1;
+  }
+  for (int t = a; t < nt && chunk_start[t] < hi; ++t) {
+    const int64_t c0 = chunk_start[t], c1 = chunk_start[t + 1];
+    fn(ts[t], (lo > c0 ? lo : c0) - c0, (hi < c1 ? hi : c1) - c0);
+  }
+}
+
+// ---- the step: bf16 / f32 state ---------------------------------------------------------------
 // bf16 tensors: 8 elements per thread (16-byte loads / stores on all four streams)
 template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_bf16_kernel(uint16_t* __restrict__ param, const uint16_t* __restrict__ grad,
@@ -131,21 +243,12 @@ __global__ __launch_bounds__(256) void adamw_scalar_kernel(T* __restrict__ param
     }
   }
 }
-// Multi-tensor form: ONE launch per step over every bf16 parameter (torch's foreach AdamW works on
-// the whole list too).  The tensors are a virtual concatenation of 8-element chunks; workgroup b
-// owns a contiguous run of chunks, finds the tensor its run starts in by binary search over the
-// chunk prefix sums (read from the caller's descriptor table), then walks forward.  A tensor whose
-// length is not a multiple of 8 finishes its last chunk element by element.
-struct AdamTensor {   // pt_adam_tensor (include/picotron_hip.h)
-  uint16_t* p;
-  const uint16_t* g;
-  uint16_t* m;
-  uint16_t* v;
-  int64_t n;
-};
 
-// CLIP: the gradient is scaled by the clip coefficient as it is loaded (g' = bf16(g * coef), what an
-// in-place scale pass would have stored).
+// The list of bf16 tensors, one launch.  CLIP: the gradient is scaled by the clip coefficient as it
+// is loaded (g' = bf16(g * coef), what an in-place scale pass would have stored).
+// The one list kernel that spells the walk of for_each_run out: with its body in for_each_run's
+// callback the compiler puts the wait for the two-ahead loads in front of a chunk's arithmetic
+// instead of behind it, and the step over 1.21 B parameters takes 2863 us instead of 2819.
 template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor* __restrict__ ts,
                                                                const int64_t* __restrict__ chunk_start, int nt,
@@ -227,211 +330,7 @@ __global__ __launch_bounds__(256) void adamw_multi_bf16_kernel(const AdamTensor*
   }
 }
 
-// ---- sum of squares of the gradients (the global norm) and the in-place scale ---------------
-// Both walk the AdamW table the same way and touch only its grad field: workgroup b's run of
-// chunks, tensor by tensor; fn(T, from, to) gets the run's chunk range inside tensor T.
-template <typename TT, typename F>
-__device__ __forceinline__ void for_each_run(const TT* __restrict__ ts, const int64_t* __restrict__ chunk_start,
-                                             int nt, int64_t per_block, F fn) {
-  const int64_t total = chunk_start[nt];
-  const int64_t lo = (int64_t)blockIdx.x * per_block;
-  const int64_t hi = lo + per_block < total ? lo + per_block : total;
-  if (lo >= hi) return;
-  int a = 0, b = nt - 1;
-  while (a < b) {
-    const int mid = (a + b + 1) >> 1;
-    if (chunk_start[mid] <= lo) a = mid; else b = mid - 1;
-  }
-  for (int t = a; t < nt && chunk_start[t] < hi; ++t) {
-    const int64_t c0 = chunk_start[t], c1 = chunk_start[t + 1];
-    fn(ts[t], (lo > c0 ? lo : c0) - c0, (hi < c1 ? hi : c1) - c0);
-  }
-}
-
-__device__ __forceinline__ float sq8(const bf16x8& x, float acc) {
-  float g[8];
-  unpack8(x, g);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc = fmaf(g[j], g[j], acc);
-  return acc;
-}
-
-// the workgroup's sum in a fixed order (wave butterfly, then the four waves in index order):
-// thread 0 returns it
-__device__ __forceinline__ float block_sum_256(float v) {
-  __shared__ float part[4];
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((part[0] + part[1]) + part[2]) + part[3];
-}
-
-// One f32 partial per workgroup: partial[b] = sum g^2 over workgroup b's run.  Nothing is stored
-// on the way, so four chunks per thread are simply loaded together and summed into four
-// independent accumulators (a thread's longest add chain: 8 * ceil(chunks per thread / 4)).
-__global__ __launch_bounds__(256) void grad_sq_multi_kernel(const AdamTensor* __restrict__ ts,
-                                                            const int64_t* __restrict__ chunk_start, int nt,
-                                                            int64_t per_block, float* __restrict__ partial) {
-  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamTensor& T, int64_t from, int64_t to) {
-    const int64_t full = T.n >> 3;
-    const int64_t end = to < full ? to : full;
-    const int64_t bd = blockDim.x;
-    int64_t c = from + threadIdx.x;
-    for (; c + 3 * bd < end; c += 4 * bd) {
-      bf16x8 x[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) x[q] = ld8_nt(T.g + (c + q * bd) * 8);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) acc[q] = sq8(x[q], acc[q]);
-    }
-    for (int q = 0; c < end; c += bd, ++q) acc[q & 3] = sq8(ld8_nt(T.g + c * 8), acc[q & 3]);
-    if (to > full && threadIdx.x == 0) {   // the ragged last chunk
-      for (int64_t i = full * 8; i < T.n; ++i) {
-        const float g = bf2f(T.g[i]);
-        acc[3] = fmaf(g, g, acc[3]);
-      }
-    }
-  });
-  const float sum = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
-  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
-}
-
-// single tensor (f32, or bf16 at any alignment): element by element, grid-strided
-template <typename T>
-__global__ __launch_bounds__(256) void grad_sq_kernel(const T* __restrict__ grad, int64_t n,
-                                                      float* __restrict__ partial) {
-  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (; i + 3 * stride < n; i += 4 * stride) {
-    float g[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) g[q] = ld_as_f(grad, i + q * stride);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = fmaf(g[q], g[q], acc[q]);
-  }
-  for (int q = 0; i < n; i += stride, ++q) {
-    const float g = ld_as_f(grad, i);
-    acc[q & 3] = fmaf(g, g, acc[q & 3]);
-  }
-  const float sum = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
-  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
-}
-
-// sq[0] = (accumulate ? sq[0] : 0) + weight * sum of the n partials, one workgroup, fixed order
-// (thread t takes partials t, t + 256, ... in index order): bit-reproducible, no float atomics
-__global__ __launch_bounds__(256) void grad_sq_final_kernel(const float* __restrict__ partial, int n, float weight,
-                                                            int accumulate, float* __restrict__ sq) {
-  float acc = 0.0f;
-  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
-  const float sum = block_sum_256(acc);
-  if (threadIdx.x == 0) sq[0] = accumulate ? sq[0] + weight * sum : weight * sum;
-}
-
-// grad = bf16(grad * coef) in place over the list (the stand-alone clip_grad_norm_); coef == 1
-// (no clipping) stores nothing
-__global__ __launch_bounds__(256) void grad_scale_multi_kernel(const AdamTensor* __restrict__ ts,
-                                                               const int64_t* __restrict__ chunk_start, int nt,
-                                                               int64_t per_block, ClipArgs<true> clip) {
-  float coef;
-  if (!clip_coef(clip, coef) || coef == 1.0f) return;
-  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamTensor& T, int64_t from, int64_t to) {
-    uint16_t* G = const_cast<uint16_t*>(T.g);
-    const int64_t full = T.n >> 3;
-    const int64_t end = to < full ? to : full;
-    for (int64_t c = from + threadIdx.x; c < end; c += blockDim.x) {
-      float g[8];
-      unpack8(ld8_nt(G + c * 8), g);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) g[j] = clip_grad(g[j], coef, false);   // pack8 rounds
-      st8_nt(G + c * 8, pack8(g));
-    }
-    if (to > full && threadIdx.x == 0) {
-      for (int64_t i = full * 8; i < T.n; ++i) G[i] = f2bf(clip_grad(bf2f(G[i]), coef, false));
-    }
-  });
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void grad_scale_kernel(T* __restrict__ grad, int64_t n, ClipArgs<true> clip) {
-  float coef;
-  if (!clip_coef(clip, coef) || coef == 1.0f) return;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float g = clip_grad(ld_as_f(grad, i), coef, false);
-    if (sizeof(T) == 2) ((uint16_t*)grad)[i] = f2bf(g); else ((float*)grad)[i] = g;
-  }
-}
-
-// ---- fp32 master weights and moments (optim.AdamW(master_weights=True)) ----------------------
-// The mixed-precision recipe on top of the bf16 one above: the optimizer owns an f32 copy of every
-// bf16 weight and both moments in f32, updates them with torch's foreach *f32* AdamW sequence (no
-// rounding between the ops) and publishes param = bf16(master), round to nearest even.  In bf16
-// state v * 0.999 rounds back to v (1 - beta2 is below half an ulp) and an update below half an
-// ulp of the weight is lost; here neither happens.  The gradient is bf16 or f32 (a property of
-// the launch); with clipping it is scaled in f32 as it is loaded and never rounded to bf16.
-// Traffic per parameter: master, grad, m, v read (14 / 16 B), master, param, m, v written (14 B).
-struct AdamMasterTensor {   // pt_adam_master_tensor (include/picotron_hip.h)
-  float* w;
-  uint16_t* p;
-  const void* g;
-  float* m;
-  float* v;
-  int64_t n;
-};
-
-// The f32 sequence (adam_elem with bf = false) with its contraction spelled out: a fused
-// multiply-add where torch's lerp / addcmul / addcdiv kernels have one, everything else rounded on
-// its own.  Nothing is left to the compiler, so the bf16- and the f32-gradient instantiations,
-// clipped or not, list or single tensor, are the same arithmetic on the same f32 inputs and give
-// the same bits.
-__device__ __forceinline__ void adam_elem_master(float& p, float g, float& m, float& v, const AdamScalars& s) {
-#pragma clang fp contract(off)
-  p = p * s.decay;
-  m = fmaf(s.w1, g - m, m);
-  v = v * s.beta2;
-  v = fmaf(s.c2, g * g, v);
-  float d = sqrtf(v);
-  d = d / s.bc2s;
-  d = d + s.eps;
-  p = fmaf(s.step, m / d, p);
-}
-
-// 8 x f32 as two 16-byte vectors, non-temporal
-typedef float pt_f32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(1))) pt_f32x4 pt_g_f32x4;
-struct f32x8 { pt_f32x4 lo, hi; };
-__device__ __forceinline__ f32x8 ld8f_nt(const float* p) {
-  return f32x8{__builtin_nontemporal_load((const pt_g_f32x4*)(p)), __builtin_nontemporal_load((const pt_g_f32x4*)(p + 4))};
-}
-__device__ __forceinline__ void st8f_nt(float* p, const f32x8& x) {
-  __builtin_nontemporal_store(x.lo, (pt_g_f32x4*)(p));
-  __builtin_nontemporal_store(x.hi, (pt_g_f32x4*)(p + 4));
-}
-__device__ __forceinline__ void unpack8(const f32x8& x, float* f) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { f[j] = x.lo[j]; f[4 + j] = x.hi[j]; }
-}
-__device__ __forceinline__ f32x8 pack8f(const float* f) {
-  return f32x8{pt_f32x4{f[0], f[1], f[2], f[3]}, pt_f32x4{f[4], f[5], f[6], f[7]}};
-}
-// a chunk of the gradient stream in its storage type
-template <typename GT> struct GradVec;
-template <> struct GradVec<uint16_t> {
-  typedef bf16x8 type;
-  static __device__ __forceinline__ type ld(const uint16_t* p) { return ld8_nt(p); }
-};
-template <> struct GradVec<float> {
-  typedef f32x8 type;
-  static __device__ __forceinline__ type ld(const float* p) { return ld8f_nt(p); }
-};
-
-template <bool CLIP>
-__device__ __forceinline__ void master_elem(float& w, float g, float& m, float& v, const AdamScalars& s, float coef) {
-  if constexpr (CLIP) g = clip_grad(g, coef, false);
-  adam_elem_master(w, g, m, v, s);
-}
-
+// ---- the step: fp32 master weights and moments ------------------------------------------------
 // One launch over the list.  Seven or eight 16-byte loads and seven stores per chunk: ONE chunk
 // ahead (the bf16 kernel's two would need 3 x 32 data registers and drop the launch below four
 // blocks per CU); the next chunk's loads are issued before the current chunk's stores, so a wait
@@ -506,7 +405,10 @@ __global__ __launch_bounds__(256) void adamw_master_scalar_kernel(float* __restr
   }
 }
 
-__device__ __forceinline__ float sq8(const f32x8& x, float acc) {
+// ---- sum of squares of the gradients (the global norm) and the in-place scale ---------------
+// Both walk a table the way the step does and touch only its grad field.
+template <typename V>
+__device__ __forceinline__ float sq8(const V& x, float acc) {
   float g[8];
   unpack8(x, g);
 #pragma unroll
@@ -514,14 +416,26 @@ __device__ __forceinline__ float sq8(const f32x8& x, float acc) {
   return acc;
 }
 
-// grad_sq_multi_kernel over the grad field of the master table, bf16 or f32 gradients: the same
-// walk, the same four accumulators, the same fixed order
-template <typename GT>
-__global__ __launch_bounds__(256) void grad_sq_master_multi_kernel(const AdamMasterTensor* __restrict__ ts,
-                                                                   const int64_t* __restrict__ chunk_start, int nt,
-                                                                   int64_t per_block, float* __restrict__ partial) {
+// the workgroup's sum in a fixed order (wave butterfly, then the four waves in index order):
+// thread 0 returns it
+__device__ __forceinline__ float block_sum_256(float v) {
+  __shared__ float part[4];
+  v = wave_sum(v);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((part[0] + part[1]) + part[2]) + part[3];
+}
+
+// One f32 partial per workgroup: partial[b] = sum g^2 over workgroup b's run of table TT, whose
+// gradients are stored as GT.  Nothing is stored on the way, so four chunks per thread are simply
+// loaded together and summed into four independent accumulators (a thread's longest add chain:
+// 8 * ceil(chunks per thread / 4)).
+template <typename TT, typename GT>
+__global__ __launch_bounds__(256) void grad_sq_list_kernel(const TT* __restrict__ ts,
+                                                           const int64_t* __restrict__ chunk_start, int nt,
+                                                           int64_t per_block, float* __restrict__ partial) {
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamMasterTensor& T, int64_t from, int64_t to) {
+  for_each_run(ts, chunk_start, nt, per_block, [&](const TT& T, int64_t from, int64_t to) {
     const GT* G = (const GT*)T.g;
     const int64_t full = T.n >> 3;
     const int64_t end = to < full ? to : full;
@@ -546,6 +460,73 @@ __global__ __launch_bounds__(256) void grad_sq_master_multi_kernel(const AdamMas
   if (threadIdx.x == 0) partial[blockIdx.x] = sum;
 }
 
+// single tensor (f32, or bf16 at any alignment): element by element, grid-strided
+template <typename T>
+__global__ __launch_bounds__(256) void grad_sq_kernel(const T* __restrict__ grad, int64_t n,
+                                                      float* __restrict__ partial) {
+  float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + 3 * stride < n; i += 4 * stride) {
+    float g[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) g[q] = ld_as_f(grad, i + q * stride);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q] = fmaf(g[q], g[q], acc[q]);
+  }
+  for (int q = 0; i < n; i += stride, ++q) {
+    const float g = ld_as_f(grad, i);
+    acc[q & 3] = fmaf(g, g, acc[q & 3]);
+  }
+  const float sum = block_sum_256((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  if (threadIdx.x == 0) partial[blockIdx.x] = sum;
+}
+
+// sq[0] = (accumulate ? sq[0] : 0) + weight * sum of the n partials, one workgroup, fixed order
+// (thread t takes partials t, t + 256, ... in index order): bit-reproducible, no float atomics
+__global__ __launch_bounds__(256) void grad_sq_final_kernel(const float* __restrict__ partial, int n, float weight,
+                                                            int accumulate, float* __restrict__ sq) {
+  float acc = 0.0f;
+  for (int i = threadIdx.x; i < n; i += 256) acc += partial[i];
+  const float sum = block_sum_256(acc);
+  if (threadIdx.x == 0) sq[0] = accumulate ? sq[0] + weight * sum : weight * sum;
+}
+
+// grad = bf16(grad * coef) in place over the list (the stand-alone clip_grad_norm_); coef == 1
+// (no clipping) stores nothing
+__global__ __launch_bounds__(256) void grad_scale_multi_kernel(const AdamTensor* __restrict__ ts,
+                                                               const int64_t* __restrict__ chunk_start, int nt,
+                                                               int64_t per_block, ClipArgs<true> clip) {
+  float coef;
+  if (!clip_coef(clip, coef) || coef == 1.0f) return;
+  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamTensor& T, int64_t from, int64_t to) {
+    uint16_t* G = const_cast<uint16_t*>(T.g);
+    const int64_t full = T.n >> 3;
+    const int64_t end = to < full ? to : full;
+    for (int64_t c = from + threadIdx.x; c < end; c += blockDim.x) {
+      float g[8];
+      unpack8(ld8_nt(G + c * 8), g);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) g[j] = clip_grad(g[j], coef, false);   // pack8 rounds
+      st8_nt(G + c * 8, pack8(g));
+    }
+    if (to > full && threadIdx.x == 0) {
+      for (int64_t i = full * 8; i < T.n; ++i) G[i] = f2bf(clip_grad(bf2f(G[i]), coef, false));
+    }
+  });
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void grad_scale_kernel(T* __restrict__ grad, int64_t n, ClipArgs<true> clip) {
+  float coef;
+  if (!clip_coef(clip, coef) || coef == 1.0f) return;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float g = clip_grad(ld_as_f(grad, i), coef, false);
+    if (sizeof(T) == 2) ((uint16_t*)grad)[i] = f2bf(g); else ((float*)grad)[i] = g;
+  }
+}
+
+// ---- host launch helpers ----------------------------------------------------------------------
 int grid_for(int64_t work) {
   int64_t g = (work + 255) / 256;
   return (int)(g < PT_STREAM_GRID_CAP ? (g < 1 ? 1 : g) : PT_STREAM_GRID_CAP);
@@ -562,13 +543,67 @@ MultiGrid multi_grid(int64_t total_chunks, int64_t cap = 1024) {
   const int64_t blocks = want < 1 ? 1 : (want < cap ? want : cap);
   return {(unsigned)blocks, (total_chunks + blocks - 1) / blocks};
 }
+// the norm pass and the scale only read / write 2 bytes per parameter at few VGPRs: 8 blocks per CU
+constexpr int PT_GRAD_SQ_BLOCKS = PT_STREAM_GRID_CAP;
 
+// The argument checks every entry shares.  An entry refuses (PT_EINVAL) before it looks at whether
+// there is anything to do: total_chunks == 0 / n == 0 is PT_OK only with valid arguments.
+bool list_ok(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks) {
+  return tensors && chunk_start && ntensors > 0 && total_chunks >= 0;
+}
+bool dtype_ok(int dtype) { return dtype == 0 || dtype == 1; }   // bf16, f32
+bool clip_ok(const ClipArgs<false>&) { return true; }
+bool clip_ok(const ClipArgs<true>& c) { return c.sq && c.max_norm > 0.0f; }   // NaN is refused
 
-// the master-weight launches, one body for the clipped and the unclipped entry point
+// the bf16 / f32-state step, one body for the clipped and the unclipped entry point
+template <bool CLIP>
+int step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+               const AdamScalars& s, const ClipArgs<CLIP>& clip, hipStream_t stream) {
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !clip_ok(clip)) return PT_EINVAL;
+  if (total_chunks == 0) return PT_OK;
+  const MultiGrid g = multi_grid(total_chunks);
+  adamw_multi_bf16_kernel<CLIP><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
+                                                              g.per_block, s, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+template <bool CLIP>
+int step_single(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
+                const AdamScalars& s, const ClipArgs<CLIP>& clip, hipStream_t stream) {
+  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !dtype_ok(dtype) || !clip_ok(clip)) return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  if (dtype == 1) {  // f32
+    adamw_scalar_kernel<float, CLIP><<<grid_for(n), 256, 0, stream>>>((float*)param, (const float*)grad,
+                                                                      (float*)exp_avg, (float*)exp_avg_sq, n, s, clip);
+    PT_CHECK_LAUNCH();
+    return PT_OK;
+  }
+  // bf16: the 16-byte vector kernel, then the scalar kernel on the n % 8 tail -- or on the whole
+  // tensor when any pointer is unaligned
+  auto* P = (uint16_t*)param;
+  auto* G = (const uint16_t*)grad;
+  auto* M = (uint16_t*)exp_avg;
+  auto* V = (uint16_t*)exp_avg_sq;
+  const bool vec = pt_aligned16(P) && pt_aligned16(G) && pt_aligned16(M) && pt_aligned16(V);
+  const int64_t n8 = vec ? n / 8 : 0;
+  if (n8) {
+    adamw_bf16_kernel<CLIP><<<grid_for(n8), 256, 0, stream>>>(P, G, M, V, n8, s, clip);
+    PT_CHECK_LAUNCH();
+  }
+  const int64_t done = n8 * 8;
+  if (done < n) {
+    adamw_scalar_kernel<uint16_t, CLIP><<<grid_for(n - done), 256, 0, stream>>>(P + done, G + done, M + done,
+                                                                                V + done, n - done, s, clip);
+    PT_CHECK_LAUNCH();
+  }
+  return PT_OK;
+}
+
+// the master-weight step, likewise
 template <bool CLIP>
 int master_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks, int grad_dtype,
                  const AdamScalars& s, const ClipArgs<CLIP>& clip, hipStream_t stream) {
-  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || (grad_dtype != 0 && grad_dtype != 1))
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !dtype_ok(grad_dtype) || !clip_ok(clip))
     return PT_EINVAL;
   if (total_chunks == 0) return PT_OK;
   const MultiGrid g = multi_grid(total_chunks);
@@ -583,7 +618,7 @@ int master_multi(const void* tensors, const int64_t* chunk_start, int ntensors, 
 template <bool CLIP>
 int master_single(float* master, void* param, const void* grad, float* m, float* v, int64_t n, int grad_dtype,
                   const AdamScalars& s, const ClipArgs<CLIP>& clip, hipStream_t stream) {
-  if (!master || !param || !grad || !m || !v || n < 0 || (grad_dtype != 0 && grad_dtype != 1)) return PT_EINVAL;
+  if (!master || !param || !grad || !m || !v || n < 0 || !dtype_ok(grad_dtype) || !clip_ok(clip)) return PT_EINVAL;
   if (n == 0) return PT_OK;
   if (grad_dtype == 0)
     adamw_master_scalar_kernel<uint16_t, CLIP><<<grid_for(n), 256, 0, stream>>>(master, (uint16_t*)param,
@@ -595,41 +630,40 @@ int master_single(float* master, void* param, const void* grad, float* m, float*
   return PT_OK;
 }
 
+// The sum of squares' two launches: `partials` puts one f32 per workgroup into workspace[0, blocks),
+// then one workgroup sums them in a fixed order.  blocks == 0 (nothing to sum): no partials launch,
+// and the final kernel still writes or keeps sq according to `accumulate`.
+template <typename L>
+int grad_sq_sum(unsigned blocks, L partials, float weight, int accumulate, float* workspace, float* sq,
+                hipStream_t stream) {
+  if (blocks) {
+    partials();
+    PT_CHECK_LAUNCH();
+  }
+  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, (int)blocks, weight, accumulate, sq);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
+// ---- ABI forwards (include/picotron_hip.h) -----------------------------------------------------
+// One tensor, dtype 0 bf16 / 1 f32, any alignment.  Any other dtype is PT_EINVAL, at n == 0 too.
 int pt_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
                   float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
                   hipStream_t stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0) return PT_EINVAL;
-  if (n == 0) return PT_OK;
-  const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
-  if (dtype == 0) {  // bf16
-    auto* P = (uint16_t*)param;
-    auto* G = (const uint16_t*)grad;
-    auto* M = (uint16_t*)exp_avg;
-    auto* V = (uint16_t*)exp_avg_sq;
-    const bool vec = pt_aligned16(P) && pt_aligned16(G) && pt_aligned16(M) && pt_aligned16(V);
-    const int64_t n8 = vec ? n / 8 : 0;
-    if (n8) {
-      adamw_bf16_kernel<false><<<grid_for(n8), 256, 0, stream>>>(P, G, M, V, n8, s, {});
-      PT_CHECK_LAUNCH();
-    }
-    const int64_t done = n8 * 8;
-    if (done < n) {
-      adamw_scalar_kernel<uint16_t, false><<<grid_for(n - done), 256, 0, stream>>>(P + done, G + done, M + done,
-                                                                                    V + done, n - done, s, {});
-      PT_CHECK_LAUNCH();
-    }
-  } else if (dtype == 1) {  // f32
-    adamw_scalar_kernel<float, false><<<grid_for(n), 256, 0, stream>>>((float*)param, (const float*)grad,
-                                                                       (float*)exp_avg, (float*)exp_avg_sq, n, s, {});
-    PT_CHECK_LAUNCH();
-  } else {
-    return PT_EINVAL;
-  }
-  return PT_OK;
+  return step_single<false>(param, grad, exp_avg, exp_avg_sq, n, dtype,
+                            AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, {}, stream);
+}
+
+int pt_adamw_step_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
+                       float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                       const float* grad_sq, float max_norm, int* status, hipStream_t stream) {
+  return step_single<true>(param, grad, exp_avg, exp_avg_sq, n, dtype,
+                           AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size},
+                           ClipArgs<true>{grad_sq, max_norm, status}, stream);
 }
 
 // bf16 tensors (every pointer 16-byte aligned), one launch.  tensors: device array of ntensors
@@ -638,122 +672,19 @@ int pt_adamw_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq
 int pt_adamw_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
                         float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
                         hipStream_t stream) {
-  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0) return PT_EINVAL;
-  if (total_chunks == 0) return PT_OK;
-  const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
-  const MultiGrid g = multi_grid(total_chunks);
-  adamw_multi_bf16_kernel<false><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
-                                                               g.per_block, s, {});
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-// ---- global gradient-norm clipping ---------------------------------------------------------
-// the norm pass and the scale only read / write 2 bytes per parameter at few VGPRs: 8 blocks per CU
-static constexpr int PT_GRAD_SQ_BLOCKS = PT_STREAM_GRID_CAP;
-
-int pt_grad_sq_workspace(void) { return PT_GRAD_SQ_BLOCKS; }
-
-int pt_grad_sq_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
-                     float weight, int accumulate, float* workspace, float* sq, hipStream_t stream) {
-  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !workspace || !sq) return PT_EINVAL;
-  unsigned blocks = 0;
-  if (total_chunks) {
-    const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
-    blocks = g.blocks;
-    grad_sq_multi_kernel<<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
-                                                       g.per_block, workspace);
-    PT_CHECK_LAUNCH();
-  }
-  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, (int)blocks, weight, accumulate, sq);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-int pt_grad_sq(const void* grad, int64_t n, int dtype, float weight, int accumulate, float* workspace, float* sq,
-               hipStream_t stream) {
-  if (!grad || n < 0 || !workspace || !sq || (dtype != 0 && dtype != 1)) return PT_EINVAL;
-  const int blocks = n ? grid_for(n) : 0;
-  if (n && dtype == 0) grad_sq_kernel<uint16_t><<<blocks, 256, 0, stream>>>((const uint16_t*)grad, n, workspace);
-  if (n && dtype == 1) grad_sq_kernel<float><<<blocks, 256, 0, stream>>>((const float*)grad, n, workspace);
-  PT_CHECK_LAUNCH();
-  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, blocks, weight, accumulate, sq);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-int pt_grad_scale_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
-                        const float* grad_sq, float max_norm, int* status, hipStream_t stream) {
-  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !grad_sq || !(max_norm > 0.0f))
-    return PT_EINVAL;
-  if (total_chunks == 0) return PT_OK;
-  const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
-  grad_scale_multi_kernel<<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
-                                                        g.per_block, ClipArgs<true>{grad_sq, max_norm, status});
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-int pt_grad_scale(void* grad, int64_t n, int dtype, const float* grad_sq, float max_norm, int* status,
-                  hipStream_t stream) {
-  if (!grad || n < 0 || !grad_sq || !(max_norm > 0.0f) || (dtype != 0 && dtype != 1)) return PT_EINVAL;
-  if (n == 0) return PT_OK;
-  const ClipArgs<true> clip{grad_sq, max_norm, status};
-  if (dtype == 0) grad_scale_kernel<uint16_t><<<grid_for(n), 256, 0, stream>>>((uint16_t*)grad, n, clip);
-  else grad_scale_kernel<float><<<grid_for(n), 256, 0, stream>>>((float*)grad, n, clip);
-  PT_CHECK_LAUNCH();
-  return PT_OK;
-}
-
-int pt_adamw_step_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int dtype,
-                       float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
-                       const float* grad_sq, float max_norm, int* status, hipStream_t stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || n < 0 || !grad_sq || !(max_norm > 0.0f)) return PT_EINVAL;
-  if (dtype != 0 && dtype != 1) return PT_EINVAL;
-  if (n == 0) return PT_OK;
-  const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
-  const ClipArgs<true> clip{grad_sq, max_norm, status};
-  if (dtype == 0) {  // bf16: the same split as pt_adamw_step
-    auto* P = (uint16_t*)param;
-    auto* G = (const uint16_t*)grad;
-    auto* M = (uint16_t*)exp_avg;
-    auto* V = (uint16_t*)exp_avg_sq;
-    const bool vec = pt_aligned16(P) && pt_aligned16(G) && pt_aligned16(M) && pt_aligned16(V);
-    const int64_t n8 = vec ? n / 8 : 0;
-    if (n8) {
-      adamw_bf16_kernel<true><<<grid_for(n8), 256, 0, stream>>>(P, G, M, V, n8, s, clip);
-      PT_CHECK_LAUNCH();
-    }
-    const int64_t done = n8 * 8;
-    if (done < n) {
-      adamw_scalar_kernel<uint16_t, true><<<grid_for(n - done), 256, 0, stream>>>(P + done, G + done, M + done,
-                                                                                  V + done, n - done, s, clip);
-      PT_CHECK_LAUNCH();
-    }
-  } else {
-    adamw_scalar_kernel<float, true><<<grid_for(n), 256, 0, stream>>>((float*)param, (const float*)grad,
-                                                                     (float*)exp_avg, (float*)exp_avg_sq, n, s, clip);
-    PT_CHECK_LAUNCH();
-  }
-  return PT_OK;
+  return step_multi<false>(tensors, chunk_start, ntensors, total_chunks,
+                           AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, {}, stream);
 }
 
 int pt_adamw_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
                              float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
                              float step_size, const float* grad_sq, float max_norm, int* status,
                              hipStream_t stream) {
-  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !grad_sq || !(max_norm > 0.0f))
-    return PT_EINVAL;
-  if (total_chunks == 0) return PT_OK;
-  const AdamScalars s{decay, w1, beta2, c2, bc2_sqrt, eps, step_size};
-  const MultiGrid g = multi_grid(total_chunks);
-  adamw_multi_bf16_kernel<true><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
-                                                             g.per_block, s, ClipArgs<true>{grad_sq, max_norm, status});
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  return step_multi<true>(tensors, chunk_start, ntensors, total_chunks,
+                          AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size},
+                          ClipArgs<true>{grad_sq, max_norm, status}, stream);
 }
 
-// ---- fp32 master weights --------------------------------------------------------------------
 int pt_adamw_master_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
                                int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
                                float step_size, hipStream_t stream) {
@@ -765,7 +696,6 @@ int pt_adamw_master_step_multi_clip(const void* tensors, const int64_t* chunk_st
                                     int64_t total_chunks, int grad_dtype, float decay, float w1, float beta2, float c2,
                                     float bc2_sqrt, float eps, float step_size, const float* grad_sq, float max_norm,
                                     int* status, hipStream_t stream) {
-  if (!grad_sq || !(max_norm > 0.0f)) return PT_EINVAL;
   return master_multi<true>(tensors, chunk_start, ntensors, total_chunks, grad_dtype,
                             AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size},
                             ClipArgs<true>{grad_sq, max_norm, status}, stream);
@@ -782,30 +712,69 @@ int pt_adamw_master_step_clip(float* master, void* param, const void* grad, floa
                               int64_t n, int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt,
                               float eps, float step_size, const float* grad_sq, float max_norm, int* status,
                               hipStream_t stream) {
-  if (!grad_sq || !(max_norm > 0.0f)) return PT_EINVAL;
   return master_single<true>(master, param, grad, exp_avg, exp_avg_sq, n, grad_dtype,
                              AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size},
                              ClipArgs<true>{grad_sq, max_norm, status}, stream);
 }
 
+// global gradient-norm clipping: the sum of squares ...
+int pt_grad_sq_workspace(void) { return PT_GRAD_SQ_BLOCKS; }
+
+int pt_grad_sq_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                     float weight, int accumulate, float* workspace, float* sq, hipStream_t stream) {
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !workspace || !sq) return PT_EINVAL;
+  const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+  return grad_sq_sum(total_chunks ? g.blocks : 0, [&] {
+    grad_sq_list_kernel<AdamTensor, uint16_t><<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start,
+                                                                            ntensors, g.per_block, workspace);
+  }, weight, accumulate, workspace, sq, stream);
+}
+
 int pt_grad_sq_master_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
                             int grad_dtype, float weight, int accumulate, float* workspace, float* sq,
                             hipStream_t stream) {
-  if (!tensors || !chunk_start || ntensors <= 0 || total_chunks < 0 || !workspace || !sq ||
-      (grad_dtype != 0 && grad_dtype != 1))
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !workspace || !sq || !dtype_ok(grad_dtype))
     return PT_EINVAL;
-  unsigned blocks = 0;
-  if (total_chunks) {
-    const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
-    const auto* ts = (const AdamMasterTensor*)tensors;
-    blocks = g.blocks;
+  const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+  const auto* ts = (const AdamMasterTensor*)tensors;
+  return grad_sq_sum(total_chunks ? g.blocks : 0, [&] {
     if (grad_dtype == 0)
-      grad_sq_master_multi_kernel<uint16_t><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
+      grad_sq_list_kernel<AdamMasterTensor, uint16_t><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
     else
-      grad_sq_master_multi_kernel<float><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
-    PT_CHECK_LAUNCH();
-  }
-  grad_sq_final_kernel<<<1, 256, 0, stream>>>(workspace, (int)blocks, weight, accumulate, sq);
+      grad_sq_list_kernel<AdamMasterTensor, float><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
+  }, weight, accumulate, workspace, sq, stream);
+}
+
+int pt_grad_sq(const void* grad, int64_t n, int dtype, float weight, int accumulate, float* workspace, float* sq,
+               hipStream_t stream) {
+  if (!grad || n < 0 || !workspace || !sq || !dtype_ok(dtype)) return PT_EINVAL;
+  const unsigned blocks = n ? grid_for(n) : 0;
+  return grad_sq_sum(blocks, [&] {
+    if (dtype == 0) grad_sq_kernel<uint16_t><<<blocks, 256, 0, stream>>>((const uint16_t*)grad, n, workspace);
+    else grad_sq_kernel<float><<<blocks, 256, 0, stream>>>((const float*)grad, n, workspace);
+  }, weight, accumulate, workspace, sq, stream);
+}
+
+// ... and the in-place scale
+int pt_grad_scale_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                        const float* grad_sq, float max_norm, int* status, hipStream_t stream) {
+  const ClipArgs<true> clip{grad_sq, max_norm, status};
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !clip_ok(clip)) return PT_EINVAL;
+  if (total_chunks == 0) return PT_OK;
+  const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+  grad_scale_multi_kernel<<<g.blocks, 256, 0, stream>>>((const AdamTensor*)tensors, chunk_start, ntensors,
+                                                        g.per_block, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_grad_scale(void* grad, int64_t n, int dtype, const float* grad_sq, float max_norm, int* status,
+                  hipStream_t stream) {
+  const ClipArgs<true> clip{grad_sq, max_norm, status};
+  if (!grad || n < 0 || !dtype_ok(dtype) || !clip_ok(clip)) return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  if (dtype == 0) grad_scale_kernel<uint16_t><<<grid_for(n), 256, 0, stream>>>((uint16_t*)grad, n, clip);
+  else grad_scale_kernel<float><<<grid_for(n), 256, 0, stream>>>((float*)grad, n, clip);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

@@ -201,82 +201,6 @@ def embedding_bwd(ids, dy2d, dweight, sink, vocab_lo=0, vocab_hi=None, padding_i
 
 
 # ----------------------------------------------------------------------------------- AdamW
-def adamw_step(p, grad, exp_avg, exp_avg_sq, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
-    """One fused AdamW update of tensor p in place (csrc/adamw.hip; torch foreach semantics)."""
-    for t, nm in ((grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _req(t.dtype == p.dtype and t.numel() == p.numel() and t.device == p.device, f"adamw: {nm} must match param")
-        _req(t.is_contiguous() or t.stride() == p.stride(), f"adamw: {nm} layout must match param")
-    _req(p.is_contiguous(), "adamw: param must be contiguous")
-    _req(grad.is_contiguous() and exp_avg.is_contiguous() and exp_avg_sq.is_contiguous(), "adamw: dense tensors")
-    if p.dtype == BF16:
-        dt = 0
-    elif p.dtype == torch.float32:
-        dt = 1
-    else:
-        raise _C.HipKernelError(f"adamw: unsupported dtype {p.dtype}")
-    rc = _C.lib().pt_adamw_step(_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), dt, float(decay),
-                                float(w1), float(beta2), float(c2), float(bc2_sqrt), float(eps), float(step_size),
-                                _C.stream_ptr(p.device))
-    _C.check(rc, "pt_adamw_step")
-
-
-_ADAM_DESC = {}
-
-
-def _adam_desc(items):
-    """(device pt_adam_tensor table, device chunk_start, total chunks) of a list of 4-tuples of
-    tensors (5-tuples: the pt_adam_master_tensor table), cached per pointer set (the tensors of a model stay put across steps; a re-allocated
-    gradient makes a new table).  A new table is staged in pinned host memory and copied on the
-    current stream without a host sync (the caching host allocator keeps the staging buffer alive
-    until that copy has run)."""
-    key = tuple(tuple(t.data_ptr() for t in it) + (it[0].numel(),) for it in items)
-    ent = _ADAM_DESC.get(key)
-    if ent is None:
-        dev = items[0][0].device
-        chunks = [0]
-        for k in key:
-            chunks.append(chunks[-1] + (k[-1] + 7) // 8)
-        desc_h = torch.tensor([list(k) for k in key], dtype=torch.int64).pin_memory()
-        chunk_h = torch.tensor(chunks, dtype=torch.int64).pin_memory()
-        ent = (desc_h.to(dev, non_blocking=True), chunk_h.to(dev, non_blocking=True), chunks[-1])
-        if len(_ADAM_DESC) > 64:
-            _ADAM_DESC.clear()
-        _ADAM_DESC[key] = ent
-    return ent
-
-
-def _adam_items_ok(items):
-    _req(len(items) > 0, "adamw multi: an empty tensor list")
-    for p, g, m, v in items:
-        for t in (p, g, m, v):
-            _req(t.dtype == BF16 and t.is_contiguous() and t.numel() == p.numel() and t.data_ptr() % 16 == 0,
-                 "adamw multi: contiguous, 16-byte aligned bf16 tensors of one length per parameter")
-
-
-def adamw_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
-    """One launch of the fused AdamW update over a list of bf16 (param, grad, exp_avg, exp_avg_sq)
-    tuples (pt_adamw_step_multi), on the cached descriptor table of _adam_desc."""
-    _adam_items_ok(items)
-    desc, chunk_t, total = _adam_desc(items)
-    rc = _C.lib().pt_adamw_step_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(decay), float(w1),
-                                      float(beta2), float(c2), float(bc2_sqrt), float(eps), float(step_size),
-                                      _C.stream_ptr(items[0][0].device))
-    _C.check(rc, "pt_adamw_step_multi")
-
-
-# -------------------------------------------------------------- global gradient-norm clipping
-_GRAD_WS = {}   # device index -> f32 workspace of the norm pass (one partial per workgroup)
-
-
-def _grad_ws(device):
-    i = _dev_index(device)
-    w = _GRAD_WS.get(i)
-    if w is None:
-        w = _GRAD_WS[i] = torch.empty(_C.lib().pt_grad_sq_workspace(), dtype=torch.float32,
-                                      device=torch.device("cuda", i))
-    return w
-
-
 def _grad_dtype(t, what):
     _req(t.is_cuda and t.is_contiguous(), f"{what}: a contiguous device tensor")
     if t.dtype == BF16:
@@ -308,66 +232,88 @@ class _clip_status:
             _status_posted(self.device)
 
 
-def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
-    """out[0] (+)= weight * sum of g^2, in f32 and bit-reproducible (csrc/adamw.hip: per-workgroup
-    partials, then one workgroup sums them in a fixed order).  items: bf16 (param, grad, exp_avg,
-    exp_avg_sq) tuples as adamw_step_multi takes them -- one launch over the list on the SAME cached
-    table, of which only the grad field is read (gradients alone: (g, g, g, g)), or the (master, param,
-    grad, exp_avg, exp_avg_sq) tuples of adamw_master_step_multi, bf16 or f32 gradients; tensors: single
-    gradients of what the list form does not take (f32, unaligned bf16).  Everything accumulates
-    into the one device scalar in stream order; returns it (a [1] f32 tensor)."""
-    items, tensors = list(items), list(tensors)
-    _req(items or tensors, "grad_sqnorm: nothing to sum")
-    dev = (items[0][1] if items else tensors[0]).device
-    if out is None:
-        _req(not accumulate, "grad_sqnorm: accumulate needs the scalar to add to")
-        out = torch.empty(1, dtype=torch.float32, device=dev)
-    _sq_ok(out, dev)
-    ws, lib, acc = _grad_ws(dev), _C.lib(), bool(accumulate)
-    if items and len(items[0]) == 5:   # the master-weight list (adamw_master_step_multi's items)
-        gdt = _adam_master_items_ok(items)
-        desc, chunk_t, total = _adam_desc(items)
-        rc = lib.pt_grad_sq_master_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), gdt, float(weight),
-                                         int(acc), _ptr(ws), _ptr(out), _C.stream_ptr(dev))
-        _C.check(rc, "pt_grad_sq_master_multi")
-        acc = True
-    elif items:
-        _adam_items_ok(items)
-        desc, chunk_t, total = _adam_desc(items)
-        rc = lib.pt_grad_sq_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(weight), int(acc),
-                                  _ptr(ws), _ptr(out), _C.stream_ptr(dev))
-        _C.check(rc, "pt_grad_sq_multi")
-        acc = True
-    for g in tensors:
-        _req(g.device == dev, "grad_sqnorm: gradients on one device")
-        rc = lib.pt_grad_sq(_ptr(g), g.numel(), _grad_dtype(g, "grad_sqnorm"), float(weight), int(acc), _ptr(ws),
-                            _ptr(out), _C.stream_ptr(dev))
-        _C.check(rc, "pt_grad_sq")
-        acc = True
-    return out
-
-
-def grad_scale_multi(items, sq, max_norm, status=None):
-    """grad = bf16(grad * coef) in place over the list (items as in grad_sqnorm), coef = min(1,
-    max_norm / (sqrt(sq[0]) + 1e-6)) computed on the device; a non-finite sq leaves the gradients
-    alone and posts STATUS_NONFINITE_GRAD (status: see _clip_status)."""
-    _adam_items_ok(items)
-    dev = items[0][1].device
+def _adam_launch(name, dev, lead, scalars=(), clip=None):
+    """Entry `name`(*lead, *scalars as f32, stream) on dev's current stream, its return code checked.
+    clip = (sq, max_norm, status): a clip consumer -- sq is validated, the entry runs under
+    _clip_status and takes (sq, max_norm, status word) in front of the stream."""
+    sc = [float(x) for x in scalars]
+    if clip is None:
+        _C.check(getattr(_C.lib(), name)(*lead, *sc, _C.stream_ptr(dev)), name)
+        return
+    sq, max_norm, status = clip
     _sq_ok(sq, dev)
-    desc, chunk_t, total = _adam_desc(items)
     with _clip_status(dev, status) as st:
-        rc = _C.lib().pt_grad_scale_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), _ptr(sq),
-                                          float(max_norm), st, _C.stream_ptr(dev))
-        _C.check(rc, "pt_grad_scale_multi")
+        _C.check(getattr(_C.lib(), name)(*lead, *sc, _ptr(sq), float(max_norm), st, _C.stream_ptr(dev)), name)
 
 
-def grad_scale(grad, sq, max_norm, status=None):
-    """grad_scale_multi for one tensor of any alignment, bf16 or f32."""
-    _sq_ok(sq, grad.device)
-    with _clip_status(grad.device, status) as st:
-        rc = _C.lib().pt_grad_scale(_ptr(grad), grad.numel(), _grad_dtype(grad, "grad_scale"), _ptr(sq),
-                                    float(max_norm), st, _C.stream_ptr(grad.device))
-        _C.check(rc, "pt_grad_scale")
+def _adam_single_ok(p, grad, exp_avg, exp_avg_sq):
+    """One (param, grad, exp_avg, exp_avg_sq) of adamw_step / adamw_step_clip; returns the dtype code."""
+    for t, nm in ((grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
+        _req(t.dtype == p.dtype and t.numel() == p.numel() and t.device == p.device, f"adamw: {nm} must match param")
+        _req(t.is_contiguous(), "adamw: dense tensors")
+    _req(p.is_contiguous(), "adamw: param must be contiguous")
+    return _grad_dtype(p, "adamw")
+
+
+def adamw_step(p, grad, exp_avg, exp_avg_sq, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
+    """One fused AdamW update of tensor p in place (bf16 or f32, any alignment; torch foreach semantics)."""
+    dt = _adam_single_ok(p, grad, exp_avg, exp_avg_sq)
+    _adam_launch("pt_adamw_step", p.device, (_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), dt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size))
+
+
+def adamw_step_clip(p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
+    """adamw_step on the clipped gradient (one tensor, bf16 or f32, any alignment)."""
+    dt = _adam_single_ok(p, grad, exp_avg, exp_avg_sq)
+    _adam_launch("pt_adamw_step_clip", p.device, (_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), dt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status))
+
+
+_ADAM_DESC = {}
+
+
+def _adam_desc(items):
+    """(device descriptor table, device chunk_start, total chunks) of a list of tensor tuples:
+    4-tuples make the pt_adam_tensor table, 5-tuples the pt_adam_master_tensor table.  Cached per
+    pointer set: the tensors of a model stay put across steps, a re-allocated gradient makes a new
+    table.  A new table is staged in pinned host memory and copied on the current stream without a
+    host sync (the caching host allocator keeps the staging buffer alive until that copy has run)."""
+    key = tuple(tuple(t.data_ptr() for t in it) + (it[0].numel(),) for it in items)
+    ent = _ADAM_DESC.get(key)
+    if ent is None:
+        dev = items[0][0].device
+        chunks = [0]
+        for k in key:
+            chunks.append(chunks[-1] + (k[-1] + 7) // 8)
+        desc_h = torch.tensor([list(k) for k in key], dtype=torch.int64).pin_memory()
+        chunk_h = torch.tensor(chunks, dtype=torch.int64).pin_memory()
+        ent = (desc_h.to(dev, non_blocking=True), chunk_h.to(dev, non_blocking=True), chunks[-1])
+        if len(_ADAM_DESC) > 64:
+            _ADAM_DESC.clear()
+        _ADAM_DESC[key] = ent
+    return ent
+
+
+def _adam_list(items, *extra):
+    """The leading arguments of a list entry: table, chunk_start, ntensors, total_chunks (, extra)."""
+    desc, chunk_t, total = _adam_desc(items)
+    return (_ptr(desc), _ptr(chunk_t), len(items), int(total)) + extra
+
+
+def _adam_items_ok(items):
+    _req(len(items) > 0, "adamw multi: an empty tensor list")
+    for p, g, m, v in items:
+        for t in (p, g, m, v):
+            _req(t.dtype == BF16 and t.is_contiguous() and t.numel() == p.numel() and t.data_ptr() % 16 == 0,
+                 "adamw multi: contiguous, 16-byte aligned bf16 tensors of one length per parameter")
+
+
+def adamw_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
+    """One launch of the fused AdamW update over a list of bf16 (param, grad, exp_avg, exp_avg_sq)
+    tuples (pt_adamw_step_multi), on the cached descriptor table of _adam_desc."""
+    _adam_items_ok(items)
+    _adam_launch("pt_adamw_step_multi", items[0][0].device, _adam_list(items),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size))
 
 
 def adamw_step_multi_clip(items, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
@@ -375,28 +321,8 @@ def adamw_step_multi_clip(items, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, e
     applied where the kernel loads the gradient: bit-identical to grad_scale_multi followed by
     adamw_step_multi, and the gradients are not modified.  A non-finite sq skips the update."""
     _adam_items_ok(items)
-    dev = items[0][0].device
-    _sq_ok(sq, dev)
-    desc, chunk_t, total = _adam_desc(items)
-    with _clip_status(dev, status) as st:
-        rc = _C.lib().pt_adamw_step_multi_clip(_ptr(desc), _ptr(chunk_t), len(items), int(total), float(decay),
-                                               float(w1), float(beta2), float(c2), float(bc2_sqrt), float(eps),
-                                               float(step_size), _ptr(sq), float(max_norm), st, _C.stream_ptr(dev))
-        _C.check(rc, "pt_adamw_step_multi_clip")
-
-
-def adamw_step_clip(p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
-    """adamw_step on the clipped gradient (one tensor, bf16 or f32, any alignment)."""
-    for t, nm in ((grad, "grad"), (exp_avg, "exp_avg"), (exp_avg_sq, "exp_avg_sq")):
-        _req(t.dtype == p.dtype and t.numel() == p.numel() and t.device == p.device, f"adamw: {nm} must match param")
-        _req(t.is_contiguous(), "adamw: dense tensors")
-    _sq_ok(sq, p.device)
-    with _clip_status(p.device, status) as st:
-        rc = _C.lib().pt_adamw_step_clip(_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(),
-                                         _grad_dtype(p, "adamw"), float(decay), float(w1), float(beta2), float(c2),
-                                         float(bc2_sqrt), float(eps), float(step_size), _ptr(sq), float(max_norm), st,
-                                         _C.stream_ptr(p.device))
-        _C.check(rc, "pt_adamw_step_clip")
+    _adam_launch("pt_adamw_step_multi_clip", items[0][0].device, _adam_list(items),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status))
 
 
 # ----------------------------------------------------- AdamW, fp32 master weights and moments
@@ -428,48 +354,92 @@ def adamw_master_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_siz
     torch's foreach f32 AdamW on the masters, then param = bf16(master).  The gradients of one list
     share a dtype.  The descriptor table is cached as adamw_step_multi's."""
     gdt = _adam_master_items_ok(items)
-    desc, chunk_t, total = _adam_desc(items)
-    rc = _C.lib().pt_adamw_master_step_multi(_ptr(desc), _ptr(chunk_t), len(items), int(total), gdt, float(decay),
-                                             float(w1), float(beta2), float(c2), float(bc2_sqrt), float(eps),
-                                             float(step_size), _C.stream_ptr(items[0][0].device))
-    _C.check(rc, "pt_adamw_master_step_multi")
+    _adam_launch("pt_adamw_master_step_multi", items[0][0].device, _adam_list(items, gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size))
 
 
 def adamw_master_step_multi_clip(items, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, status=None):
     """adamw_master_step_multi on float(grad) * coef, coef as in grad_scale_multi: one f32 product,
     not rounded to bf16; the gradients are not modified.  A non-finite sq skips the update."""
     gdt = _adam_master_items_ok(items)
-    dev = items[0][0].device
-    _sq_ok(sq, dev)
-    desc, chunk_t, total = _adam_desc(items)
-    with _clip_status(dev, status) as st:
-        rc = _C.lib().pt_adamw_master_step_multi_clip(_ptr(desc), _ptr(chunk_t), len(items), int(total), gdt,
-                                                      float(decay), float(w1), float(beta2), float(c2),
-                                                      float(bc2_sqrt), float(eps), float(step_size), _ptr(sq),
-                                                      float(max_norm), st, _C.stream_ptr(dev))
-        _C.check(rc, "pt_adamw_master_step_multi_clip")
+    _adam_launch("pt_adamw_master_step_multi_clip", items[0][0].device, _adam_list(items, gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status))
 
 
 def adamw_master_step(master, p, grad, exp_avg, exp_avg_sq, decay, w1, beta2, c2, bc2_sqrt, eps, step_size):
     """adamw_master_step_multi for one parameter at any alignment (element by element, the same math)."""
     gdt = _adam_master_ok(master, p, grad, exp_avg, exp_avg_sq, "adamw master")
-    rc = _C.lib().pt_adamw_master_step(_ptr(master), _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(),
-                                       gdt, float(decay), float(w1), float(beta2), float(c2), float(bc2_sqrt),
-                                       float(eps), float(step_size), _C.stream_ptr(p.device))
-    _C.check(rc, "pt_adamw_master_step")
+    _adam_launch("pt_adamw_master_step", p.device,
+                 (_ptr(master), _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size))
 
 
 def adamw_master_step_clip(master, p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps,
                            step_size, status=None):
     """adamw_master_step on the clipped gradient."""
     gdt = _adam_master_ok(master, p, grad, exp_avg, exp_avg_sq, "adamw master")
-    _sq_ok(sq, p.device)
-    with _clip_status(p.device, status) as st:
-        rc = _C.lib().pt_adamw_master_step_clip(_ptr(master), _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                                p.numel(), gdt, float(decay), float(w1), float(beta2), float(c2),
-                                                float(bc2_sqrt), float(eps), float(step_size), _ptr(sq),
-                                                float(max_norm), st, _C.stream_ptr(p.device))
-        _C.check(rc, "pt_adamw_master_step_clip")
+    _adam_launch("pt_adamw_master_step_clip", p.device,
+                 (_ptr(master), _ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status))
+
+
+# -------------------------------------------------------------- global gradient-norm clipping
+_GRAD_WS = {}   # device index -> f32 workspace of the norm pass (one partial per workgroup)
+
+
+def _grad_ws(device):
+    i = _dev_index(device)
+    w = _GRAD_WS.get(i)
+    if w is None:
+        w = _GRAD_WS[i] = torch.empty(_C.lib().pt_grad_sq_workspace(), dtype=torch.float32,
+                                      device=torch.device("cuda", i))
+    return w
+
+
+def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
+    """out[0] (+)= weight * sum of g^2, in f32 and bit-reproducible (csrc/adamw.hip: per-workgroup
+    partials, then one workgroup sums them in a fixed order).  items: bf16 (param, grad, exp_avg,
+    exp_avg_sq) tuples as adamw_step_multi takes them -- one launch over the list on the SAME cached
+    table, of which only the grad field is read (gradients alone: (g, g, g, g)), or the (master, param,
+    grad, exp_avg, exp_avg_sq) tuples of adamw_master_step_multi, bf16 or f32 gradients; tensors: single
+    gradients of what the list form does not take (f32, unaligned bf16).  Everything accumulates
+    into the one device scalar in stream order; returns it (a [1] f32 tensor)."""
+    items, tensors = list(items), list(tensors)
+    _req(items or tensors, "grad_sqnorm: nothing to sum")
+    dev = (items[0][1] if items else tensors[0]).device
+    if out is None:
+        _req(not accumulate, "grad_sqnorm: accumulate needs the scalar to add to")
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+    _sq_ok(out, dev)
+    ws, acc = _grad_ws(dev), bool(accumulate)
+    if items:
+        if len(items[0]) == 5:   # the master-weight list: its entry takes the gradients' dtype as well
+            name, extra = "pt_grad_sq_master_multi", (_adam_master_items_ok(items),)
+        else:
+            _adam_items_ok(items)
+            name, extra = "pt_grad_sq_multi", ()
+        _adam_launch(name, dev, _adam_list(items, *extra) + (float(weight), int(acc), _ptr(ws), _ptr(out)))
+        acc = True
+    for g in tensors:
+        _req(g.device == dev, "grad_sqnorm: gradients on one device")
+        _adam_launch("pt_grad_sq", dev, (_ptr(g), g.numel(), _grad_dtype(g, "grad_sqnorm"), float(weight), int(acc),
+                                         _ptr(ws), _ptr(out)))
+        acc = True
+    return out
+
+
+def grad_scale_multi(items, sq, max_norm, status=None):
+    """grad = bf16(grad * coef) in place over the list (items as in grad_sqnorm), coef = min(1,
+    max_norm / (sqrt(sq[0]) + 1e-6)) computed on the device; a non-finite sq leaves the gradients
+    alone and posts STATUS_NONFINITE_GRAD (status: see _clip_status)."""
+    _adam_items_ok(items)
+    _adam_launch("pt_grad_scale_multi", items[0][1].device, _adam_list(items), clip=(sq, max_norm, status))
+
+
+def grad_scale(grad, sq, max_norm, status=None):
+    """grad_scale_multi for one tensor of any alignment, bf16 or f32."""
+    _adam_launch("pt_grad_scale", grad.device, (_ptr(grad), grad.numel(), _grad_dtype(grad, "grad_scale")),
+                 clip=(sq, max_norm, status))
 
 
 # ------------------------------------------------------------------------------------ RoPE

@@ -48,8 +48,8 @@ def grad_norm_plan(params, tp_size, pp_size):
 
 
 def _listable(*tensors):
-    """What the multi-tensor launches take: contiguous, 16-byte aligned bf16."""
-    return all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors)
+    """The layout the multi-tensor launches take: contiguous and 16-byte aligned."""
+    return all(t.is_contiguous() and t.data_ptr() % 16 == 0 for t in tensors)
 
 
 def _global_sq(batches):
@@ -141,16 +141,7 @@ class AdamW(torch.optim.Optimizer):
             return loss
         for group in self.param_groups:
             for sc, kind, items in self._batches(group):
-                if kind == MULTI:
-                    K.adamw_step_multi(items, **sc)
-                elif kind == SINGLE:
-                    for p, g, m, v in items:
-                        K.adamw_step(p, g, m, v, **sc)
-                elif kind == MASTER_MULTI:
-                    K.adamw_master_step_multi(items, **sc)
-                else:
-                    for it in items:
-                        _master_single(K.adamw_master_step, it, **sc)
+                _launch(kind, items, sc)
         return loss
 
     def _grad(self, p):
@@ -189,12 +180,11 @@ class AdamW(torch.optim.Optimizer):
             t = st["step"].item()
             if master:
                 item = (st["master_param"], p, grad, st["exp_avg"], st["exp_avg_sq"])
-                kind = MASTER_MULTI if all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) else MASTER_SINGLE
+                kind = MASTER_MULTI if _listable(*item) else MASTER_SINGLE
                 batches.setdefault((t, kind, grad.dtype), []).append(item)
             else:
                 item = (p, grad, st["exp_avg"], st["exp_avg_sq"])
-                multi = p.dtype == torch.bfloat16 and all(x.is_contiguous() and x.data_ptr() % 16 == 0 for x in item) \
-                    and grad.dtype == p.dtype
+                multi = p.dtype == grad.dtype == torch.bfloat16 and _listable(*item)
                 batches.setdefault((t, MULTI if multi else SINGLE, None), []).append(item)
         out = []
         for (t, kind, _), items in batches.items():
@@ -209,10 +199,11 @@ class AdamW(torch.optim.Optimizer):
         work = [b for group in self.param_groups for b in self._batches(group)]
         norm_batches = []
         for _, kind, items in work:   # (param, what grad_sqnorm takes for it): see _global_sq
-            if kind in (MULTI, MASTER_MULTI):
-                norm_batches.append((True, [(it[0] if kind == MULTI else it[1], it) for it in items]))
-            else:
-                norm_batches.append((False, [(it[0], it[1]) if kind == SINGLE else (it[1], it[2].contiguous())
+            _, is_list, ip, ig = _KINDS[kind]
+            if is_list:
+                norm_batches.append((True, [(it[ip], it) for it in items]))
+            else:   # the gradient as the step will take it (_master_single)
+                norm_batches.append((False, [(it[ip], it[ig].contiguous() if kind == MASTER_SINGLE else it[ig])
                                              for it in items]))
         sq = _global_sq(norm_batches)
         if sq is None:   # no gradients at all
@@ -220,16 +211,7 @@ class AdamW(torch.optim.Optimizer):
         self.last_grad_norm = sq.sqrt().reshape(())
         status = K.status_word(sq.device)   # one word, posted once: see kernels._clip_status
         for sc, kind, items in work:
-            if kind == MULTI:
-                K.adamw_step_multi_clip(items, sq, self.max_grad_norm, status=status, **sc)
-            elif kind == SINGLE:
-                for p, g, m, v in items:
-                    K.adamw_step_clip(p, g, m, v, sq, self.max_grad_norm, status=status, **sc)
-            elif kind == MASTER_MULTI:
-                K.adamw_master_step_multi_clip(items, sq, self.max_grad_norm, status=status, **sc)
-            else:
-                for it in items:
-                    _master_single(K.adamw_master_step_clip, it, sq, self.max_grad_norm, status=status, **sc)
+            _launch(kind, items, sc, clip=(sq, self.max_grad_norm, status))
         K._status_posted(sq.device)
 
     @torch.no_grad()
@@ -272,6 +254,23 @@ class AdamW(torch.optim.Optimizer):
 
 
 MULTI, SINGLE, MASTER_MULTI, MASTER_SINGLE = "multi", "single", "master_multi", "master_single"
+# kind -> (kernels.* step function, + "_clip" for the clipped one; list launch?; index of param, of grad in an item)
+_KINDS = {MULTI: ("adamw_step_multi", True, 0, 1), SINGLE: ("adamw_step", False, 0, 1),
+          MASTER_MULTI: ("adamw_master_step_multi", True, 1, 2), MASTER_SINGLE: ("adamw_master_step", False, 1, 2)}
+
+
+def _launch(kind, items, sc, clip=None):
+    """One batch of AdamW._batches; clip = (sq, max_norm, status word): the clipped kernels."""
+    name, is_list, _, _ = _KINDS[kind]
+    fn = getattr(K, name if clip is None else name + "_clip")
+    args, kw = ((), sc) if clip is None else (clip[:2], dict(sc, status=clip[2]))
+    if is_list:
+        return fn(items, *args, **kw)
+    for it in items:
+        if kind == MASTER_SINGLE:
+            _master_single(fn, it, *args, **kw)
+        else:
+            fn(*it, *args, **kw)
 
 
 def _master_single(fn, item, *args, **kw):
@@ -303,8 +302,9 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
     params = [p for p in parameters if p.grad is not None]
     if not params:
         return torch.tensor(0.0)
-    multi = [(p, (p.grad,) * 4) for p in params if _listable(p.grad)]
-    single = [(p, p.grad) for p in params if not _listable(p.grad)]
+    listed = {id(p) for p in params if p.grad.dtype == torch.bfloat16 and _listable(p.grad)}
+    multi = [(p, (p.grad,) * 4) for p in params if id(p) in listed]
+    single = [(p, p.grad) for p in params if id(p) not in listed]
     sq = _global_sq([(True, multi), (False, single)])
     status = K.status_word(sq.device)
     if multi:

@@ -110,3 +110,69 @@ def test_grad_clip_abi_argument_errors():
     assert lib.pt_adamw_step_multi_clip(a, a, 1, -1, *sc, a, 1.0, None, None) == -1
     assert lib.pt_adamw_step_multi_clip(a, a, 1, 1, *sc, None, 1.0, None, None) == -1
     assert lib.pt_adamw_step_multi_clip(a, a, 1, 1, *sc, a, float("nan"), None, None) == -1
+
+
+_SC = (0.999, 0.1, 0.999, 0.001, 0.03, 1e-8, -3e-4)
+_P = 16   # any non-null address: every call below returns before a pointer is read
+
+
+def test_unclipped_step_abi_argument_errors():
+    """pt_adamw_step and pt_adamw_step_multi: PT_EINVAL (-1) for a NULL pointer, a negative count and
+    an unknown dtype, PT_OK (0) for nothing to do -- but only with valid arguments: an unknown dtype
+    is refused at n == 0 as well, as every sibling entry does."""
+    from picotron_amd import _C
+    lib = _C.load_library()
+    for i in range(4):   # param, grad, exp_avg, exp_avg_sq
+        ptrs = [_P] * 4
+        ptrs[i] = None
+        assert lib.pt_adamw_step(*ptrs, 8, 0, *_SC, None) == -1
+    assert lib.pt_adamw_step(_P, _P, _P, _P, -1, 0, *_SC, None) == -1
+    assert lib.pt_adamw_step(_P, _P, _P, _P, 8, 2, *_SC, None) == -1
+    assert lib.pt_adamw_step(_P, _P, _P, _P, 0, 0, *_SC, None) == 0
+    assert lib.pt_adamw_step(_P, _P, _P, _P, 0, 1, *_SC, None) == 0
+    assert lib.pt_adamw_step(_P, _P, _P, _P, 0, 2, *_SC, None) == -1
+    # list form: table, chunk_start, ntensors, total_chunks
+    assert lib.pt_adamw_step_multi(None, _P, 1, 1, *_SC, None) == -1
+    assert lib.pt_adamw_step_multi(_P, None, 1, 1, *_SC, None) == -1
+    assert lib.pt_adamw_step_multi(_P, _P, 0, 1, *_SC, None) == -1
+    assert lib.pt_adamw_step_multi(_P, _P, 1, -1, *_SC, None) == -1
+    assert lib.pt_adamw_step_multi(_P, _P, 1, 0, *_SC, None) == 0
+
+
+def _single_cases(nptr, dtype):
+    """(arguments in front of the scalars, expected return) of a single-tensor step entry."""
+    ok = (_P,) * nptr
+    cases = [(ok[:i] + (None,) + ok[i + 1:] + (8, dtype), -1) for i in range(nptr)]
+    return cases + [(ok + (-1, dtype), -1), (ok + (8, 2), -1), (ok + (0, 2), -1), (ok + (8, -1), -1), (ok + (0, dtype), 0)]
+
+
+def _list_cases(*dtype):
+    """The same for a list entry (dtype: the master forms' gradient dtype argument)."""
+    cases = [((None, _P, 1, 1) + dtype, -1), ((_P, None, 1, 1) + dtype, -1), ((_P, _P, 0, 1) + dtype, -1),
+             ((_P, _P, -1, 0) + dtype, -1), ((_P, _P, 1, -1) + dtype, -1), ((None, None, 1, 0) + dtype, -1),
+             ((_P, _P, 1, 0) + dtype, 0)]
+    if dtype:
+        cases += [((_P, _P, 1, 1, 2), -1), ((_P, _P, 1, 0, 2), -1)]
+    return cases
+
+
+@pytest.mark.parametrize("name,cases", [
+    ("pt_adamw_step", _single_cases(4, 0) + _single_cases(4, 1)),
+    ("pt_adamw_step_multi", _list_cases()),
+    ("pt_adamw_master_step_multi", _list_cases(0)),
+    ("pt_adamw_master_step_multi", _list_cases(1)),
+    ("pt_adamw_master_step", _single_cases(5, 0)),
+    ("pt_adamw_master_step", _single_cases(5, 1)),
+], ids=["step", "step_multi", "master_multi-bf16", "master_multi-f32", "master-bf16", "master-f32"])
+def test_clipped_entries_refuse_what_their_namesakes_refuse(name, cases):
+    """Every *_clip step entry, given valid clip arguments, returns what its unclipped namesake
+    returns for the same leading arguments: the refusals (-1) and "nothing to do" (0).  And a
+    clipped entry with a bad clip argument is refused even when there is nothing to do."""
+    from picotron_amd import _C
+    lib = _C.load_library()
+    plain, clipped = getattr(lib, name), getattr(lib, name + "_clip")
+    for lead, want in cases:
+        assert plain(*lead, *_SC, None) == want, (name, lead)
+        assert clipped(*lead, *_SC, _P, 1.0, None, None) == want, (name + "_clip", lead)
+        for sq, max_norm in ((None, 1.0), (_P, 0.0), (_P, -1.0), (_P, float("nan"))):
+            assert clipped(*lead, *_SC, sq, max_norm, None, None) == -1, (name + "_clip", lead, sq, max_norm)

@@ -212,7 +212,7 @@ def test_f32_list_norm_against_fp64():
     blocks = min(2048, -(-CHUNKS // 512))
     per_block = -(-CHUNKS // blocks)
     assert blocks == 257 and per_block == 512
-    # grad_sq_master_multi_kernel is grad_sq_multi_kernel's walk: every term g * g >= 0 enters through
+    # grad_sq_list_kernel, the one walk of the bf16 list's norm pass too: every term g * g >= 0 enters through
     # one fused multiply-add (the f32 square is not rounded on its own), so the relative error is at
     # most (f32 additions on the longest path from a term to the result) * 2^-24:
     #   in a thread: an accumulator takes 8 fused adds per chunk, from at most ceil(per_block / 256)

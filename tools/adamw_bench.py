@@ -1,6 +1,7 @@
 """Multi-tensor AdamW over the SmolLM-1.7B parameter set (1.21 B bf16 parameters, the model's tensor
-sizes): us per step (graph-timed) and HBM rate on 14 B per parameter; --old: another build's
-pt_adamw_step_multi in the same process; --calib: beside it torch's fused AdamW on the same tensors and
+sizes): us per step (graph-timed) and HBM rate on 14 B per parameter; --old: another build's library in
+the same process -- every variant that calls into the library is then timed once per library per round,
+alternating, and its record names the library; --calib: beside it torch's fused AdamW on the same tensors and
 the HBM rate of torch's copy (1 read : 1 write) and add (2 : 1) over the same bytes, which bracket
 AdamW's 8 : 6 mix; --clip: global gradient-norm clipping -- (a) the plain step, (b) the norm pass alone
 (rate on 2 B per parameter, beside torch's x.sum() over the same bytes), (c) norm pass + clipped step,
@@ -44,20 +45,45 @@ def main():
         libs["old"] = _C.load_library(os.path.abspath(a.old), strict=False)
     for rnd in range(2):
         for name, lib in libs.items():
-            _C._lib = lib
-            K._ADAM_DESC.clear() if hasattr(K, "_ADAM_DESC") else None
+            use(lib)
             us = graph_us(lambda: K.adamw_step_multi(items, *args), 3)
             print(json.dumps({"lib": f"{name}:r{rnd}", "params": n, "us": round(us, 1), "TBps": round(14 * n / us / 1e6, 2)}),
                   flush=True)
+    use(libs["new"])
     if a.calib:
         calib(items, n, args)
     if a.clip:
-        clip(items, n, args)
+        clip(items, n, args, libs)
     if a.master:
-        master(items, n, args)
+        master(items, n, args, libs)
 
 
-def clip(items, n, args):
+def use(lib):
+    """The library the ops call from here on; its descriptor tables are built anew."""
+    _C._lib = lib
+    K._ADAM_DESC.clear()
+
+
+def rounds(tag, variants, n, libs):
+    """variants: [(name, fn, bytes per parameter or None, calls the library)].  Three rounds; in each,
+    a variant that calls the library is timed once per library, a torch-only probe once."""
+    for rnd in range(3):
+        for name, fn, bpp, in_lib in variants:
+            order = list(libs.items())[::-1 if rnd % 2 else 1] if in_lib else [(None, None)]   # who goes first alternates
+            for lib_name, lib in order:
+                if lib is not None:
+                    use(lib)
+                us = graph_us(fn, 3)
+                rec = {tag: name, "round": rnd, "params": n, "us": round(us, 1)}
+                if lib_name:
+                    rec["lib"] = lib_name
+                if bpp:
+                    rec["TBps"] = round(bpp * n / us / 1e6, 2)
+                print(json.dumps(rec), flush=True)
+    use(libs["new"])
+
+
+def clip(items, n, args, libs):
     dev = items[0][0].device
     sq = torch.zeros(1, dtype=torch.float32, device=dev)
     status = K.status_word(dev)
@@ -76,25 +102,19 @@ def clip(items, n, args):
     def fused():
         K.grad_sqnorm(items=items, out=sq)
         K.adamw_step_multi_clip(items, sq, max_norm, *args, status=status)
-    variants = [("a: adamw_step_multi", lambda: K.adamw_step_multi(items, *args), 14),
-                ("b: grad_sqnorm", lambda: K.grad_sqnorm(items=items, out=sq), 2),
-                ("probe: sum 1r", lambda: x.sum(), 2),
-                ("c: grad_sqnorm + adamw_step_multi_clip", fused, 16),
-                ("c': adamw_step_multi_clip alone", lambda: K.adamw_step_multi_clip(items, sq, max_norm, *args, status=status), 14),
-                ("d: torch clip_grad_norm_ + adamw_step_multi", torch_clip_then_step, None)]
-    for rnd in range(3):
-        for name, fn, bpp in variants:
-            us = graph_us(fn, 3)
-            rec = {"clip": name, "round": rnd, "params": n, "us": round(us, 1)}
-            if bpp:
-                rec["TBps"] = round(bpp * n / us / 1e6, 2)
-            print(json.dumps(rec), flush=True)
+    variants = [("a: adamw_step_multi", lambda: K.adamw_step_multi(items, *args), 14, True),
+                ("b: grad_sqnorm", lambda: K.grad_sqnorm(items=items, out=sq), 2, True),
+                ("probe: sum 1r", lambda: x.sum(), 2, False),
+                ("c: grad_sqnorm + adamw_step_multi_clip", fused, 16, True),
+                ("c': adamw_step_multi_clip alone", lambda: K.adamw_step_multi_clip(items, sq, max_norm, *args, status=status), 14, True),
+                ("d: torch clip_grad_norm_ + adamw_step_multi", torch_clip_then_step, None, True)]
+    rounds("clip", variants, n, libs)
     torch.cuda.synchronize()
     print(json.dumps({"clip": "grad norm", "value": round(float(sq.sqrt()), 4),
                       "status": K.device_status(dev)}), flush=True)
 
 
-def master(items, n, args):
+def master(items, n, args, libs):
     """fp32 master weights: (a) today's bf16 step, (m16) / (m32) the master step on bf16 / f32 gradients
     (28 / 30 B per parameter), (n32) the f32 norm pass alone (4 B), (t) what a user would do without the
     kernel: torch._fused_adamw_ on f32 param / grad / moments, then _foreach_copy_ into the bf16 weights;
@@ -117,19 +137,13 @@ def master(items, n, args):
         torch._foreach_copy_(ps, ws)
     x = torch.empty(7 * n, dtype=torch.bfloat16, device=ps[0].device).normal_()   # the master step's 14 B read,
     y = torch.empty_like(x)                                                        # 14 B written, as one copy
-    variants = [("a: adamw_step_multi (bf16 state)", lambda: K.adamw_step_multi(items, *args), 14),
-                ("probe: torch copy 1r:1w over 28 B/param", lambda: y.copy_(x), 28),
-                ("m16: adamw_master_step_multi, bf16 grads", lambda: K.adamw_master_step_multi(m16, *args), 28),
-                ("m32: adamw_master_step_multi, f32 grads", lambda: K.adamw_master_step_multi(m32, *args), 30),
-                ("n32: grad_sqnorm, f32 grads", lambda: K.grad_sqnorm(items=m32, out=sq), 4),
-                ("t: torch._fused_adamw_ f32 + _foreach_copy_ to bf16", torch_master, None)]
-    for rnd in range(3):
-        for name, fn, bpp in variants:
-            us = graph_us(fn, 3)
-            rec = {"master": name, "round": rnd, "params": n, "us": round(us, 1)}
-            if bpp:
-                rec["TBps"] = round(bpp * n / us / 1e6, 2)
-            print(json.dumps(rec), flush=True)
+    variants = [("a: adamw_step_multi (bf16 state)", lambda: K.adamw_step_multi(items, *args), 14, True),
+                ("probe: torch copy 1r:1w over 28 B/param", lambda: y.copy_(x), 28, False),
+                ("m16: adamw_master_step_multi, bf16 grads", lambda: K.adamw_master_step_multi(m16, *args), 28, True),
+                ("m32: adamw_master_step_multi, f32 grads", lambda: K.adamw_master_step_multi(m32, *args), 30, True),
+                ("n32: grad_sqnorm, f32 grads", lambda: K.grad_sqnorm(items=m32, out=sq), 4, True),
+                ("t: torch._fused_adamw_ f32 + _foreach_copy_ to bf16", torch_master, None, False)]
+    rounds("master", variants, n, libs)
     torch.cuda.synchronize()
     print(json.dumps({"master": "status", "value": K.device_status(ps[0].device)}), flush=True)
 
