@@ -6,7 +6,10 @@ hot path reads the environment again.  `PICOTRON_<NAME>` (upper case) sets a swi
 process (an A/B run); tests and tools change one for a block with `override(name=value)`.
 Every non-default form runs through the whole GPU path against the oracle in
 tests/test_switch_forms_gpu.py (ring_zigzag / tp_sp_chunks in test_parallel_gpu.py, gemm_kh and
-wgrad_pair in test_kernels_gpu.py);
+wgrad_pair in test_kernels_gpu.py), which also asserts from the recorded kernel calls that the form
+was taken; tests/test_model_stages_gpu.py checks every stage of the autograd layer per element under
+the forms that change a launch of functional.py, tests/test_grad_sinks_exact_gpu.py the gradient sinks
+(norm_defer, wgrad_pair) by bits;
 tools/switch_kernels.py traces which launches each changes (profiles/r05/switch_kernels_r05k.txt).
 
 The native switches (attention causal pairing, dK/dV kernel form, few-head split chunk; GEMM
