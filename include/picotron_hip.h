@@ -323,6 +323,59 @@ int pt_grad_sq_master_multi(const void* tensors, const int64_t* chunk_start, int
                             int grad_dtype, float weight, int accumulate, float* workspace, float* sq,
                             hipStream_t stream);
 
+/* ---- AdamW in bf16 state with stochastic rounding -------------------------------------------
+ * The recipe between the two above: param, exp_avg and exp_avg_sq stay bf16 (the plain step's 6 B
+ * of state and 14 B of traffic per parameter, 16 B with f32 gradients), the update is the master
+ * step's f32 sequence on the widened values -- g32 = float(grad) (grad_dtype 0 bf16, 1 f32; with
+ * clipping g32 *= clip_coef, never rounded to bf16) -- and the three results are stored with
+ * sr_bf16: rounded up or down with probability equal to the discarded fraction, so E[stored] is
+ * the f32 value.  No other rounding to bf16 happens in the step.
+ *
+ * Random bits: Philox4x32-10 (Random123's constants), key = (seed_lo, seed_hi), counter =
+ * (c & 0xffffffff, c >> 32, step, (rng_stream << 2) | which): c = i >> 3, the 8-element chunk of
+ * element i inside its tensor; step the parameter's step count t >= 1; rng_stream < 2^30 the
+ * parameter's fixed stream id; which = 0 param, 1 exp_avg, 2 exp_avg_sq.  Of the four words w the
+ * element takes r = (w[(i & 7) >> 1] >> (16 * (i & 1))) & 0xffff.  The bits are a pure function of
+ * (seed, stream, step, element index, which): launch geometry, list order, neighbours, alignment
+ * and list or single-tensor form do not enter, and every form gives the same result bit for bit.
+ * sr_bf16(x, r) for x with bits u: inf and NaN take the plain cast; otherwise the 16-bit value
+ * (u + r) >> 16.  A bf16 value never changes; the magnitude goes up with probability
+ * low16 / 65536 exactly; -0 stays -0; a value inside the last bf16 ulp below the largest finite
+ * one may become inf.
+ *
+ * List form: `tensors` is a device array of pt_adam_sr_tensor (every pointer 16-byte aligned),
+ * chunk_start / total_chunks as for pt_adamw_step_multi.  The table's builder keeps rng_stream in
+ * [0, 2^30).  Single-tensor form: any alignment.  step == 0, rng_stream outside [0, 2^30), a
+ * grad_dtype outside {0, 1} or `which` outside {0, 1, 2} is PT_EINVAL.  The *_clip forms and
+ * pt_grad_sq_sr_multi behave as their namesakes above.  pt_sr_cast_bf16 is the rounding alone:
+ * y[i] = sr_bf16(x[i], the draw of element i). */
+typedef struct {
+  void* param;
+  const void* grad; /* bf16 or f32 */
+  void* exp_avg;
+  void* exp_avg_sq;
+  int64_t n;
+  int64_t rng_stream;
+} pt_adam_sr_tensor;
+int pt_adamw_sr_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                           int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                           float step_size, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, hipStream_t stream);
+int pt_adamw_sr_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                                int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                                float step_size, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, const float* grad_sq,
+                                float max_norm, int* status, hipStream_t stream);
+int pt_adamw_sr_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int grad_dtype,
+                     float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                     uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int64_t rng_stream, hipStream_t stream);
+int pt_adamw_sr_step_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int grad_dtype,
+                          float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                          uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int64_t rng_stream, const float* grad_sq,
+                          float max_norm, int* status, hipStream_t stream);
+int pt_grad_sq_sr_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                        int grad_dtype, float weight, int accumulate, float* workspace, float* sq, hipStream_t stream);
+int pt_sr_cast_bf16(const float* x, void* y, int64_t n, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                    int64_t rng_stream, int which, hipStream_t stream);
+
 /* ---- bf16 GEMM, f32 accumulate -------------------------------------------------------------
  * replaces every F.linear / matmul of the layer: model.py:124-126,161,186,270,
  * tensor_parallel.py:186, tp_communications.py:79,93,98,105.

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpicotron_hip.so")
 
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
+_u32 = ctypes.c_uint32
 _f32 = ctypes.c_float
 _vp = ctypes.c_void_p
 _i64p = ctypes.POINTER(ctypes.c_int64)
@@ -57,6 +58,16 @@ SIGNATURES = {
     "pt_adamw_master_step_clip": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32,
                                          _f32, _vp, _f32, _vp, _vp]),
     "pt_grad_sq_master_multi": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "pt_adamw_sr_step_multi": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _u32, _u32,
+                                      _u32, _vp]),
+    "pt_adamw_sr_step_multi_clip": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _u32,
+                                           _u32, _u32, _vp, _f32, _vp, _vp]),
+    "pt_adamw_sr_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _u32, _u32,
+                                _u32, _i64, _vp]),
+    "pt_adamw_sr_step_clip": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _u32, _u32,
+                                     _u32, _i64, _vp, _f32, _vp, _vp]),
+    "pt_grad_sq_sr_multi": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
+    "pt_sr_cast_bf16": (_i32, [_vp, _vp, _i64, _u32, _u32, _u32, _i64, _i32, _vp]),
     "pt_rmsnorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pt_rmsnorm_colsum_batch": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "pt_rmsnorm_bwd_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),

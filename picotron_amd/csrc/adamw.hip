@@ -18,14 +18,18 @@
 // Also here, because they walk the same tensor tables: global gradient-norm clipping
 // (torch.nn.utils.clip_grad_norm_ in front of the step) -- the f32 sum of squares of every
 // gradient, and the clip coefficient applied where the AdamW kernels load the gradient (a
-// compile-time variant of each) or in place.  And the opt-in mixed-precision form of the step: f32
-// master weights and moments behind the bf16 parameters.
+// compile-time variant of each) or in place.  And the two opt-in forms of the step that keep small
+// updates: f32 master weights and moments behind the bf16 parameters, or bf16 state all the way with
+// the three stores rounded stochastically (Philox4x32-10 bits, a pure function of seed, stream,
+// step and element index).
 //
-// Top to bottom: element functions (adam_elem, adam_elem_master, the clip coefficient); the table
-// walk (the two descriptor structs and for_each_run, a workgroup's run of 8-element chunks tensor
-// by tensor); the kernels (step, sum of squares, in-place scale); the host launch helpers (geometry,
-// the shared argument checks, one body per form with the clipping as a template argument:
-// step_single / step_multi, master_single / master_multi, grad_sq_sum); the extern "C" forwards.
+// Top to bottom: element functions (adam_elem, adam_elem_master, the clip coefficient, the random
+// bits and sr_bf16); the table walk (the three descriptor structs and for_each_run, a workgroup's
+// run of 8-element chunks tensor by tensor); the kernels (step, master step, stochastic-rounding
+// step and cast, sum of squares, in-place scale); the host launch helpers (geometry, the shared
+// argument checks, one body per form with the clipping as a template argument: step_single /
+// step_multi, master_single / master_multi, sr_single / sr_multi, grad_sq_sum); the extern "C"
+// forwards.
 #include "common.h"
 
 namespace {
@@ -148,6 +152,63 @@ template <> struct GradVec<float> {
   static __device__ __forceinline__ type ld(const float* p) { return ld8f_nt(p); }
 };
 
+// Stochastic rounding (optim.AdamW(stochastic_rounding=True)): every tensor stays bf16, the update
+// is adam_elem_master's f32 sequence on the widened values, and each of the three stores rounds up
+// or down with probability equal to the discarded fraction, so E[stored] = the f32 value: updates
+// below half an ulp accumulate in expectation and v * 0.999 no longer sticks, at the plain step's
+// 14 / 16 B per parameter.
+//
+// The bits: Philox4x32-10 (Random123's constants), key = the 64-bit seed's halves, counter =
+// (c lo, c hi, step, stream << 2 | which) with c = i >> 3 the 8-element chunk of element i INSIDE
+// ITS TENSOR, step the parameter's step count (>= 1), stream < 2^30 the parameter's fixed id and
+// which = 0 param, 1 exp_avg, 2 exp_avg_sq.  Element i takes the 16 bits
+// r = (w[(i & 7) >> 1] >> (16 * (i & 1))) & 0xffff of the call's four words: the two halves of
+// word j are the draws of the two elements packed into word j of the chunk's 16-byte store.
+// Nothing of the launch (geometry, list order, neighbours, alignment, list or single form) enters.
+struct SrArgs {
+  uint32_t seed_lo, seed_hi, step;
+};
+constexpr int SR_PARAM = 0, SR_EXP_AVG = 1, SR_EXP_AVG_SQ = 2;
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                              uint32_t k1, uint32_t (&w)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {   // one 32 x 32 -> 64 product per half (v_mad_u64_u32)
+    const uint64_t a = (uint64_t)0xD2511F53u * c0, b = (uint64_t)0xCD9E8D57u * c2;
+    c0 = (uint32_t)(b >> 32) ^ c1 ^ k0;
+    c2 = (uint32_t)(a >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)b;
+    c3 = (uint32_t)a;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+// the three calls of chunk c (indexed by `which`)
+__device__ __forceinline__ void sr_draw(const SrArgs& k, uint32_t rng_stream, int64_t c, uint32_t (&w)[3][4]) {
+#pragma unroll
+  for (int which = 0; which < 3; ++which)
+    philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), k.step, (rng_stream << 2) | which, k.seed_lo, k.seed_hi,
+                  w[which]);
+}
+__device__ __forceinline__ uint32_t sr_pick(const uint32_t (&w)[4], int j) {   // element j of the chunk
+  return (w[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+}
+// sr_bf16(x, r), r in [0, 65536): the 16-bit value (u + r) >> 16 of x's bits u -- a bf16 value
+// stays what it is, the magnitude goes up with probability low16 / 65536 exactly, -0 stays -0, and
+// a value inside the last bf16 ulp below the largest finite one may become inf.  inf and NaN take
+// the plain cast: the integer carry would turn some NaNs into a zero or an infinity.
+__device__ __forceinline__ uint32_t sr_bf16(float x, uint32_t r) {
+  const uint32_t u = __float_as_uint(x);
+  return (u & 0x7f800000u) == 0x7f800000u ? (uint32_t)f2bf(x) : (u + r) >> 16;
+}
+__device__ __forceinline__ bf16x8 sr_pack8(const float* f, const uint32_t (&w)[4]) {
+  bf16x8 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) v.w[j] = sr_bf16(f[2 * j], w[j] & 0xffffu) | (sr_bf16(f[2 * j + 1], w[j] >> 16) << 16);
+  return v;
+}
+
 // ---- table walk -------------------------------------------------------------------------------
 // Multi-tensor form: ONE launch per step over every listed parameter (torch's foreach AdamW works
 // on the whole list too).  The tensors are a virtual concatenation of 8-element chunks; workgroup b
@@ -168,6 +229,15 @@ struct AdamMasterTensor {   // pt_adam_master_tensor (include/picotron_hip.h)
   float* m;
   float* v;
   int64_t n;
+};
+
+struct AdamSrTensor {   // pt_adam_sr_tensor (include/picotron_hip.h)
+  uint16_t* p;
+  const void* g;
+  uint16_t* m;
+  uint16_t* v;
+  int64_t n;
+  int64_t stream;   // the parameter's random stream, < 2^30 (the table's builder checks it)
 };
 
 // workgroup b's run of chunks, tensor by tensor; fn(T, from, to) gets the run's chunk range inside
@@ -405,6 +475,105 @@ __global__ __launch_bounds__(256) void adamw_master_scalar_kernel(float* __restr
   }
 }
 
+// ---- the step: bf16 state, stochastic rounding ------------------------------------------------
+// One chunk of the step in registers: adam_elem_master on the widened values, then the three
+// stochastically rounded 16-byte vectors.
+template <bool CLIP>
+__device__ __forceinline__ void sr_chunk(float* p, float* g, float* m, float* v, const AdamScalars& s, float coef) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) master_elem<CLIP>(p[j], g[j], m[j], v[j], s, coef);
+}
+// elements [i0, i1) of chunk c one by one (the ragged last chunk; a tensor at any alignment)
+template <typename GT, bool CLIP>
+__device__ __forceinline__ void sr_elems(uint16_t* P, const GT* G, uint16_t* M, uint16_t* V, int64_t c, int64_t i1,
+                                         uint32_t rng_stream, const AdamScalars& s, const SrArgs& k, float coef) {
+  uint32_t w[3][4];
+  sr_draw(k, rng_stream, c, w);
+  for (int64_t i = c * 8; i < i1; ++i) {
+    const int j = (int)(i & 7);
+    float p = bf2f(P[i]), m = bf2f(M[i]), v = bf2f(V[i]);
+    master_elem<CLIP>(p, ld_as_f(G, i), m, v, s, coef);
+    P[i] = (uint16_t)sr_bf16(p, sr_pick(w[SR_PARAM], j));
+    M[i] = (uint16_t)sr_bf16(m, sr_pick(w[SR_EXP_AVG], j));
+    V[i] = (uint16_t)sr_bf16(v, sr_pick(w[SR_EXP_AVG_SQ], j));
+  }
+}
+
+// One launch over the list, bf16 or f32 gradients.  The loads of a thread's next two chunks are in
+// flight while the current one is computed, as in the bf16 list kernel (three or four 16-byte loads
+// and three stores per chunk); the chunk's three Philox calls depend on nothing that is loaded.
+template <typename GT, bool CLIP>
+__global__ __launch_bounds__(256, 4) void adamw_sr_multi_kernel(const AdamSrTensor* __restrict__ ts,
+                                                                const int64_t* __restrict__ chunk_start, int nt,
+                                                                int64_t per_block, AdamScalars s, SrArgs k,
+                                                                ClipArgs<CLIP> clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
+  for_each_run(ts, chunk_start, nt, per_block, [&](const AdamSrTensor& T, int64_t from, int64_t to) {
+    const GT* G = (const GT*)T.g;
+    const uint32_t rs = (uint32_t)T.stream;
+    const int64_t full = T.n >> 3;
+    const int64_t end = to < full ? to : full;   // this run's full chunks in tensor T
+    const int64_t bd = blockDim.x;
+    int64_t c = from + threadIdx.x;
+    struct In {
+      bf16x8 p, m, v;
+      typename GradVec<GT>::type g;
+    } cur, nx1, nx2;
+    auto load = [&](int64_t cc, In& r) {
+      r.p = ld8_nt(T.p + cc * 8); r.g = GradVec<GT>::ld(G + cc * 8); r.m = ld8_nt(T.m + cc * 8);
+      r.v = ld8_nt(T.v + cc * 8);
+    };
+    if (c < end) load(c, cur);
+    if (c + bd < end) load(c + bd, nx1);
+    for (; c < end; c += bd) {
+      if (c + 2 * bd < end) load(c + 2 * bd, nx2);
+      uint32_t w[3][4];
+      sr_draw(k, rs, c, w);
+      float p[8], g[8], m[8], v[8];
+      unpack8(cur.p, p); unpack8(cur.g, g); unpack8(cur.m, m); unpack8(cur.v, v);
+      sr_chunk<CLIP>(p, g, m, v, s, coef);
+      st8_nt(T.p + c * 8, sr_pack8(p, w[SR_PARAM]));
+      st8_nt(T.m + c * 8, sr_pack8(m, w[SR_EXP_AVG]));
+      st8_nt(T.v + c * 8, sr_pack8(v, w[SR_EXP_AVG_SQ]));
+      cur = nx1; nx1 = nx2;
+    }
+    if (to > full && threadIdx.x == 0)   // the ragged last chunk
+      sr_elems<GT, CLIP>(T.p, G, T.m, T.v, full, T.n, rs, s, k, coef);
+  });
+}
+
+// one tensor at any alignment: a thread takes a chunk element by element, the same bits as the list
+template <typename GT, bool CLIP>
+__global__ __launch_bounds__(256) void adamw_sr_scalar_kernel(uint16_t* __restrict__ param, const GT* __restrict__ grad,
+                                                              uint16_t* __restrict__ em, uint16_t* __restrict__ ev,
+                                                              int64_t n, uint32_t rng_stream, AdamScalars s, SrArgs k,
+                                                              ClipArgs<CLIP> clip) {
+  float coef = 1.0f;
+  if constexpr (CLIP) {
+    if (!clip_coef(clip, coef)) return;
+  }
+  const int64_t chunks = (n + 7) >> 3;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i1 = c * 8 + 8 < n ? c * 8 + 8 : n;
+    sr_elems<GT, CLIP>(param, grad, em, ev, c, i1, rng_stream, s, k, coef);
+  }
+}
+
+// the rounding alone: y[i] = sr_bf16(x[i], the draw of element i for output `which`)
+__global__ __launch_bounds__(256) void sr_cast_kernel(const float* __restrict__ x, uint16_t* __restrict__ y, int64_t n,
+                                                      uint32_t rng_stream, uint32_t which, SrArgs k) {
+  const int64_t chunks = (n + 7) >> 3;
+  for (int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * blockDim.x) {
+    uint32_t w[4];
+    philox4x32_10((uint32_t)c, (uint32_t)((uint64_t)c >> 32), k.step, (rng_stream << 2) | which, k.seed_lo, k.seed_hi, w);
+    const int64_t i1 = c * 8 + 8 < n ? c * 8 + 8 : n;
+    for (int64_t i = c * 8; i < i1; ++i) y[i] = (uint16_t)sr_bf16(x[i], sr_pick(w, (int)(i & 7)));
+  }
+}
+
 // ---- sum of squares of the gradients (the global norm) and the in-place scale ---------------
 // Both walk a table the way the step does and touch only its grad field.
 template <typename V>
@@ -630,6 +799,42 @@ int master_single(float* master, void* param, const void* grad, float* m, float*
   return PT_OK;
 }
 
+// the stochastic-rounding step, likewise.  step >= 1; a stream id is below 2^30 (the list's ids sit
+// in the caller's table and are checked where it is built)
+bool sr_stream_ok(int64_t rng_stream) { return rng_stream >= 0 && rng_stream < ((int64_t)1 << 30); }
+template <bool CLIP>
+int sr_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks, int grad_dtype,
+             const AdamScalars& s, const SrArgs& k, const ClipArgs<CLIP>& clip, hipStream_t stream) {
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !dtype_ok(grad_dtype) || k.step == 0 || !clip_ok(clip))
+    return PT_EINVAL;
+  if (total_chunks == 0) return PT_OK;
+  const MultiGrid g = multi_grid(total_chunks);
+  const auto* ts = (const AdamSrTensor*)tensors;
+  if (grad_dtype == 0)
+    adamw_sr_multi_kernel<uint16_t, CLIP><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, s, k, clip);
+  else
+    adamw_sr_multi_kernel<float, CLIP><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, s, k, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+template <bool CLIP>
+int sr_single(void* param, const void* grad, void* m, void* v, int64_t n, int grad_dtype, const AdamScalars& s,
+              const SrArgs& k, int64_t rng_stream, const ClipArgs<CLIP>& clip, hipStream_t stream) {
+  if (!param || !grad || !m || !v || n < 0 || !dtype_ok(grad_dtype) || k.step == 0 || !sr_stream_ok(rng_stream) ||
+      !clip_ok(clip))
+    return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  const int grid = grid_for((n + 7) / 8);
+  if (grad_dtype == 0)
+    adamw_sr_scalar_kernel<uint16_t, CLIP><<<grid, 256, 0, stream>>>((uint16_t*)param, (const uint16_t*)grad, (uint16_t*)m,
+                                                                     (uint16_t*)v, n, (uint32_t)rng_stream, s, k, clip);
+  else
+    adamw_sr_scalar_kernel<float, CLIP><<<grid, 256, 0, stream>>>((uint16_t*)param, (const float*)grad, (uint16_t*)m,
+                                                                  (uint16_t*)v, n, (uint32_t)rng_stream, s, k, clip);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
 // The sum of squares' two launches: `partials` puts one f32 per workgroup into workspace[0, blocks),
 // then one workgroup sums them in a fixed order.  blocks == 0 (nothing to sum): no partials launch,
 // and the final kernel still writes or keeps sq according to `accumulate`.
@@ -717,6 +922,53 @@ int pt_adamw_master_step_clip(float* master, void* param, const void* grad, floa
                              ClipArgs<true>{grad_sq, max_norm, status}, stream);
 }
 
+// bf16 state with stochastic rounding.  tensors: device array of ntensors pt_adam_sr_tensor (every
+// pointer 16-byte aligned, the gradients of one dtype: grad_dtype 0 bf16 / 1 f32).
+int pt_adamw_sr_step_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                           int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                           float step_size, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, hipStream_t stream) {
+  return sr_multi<false>(tensors, chunk_start, ntensors, total_chunks, grad_dtype,
+                         AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, SrArgs{seed_lo, seed_hi, step}, {},
+                         stream);
+}
+
+int pt_adamw_sr_step_multi_clip(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                                int grad_dtype, float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps,
+                                float step_size, uint32_t seed_lo, uint32_t seed_hi, uint32_t step, const float* grad_sq,
+                                float max_norm, int* status, hipStream_t stream) {
+  return sr_multi<true>(tensors, chunk_start, ntensors, total_chunks, grad_dtype,
+                        AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, SrArgs{seed_lo, seed_hi, step},
+                        ClipArgs<true>{grad_sq, max_norm, status}, stream);
+}
+
+int pt_adamw_sr_step(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int grad_dtype,
+                     float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                     uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int64_t rng_stream, hipStream_t stream) {
+  return sr_single<false>(param, grad, exp_avg, exp_avg_sq, n, grad_dtype,
+                          AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, SrArgs{seed_lo, seed_hi, step},
+                          rng_stream, {}, stream);
+}
+
+int pt_adamw_sr_step_clip(void* param, const void* grad, void* exp_avg, void* exp_avg_sq, int64_t n, int grad_dtype,
+                          float decay, float w1, float beta2, float c2, float bc2_sqrt, float eps, float step_size,
+                          uint32_t seed_lo, uint32_t seed_hi, uint32_t step, int64_t rng_stream, const float* grad_sq,
+                          float max_norm, int* status, hipStream_t stream) {
+  return sr_single<true>(param, grad, exp_avg, exp_avg_sq, n, grad_dtype,
+                         AdamScalars{decay, w1, beta2, c2, bc2_sqrt, eps, step_size}, SrArgs{seed_lo, seed_hi, step},
+                         rng_stream, ClipArgs<true>{grad_sq, max_norm, status}, stream);
+}
+
+// y = sr_bf16(x) with the draws of (seed, rng_stream, step, which): the rounding on its own, any alignment
+int pt_sr_cast_bf16(const float* x, void* y, int64_t n, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
+                    int64_t rng_stream, int which, hipStream_t stream) {
+  if (!x || !y || n < 0 || step == 0 || !sr_stream_ok(rng_stream) || which < 0 || which > 2) return PT_EINVAL;
+  if (n == 0) return PT_OK;
+  sr_cast_kernel<<<grid_for((n + 7) / 8), 256, 0, stream>>>(x, (uint16_t*)y, n, (uint32_t)rng_stream, (uint32_t)which,
+                                                            SrArgs{seed_lo, seed_hi, step});
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
 // global gradient-norm clipping: the sum of squares ...
 int pt_grad_sq_workspace(void) { return PT_GRAD_SQ_BLOCKS; }
 
@@ -742,6 +994,20 @@ int pt_grad_sq_master_multi(const void* tensors, const int64_t* chunk_start, int
       grad_sq_list_kernel<AdamMasterTensor, uint16_t><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
     else
       grad_sq_list_kernel<AdamMasterTensor, float><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
+  }, weight, accumulate, workspace, sq, stream);
+}
+
+int pt_grad_sq_sr_multi(const void* tensors, const int64_t* chunk_start, int ntensors, int64_t total_chunks,
+                        int grad_dtype, float weight, int accumulate, float* workspace, float* sq, hipStream_t stream) {
+  if (!list_ok(tensors, chunk_start, ntensors, total_chunks) || !workspace || !sq || !dtype_ok(grad_dtype))
+    return PT_EINVAL;
+  const MultiGrid g = multi_grid(total_chunks, PT_GRAD_SQ_BLOCKS);
+  const auto* ts = (const AdamSrTensor*)tensors;
+  return grad_sq_sum(total_chunks ? g.blocks : 0, [&] {
+    if (grad_dtype == 0)
+      grad_sq_list_kernel<AdamSrTensor, uint16_t><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
+    else
+      grad_sq_list_kernel<AdamSrTensor, float><<<g.blocks, 256, 0, stream>>>(ts, chunk_start, ntensors, g.per_block, workspace);
   }, weight, accumulate, workspace, sq, stream);
 }
 

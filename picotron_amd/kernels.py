@@ -232,11 +232,11 @@ class _clip_status:
             _status_posted(self.device)
 
 
-def _adam_launch(name, dev, lead, scalars=(), clip=None):
-    """Entry `name`(*lead, *scalars as f32, stream) on dev's current stream, its return code checked.
-    clip = (sq, max_norm, status): a clip consumer -- sq is validated, the entry runs under
+def _adam_launch(name, dev, lead, scalars=(), clip=None, ints=()):
+    """Entry `name`(*lead, *scalars as f32, *ints, stream) on dev's current stream, its return code
+    checked.  clip = (sq, max_norm, status): a clip consumer -- sq is validated, the entry runs under
     _clip_status and takes (sq, max_norm, status word) in front of the stream."""
-    sc = [float(x) for x in scalars]
+    sc = [float(x) for x in scalars] + [int(x) for x in ints]
     if clip is None:
         _C.check(getattr(_C.lib(), name)(*lead, *sc, _C.stream_ptr(dev)), name)
         return
@@ -272,20 +272,31 @@ def adamw_step_clip(p, grad, exp_avg, exp_avg_sq, sq, max_norm, decay, w1, beta2
 _ADAM_DESC = {}
 
 
+def _is_sr(items):
+    """A stochastic-rounding list: (param, grad, exp_avg, exp_avg_sq, stream id) tuples."""
+    return len(items[0]) == 5 and not torch.is_tensor(items[0][4])
+
+
 def _adam_desc(items):
     """(device descriptor table, device chunk_start, total chunks) of a list of tensor tuples:
-    4-tuples make the pt_adam_tensor table, 5-tuples the pt_adam_master_tensor table.  Cached per
-    pointer set: the tensors of a model stay put across steps, a re-allocated gradient makes a new
-    table.  A new table is staged in pinned host memory and copied on the current stream without a
-    host sync (the caching host allocator keeps the staging buffer alive until that copy has run)."""
-    key = tuple(tuple(t.data_ptr() for t in it) + (it[0].numel(),) for it in items)
+    4-tuples make the pt_adam_tensor table, 5-tuples the pt_adam_master_tensor table, (param, grad,
+    exp_avg, exp_avg_sq, stream id) the pt_adam_sr_tensor table with the id in the row and in the
+    key.  Cached per pointer set: the tensors of a model stay put across steps, a re-allocated
+    gradient makes a new table.  A new table is staged in pinned host memory and copied on the
+    current stream without a host sync (the caching host allocator keeps the staging buffer alive
+    until that copy has run)."""
+    if _is_sr(items):
+        rows = tuple(tuple(t.data_ptr() for t in it[:4]) + (it[0].numel(), int(it[4])) for it in items)
+        key = ("sr",) + rows
+    else:
+        key = rows = tuple(tuple(t.data_ptr() for t in it) + (it[0].numel(),) for it in items)
     ent = _ADAM_DESC.get(key)
     if ent is None:
         dev = items[0][0].device
         chunks = [0]
-        for k in key:
-            chunks.append(chunks[-1] + (k[-1] + 7) // 8)
-        desc_h = torch.tensor([list(k) for k in key], dtype=torch.int64).pin_memory()
+        for it in items:
+            chunks.append(chunks[-1] + (it[0].numel() + 7) // 8)
+        desc_h = torch.tensor([list(k) for k in rows], dtype=torch.int64).pin_memory()
         chunk_h = torch.tensor(chunks, dtype=torch.int64).pin_memory()
         ent = (desc_h.to(dev, non_blocking=True), chunk_h.to(dev, non_blocking=True), chunks[-1])
         if len(_ADAM_DESC) > 64:
@@ -383,6 +394,102 @@ def adamw_master_step_clip(master, p, grad, exp_avg, exp_avg_sq, sq, max_norm, d
                  (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status))
 
 
+# ---------------------------------------------- AdamW, bf16 state with stochastic rounding
+SR_STREAMS = 1 << 30   # stream ids are below this
+SR_PARAM, SR_EXP_AVG, SR_EXP_AVG_SQ = 0, 1, 2   # `which` of the three stores
+
+
+def _sr_key(seed, step):
+    """(seed_lo, seed_hi, step) as the entries take them: a 64-bit seed, a step count t >= 1."""
+    _req(int(seed) == seed and 0 <= int(seed) < 1 << 64, "stochastic rounding: the seed is an unsigned 64-bit integer")
+    _req(int(step) == step and 1 <= int(step) < 1 << 32, "stochastic rounding: the step count is an integer >= 1")
+    seed = int(seed)
+    return seed & 0xFFFFFFFF, seed >> 32, int(step)
+
+
+def _sr_stream_ok(stream):
+    _req(isinstance(stream, int) and 0 <= stream < SR_STREAMS, "stochastic rounding: a stream id in [0, 2^30)")
+    return stream
+
+
+def _adam_sr_ok(p, g, m, v, what):
+    """One (param, grad, exp_avg, exp_avg_sq) entry; returns the gradient's dtype code."""
+    _req(p.dtype == m.dtype == v.dtype == BF16, f"{what}: bf16 param, exp_avg and exp_avg_sq")
+    _req(g.dtype in (BF16, torch.float32), f"{what}: bf16 or f32 gradients")
+    for t in (p, g, m, v):
+        _req(t.is_cuda and t.device == p.device and t.is_contiguous() and t.numel() == p.numel(),
+             f"{what}: contiguous device tensors of one length per parameter")
+    return 0 if g.dtype == BF16 else 1
+
+
+def _adam_sr_items_ok(items):
+    _req(len(items) > 0, "adamw sr multi: an empty tensor list")
+    gdt = None
+    for it in items:
+        _req(len(it) == 5, "adamw sr multi: (param, grad, exp_avg, exp_avg_sq, stream id) tuples")
+        d = _adam_sr_ok(*it[:4], "adamw sr multi")
+        _req(gdt in (None, d), "adamw sr multi: the gradients of one launch share a dtype")
+        gdt = d
+        _req(all(t.data_ptr() % 16 == 0 for t in it[:4]), "adamw sr multi: 16-byte aligned tensors")
+        _sr_stream_ok(it[4])
+    return gdt
+
+
+def adamw_sr_step_multi(items, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, seed, step):
+    """One launch of the AdamW update in bf16 state with stochastic rounding over a list of (param
+    bf16, grad bf16 | f32, exp_avg bf16, exp_avg_sq bf16, stream id) tuples (pt_adamw_sr_step_multi):
+    adamw_master_step's f32 sequence on the widened values, the three results stored with sr_bf16
+    on the Philox bits of (seed, stream id, step, element index, which output) -- see
+    include/picotron_hip.h.  The gradients of one list share a dtype; the table is cached as
+    adamw_step_multi's, stream ids included."""
+    gdt = _adam_sr_items_ok(items)
+    _adam_launch("pt_adamw_sr_step_multi", items[0][0].device, _adam_list(items, gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), ints=_sr_key(seed, step))
+
+
+def adamw_sr_step_multi_clip(items, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, seed, step,
+                             status=None):
+    """adamw_sr_step_multi on float(grad) * coef, coef as in grad_scale_multi: one f32 product, not
+    rounded to bf16; the gradients are not modified.  A non-finite sq skips the update."""
+    gdt = _adam_sr_items_ok(items)
+    _adam_launch("pt_adamw_sr_step_multi_clip", items[0][0].device, _adam_list(items, gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status), ints=_sr_key(seed, step))
+
+
+def adamw_sr_step(p, grad, exp_avg, exp_avg_sq, stream, decay, w1, beta2, c2, bc2_sqrt, eps, step_size, seed, step):
+    """adamw_sr_step_multi for one parameter at any alignment: the same bits."""
+    gdt = _adam_sr_ok(p, grad, exp_avg, exp_avg_sq, "adamw sr")
+    _adam_launch("pt_adamw_sr_step", p.device, (_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), ints=_sr_key(seed, step) + (_sr_stream_ok(stream),))
+
+
+def adamw_sr_step_clip(p, grad, exp_avg, exp_avg_sq, stream, sq, max_norm, decay, w1, beta2, c2, bc2_sqrt, eps,
+                       step_size, seed, step, status=None):
+    """adamw_sr_step on the clipped gradient."""
+    gdt = _adam_sr_ok(p, grad, exp_avg, exp_avg_sq, "adamw sr")
+    _adam_launch("pt_adamw_sr_step_clip", p.device, (_ptr(p), _ptr(grad), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), gdt),
+                 (decay, w1, beta2, c2, bc2_sqrt, eps, step_size), (sq, max_norm, status),
+                 ints=_sr_key(seed, step) + (_sr_stream_ok(stream),))
+
+
+def sr_cast_bf16(x, seed, step, stream, which, out=None):
+    """bf16 of an f32 tensor by stochastic rounding alone (pt_sr_cast_bf16): element i of the flattened
+    x is rounded with the draw the AdamW step gives element i of output `which` (SR_PARAM, SR_EXP_AVG,
+    SR_EXP_AVG_SQ) of the parameter with this stream id at this step.  E[out] = x; a bf16 value
+    comes out unchanged; inf and NaN take the plain cast."""
+    _req(x.is_cuda and x.dtype == torch.float32 and x.is_contiguous(), "sr_cast_bf16: a contiguous f32 device tensor")
+    _req(which in (SR_PARAM, SR_EXP_AVG, SR_EXP_AVG_SQ), "sr_cast_bf16: which is 0, 1 or 2")
+    if out is None:
+        out = torch.empty(x.shape, dtype=BF16, device=x.device)
+    _req(out.dtype == BF16 and out.is_contiguous() and out.numel() == x.numel() and out.device == x.device,
+         "sr_cast_bf16: a contiguous bf16 output of x's length")
+    key = _sr_key(seed, step)
+    if x.numel():   # an empty tensor has no address to hand to the entry's argument check
+        _C.check(_C.lib().pt_sr_cast_bf16(_ptr(x), _ptr(out), x.numel(), *key, _sr_stream_ok(stream), int(which),
+                                          _C.stream_ptr(x.device)), "pt_sr_cast_bf16")
+    return out
+
+
 # -------------------------------------------------------------- global gradient-norm clipping
 _GRAD_WS = {}   # device index -> f32 workspace of the norm pass (one partial per workgroup)
 
@@ -401,7 +508,8 @@ def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
     partials, then one workgroup sums them in a fixed order).  items: bf16 (param, grad, exp_avg,
     exp_avg_sq) tuples as adamw_step_multi takes them -- one launch over the list on the SAME cached
     table, of which only the grad field is read (gradients alone: (g, g, g, g)), or the (master, param,
-    grad, exp_avg, exp_avg_sq) tuples of adamw_master_step_multi, bf16 or f32 gradients; tensors: single
+    grad, exp_avg, exp_avg_sq) tuples of adamw_master_step_multi or the (param, grad, exp_avg, exp_avg_sq,
+    stream id) tuples of adamw_sr_step_multi, bf16 or f32 gradients; tensors: single
     gradients of what the list form does not take (f32, unaligned bf16).  Everything accumulates
     into the one device scalar in stream order; returns it (a [1] f32 tensor)."""
     items, tensors = list(items), list(tensors)
@@ -413,7 +521,9 @@ def grad_sqnorm(items=(), tensors=(), out=None, accumulate=False, weight=1.0):
     _sq_ok(out, dev)
     ws, acc = _grad_ws(dev), bool(accumulate)
     if items:
-        if len(items[0]) == 5:   # the master-weight list: its entry takes the gradients' dtype as well
+        if _is_sr(items):
+            name, extra = "pt_grad_sq_sr_multi", (_adam_sr_items_ok(items),)
+        elif len(items[0]) == 5:   # the master-weight list: its entry takes the gradients' dtype as well
             name, extra = "pt_grad_sq_master_multi", (_adam_master_items_ok(items),)
         else:
             _adam_items_ok(items)

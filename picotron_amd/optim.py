@@ -13,6 +13,10 @@ parallel ranks too -- in f32 on the device, and nothing of it is read on the hos
 
 AdamW(..., master_weights=True) is the mixed-precision recipe on top (opt-in; not torch's layout): an
 f32 `master_param` and f32 moments in the state of every bf16 parameter, one multi-tensor launch.
+
+AdamW(..., stochastic_rounding=True) is the recipe in between (opt-in; torch's layout): bf16 state, the
+update in f32 registers, and the three stores rounded up or down with probability equal to the
+discarded fraction, on counter-based random bits that a resumed run reproduces.
 """
 import itertools
 
@@ -107,31 +111,59 @@ class AdamW(torch.optim.Optimizer):
     Gradients may be bf16 or f32; with max_grad_norm the coefficient multiplies the f32 gradient.
     f32 parameters take the ordinary f32 path.  use_main_grad=True (needs master_weights): a
     parameter with a `main_grad` attribute (DataParallelBucket's f32 accumulator, with
-    publish_grad=False the only gradient) is stepped on that tensor and its p.grad is ignored."""
+    publish_grad=False the only gradient) is stepped on that tensor and its p.grad is ignored.
+
+    stochastic_rounding=True (opt-in; one or the other, not with master_weights): the state is the
+    plain recipe's -- exp_avg / exp_avg_sq in bf16, 6 B per parameter, and a plain-bf16 checkpoint
+    loads into such an optimizer and the other way round -- but a bf16 parameter's update is the
+    master step's f32 sequence on the widened values, and param, exp_avg and exp_avg_sq are each
+    stored with stochastic rounding: E[stored] = the f32 value, so updates below half an ulp
+    accumulate in expectation and exp_avg_sq * 0.999 no longer sticks.  Gradients may be bf16 or f32
+    (use_main_grad is allowed: an f32 main_grad is consumed as it is); with max_grad_norm the
+    coefficient multiplies the f32 gradient.  f32 parameters take the ordinary f32 path.  The random
+    bits are Philox4x32-10 on (sr_seed, the parameter's stream id, its step count, the element's
+    index, which of the three outputs) and nothing else: sr_seed lives in the param groups, so
+    state_dict() carries it, and a parameter's stream id is its position in the flattened
+    param_groups (the number state_dict() gives it), so a run resumed from a checkpoint reproduces
+    an unbroken one bit for bit.  A non-contiguous parameter is indexed in its logical (row-major)
+    order.  dp, cp and tp ranks compute identical bits for replicated parameters; the tp shards of
+    one parameter draw from the same stream on every rank, which correlates their rounding noise
+    and biases nothing."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, amsgrad=False,
-                 maximize=False, max_grad_norm=None, master_weights=False, use_main_grad=False):
+                 maximize=False, max_grad_norm=None, master_weights=False, use_main_grad=False,
+                 stochastic_rounding=False, sr_seed=0):
         if amsgrad or maximize:
             raise ValueError("picotron_amd.optim.AdamW: amsgrad / maximize are not used by picotron (train.py:209)")
         if not 0.0 <= lr or not 0.0 <= eps or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"invalid AdamW hyper-parameters lr={lr} betas={betas} eps={eps}")
         if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
             raise ValueError(f"invalid AdamW max_grad_norm={max_grad_norm}: a positive number or None")
-        if use_main_grad and not master_weights:
-            raise ValueError("AdamW(use_main_grad=True) needs master_weights=True: the bf16-state step takes the "
-                             "gradient in the parameter's dtype, p.grad")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+        if stochastic_rounding and master_weights:
+            raise ValueError("AdamW: stochastic_rounding=True or master_weights=True, one or the other: the masters "
+                             "already keep what the rounding would")
+        if use_main_grad and not (master_weights or stochastic_rounding):
+            raise ValueError("AdamW(use_main_grad=True) needs master_weights=True or stochastic_rounding=True: the "
+                             "plain bf16-state step takes the gradient in the parameter's dtype, p.grad")
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        if stochastic_rounding:
+            if int(sr_seed) != sr_seed or not 0 <= int(sr_seed) < 1 << 64:
+                raise ValueError(f"invalid AdamW sr_seed={sr_seed}: an unsigned 64-bit integer")
+            defaults["sr_seed"] = int(sr_seed)   # in the param groups: state_dict() carries it
+        super().__init__(params, defaults)
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.last_grad_norm = None
         self.master_weights = bool(master_weights)
         self.use_main_grad = bool(use_main_grad)
+        self.stochastic_rounding = bool(stochastic_rounding)
+        self.sr_seed = int(sr_seed)   # for a group loaded from a checkpoint that has none
 
     @torch.no_grad()
     def step(self, closure=None):
         """torch.optim.AdamW.step (foreach, decoupled weight decay) on the HIP kernel: the bf16 tensors
         that share a step count go through ONE multi-tensor launch; anything else (f32, unaligned)
         per tensor.  master_weights: the bf16 tensors that share a step count and a gradient dtype
-        go through one master-weight launch."""
+        go through one master-weight launch; stochastic_rounding: likewise, one launch of its own."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -155,10 +187,18 @@ class AdamW(torch.optim.Optimizer):
         """[(kernel scalars, kind, items)] of one param group; counts the step.  kind MULTI / SINGLE:
         items are (param, grad, exp_avg, exp_avg_sq), one list launch / one launch each.
         MASTER_MULTI / MASTER_SINGLE (master_weights, bf16 parameters): items are (master_param,
-        param, grad, exp_avg, exp_avg_sq); a batch shares the step count and the gradient dtype."""
+        param, grad, exp_avg, exp_avg_sq); a batch shares the step count and the gradient dtype.
+        SR_MULTI / SR_SINGLE (stochastic_rounding, bf16 parameters): items are (param, grad, exp_avg,
+        exp_avg_sq, stream id), batched likewise; their scalars carry `seed` and `step` as well."""
         lr, (beta1, beta2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
         batches = {}
-        for p in group["params"]:
+        first = 0   # the group's first position in the flattened param_groups
+        if self.stochastic_rounding:
+            for g in self.param_groups:
+                if g is group:
+                    break
+                first += len(g["params"])
+        for pos, p in enumerate(group["params"]):
             grad = self._grad(p)
             if grad is None:
                 continue
@@ -182,6 +222,10 @@ class AdamW(torch.optim.Optimizer):
                 item = (st["master_param"], p, grad, st["exp_avg"], st["exp_avg_sq"])
                 kind = MASTER_MULTI if _listable(*item) else MASTER_SINGLE
                 batches.setdefault((t, kind, grad.dtype), []).append(item)
+            elif self.stochastic_rounding and p.dtype == torch.bfloat16:
+                item = (p, grad, st["exp_avg"], st["exp_avg_sq"])
+                kind = SR_MULTI if _listable(*item) else SR_SINGLE
+                batches.setdefault((t, kind, grad.dtype), []).append(item + (first + pos,))
             else:
                 item = (p, grad, st["exp_avg"], st["exp_avg_sq"])
                 multi = p.dtype == grad.dtype == torch.bfloat16 and _listable(*item)
@@ -192,6 +236,8 @@ class AdamW(torch.optim.Optimizer):
             bc2 = 1 - beta2 ** t
             sc = dict(decay=1 - lr * wd, w1=1 - beta1, beta2=beta2, c2=1 - beta2, bc2_sqrt=bc2 ** 0.5, eps=eps,
                       step_size=(lr / bc1) * -1)
+            if kind in (SR_MULTI, SR_SINGLE):
+                sc.update(seed=group.get("sr_seed", self.sr_seed), step=int(t))
             out.append((sc, kind, items))
         return out
 
@@ -202,9 +248,9 @@ class AdamW(torch.optim.Optimizer):
             _, is_list, ip, ig = _KINDS[kind]
             if is_list:
                 norm_batches.append((True, [(it[ip], it) for it in items]))
-            else:   # the gradient as the step will take it (_master_single)
-                norm_batches.append((False, [(it[ip], it[ig].contiguous() if kind == MASTER_SINGLE else it[ig])
-                                             for it in items]))
+            else:   # the gradient as the step will take it (_master_single, _sr_single)
+                dense = kind in (MASTER_SINGLE, SR_SINGLE)
+                norm_batches.append((False, [(it[ip], it[ig].contiguous() if dense else it[ig]) for it in items]))
         sq = _global_sq(norm_batches)
         if sq is None:   # no gradients at all
             return
@@ -227,7 +273,9 @@ class AdamW(torch.optim.Optimizer):
         parameter's dtype -- with master_weights the f32 `master_param`, `exp_avg` and `exp_avg_sq`
         of a bf16 parameter are put back from the saved dict afterwards, bit for bit.  A bf16-state
         dict (master_weights=False) loads into master_weights=True: the moments are widened and the
-        masters are taken from the parameters at the next step.  The other direction is refused."""
+        masters are taken from the parameters at the next step.  The other direction is refused.
+        stochastic_rounding keeps the plain recipe's bf16 state: it loads a plain checkpoint and a
+        plain optimizer loads its, and f32 master state is refused as without it."""
         saved = list(itertools.chain.from_iterable(g["params"] for g in state_dict["param_groups"]))
         mine = list(itertools.chain.from_iterable(g["params"] for g in self.param_groups))
         pairs = [(state_dict["state"][k], p) for k, p in zip(saved, mine) if k in state_dict["state"]]
@@ -240,13 +288,13 @@ class AdamW(torch.optim.Optimizer):
                                      "master_weights=False and would round them to bf16 -- construct it with "
                                      "master_weights=True")
         super().load_state_dict(state_dict)
-        if self.master_weights:
+        if self.master_weights or self.stochastic_rounding:
             for s, p in pairs:
                 if torch.is_tensor(self.state[p].get("step")):
                     # torch hands the saved `step` tensor through as it is; a live optimizer's
                     # state_dict() loaded here would share (and double-count) it
                     self.state[p]["step"] = self.state[p]["step"].clone()
-                if p.dtype != torch.bfloat16:
+                if not self.master_weights or p.dtype != torch.bfloat16:
                     continue
                 for k in ("master_param", "exp_avg", "exp_avg_sq"):
                     if torch.is_tensor(s.get(k)):
@@ -254,9 +302,11 @@ class AdamW(torch.optim.Optimizer):
 
 
 MULTI, SINGLE, MASTER_MULTI, MASTER_SINGLE = "multi", "single", "master_multi", "master_single"
+SR_MULTI, SR_SINGLE = "sr_multi", "sr_single"
 # kind -> (kernels.* step function, + "_clip" for the clipped one; list launch?; index of param, of grad in an item)
 _KINDS = {MULTI: ("adamw_step_multi", True, 0, 1), SINGLE: ("adamw_step", False, 0, 1),
-          MASTER_MULTI: ("adamw_master_step_multi", True, 1, 2), MASTER_SINGLE: ("adamw_master_step", False, 1, 2)}
+          MASTER_MULTI: ("adamw_master_step_multi", True, 1, 2), MASTER_SINGLE: ("adamw_master_step", False, 1, 2),
+          SR_MULTI: ("adamw_sr_step_multi", True, 0, 1), SR_SINGLE: ("adamw_sr_step", False, 0, 1)}
 
 
 def _launch(kind, items, sc, clip=None):
@@ -269,6 +319,8 @@ def _launch(kind, items, sc, clip=None):
     for it in items:
         if kind == MASTER_SINGLE:
             _master_single(fn, it, *args, **kw)
+        elif kind == SR_SINGLE:
+            _sr_single(fn, it, *args, **kw)
         else:
             fn(*it, *args, **kw)
 
@@ -283,6 +335,18 @@ def _master_single(fn, item, *args, **kw):
         dense = p.detach().contiguous()   # the current weights: a skipped (non-finite) step leaves them
         fn(w, dense, g.contiguous(), m, v, *args, **kw)
         p.copy_(dense)
+
+
+def _sr_single(fn, item, *args, **kw):
+    """One stochastic-rounding entry the list launch does not take: an unaligned view goes to the
+    single-tensor kernel as it is; a non-contiguous parameter, moment or gradient through a dense
+    copy (the element index of the random bits is the logical, row-major one)."""
+    p, g, m, v, stream = item
+    dense = [t if t.is_contiguous() else t.detach().contiguous() for t in (p, m, v)]
+    fn(dense[0], g.contiguous(), dense[1], dense[2], stream, *args, **kw)
+    for t, d in zip((p, m, v), dense):
+        if d is not t:   # the current values: a skipped (non-finite) step left them
+            t.copy_(d)
 
 
 @torch.no_grad()

@@ -7,8 +7,10 @@ AdamW's 8 : 6 mix; --clip: global gradient-norm clipping -- (a) the plain step, 
 (rate on 2 B per parameter, beside torch's x.sum() over the same bytes), (c) norm pass + clipped step,
 (c') the clipped step alone, (d) torch.nn.utils.clip_grad_norm_(foreach=True) + (a), alternating over three rounds in one call;
 --master: fp32 master weights -- (a), the master step on bf16 / f32 gradients (28 / 30 B per parameter), the f32
-norm pass, and torch's fused f32 AdamW + a copy into the bf16 weights, alternating over three rounds in one call.
-python tools/adamw_bench.py [--old lib.so] [--calib] [--clip] [--master]"""
+norm pass, and torch's fused f32 AdamW + a copy into the bf16 weights, alternating over three rounds in one call;
+--sr: stochastic rounding in bf16 state -- (a), (m16) the master step on bf16 gradients, and the SR list step on
+bf16 / f32 gradients (14 / 16 B per parameter), clipped and not, alternating over three rounds in one call.
+python tools/adamw_bench.py [--old lib.so] [--calib] [--clip] [--master] [--sr]"""
 import argparse
 import json
 import os
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--calib", action="store_true")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--master", action="store_true")
+    ap.add_argument("--sr", action="store_true")
     a = ap.parse_args()
     H, I, V, L = 2048, 8192, 49152, 15
     shapes = [(V, H)] + [s for _ in range(L) for s in ((H,), (H, H), (H, H), (H, H), (H, H), (I, H), (I, H), (H, I), (H,))] + [(H,)]
@@ -56,6 +59,8 @@ def main():
         clip(items, n, args, libs)
     if a.master:
         master(items, n, args, libs)
+    if a.sr:
+        sr(items, n, args, libs)
 
 
 def use(lib):
@@ -146,6 +151,35 @@ def master(items, n, args, libs):
     rounds("master", variants, n, libs)
     torch.cuda.synchronize()
     print(json.dumps({"master": "status", "value": K.device_status(ps[0].device)}), flush=True)
+
+
+def sr(items, n, args, libs):
+    """Stochastic rounding: (a) the plain bf16 step and (m16) the master step on bf16 gradients, the two recipes it
+    sits between; (sr16) / (sr32) the SR list step on bf16 / f32 gradients (14 / 16 B per parameter, the plain
+    step's traffic; the state is 8 B per parameter smaller than the master recipe's); (sr16c) / (sr32c) the same with
+    the clip coefficient applied to the loaded gradient (the norm pass is timed by --clip and --master)."""
+    ps = [p for p, _, _, _ in items]
+    g16 = [g for _, g, _, _ in items]
+    g32 = [g.float() for g in g16]
+    m16 = list(zip([p.float() for p in ps], ps, g16, [torch.zeros_like(g) for g in g32], [torch.zeros_like(g) for g in g32]))
+    s16 = [(p, g, m, v, i) for i, (p, g, m, v) in enumerate(items)]
+    s32 = [(p, g, m, v, i) for i, ((p, _, m, v), g) in enumerate(zip(items, g32))]
+    dev = ps[0].device
+    sq = K.grad_sqnorm(items=s16)
+    status = K.status_word(dev)
+    key = dict(seed=0x123456789ABCDEF0, step=3)
+    max_norm = 1.0   # the gradients' norm is ~35: clipping is active
+    variants = [("a: adamw_step_multi (bf16 state)", lambda: K.adamw_step_multi(items, *args), 14, True),
+                ("m16: adamw_master_step_multi, bf16 grads", lambda: K.adamw_master_step_multi(m16, *args), 28, True),
+                ("sr16: adamw_sr_step_multi, bf16 grads", lambda: K.adamw_sr_step_multi(s16, *args, **key), 14, True),
+                ("sr32: adamw_sr_step_multi, f32 grads", lambda: K.adamw_sr_step_multi(s32, *args, **key), 16, True),
+                ("sr16c: adamw_sr_step_multi_clip, bf16 grads",
+                 lambda: K.adamw_sr_step_multi_clip(s16, sq, max_norm, *args, status=status, **key), 14, True),
+                ("sr32c: adamw_sr_step_multi_clip, f32 grads",
+                 lambda: K.adamw_sr_step_multi_clip(s32, sq, max_norm, *args, status=status, **key), 16, True)]
+    rounds("sr", variants, n, libs)
+    torch.cuda.synchronize()
+    print(json.dumps({"sr": "status", "value": K.device_status(dev), "grad norm": round(float(sq.sqrt()), 4)}), flush=True)
 
 
 def calib(items, n, args):
