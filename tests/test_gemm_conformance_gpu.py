@@ -15,7 +15,9 @@ split), plus one K = 2048 run per tile.
 What is built (mirrors kTiles / epi_layouts of gemm.hip, pinned by tests/test_gemm_host_cpu.py): the
 plain sinks 0-3 on every layout of tiles 2, 3 and on every layout but (A M-contiguous, B K-contiguous)
 of tiles 12-15; EPI_BF16_RES on the forward layout (A and B K-contiguous) only: 86 combinations, the
-other 34 answer PT_EUNSUPPORTED (test_unbuilt_combinations_are_refused).
+other 34 answer PT_EUNSUPPORTED (test_unbuilt_combinations_are_refused).  The fused epilogues 5-8 (SwiGLU
+forward and backward, RoPE, CE statistics) and the launch forms that exist only for them are held to the
+same kind of reference in tests/test_gemm_epilogue_conformance_gpu.py.
 
 Worst observed |got - ref| / bound (1 = the bound) per family and tile over the dispatch-table test
 (sections a, b), and per form for section f, on an MI355X (each check prints its figure: run with
