@@ -566,6 +566,37 @@ int pt_attn_bwd_band(const void* q, const int64_t* q_str, const void* k, const i
                      int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, const void* rope_cos,
                      const void* rope_sin, int64_t rope_stride, const int32_t* kv_lo, const int32_t* q_hi,
                      hipStream_t stream);
+/* Block bands: the band of one block of a context-parallel schedule (a rank's queries against one
+ * owner's keys), where the block is rectangular and usually not causal.  Key j of the block is
+ * visible to query i of batch row b iff kv_lo[b, i] <= j, and also j <= i when causal = 1 (the
+ * diagonal block; Sq == Sk).  kv_lo: int32 [B, Sq], 0 <= kv_lo <= Sk, non-decreasing in i; Sk = the
+ * row sees no key of this block.  q_hi: int32 [B, Sk], q_hi[b, j] = the first i with kv_lo[b, i] > j,
+ * or Sq; non-decreasing, 0 <= q_hi <= Sq; 0 = no query of this block sees key j.  Both are dense
+ * whatever lse_ld is.
+ * pt_attn_fwd_block_band = pt_attn_fwd plus the bounds (causal 0 / 1, merge 0 / 1, lse_ld);
+ * pt_attn_bwd_block_band = pt_attn_bwd_part plus the bounds (the given delta, grad_f32 0 / 1, parts
+ * 1 / 2 / 3, lse_ld, causal 0 / 1).  Sq % 128 == 0, Sk % 128 == 0 (forward: Sk % 64), D in {64, 128}.
+ *  - Trivial bounds (kv_lo = 0, q_hi = Sq): bit-identical to pt_attn_fwd / pt_attn_bwd_part called with
+ *    the same causal, merge, grad_f32, lse_ld and parts.
+ *  - A query row with no visible key in the block: merge = 1 leaves its accumulator row and its
+ *    running LSE bitwise untouched (also a running LSE of -inf); merge = 0 stores o = 0, lse = -inf;
+ *    the backward (lse: the global, finite one) adds exactly 0 to dQ, dK and dV.  No NaN is formed.
+ *  - A key no query sees (q_hi = 0): dK = dV = 0 (f32 accumulators keep their value).
+ *  - The bounds are trusted but clamped: a wrong bound gives a wrong mask, never a wrong address.
+ *  - A NULL bound is PT_EINVAL; causal with Sq != Sk is PT_EUNSUPPORTED.  A refused call launches
+ *    nothing.
+ * The dK/dV kernel form follows "attn_split" and causal blocks pair under "attn_pair", with identical
+ * bits; the few-head split forms are not used. */
+int pt_attn_fwd_block_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                           const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H,
+                           int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, int causal, int merge,
+                           int64_t lse_ld, const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream);
+int pt_attn_bwd_block_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                           const int64_t* v_str, const void* dout, const int64_t* do_str, const float* lse,
+                           const float* delta, void* dq, const int64_t* dq_str, void* dk, const int64_t* dk_str,
+                           void* dv, const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk,
+                           int64_t D, float scale, int causal, int grad_f32, int64_t lse_ld, int parts,
+                           const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream);
 
 /* ---- measurement variants ------------------------------------------------------------------
  * Not a reference interface: selects between kernel forms with identical results, for A/B runs and

@@ -37,7 +37,11 @@ What differs (MI355X-first):
     owner in ONE batched p2p (C - 1 transfers on C - 1 distinct links at once, overlapped with the
     causal diagonal block), and in the backward sends each visiting shard's fp32 dK|dV partial
     straight back to its owner, which sums them -- one link-time of K|V per pass instead of C - 1
-    sequential ring hops (PICOTRON_RING_MESH=0: the ring, A/B only).
+    sequential ring hops (PICOTRON_RING_MESH=0: the ring, A/B only);
+  * document masks and sliding windows (not in the reference, whose packed rows attend across
+    documents): a CPBand holds the whole row's lower bounds and hands every block of the three
+    schedules its own block band (kernels.attn_block_band), built on each rank from those bounds
+    alone; the [B, H, S, D] API (RingAttentionFunc / ring_attention) stays band-less.
 """
 import math
 import os
@@ -155,24 +159,111 @@ class HipBlocks:
     align = 128   # the kernels tile query / key blocks of 128 rows (a zig-zag half must be a multiple)
 
     @staticmethod
-    def fwd(q, k, v, scale, causal, acc, lse):
-        K.attn_fwd(q, k, v, scale, causal, out=acc, lse=lse, merge=True)
+    def fwd(q, k, v, scale, causal, acc, lse, band=None):
+        K.attn_fwd(q, k, v, scale, causal, out=acc, lse=lse, merge=True, band=band)
 
     @staticmethod
     def delta(do, o):
         return K.attn_delta(do, o)
 
     @staticmethod
-    def bwd(do, q, k, v, o, lse, delta, scale, causal, dq, dk, dv):
-        K.attn_bwd(do, q, k, v, o, lse, scale, causal, dq=dq, dk=dk, dv=dv, grad_f32=True, delta=delta)
+    def bwd(do, q, k, v, o, lse, delta, scale, causal, dq, dk, dv, band=None):
+        K.attn_bwd(do, q, k, v, o, lse, scale, causal, dq=dq, dk=dk, dv=dv, grad_f32=True, delta=delta, band=band)
 
     @staticmethod
-    def bwd_dq(do, q, k, v, lse, delta, scale, causal, dq):
-        K.attn_bwd_part(do, q, k, v, lse, delta, scale, causal, dq=dq)
+    def bwd_dq(do, q, k, v, lse, delta, scale, causal, dq, band=None):
+        K.attn_bwd_part(do, q, k, v, lse, delta, scale, causal, dq=dq, band=band)
 
     @staticmethod
-    def bwd_dkdv(do, q, k, v, lse, delta, scale, causal, dk, dv):
-        K.attn_bwd_part(do, q, k, v, lse, delta, scale, causal, dk=dk, dv=dv)
+    def bwd_dkdv(do, q, k, v, lse, delta, scale, causal, dk, dv, band=None):
+        K.attn_bwd_part(do, q, k, v, lse, delta, scale, causal, dk=dk, dv=dv, band=band)
+
+
+class CPBand:
+    """Document masks and sliding windows under context parallelism: the whole row's lower bounds
+    lo [B, C * S] (lo[b, g] = the first global key token g sees; kernels.attn_band(...).kv_lo) and the
+    position lists of every cp rank -- the contiguous chunk [r S, (r + 1) S), or, zig-zag, half-chunks
+    r and 2C - 1 - r.  block() hands out the kernels.AttnBlockBand of any (query owner and slice, key
+    owner and slice) a schedule runs, built on the device from lo alone (no bound travels, nothing is
+    read back) and cached: the layers of one forward and its backward share them."""
+
+    def __init__(self, lo, rank, world, zigzag):
+        if lo.dim() != 2 or lo.shape[1] % world:
+            raise ValueError(f"CPBand: lo must be [B, cp * S_local] (got {tuple(lo.shape)} for cp = {world})")
+        self.lo, self.rank, self.world, self.zigzag = lo, int(rank), int(world), bool(zigzag)
+        self.S = lo.shape[1] // world
+        if self.zigzag and self.S % 2:
+            raise ValueError("CPBand: a zig-zag shard has two half-chunks (S_local must be even)")
+        self._blocks = {}
+
+    def positions(self, owner):
+        """Global positions of rank `owner`'s S local tokens, in its local order (increasing)."""
+        S, C, dev = self.S, self.world, self.lo.device
+        if not self.zigzag:
+            return torch.arange(owner * S, (owner + 1) * S, device=dev)
+        h = S // 2
+        return torch.cat([torch.arange(c * h, (c + 1) * h, device=dev) for c in (owner, 2 * C - 1 - owner)])
+
+    def block(self, q_owner, q_slice, k_owner, k_slice, causal):
+        """The band of rank q_owner's local queries [q_slice) against rank k_owner's local keys
+        [k_slice); causal: the diagonal block (same owner, same slice)."""
+        key = (q_owner, tuple(q_slice), k_owner, tuple(k_slice), bool(causal))
+        if key not in self._blocks:
+            qpos = self.positions(q_owner)[q_slice[0]:q_slice[1]]
+            kpos = self.positions(k_owner)[k_slice[0]:k_slice[1]]
+            self._blocks[key] = K.attn_block_band(self.lo, qpos, kpos, causal)
+        return self._blocks[key]
+
+
+def make_cp_band(B, S, device, document_ids=None, window=None):
+    """The CPBand of a forward whose ranks each hold S local tokens of B rows: document_ids is this
+    rank's [B, S] chunk (sliced like input_ids; the shards are all-gathered over the cp group, B x C S
+    integers, once) or the full [B, C S] rows (no collective); window: a sliding-window width.  lo is
+    formed on the whole row (kernels.attn_band).  None when neither is given; a ready CPBand is taken
+    as it is."""
+    if isinstance(document_ids, CPBand):
+        return document_ids
+    if document_ids is None and window is None:
+        return None
+    m = pgm.current()
+    C = m.cp_world_size
+    if C == 1 or isinstance(document_ids, K.AttnBand):
+        raise NotImplementedError("document masking / sliding-window attention under context parallelism takes "
+                                  "[B, S] document ids on a cp group of more than one rank (a plain AttnBand "
+                                  "describes one rank's rows only)")
+    ids = document_ids
+    if ids is not None:
+        if ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] not in (S, C * S):
+            raise ValueError(f"document_ids must be this rank's [B, S_local] = [{B}, {S}] chunk or the full "
+                             f"[{B}, {C * S}] rows (got {tuple(ids.shape)})")
+        ids = ids.to(device)
+        if ids.shape[1] == S:
+            ids = ids.contiguous()
+            parts = torch.empty((C,) + tuple(ids.shape), dtype=ids.dtype, device=ids.device)
+            if dist.get_backend(m.cp_group) == "nccl":
+                dist.all_gather_into_tensor(parts, ids, group=m.cp_group)
+            else:   # gloo (CPU tests, one-GPU rehearsals): the list form
+                dist.all_gather(list(parts.unbind(0)), ids, group=m.cp_group)
+            ids = parts.permute(1, 0, 2).reshape(B, C * S)
+    lo = K.attn_band(B, C * S, device, document_ids=ids, window=None if window is None else int(window)).kv_lo
+    return CPBand(lo, m.cp_rank, C, zigzag_enabled(S, True))
+
+
+def _bw(band, q_owner, q_slice, k_owner, k_slice, causal=False):
+    """The trailing band= keyword of one block call ({}: no band, the band-less signature)."""
+    return {} if band is None else {"band": band.block(q_owner, q_slice, k_owner, k_slice, causal)}
+
+
+def _check_band(band, rank, world, S, is_causal, zigzag):
+    if band is None:
+        return
+    if not isinstance(band, CPBand):
+        raise TypeError("ring attention: band must be a CPBand")
+    if not is_causal:
+        raise ValueError("ring attention: a band is a causal mask")
+    if (band.rank, band.world, band.S, band.zigzag) != (rank, world, S, bool(zigzag)):
+        raise ValueError(f"ring attention: the CPBand is for rank {band.rank} of {band.world}, S_local {band.S}, "
+                         f"zigzag {band.zigzag}; the call is rank {rank} of {world}, S_local {S}, zigzag {bool(zigzag)}")
 
 
 def _kv_views(kv, B, S, nkv, d):
@@ -194,15 +285,18 @@ def _zz_kind(step, rank, world):
     return "kv0" if (rank - step) % world < rank else "q1"
 
 
-def ring_forward(q, kv, nkv, scale, is_causal, blocks=HipBlocks, comm=None, zigzag=False):
+def ring_forward(q, kv, nkv, scale, is_causal, blocks=HipBlocks, comm=None, zigzag=False, band=None):
     """RingAttentionFunc.forward (context_parallel.py:19-51) on token-major shards.
     q [B, S, nh, d] (any strides, d contiguous); kv [B*S, 2*nkv*d] contiguous (this rank's K|V).
     zigzag: q / kv are in the zig-zag layout (zigzag_exchange) and the balanced schedule runs.
+    band (a CPBand): document masks / sliding windows; every block runs under its own block band.
     Returns (out_f32 [B, S, nh, d], lse f32 [B, nh, S])."""
     if zigzag and comm is None and SW.ring_mesh != 0:
-        return mesh_forward(q, kv, nkv, scale, blocks)
+        return mesh_forward(q, kv, nkv, scale, blocks, band=band)
     comm = comm or ContextCommunicate("comm")
     B, S, nh, d = q.shape
+    r, W = comm.rank, comm.world_size
+    _check_band(band, r, W, S, is_causal, zigzag)
     acc = torch.zeros(B, S, nh, d, dtype=torch.float32, device=q.device)
     lse = torch.full((B, nh, S), float("-inf"), dtype=torch.float32, device=q.device)
     cur = kv
@@ -214,12 +308,14 @@ def ring_forward(q, kv, nkv, scale, is_causal, blocks=HipBlocks, comm=None, zigz
             comm.commit()
         k, v = _kv_views(cur, B, S, nkv, d)
         if zigzag and step > 0:
-            if _zz_kind(step, comm.rank, comm.world_size) == "kv0":
-                blocks.fwd(q, k[:, :h], v[:, :h], scale, False, acc, lse)
+            j = (r - step) % W
+            if _zz_kind(step, r, W) == "kv0":
+                blocks.fwd(q, k[:, :h], v[:, :h], scale, False, acc, lse, **_bw(band, r, (0, S), j, (0, h)))
             else:
-                blocks.fwd(q[:, h:], k, v, scale, False, acc[:, h:], lse[:, :, h:])
-        elif zigzag or not is_causal or step <= comm.rank:
-            blocks.fwd(q, k, v, scale, is_causal and step == 0, acc, lse)
+                blocks.fwd(q[:, h:], k, v, scale, False, acc[:, h:], lse[:, :, h:], **_bw(band, r, (h, S), j, (0, S)))
+        elif zigzag or not is_causal or step <= r:
+            blocks.fwd(q, k, v, scale, is_causal and step == 0, acc, lse,
+                       **_bw(band, r, (0, S), (r - step) % W, (0, S), is_causal and step == 0))
         if step + 1 != comm.world_size:
             comm.wait()
             cur = nxt
@@ -227,14 +323,15 @@ def ring_forward(q, kv, nkv, scale, is_causal, blocks=HipBlocks, comm=None, zigz
 
 
 def ring_backward(do, q, kv, o, lse, nkv, scale, is_causal, blocks=HipBlocks, kv_comm=None, d_kv_comm=None,
-                  zigzag=False):
+                  zigzag=False, band=None):
     """RingAttentionFunc.backward (context_parallel.py:53-110).  Returns (dq f32 [B,S,nh,d],
     dkv f32 [B*S, 2*nkv*d]) for this rank's own shards (zigzag: all in the zig-zag layout)."""
     if zigzag and kv_comm is None and SW.ring_mesh != 0:
-        return mesh_backward(do, q, kv, o, lse, nkv, scale, blocks)
+        return mesh_backward(do, q, kv, o, lse, nkv, scale, blocks, band=band)
     kv_comm = kv_comm or ContextCommunicate("kv_comm")
     d_kv_comm = d_kv_comm or ContextCommunicate("d_kv_comm")
     B, S, nh, d = q.shape
+    _check_band(band, kv_comm.rank, kv_comm.world_size, S, is_causal, zigzag)
     delta = blocks.delta(do, o)
     dq = torch.zeros(B, S, nh, d, dtype=torch.float32, device=q.device)
     cur = kv
@@ -254,13 +351,16 @@ def ring_backward(do, q, kv, o, lse, nkv, scale, is_causal, blocks=HipBlocks, kv
         dk, dv = _kv_views(dkv, B, S, nkv, d)
         h = S // 2
         if zigzag and step > 0:
+            j = (r - step) % W
             if _zz_kind(step, r, W) == "kv0":
-                blocks.bwd(do, q, k[:, :h], v[:, :h], o, lse, delta, scale, False, dq, dk[:, :h], dv[:, :h])
+                blocks.bwd(do, q, k[:, :h], v[:, :h], o, lse, delta, scale, False, dq, dk[:, :h], dv[:, :h],
+                           **_bw(band, r, (0, S), j, (0, h)))
             else:
                 blocks.bwd(do[:, h:], q[:, h:], k, v, o[:, h:], lse[:, :, h:], delta[:, :, h:], scale, False,
-                           dq[:, h:], dk, dv)
+                           dq[:, h:], dk, dv, **_bw(band, r, (h, S), j, (0, S)))
         elif zigzag or step <= r or not is_causal:
-            blocks.bwd(do, q, k, v, o, lse, delta, scale, is_causal and step == 0, dq, dk, dv)
+            blocks.bwd(do, q, k, v, o, lse, delta, scale, is_causal and step == 0, dq, dk, dv,
+                       **_bw(band, r, (0, S), (r - step) % W, (0, S), is_causal and step == 0))
         if step + 1 != W:
             kv_comm.wait()
             cur = nxt
@@ -302,7 +402,7 @@ def _halves(kv, B, S):
     return kv3[:, :h].contiguous().view(B * h, w2), kv3[:, h:].contiguous().view(B * h, w2)
 
 
-def mesh_forward(q, kv, nkv, scale, blocks=HipBlocks):
+def mesh_forward(q, kv, nkv, scale, blocks=HipBlocks, band=None):
     """The zig-zag causal forward on the mesh: the diagonal block (local causal mask over this
     rank's two half-chunks) runs while the visiting K|V arrive; then each visiting shard j is half a
     block -- j < r: all my queries x its first half ('kv0'), j > r: my second half x all of it
@@ -314,6 +414,7 @@ def mesh_forward(q, kv, nkv, scale, blocks=HipBlocks):
     C, r, ids, group = m.cp_world_size, m.cp_rank, m.cp_group_ids, m.cp_group
     B, S, nh, d = q.shape
     h = S // 2
+    _check_band(band, r, C, S, True, True)
     acc = torch.zeros(B, S, nh, d, dtype=torch.float32, device=q.device)
     lse = torch.full((B, nh, S), float("-inf"), dtype=torch.float32, device=q.device)
     first, second = _halves(kv, B, S)
@@ -324,23 +425,23 @@ def mesh_forward(q, kv, nkv, scale, blocks=HipBlocks):
     ops_b = _mesh_ops([(second, j) for j in peers if j < r], [(s[j], j) for j in s], group, ids)
     pend_b = _p2p(ops_b, group) if ops_b else None
     k, v = _kv_views(kv, B, S, nkv, d)
-    blocks.fwd(q, k, v, scale, True, acc, lse)
+    blocks.fwd(q, k, v, scale, True, acc, lse, **_bw(band, r, (0, S), r, (0, S), True))
     _p2p_wait(pend_a)
     for j in peers:
         k, v = _kv_views(f[j], B, h, nkv, d)
         if j < r:
-            blocks.fwd(q, k, v, scale, False, acc, lse)
+            blocks.fwd(q, k, v, scale, False, acc, lse, **_bw(band, r, (0, S), j, (0, h)))
         else:
-            blocks.fwd(q[:, h:], k, v, scale, False, acc[:, h:], lse[:, :, h:])
+            blocks.fwd(q[:, h:], k, v, scale, False, acc[:, h:], lse[:, :, h:], **_bw(band, r, (h, S), j, (0, h)))
     if pend_b is not None:
         _p2p_wait(pend_b)
     for j in s:
         k, v = _kv_views(s[j], B, h, nkv, d)
-        blocks.fwd(q[:, h:], k, v, scale, False, acc[:, h:], lse[:, :, h:])
+        blocks.fwd(q[:, h:], k, v, scale, False, acc[:, h:], lse[:, :, h:], **_bw(band, r, (h, S), j, (h, S)))
     return acc, lse
 
 
-def mesh_backward(do, q, kv, o, lse, nkv, scale, blocks=HipBlocks):
+def mesh_backward(do, q, kv, o, lse, nkv, scale, blocks=HipBlocks, band=None):
     """The zig-zag causal backward on the mesh, with no gradient partial on the wire: every rank
     fetches, besides the visiting K|V shards (for its own queries' dQ), the visiting ranks' queries,
     dO, LSE and D = rowsum(dO * O) -- 64 MiB + 0.5 MiB per peer at Llama-2-7B CP8, half of an fp32
@@ -355,6 +456,7 @@ def mesh_backward(do, q, kv, o, lse, nkv, scale, blocks=HipBlocks):
     C, r, ids, group = m.cp_world_size, m.cp_rank, m.cp_group_ids, m.cp_group
     B, S, nh, d = q.shape
     h = S // 2
+    _check_band(band, r, C, S, True, True)
     delta = blocks.delta(do, o)
     dq = torch.zeros(B, S, nh, d, dtype=torch.float32, device=q.device)
     dkv = torch.zeros(kv.shape, dtype=torch.float32, device=kv.device)
@@ -373,14 +475,15 @@ def mesh_backward(do, q, kv, o, lse, nkv, scale, blocks=HipBlocks):
                             [(t[j], j) for j in peers for t in (qdos, lds)], group, ids), group)
     k, v = _kv_views(kv, B, S, nkv, d)
     dk, dv = _kv_views(dkv, B, S, nkv, d)
-    blocks.bwd(do, q, k, v, o, lse, delta, scale, True, dq, dk, dv)
+    blocks.bwd(do, q, k, v, o, lse, delta, scale, True, dq, dk, dv, **_bw(band, r, (0, S), r, (0, S), True))
     _p2p_wait(pend_kv)
     for j in peers:
         kj, vj = _kv_views(kvs[j], B, S, nkv, d)
         if j < r:    # my queries x its first half
-            blocks.bwd_dq(do, q, kj[:, :h], vj[:, :h], lse, delta, scale, False, dq)
+            blocks.bwd_dq(do, q, kj[:, :h], vj[:, :h], lse, delta, scale, False, dq, **_bw(band, r, (0, S), j, (0, h)))
         else:        # my second half x all of it
-            blocks.bwd_dq(do[:, h:], q[:, h:], kj, vj, lse[:, :, h:], delta[:, :, h:], scale, False, dq[:, h:])
+            blocks.bwd_dq(do[:, h:], q[:, h:], kj, vj, lse[:, :, h:], delta[:, :, h:], scale, False, dq[:, h:],
+                          **_bw(band, r, (h, S), j, (0, S)))
     kvs = kj = vj = None   # the visiting K|V shards are done with: release them before the dK|dV parts
     _p2p_wait(pend_q)
     for j in peers:
@@ -388,10 +491,11 @@ def mesh_backward(do, q, kv, o, lse, nkv, scale, blocks=HipBlocks):
         qj = qdos[j][:, :, :nh * d].view(B, n, nh, d)
         doj = qdos[j][:, :, nh * d:].view(B, n, nh, d)
         lsej, dj = lds[j][:, :, 0], lds[j][:, :, 1]
-        if j > r:    # all its queries x my first half
-            blocks.bwd_dkdv(doj, qj, k[:, :h], v[:, :h], lsej, dj, scale, False, dk[:, :h], dv[:, :h])
+        if j > r:    # all its queries x my first half (the visiting queries' bounds come from lo, as all do)
+            blocks.bwd_dkdv(doj, qj, k[:, :h], v[:, :h], lsej, dj, scale, False, dk[:, :h], dv[:, :h],
+                            **_bw(band, j, (0, S), r, (0, h)))
         else:        # its second-half queries x all my keys
-            blocks.bwd_dkdv(doj, qj, k, v, lsej, dj, scale, False, dk, dv)
+            blocks.bwd_dkdv(doj, qj, k, v, lsej, dj, scale, False, dk, dv, **_bw(band, j, (h, S), r, (0, S)))
     return dq, dkv
 
 
@@ -402,35 +506,39 @@ def ring_attention_tokens(qkv, sh, scale, is_causal, resident=False):
     apply_context_parallel) and so is o; otherwise, with the zig-zag schedule, q and K|V are re-laid
     here and o re-laid back (the LSE stays in the zig-zag layout: only the ring backward reads it)."""
     B, S, T = sh.B, sh.S, sh.T
+    band = getattr(sh, "band", None)   # a CPBand (AttnShape refuses anything else under the ring)
     if resident:
-        acc, lse = ring_forward(sh.q(qkv), qkv[:, sh.wq:].contiguous(), sh.nkv, scale, is_causal, zigzag=True)
+        acc, lse = ring_forward(sh.q(qkv), qkv[:, sh.wq:].contiguous(), sh.nkv, scale, is_causal, zigzag=True,
+                                band=band)
         return acc.to(torch.bfloat16), lse
     if zigzag_enabled(S, is_causal):
         qz, kvz = zigzag_exchange([sh.q(qkv), qkv[:, sh.wq:].view(B, S, 2 * sh.wkv)], [1, 1], True)
-        acc, lse = ring_forward(qz, kvz.view(T, 2 * sh.wkv), sh.nkv, scale, is_causal, zigzag=True)
+        acc, lse = ring_forward(qz, kvz.view(T, 2 * sh.wkv), sh.nkv, scale, is_causal, zigzag=True, band=band)
         (o,) = zigzag_exchange([acc.to(torch.bfloat16)], [1], False)
         return o, lse
     kv = qkv[:, sh.wq:].contiguous()
-    acc, lse = ring_forward(sh.q(qkv), kv, sh.nkv, scale, is_causal)
+    acc, lse = ring_forward(sh.q(qkv), kv, sh.nkv, scale, is_causal, band=band)
     return acc.to(torch.bfloat16), lse
 
 
 def ring_attention_tokens_bwd(do, qkv, o, lse, sh, scale, is_causal, dqkv, resident=False):
     B, S, T = sh.B, sh.S, sh.T
+    band = getattr(sh, "band", None)
     if resident:
         dq, dkv = ring_backward(do, sh.q(qkv), qkv[:, sh.wq:].contiguous(), o, lse, sh.nkv, scale, is_causal,
-                                zigzag=True)
+                                zigzag=True, band=band)
     elif zigzag_enabled(S, is_causal):
         # the standalone layer (contiguous residual): q / K|V / o / dO re-laid in one exchange
         qz, kvz, oz, doz = zigzag_exchange([sh.q(qkv), qkv[:, sh.wq:].view(B, S, 2 * sh.wkv), o, do],
                                            [1, 1, 1, 1], True)
-        dq, dkv = ring_backward(doz, qz, kvz.view(T, 2 * sh.wkv), oz, lse, sh.nkv, scale, is_causal, zigzag=True)
+        dq, dkv = ring_backward(doz, qz, kvz.view(T, 2 * sh.wkv), oz, lse, sh.nkv, scale, is_causal, zigzag=True,
+                                band=band)
         # rounded to bf16 before the way back (the same single rounding as the copy below)
         dq, dkv = zigzag_exchange([dq.to(torch.bfloat16), dkv.to(torch.bfloat16).view(B, S, 2 * sh.wkv)], [1, 1],
                                   False)
     else:
         kv = qkv[:, sh.wq:].contiguous()
-        dq, dkv = ring_backward(do, sh.q(qkv), kv, o, lse, sh.nkv, scale, is_causal)
+        dq, dkv = ring_backward(do, sh.q(qkv), kv, o, lse, sh.nkv, scale, is_causal, band=band)
     dqkv[:, :sh.wq].copy_(dq.view(T, sh.wq))
     dqkv[:, sh.wq:].copy_(dkv.view(T, 2 * sh.wkv))
 

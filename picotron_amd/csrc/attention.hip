@@ -23,6 +23,14 @@
 // gradients with D = rowsum(dO * O) formed in the dQ kernel, dense lse, no merge; never the few-head
 // split forms.  RoPE-inverse positions are sequence indices (RoPE scores
 // depend on i - j only: per-document positions would give the same attention).
+// Block bands (pt_attn_fwd_block_band / pt_attn_bwd_block_band; the same BAND instantiations): one
+// block of a context-parallel schedule, rectangular and usually not causal.  Key j visible to query
+// i iff kv_lo[b, i] <= j (and j <= i when causal); kv_lo int32 [B, Sq], 0 <= kv_lo <= Sk,
+// non-decreasing, Sk = the row sees no key of this block; q_hi int32 [B, Sk], 0 <= q_hi <= Sq, 0 = no
+// query of this block sees the key.  They take merge, a strided lse, a given delta, f32 gradient
+// accumulation and parts.  A query row without a visible key leaves its merge accumulator and
+// running LSE untouched (merge = 0: o = 0, lse = -inf) and adds 0 to dQ / dK / dV; a query block
+// whose first row has kv_lo = Sk runs no tile.
 //
 // Fragment scheme (all v_mfma_f32_32x32x16_bf16): scores are computed "key on the row",
 // S^T = K . Q^T, so a lane owns one query column and softmax statistics are lane-local (plus one
@@ -385,9 +393,10 @@ constexpr int dq_stages() { return D == 64 ? 4 : 2; }
 // ============================================================================ forward
 // NWK waves per workgroup (32 query rows each): 4, or 8 at d 128 (the K/V tiles staged once for
 // twice the queries; measured 7-8 % faster at S_local 4096, equal at d 64)
-// BAND (causal, no split items): the block's tiles start at the tile of kv_lo of its first row (the
-// block minimum: kv_lo is non-decreasing); a wave skips tiles wholly below the bound of its first row
-// and masks keys below a lane's own bound on tiles that reach under the bound of its last row.
+// BAND (causal, or one block of a context-parallel schedule; no split items): the block's tiles start
+// at the tile of kv_lo of its first row (the block minimum: kv_lo is non-decreasing); a wave skips
+// tiles wholly below the bound of its first row and masks keys below a lane's own bound on tiles that
+// reach under the bound of its last row.
 template <int D, int NWK, bool BAND = false>
 __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_or_hk, int b, int kt_lo = 0,
                                                int kt_hi = -1, int item = -1) {
@@ -409,8 +418,10 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     mylo = lo_row[myq];
     wlo_min = __builtin_amdgcn_readfirstlane(mylo);
     wlo_max = __builtin_amdgcn_readlane(mylo, 31);
-    // the block's first tile (clamped: whatever the bound holds, the tile range stays inside K / V)
-    kt_lo = min(max(lo_row[qb * NWK * 32], 0), qb * NWK * 32) / KT;
+    // the block's first tile (clamped: whatever the bound holds, the tile range stays inside K / V);
+    // a non-causal block whose first row sees nothing (kv_lo = Sk) gets no tile at all: nkt = 0 is
+    // uniform over the workgroup, so every wave still passes the prologue's waits and barriers
+    kt_lo = min(max(lo_row[qb * NWK * 32], 0), a.causal ? qb * NWK * 32 : a.Sk) / KT;
   }
 
   bf16x8_t qf[KS];
@@ -600,7 +611,10 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
     if (lane < 32) a.split_lse[(int64_t)item * (NWK * 32) + row] = l > 0.f ? m * kLn2 + __logf(l) : -INFINITY;
     return;
   }
-  const float inv_l = 1.0f / l;
+  // band: a row that saw no key of this block (l = 0, m = -inf; both lane halves agree after the sum)
+  // stores o = 0, lse = -inf, and under merge leaves its accumulator row and running LSE untouched
+  const bool empty = BAND && !(l > 0.f);
+  const float inv_l = empty ? 0.f : 1.0f / l;
   // (band d64: spelled as the fma this expression is contracted to in the causal d64 kernel -- the
   // d128 kernels keep a multiply and an add -- so a band that masks nothing gives the causal bits)
   const float lse = (BAND && D == 64) ? __builtin_fmaf(m, kLn2, __logf(l)) : m * kLn2 + __logf(l);
@@ -613,24 +627,35 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
   } else {
     // update_out_and_lse: out <- out*exp(lse_old - lse_new) + blk*exp(lse_blk - lse_new)
     float* orow = a.o.row<float>(b, myq, h);
-    const float lold = *lse_p;
+    const float lold = empty ? 0.f : *lse_p;
     const float lnew = fmaxf(lold, lse) + log1pf(__expf(-fabsf(lold - lse)));
     const float wold = lold == -INFINITY ? 0.f : __expf(lold - lnew);
     const float wblk = __expf(lse - lnew) * inv_l;
+    // (band: the sum of two products spelled as the multiply and fma it is contracted to in the
+    // band-less kernels, so that a band that masks nothing gives their bits -- there the product that
+    // is rounded is the block's, except in the d128 kernels' 16-byte chunks 9 .. 15 of a row, where it
+    // is the accumulator's; tests/test_attn_block_band_gpu.py compares the two kernels' bits)
+    auto mrg = [&](float acc, float blk, bool round_acc) {
+      if constexpr (!BAND) return acc * wold + blk * wblk;
+      return round_acc ? __builtin_fmaf(blk, wblk, acc * wold) : __builtin_fmaf(acc, wold, blk * wblk);
+    };
+    if (!empty) {
 #pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
+      for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        const int d = 32 * dt + 8 * g4 + 4 * (lane >> 5);
-        float4 ov = *(float4*)(orow + d);
-        ov.x = ov.x * wold + o[dt][4 * g4 + 0] * wblk;
-        ov.y = ov.y * wold + o[dt][4 * g4 + 1] * wblk;
-        ov.z = ov.z * wold + o[dt][4 * g4 + 2] * wblk;
-        ov.w = ov.w * wold + o[dt][4 * g4 + 3] * wblk;
-        *(float4*)(orow + d) = ov;
-      }
+        for (int g4 = 0; g4 < 4; ++g4) {
+          const int d = 32 * dt + 8 * g4 + 4 * (lane >> 5);
+          const bool ra = D == 128 && 4 * dt + g4 >= 9;
+          float4 ov = *(float4*)(orow + d);
+          ov.x = mrg(ov.x, o[dt][4 * g4 + 0], ra);
+          ov.y = mrg(ov.y, o[dt][4 * g4 + 1], ra);
+          ov.z = mrg(ov.z, o[dt][4 * g4 + 2], ra);
+          ov.w = mrg(ov.w, o[dt][4 * g4 + 3], ra);
+          *(float4*)(orow + d) = ov;
+        }
+    }
     __syncthreads();  // both lane halves have read lse_old before it is overwritten
-    if (lane < 32) *lse_p = lnew;
+    if (lane < 32 && !empty) *lse_p = lnew;
   }
 }
 
@@ -784,9 +809,10 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(View4<const uint16_t> d
 }
 
 // ============================================================================ dK / dV
-// BAND (causal, no split items): a head's q tiles end at the tile of q_hi of the block's last key (the
-// block maximum: q_hi is non-decreasing); every step runs the edge form, which skips half tiles
-// wholly past the wave's greatest q_hi and masks queries at or past a lane's own q_hi.
+// BAND (causal or a block band, no split items): a head's q tiles end at the tile of q_hi of the
+// block's last key (the block maximum: q_hi is non-decreasing; at least one tile, so a block no query
+// sees still has a step to run); every step runs the edge form, which skips half tiles wholly past
+// the wave's greatest q_hi and masks queries at or past a lane's own q_hi.
 template <int D, bool BAND = false>
 __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, int h_or_hk, int b, int it_lo = 0,
                                                     int it_hi = -1, int item = -1) {
@@ -1242,7 +1268,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
     mylo = lo_row[myq];
     wlo_min = __builtin_amdgcn_readfirstlane(mylo);
     wlo_max = __builtin_amdgcn_readlane(mylo, 31);
-    kt_lo = min(max(lo_row[qb * NW * 32], 0), qb * NW * 32) / KT;
+    kt_lo = min(max(lo_row[qb * NW * 32], 0), a.causal ? qb * NW * 32 : a.Sk) / KT;
   }
 
   const uint16_t* qrow = a.q.row(b, myq, h);
@@ -1728,6 +1754,41 @@ int pt_attn_bwd_band(const void* q, const int64_t* q_str, const void* k, const i
             dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, 0, nullptr, o, o_str, delta_out};
   c.rope_cos = rope_cos; c.rope_sin = rope_sin; c.rope_stride = rope_stride;
   c.parts = 3;
+  c.kv_lo = kv_lo; c.q_hi = q_hi;
+  return attn_bwd(c, stream);
+}
+
+// pt_attn_fwd under a block band (one block of a context-parallel schedule; see the header): key j
+// visible to query i of batch row b iff kv_lo[b, i] <= j, and j <= i when causal.  kv_lo int32 [B, Sq]
+// and q_hi int32 [B, Sk], dense whatever lse_ld is.
+int pt_attn_fwd_block_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                           const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H,
+                           int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, int causal, int merge,
+                           int64_t lse_ld, const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream) {
+  if (!q || !k || !v || !o || !lse || !kv_lo || !q_hi) return PT_EINVAL;
+  if (lse_ld != 0 && lse_ld < Sq) return PT_EINVAL;
+  AttnArgs a{};
+  a.lse_ld = lse_ld ? lse_ld : Sq;
+  a.o = view(o, o_str);
+  a.lse = lse;
+  a.merge = merge;
+  a.kv_lo = kv_lo; a.q_hi = q_hi;
+  return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal}, stream);
+}
+
+// pt_attn_bwd_part under a block band: the given delta, bf16 stores or f32 accumulation, parts 1 (dQ),
+// 2 (dK / dV) or 3 (both)
+int pt_attn_bwd_block_band(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                           const int64_t* v_str, const void* dout, const int64_t* do_str, const float* lse,
+                           const float* delta, void* dq, const int64_t* dq_str, void* dk, const int64_t* dk_str,
+                           void* dv, const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk,
+                           int64_t D, float scale, int causal, int grad_f32, int64_t lse_ld, int parts,
+                           const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream) {
+  if (!delta || !kv_lo || !q_hi) return PT_EINVAL;
+  BwdCall c{{q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, causal},
+            dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, lse_ld, delta};
+  c.grad_f32 = grad_f32;
+  c.parts = parts;
   c.kv_lo = kv_lo; c.q_hi = q_hi;
   return attn_bwd(c, stream);
 }

@@ -777,11 +777,14 @@ class AttnShape:
         self.T = B * S
         self.wq, self.wkv = nh * d, nkv * d
         self.zz = zz    # the tokens are a zig-zag CP shard (context_parallel.apply_context_parallel)
-        # a kernels.AttnBand: document-masked / sliding-window causal attention (None: plain causal)
+        # a kernels.AttnBand: document-masked / sliding-window causal attention (None: plain causal);
+        # under context parallelism a context_parallel.CPBand, which ring_attention_tokens* take
         self.band = band
-        if band is not None and ring_enabled():
-            raise NotImplementedError("document masking / sliding-window attention under context parallelism "
-                                      "(the ring's blocks take no band)")
+        if band is not None:
+            from .context_parallel.context_parallel import CPBand
+            if ring_enabled() != isinstance(band, CPBand):
+                raise NotImplementedError("document masking / sliding-window attention under context parallelism "
+                                          "takes a CPBand (context_parallel.make_cp_band), and a CPBand only there")
 
     def q(self, t):
         return t[:, :self.wq].view(self.B, self.S, self.nh, self.d)

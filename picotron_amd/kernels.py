@@ -2001,6 +2001,66 @@ def attn_band(B, S, device, document_ids=None, window=None):
     return AttnBand(_BAND_KEY, kv_lo, q_hi)
 
 
+# Block bands (include/picotron_hip.h pt_attn_fwd_block_band): the band of one block of a
+# context-parallel schedule -- a rank's queries (global positions qpos) against one owner's keys
+# (kpos).  Key j of the block is visible to query i iff kv_lo[b, i] <= j, and j <= i on the diagonal
+# block.
+class AttnBlockBand:
+    """The bounds of one block, int32 on the device: kv_lo [B, Sq] = the first key of the block query i
+    sees (Sk: none), q_hi [B, Sk] = one past the last query of the block that sees key j (0: none);
+    causal: the diagonal block (qpos == kpos).  Built only by attn_block_band()."""
+
+    def __init__(self, key, kv_lo, q_hi, causal):
+        if key is not _BAND_KEY:
+            raise TypeError("AttnBlockBand is built by attn_block_band()")
+        self.kv_lo, self.q_hi, self.causal = kv_lo, q_hi, bool(causal)
+        (self.B, self.Sq), self.Sk = kv_lo.shape, q_hi.shape[1]
+
+    @property
+    def device(self):
+        return self.kv_lo.device
+
+    def mask(self):
+        """The boolean [B, 1, Sq, Sk] mask (query on dim 2), from kv_lo; for tests and references."""
+        j = torch.arange(self.Sk, device=self.device)
+        m = j[None, None, :] >= self.kv_lo[:, :, None]
+        if self.causal:
+            m = m & (j[None, None, :] <= torch.arange(self.Sq, device=self.device)[None, :, None])
+        return m[:, None]
+
+
+def attn_block_band(lo, qpos, kpos, causal):
+    """The AttnBlockBand of the queries at global positions qpos [Sq] against the keys at kpos [Sk]
+    (both increasing), under the whole row's lower bounds lo [B, S] (lo[b, g] = the first global key
+    token g sees: attn_band(...).kv_lo).  causal: the diagonal block (qpos == kpos, j <= i in local
+    index); otherwise every key must lie before every query.  Runs on lo's device, nothing read back."""
+    _req(isinstance(lo, torch.Tensor) and lo.dim() == 2 and not lo.dtype.is_floating_point,
+         "attn_block_band: lo must be an integer [B, S] tensor")
+    dev = lo.device
+    qpos = torch.as_tensor(qpos, dtype=torch.int64, device=dev)
+    kpos = torch.as_tensor(kpos, dtype=torch.int64, device=dev)
+    _req(qpos.dim() == 1 and kpos.dim() == 1 and qpos.numel() > 0 and kpos.numel() > 0,
+         "attn_block_band: qpos / kpos are non-empty 1-D position lists")
+    _req(not causal or qpos.numel() == kpos.numel(), "attn_block_band: the diagonal block has qpos == kpos")
+    B, Sk = lo.shape[0], kpos.numel()
+    kv_lo = torch.searchsorted(kpos, lo[:, qpos].to(torch.int64).contiguous()).to(torch.int32).contiguous()
+    # the first i with kv_lo[b, i] > j (kv_lo is non-decreasing along a row), Sq when there is none
+    keys = torch.arange(Sk, dtype=torch.int32, device=dev).expand(B, Sk).contiguous()
+    q_hi = torch.searchsorted(kv_lo, keys, right=True).to(torch.int32).contiguous()
+    return AttnBlockBand(_BAND_KEY, kv_lo, q_hi, causal)
+
+
+def _block_band_for(band, q, k, causal, what):
+    """The checks every block-band call shares."""
+    B, Sq, Sk = q.shape[0], q.shape[1], k.shape[1]
+    _req(bool(causal) == band.causal, f"{what}: causal={bool(causal)} but the block band was built causal={band.causal}")
+    _req((band.B, band.Sq, band.Sk) == (B, Sq, Sk) and band.device == q.device,
+         f"{what}: the block band is [{band.B}, {band.Sq} x {band.Sk}] on {band.device}, the block "
+         f"[{B}, {Sq} x {Sk}] on {q.device}")
+    _req(Sq % ATTN_Q_BLOCK == 0 and Sk % ATTN_Q_BLOCK == 0,
+         f"{what}: a block band needs Sq and Sk on the kernels' {ATTN_Q_BLOCK}-row blocks (no padded path)")
+
+
 def _band_for(band, q, k, causal, what):
     """The checks every band call shares; returns the band padded to the kernels' 128-row blocks."""
     B, Sq = q.shape[0], q.shape[1]
@@ -2017,9 +2077,24 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None)
     merge=True: `out` is an f32 accumulator and `lse` the running LSE; this block is merged in.
     lse may be the Sq-column slice of a longer [B, H, S] LSE (rows evenly spaced).
     band (an AttnBand): document-masked / sliding-window causal attention; causal only, no merge,
-    dense lse; the few-head split forms are not taken."""
+    dense lse; the few-head split forms are not taken.
+    band (an AttnBlockBand): one block of a context-parallel schedule; causal or not, merge, a strided
+    lse; Sq and Sk on the 128-row blocks."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if isinstance(band, AttnBlockBand):
+        _block_band_for(band, q, k, causal, "attn_fwd")
+        _req(not merge or (out is not None and lse is not None), "attn_fwd: merge=True needs out and lse")
+        if out is None:
+            out = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device)
+        if lse is None:
+            lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+        rc = _C.lib().pt_attn_fwd_block_band(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out),
+                                             _str3(out), _ptr(lse), B, H, HKV, Sq, Sk, D, float(scale),
+                                             int(bool(causal)), int(bool(merge)), _lse_ld(lse, B, H, Sq),
+                                             _ptr(band.kv_lo), _ptr(band.q_hi), _C.stream_ptr(q.device))
+        _C.check(rc, "pt_attn_fwd_block_band")
+        return out, lse
     if band is not None:
         _req(not merge, "attn_fwd: a band does not combine with merge=True")
         bp = _band_for(band, q, k, causal, "attn_fwd")
@@ -2096,14 +2171,18 @@ def attn_delta(dout, out, delta=None):
     return delta
 
 
-def attn_bwd_part(dout, q, k, v, lse, delta, scale, causal, dq=None, dk=None, dv=None, grad_f32=True):
+def attn_bwd_part(dout, q, k, v, lse, delta, scale, causal, dq=None, dk=None, dv=None, grad_f32=True, band=None):
     """Only dQ (dk = dv = None) or only dK / dV (dq = None) of one attention block, accumulated into the
     given f32 (grad_f32) or stored into bf16 tensors (pt_attn_bwd_part); lse / delta: the queries'
-    rows (f32 [B, H, Sq], any row stride shared by both)."""
+    rows (f32 [B, H, Sq], any row stride shared by both).  band: the block's AttnBlockBand."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
     parts = (1 if dq is not None else 0) | (2 if dk is not None else 0)
     _req(parts in (1, 2) and (dk is None) == (dv is None), "attn_bwd_part: dq alone, or dk and dv")
+    if band is not None:
+        _req(isinstance(band, AttnBlockBand), "attn_bwd_part: band must be an AttnBlockBand (attn_block_band())")
+        return _attn_bwd_block_band(dout, q, k, v, lse, delta, scale, causal, dq, dk, dv, grad_f32, parts, band,
+                                    "attn_bwd_part")
     ld = _lse_ld(lse, B, H, Sq)
     _req(_lse_ld(delta, B, H, Sq, "delta") == ld, "attn_bwd_part: delta and lse rows must share a stride")
     z = _C.i64arr([0, 0, 0])
@@ -2120,9 +2199,24 @@ def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, 
     """rope = (cos, sin) [S, d] bf16 tables: dq / dk are stored rotated back by -theta (the RoPE
     backward fused into the attention backward; positions = sequence index).
     band (an AttnBand): the backward of attn_fwd(band=); bf16 gradients, dense lse, D = rowsum(dO * O)
-    always formed inside the dQ kernel (no `delta` argument)."""
+    always formed inside the dQ kernel (no `delta` argument).
+    band (an AttnBlockBand): one block of a context-parallel schedule; bf16 stores or f32 accumulation,
+    a given (or separately formed) delta, a strided lse; no fused RoPE inverse."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if isinstance(band, AttnBlockBand):
+        _req(rope is None, "attn_bwd: a block band has no fused RoPE inverse")
+        if delta is None:
+            ld0 = _lse_ld(lse, B, H, Sq)
+            delta = attn_delta(dout, out, torch.empty(B, H, ld0, dtype=torch.float32, device=q.device)[:, :, :Sq]
+                               if ld0 != Sq else None)
+        gdt = torch.float32 if grad_f32 else BF16
+        new = torch.zeros if grad_f32 else torch.empty
+        dq = new(B, Sq, H, D, dtype=gdt, device=q.device) if dq is None else dq
+        dk = new(B, Sk, HKV, D, dtype=gdt, device=q.device) if dk is None else dk
+        dv = new(B, Sk, HKV, D, dtype=gdt, device=q.device) if dv is None else dv
+        _attn_bwd_block_band(dout, q, k, v, lse, delta, scale, causal, dq, dk, dv, grad_f32, 3, band, "attn_bwd")
+        return dq, dk, dv, delta
     if band is not None:
         return _attn_bwd_band(dout, q, k, v, out, lse, scale, causal, dq, dk, dv, grad_f32, delta, rope, band)
     if not grad_f32 and _attn_off_block(causal, Sq, Sk, lse, B, H) and \
@@ -2197,6 +2291,23 @@ def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, 
                          _ptr(rc_cos), _ptr(rc_sin), rstride, ld, _C.stream_ptr(q.device))
     _C.check(rc, "pt_attn_bwd")
     return dq, dk, dv, delta
+
+
+def _attn_bwd_block_band(dout, q, k, v, lse, delta, scale, causal, dq, dk, dv, grad_f32, parts, band, what):
+    B, Sq, H, D = q.shape
+    Sk, HKV = k.shape[1], k.shape[2]
+    _block_band_for(band, q, k, causal, what)
+    ld = _lse_ld(lse, B, H, Sq)
+    _req(_lse_ld(delta, B, H, Sq, "delta") == ld, f"{what}: delta and lse rows must share a stride")
+    z = _C.i64arr([0, 0, 0])
+    rc = _C.lib().pt_attn_bwd_block_band(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(dout),
+                                         _str3(dout), _ptr(lse), _ptr(delta), _ptr(dq),
+                                         _str3(dq) if dq is not None else z, _ptr(dk),
+                                         _str3(dk) if dk is not None else z, _ptr(dv),
+                                         _str3(dv) if dv is not None else z, B, H, HKV, Sq, Sk, D, float(scale),
+                                         int(bool(causal)), int(bool(grad_f32)), ld, parts, _ptr(band.kv_lo),
+                                         _ptr(band.q_hi), _C.stream_ptr(q.device))
+    _C.check(rc, "pt_attn_bwd_block_band")
 
 
 def _attn_bwd_band(dout, q, k, v, out, lse, scale, causal, dq, dk, dv, grad_f32, delta, rope, band):

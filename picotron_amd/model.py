@@ -266,7 +266,11 @@ class Attention(nn.Module):
     def band(self, x, document_ids):
         """The kernels.AttnBand of this forward (None: plain causal): document_ids a [B, S] integer
         tensor (a boundary wherever the value changes along a row), combined with the config's
-        sliding_window -- or an AttnBand built once by the caller, taken as it is."""
+        sliding_window -- or an AttnBand built once by the caller, taken as it is.  Under context
+        parallelism (cp > 1) a context_parallel.CPBand: x is this rank's chunk and document_ids its
+        [B, S_local] chunk (all-gathered over the cp group) or the full rows."""
+        if FN.ring_enabled() and not isinstance(document_ids, K.AttnBand):   # (an AttnBand there: AttnShape refuses)
+            return context_parallel.make_cp_band(x.shape[0], x.shape[1], x.device, document_ids, self.sliding_window)
         return FN.make_band(x.shape[0], x.shape[1], x.device, document_ids, self.sliding_window)
 
     def forward(self, x, cos, sin, attention_mask=None, position_ids=None, document_ids=None):
@@ -345,12 +349,12 @@ class DecoderLayer(nn.Module):
         st = getattr(self, "_pt_sp_state", None)
         sp = st.chunks if (self.tp_sequence_parallel and st is not None and st.local_len and
                            st.local_len == x.shape[1]) else 0
-        band = document_ids if isinstance(document_ids, K.AttnBand) else None
+        band = document_ids if isinstance(document_ids, (K.AttnBand, context_parallel.CPBand)) else None
         if band is None and (document_ids is not None or at.sliding_window is not None):
-            if sp or zz:
+            if sp or (zz and not FN.ring_enabled()):
                 raise NotImplementedError("document masking / sliding-window attention on a sharded residual "
-                                          "stream (sequence-parallel TP, zig-zag context parallelism)")
-            band = at.band(x, document_ids)
+                                          "stream (sequence-parallel TP, a zig-zag shard outside the ring)")
+            band = at.band(x, document_ids)   # (under context parallelism: a CPBand over the cp group's rows)
         qk = at.qk_norm_args()   # (): no QK-norm; else its two weights, in the layer norms' flavour
         if qk and qk[2:] != (_norm_eps(n1), _norm_mode(n1)):
             raise ValueError("DecoderLayer: q_norm / k_norm must be the layer norms' flavour")
@@ -417,15 +421,20 @@ class Llama(nn.Module):
         """document_ids ([B, S] integer tensor, or a kernels.AttnBand): intra-document causal masking
         of packed rows; with the config's `sliding_window`, both.  The band is built once per forward
         and shared by the layers.  position_ids stays unused: RoPE positions are sequence indices, and
-        RoPE scores depend on i - j only, so per-document positions would give the same attention."""
+        RoPE scores depend on i - j only, so per-document positions would give the same attention.
+        Under context parallelism (cp > 1) document_ids is this rank's [B, S_local] chunk, sliced like
+        input_ids (the shards are all-gathered over the cp group once), or the full [B, cp * S_local]
+        rows; one context_parallel.CPBand is built and handed to every layer."""
         x = self.embedding(input_ids)
         band = None
-        if document_ids is not None or getattr(self.model_config, "sliding_window", None) is not None:
-            if FN.ring_enabled():
-                raise NotImplementedError("document masking / sliding-window attention under context parallelism")
-            # (ids of the full rows: a token-row shard of the stream has no band of its own)
-            band = FN.make_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids,
-                                getattr(self.model_config, "sliding_window", None))
+        window = getattr(self.model_config, "sliding_window", None)
+        if document_ids is not None or window is not None:
+            if FN.ring_enabled():   # (a cp group of one rank, or a plain AttnBand: refused there)
+                band = context_parallel.make_cp_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids,
+                                                     window)
+            else:
+                # (ids of the full rows: a token-row shard of the stream has no band of its own)
+                band = FN.make_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids, window)
         for layer in self.decoder_layers:
             x = layer(x) if band is None else layer(x, document_ids=band)
         x = self.final_norm(x)
