@@ -376,7 +376,25 @@ class TPContext:
         """Sum over the tp group (tp_communications.py:32,44).  Identity at tp=1."""
         if self.world_size == 1:
             return None
+        if self._wide_sum(t):
+            self._sum_gloo(t)
+            return None
         return dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=async_op)
+
+    def _wide_sum(self, t):
+        """gloo adds bf16 / f16 partials pairwise in their own type: W - 1 roundings of the running sum.  With
+        more than two ranks the sum is taken in f32 and rounded once instead (_sum_gloo; two partials are one
+        rounding either way, and keep the transport's own call).  RCCL's reduction is RCCL's."""
+        return self.world_size > 2 and t.dtype in (torch.bfloat16, torch.float16) and not self._nccl()
+
+    def _sum_gloo(self, t):
+        """t summed over the group in place, complete at the return: in f32, one rounding, when _wide_sum."""
+        if self._wide_sum(t):
+            s = t.float()
+            dist.all_reduce(s, op=dist.ReduceOp.SUM, group=self.group)
+            t.copy_(s)
+        else:
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
 
     # ---- sequence parallelism (tensor_parallel/sequence_parallel.py): the residual stream between
     # the TP blocks is sharded by token rows over the tp group; the all-reduce of a row-parallel
@@ -412,7 +430,7 @@ class TPContext:
             h = dist.reduce_scatter_tensor(out, t.contiguous(), op=dist.ReduceOp.SUM, group=self.group,
                                            async_op=async_op)
             return out, h
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)   # gloo: the sum, then my rows
+        self._sum_gloo(t)   # gloo: the sum, then my rows
         return t[self.rank * n:(self.rank + 1) * n], None
 
     def reduce_scatter_rows_into(self, out, t, async_op=False):
@@ -423,7 +441,7 @@ class TPContext:
                                               async_op=async_op)
         n = out.shape[0]
         t = t.clone()
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)   # gloo: the sum, then my rows
+        self._sum_gloo(t)   # gloo: the sum, then my rows
         out.copy_(t[self.rank * n:(self.rank + 1) * n])
         return None
 

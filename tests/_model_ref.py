@@ -837,15 +837,25 @@ def layer_config(layer, B, S, mask=None):
 
 def extract_layer_fwd(K, layer, cur, c):
     """The forward roles of one decoder layer from the trace at cursor `cur` (advanced past the layer)."""
-    at, mlp = layer.attention, layer.mlp
-    P = dict(w1=layer.input_layernorm.weight, w2=layer.post_attention_layernorm.weight, wq=at.q_proj.weight,
-             wo=at.out_proj.weight, wg=mlp.gate_proj.weight, wd=mlp.down_proj.weight)
-    r, dev = {}, {}
+    P = dict(w1=layer.input_layernorm.weight, w2=layer.post_attention_layernorm.weight)
+    r = {}
     n1 = cur.next("rmsnorm_fwd", lambda k: _is(k.arg(1), P["w1"]) and k.kwargs.get("residual") is None, "h1")
-    r["x"], dev["x"] = cpu(n1.arg(0).pre), n1.arg(0).pre
+    r["x"] = cpu(n1.arg(0).pre)
     r["h1"], r["rstd1"] = cpu(n1.result[0].post), cpu(n1.result[1].post)
-    dev["h1"] = n1.result[0].post
+    extract_attn_fwd(K, layer, cur, c, r, n1.result[0].post)
+    n2 = cur.next("rmsnorm_fwd", lambda k: _is(k.arg(1), P["w2"]) and k.kwargs.get("residual") is not None, "h2")
+    r["h2"], r["rstd2"], r["z"] = (cpu(t.post) for t in n2.result)
+    extract_mlp_fwd(K, layer, cur, c, r, n2.result[0].post)
+    return r
+
+
+def extract_attn_fwd(K, layer, cur, c, r, h1):
+    """The attention block's forward roles (qkv_raw, qkv / qk, o, lse, a) from the trace at `cur`; h1: the
+    device value the q|k|v GEMM read (the replays run on it)."""
+    at = layer.attention
+    P = dict(wq=at.q_proj.weight, wo=at.out_proj.weight)
     qc = cur.next(("linear_fwd_rope", "linear_fwd"), lambda k: _is(_first_weight(k), P["wq"]), "qkv")
+    dev = dict(h1=qc.arg(0).pre if h1 is None else h1)   # (None: the recorded input of the launch)
     ws = [at.q_proj.weight, at.k_proj.weight, at.v_proj.weight]
     if qc.name == "linear_fwd_rope":
         with single_pass():
@@ -872,10 +882,17 @@ def extract_layer_fwd(K, layer, cur, c):
     r["o"], r["lse"] = cpu(ac.result[0].post), cpu(ac.result[1].post)
     oc = cur.next("linear_fwd", lambda k: _is(_first_weight(k), P["wo"]), "a")
     r["a"] = cpu(oc.result.post)
-    n2 = cur.next("rmsnorm_fwd", lambda k: _is(k.arg(1), P["w2"]) and k.kwargs.get("residual") is not None, "h2")
-    r["h2"], r["rstd2"], r["z"] = (cpu(t.post) for t in n2.result)
-    dev["h2"] = n2.result[0].post
+    return qc
+
+
+def extract_mlp_fwd(K, layer, cur, c, r, h2, residual=True):
+    """The MLP block's forward roles (gu, hh, out) from the trace at `cur`; h2: the device value the gate|up GEMM
+    read.  residual: whether the down projection's launch carries the residual epilogue (None: either; the
+    tensor-parallel forms: tests/_tp_ref.py)."""
+    mlp = layer.mlp
+    P = dict(wg=mlp.gate_proj.weight, wd=mlp.down_proj.weight)
     gc = cur.next(("linear_swiglu_fwd", "linear_fwd"), lambda k: _is(k.arg(1), P["wg"]) or _is(_first_weight(k), P["wg"]), "gu")
+    dev = dict(h2=gc.arg(0).pre if h2 is None else h2)   # (None: the recorded input of the launch)
     if gc.name == "linear_swiglu_fwd":
         with single_pass():
             gu = K.linear_fwd(dev["h2"], [mlp.gate_proj.weight, mlp.up_proj.weight])
@@ -887,20 +904,38 @@ def extract_layer_fwd(K, layer, cur, c):
         r["gu"] = cpu(gc.result.post)
         sc = cur.next("swiglu_fwd", None, "hh")
         r["hh"] = cpu(sc.result.post)
-    dc = cur.next("linear_fwd", lambda k: _is(_first_weight(k), P["wd"]) and k.kwargs.get("residual") is not None, "out")
+    dc = cur.next("linear_fwd", lambda k: _is(_first_weight(k), P["wd"]) and
+                  (residual is None or (k.kwargs.get("residual") is not None) == residual), "out")
     r["out"] = cpu(dc.result.post)
     r["_dev"] = dict(gu=gc.result[0].post if gc.name == "linear_swiglu_fwd" else gc.result.post)
-    return r
+    return gc, dc
 
 
 def extract_layer_bwd(K, layer, names, cur, c, r, wev, nev, wgrads=True):
     """The backward roles of one decoder layer (its forward roles in r) from the trace at cursor `cur`.
     names: the parameters' names in the sink tables wev / nev (dict w1, w2, wq, wk, wv, wo, wg, wu, wd[, wqn, wkn]).
     wgrads=False: a micro-batch that deferred its weight-gradient GEMMs to its pair -- no dW role."""
-    at, mlp = layer.attention, layer.mlp
-    wd, wg, wo, wq = mlp.down_proj.weight, mlp.gate_proj.weight, at.out_proj.weight, at.q_proj.weight
     if not wgrads:
         wev = None
+    start = cur.at
+    extract_mlp_bwd(K, layer, names, cur, c, r, wev)
+    n2 = cur.next("rmsnorm_bwd", lambda k: _is(k.arg(2), layer.post_attention_layernorm.weight), "dz")
+    r["dz"] = cpu(n2.result[0].post)
+    if c.w2_grad:
+        r["dw2"] = _norm_sink(nev, names["w2"], n2.result[1] if n2.kwargs.get("defer_dw") else None, start, "dw2")
+    extract_attn_bwd(K, layer, names, cur, c, r, wev, nev, start)
+    n1 = cur.next("rmsnorm_bwd", lambda k: _is(k.arg(2), layer.input_layernorm.weight), "dx")
+    r["dx"] = cpu(n1.result[0].post)
+    if c.w1_grad:
+        r["dw1"] = _norm_sink(nev, names["w1"], n1.result[1] if n1.kwargs.get("defer_dw") else None, start, "dw1")
+    return r
+
+
+def extract_mlp_bwd(K, layer, names, cur, c, r, wev):
+    """The MLP block's backward roles (dout, dhh, dgu, dW_d, dh2, dW_g, dW_u) from the trace at `cur`; returns
+    the gate|up dX call."""
+    mlp = layer.mlp
+    wd, wg = mlp.down_proj.weight, mlp.gate_proj.weight
     I, start = c.I, cur.at
     dc = cur.next(("linear_dgrad_dual", "linear_dgrad_swiglu", "linear_dgrad"),
                   lambda k: _is(_first_weight(k), wd) or _is(k.arg(1), wd), "dgu")
@@ -928,11 +963,17 @@ def extract_layer_bwd(K, layer, names, cur, c, r, wev, nev, wgrads=True):
     for nm, role in (("wg", "dW_g"), ("wu", "dW_u")):
         if wev is not None:
             r[role] = _sink_role(_wsink(wev, names[nm], start, role))
-    n2 = cur.next("rmsnorm_bwd", lambda k: _is(k.arg(2), layer.post_attention_layernorm.weight), "dz")
-    r["dz"] = cpu(n2.result[0].post)
-    if c.w2_grad:
-        r["dw2"] = _norm_sink(nev, names["w2"], n2.result[1] if n2.kwargs.get("defer_dw") else None, start, "dw2")
+    return gc
+
+
+def extract_attn_bwd(K, layer, names, cur, c, r, wev, nev, start=None):
+    """The attention block's backward roles (do, dqkv_unrot, dqkv_rot, dqkv, dW_o, dh1, dW_q / k / v) from the
+    trace at `cur`; returns the q|k|v dX call."""
+    at = layer.attention
+    wo, wq = at.out_proj.weight, at.q_proj.weight
+    start = cur.at if start is None else start
     oc = cur.next("linear_dgrad", lambda k: _is(_first_weight(k), wo), "do")
+    r.setdefault("dz", cpu(oc.arg(0).pre))   # (a block on its own: the gradient the out projection's dX read)
     r["do"] = cpu(oc.result.post)
     ab = cur.next("attn_bwd", None, "dqkv")
     got = torch.cat([cpu(ab.kwargs[k].post).reshape(c.B * c.S, -1) for k in ("dq", "dk", "dv")], 1)
@@ -964,11 +1005,7 @@ def extract_layer_bwd(K, layer, names, cur, c, r, wev, nev, wgrads=True):
     for nm, p in (("q", at.q_proj.weight), ("k", at.k_proj.weight), ("v", at.v_proj.weight)):
         if p.requires_grad and wev is not None:
             r["dW_" + nm] = _sink_role(_wsink(wev, names["w" + nm], start, "dW_qkv"))
-    n1 = cur.next("rmsnorm_bwd", lambda k: _is(k.arg(2), layer.input_layernorm.weight), "dx")
-    r["dx"] = cpu(n1.result[0].post)
-    if c.w1_grad:
-        r["dw1"] = _norm_sink(nev, names["w1"], n1.result[1] if n1.kwargs.get("defer_dw") else None, start, "dw1")
-    return r
+    return xc
 
 
 def head_config(model, reduction="mean", ignore=IGNORE):
