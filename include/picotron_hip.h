@@ -376,6 +376,68 @@ int pt_grad_sq_sr_multi(const void* tensors, const int64_t* chunk_start, int nte
 int pt_sr_cast_bf16(const float* x, void* y, int64_t n, uint32_t seed_lo, uint32_t seed_hi, uint32_t step,
                     int64_t rng_stream, int which, hipStream_t stream);
 
+/* ---- Muon: everything of the step that is not a GEMM ----------------------------------------
+ * replaces torch.optim.Muon (torch/optim/_muon.py) for 2-D bf16 parameters; the products of the
+ * Newton-Schulz iteration run on pt_gemm_grouped (kernels.muon_newton_schulz).
+ *
+ * List entries: `tensors` is a device array of pt_muon_tensor, `block_start` a device int64
+ * [ntensors + 1] of prefix sums of ceil(ceil(n / 8) / pt_muon_block_chunks()), total_blocks its
+ * last entry.  A tensor is a [R, C] view with unit column stride and a row stride (ld*); 16-byte
+ * vector accesses where bases are 16-byte aligned and C and the row strides are multiples of 8,
+ * element by element otherwise -- the same bits.  A tensor's blocks are counted from its own first
+ * element, so nothing a kernel computes for it depends on its place in the list.
+ * grad_dtype 0 bf16 / 1 f32: the gradients and the momentum buffers of one launch. */
+typedef struct {
+  void* param;            /* bf16 [R, C], row stride ldp */
+  const void* grad;       /* row stride ldg */
+  void* momentum_buffer;  /* the gradient's dtype, row stride ldb */
+  void* x;                /* bf16 workspace image, row stride ldx: X0 out (scale), O in (apply) */
+  int64_t n, cols;        /* R * C, C */
+  int64_t ldp, ldg, ldb, ldx;
+  float lr_ratio;         /* _adjust_lr's ratio for the shape: lr_adj = lr * lr_ratio */
+  int32_t sq_slot;        /* the tensor's entry of `sq` */
+} pt_muon_tensor;
+int pt_muon_block_chunks(void);
+/* _muon.py:310-311 `buf.lerp_(grad, 1 - momentum); update = grad.lerp(buf, momentum) if nesterov
+ * else buf`, each result rounded once to its storage dtype (update to bf16; it is not stored), and
+ * the first half of :59 `ortho_grad.norm()`: sq[sq_slot] = sum update^2 in f32 over the bf16
+ * values.  w_buf = f32(1 - momentum), w_nes = f32(momentum); torch's lerp, both branches.
+ * `partial`: total_blocks floats, one per block, summed per tensor by one workgroup in a fixed
+ * order -- no float atomics, bit-reproducible, nothing read on the host. */
+int pt_muon_momentum(const void* tensors, const int64_t* block_start, int ntensors, int64_t total_blocks,
+                     int grad_dtype, float w_buf, float w_nes, int nesterov, float* partial, float* sq,
+                     hipStream_t stream);
+/* The same on g' = r(grad * clip_coef), clip_coef from the device scalar grad_sq exactly as
+ * pt_adamw_step_multi_clip computes it (torch.nn.utils.clip_grad_norm_ in front of the step).  A
+ * non-finite grad_sq: nothing is written (buffers, partials and sq alike) and PT_STATUS_NONFINITE_GRAD
+ * is set in *status. */
+int pt_muon_momentum_clip(const void* tensors, const int64_t* block_start, int ntensors, int64_t total_blocks,
+                          int grad_dtype, float w_buf, float w_nes, int nesterov, float* partial, float* sq,
+                          const float* grad_sq, float max_norm, int* status, hipStream_t stream);
+/* _muon.py:55,59 `ortho_grad = grad.bfloat16(); ortho_grad.div_(ortho_grad.norm().clamp(min=eps))`:
+ * x = bf16(update / max(sqrt(sq[sq_slot]), eps)) with update recomputed from (grad, momentum_buffer)
+ * (torch rounds the norm itself to bf16; this does not).  The *_clip form recomputes the clipped
+ * gradient, and writes nothing on a non-finite grad_sq (status is not posted again). */
+int pt_muon_scale(const void* tensors, const int64_t* block_start, int ntensors, int64_t total_blocks, int grad_dtype,
+                  float w_nes, int nesterov, const float* sq, float eps, hipStream_t stream);
+int pt_muon_scale_clip(const void* tensors, const int64_t* block_start, int ntensors, int64_t total_blocks,
+                       int grad_dtype, float w_nes, int nesterov, const float* sq, float eps, const float* grad_sq,
+                       float max_norm, int* status, hipStream_t stream);
+/* _muon.py:63-66 `gram_update = addmm(gram, gram, gram, beta=b, alpha=c)` with the `beta=a` of the
+ * following addmm folded in: P[i] = bf16(a I + b A[i] + c S[i]) for nmat (<= 4) matrices [m, m]
+ * (dense, m a multiple of 8; A bf16, S f32), so a X + (b A + c A^2) X is one plain GEMM P X. */
+int pt_muon_poly(const void* const* A, const float* const* S, void* const* P, int nmat, int64_t m, float a, float b,
+                 float c, hipStream_t stream);
+/* _muon.py:317-318 `param.mul_(1 - lr * weight_decay); param.add_(update, alpha=-adjusted_lr)`:
+ * param = bf16(bf16(param * decay) - lr_adj * x), both roundings, decay = 1 - lr * weight_decay and
+ * lr_adj = lr * lr_ratio in f32 (the table holds only the shape's ratio, so a scheduler's new lr
+ * needs no new table).  The *_clip form does nothing on a non-finite grad_sq (the whole step is
+ * skipped). */
+int pt_muon_apply(const void* tensors, const int64_t* block_start, int ntensors, int64_t total_blocks, float decay,
+                  float lr, hipStream_t stream);
+int pt_muon_apply_clip(const void* tensors, const int64_t* block_start, int ntensors, int64_t total_blocks,
+                       float decay, float lr, const float* grad_sq, float max_norm, int* status, hipStream_t stream);
+
 /* ---- bf16 GEMM, f32 accumulate -------------------------------------------------------------
  * replaces every F.linear / matmul of the layer: model.py:124-126,161,186,270,
  * tensor_parallel.py:186, tp_communications.py:79,93,98,105.

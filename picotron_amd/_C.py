@@ -68,6 +68,14 @@ SIGNATURES = {
                                      _u32, _i64, _vp, _f32, _vp, _vp]),
     "pt_grad_sq_sr_multi": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
     "pt_sr_cast_bf16": (_i32, [_vp, _vp, _i64, _u32, _u32, _u32, _i64, _i32, _vp]),
+    "pt_muon_block_chunks": (_i32, []),
+    "pt_muon_momentum": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _vp, _vp, _vp]),
+    "pt_muon_momentum_clip": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _f32, _i32, _vp, _vp, _vp, _f32, _vp, _vp]),
+    "pt_muon_scale": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _f32, _vp]),
+    "pt_muon_scale_clip": (_i32, [_vp, _vp, _i32, _i64, _i32, _f32, _i32, _vp, _f32, _vp, _f32, _vp, _vp]),
+    "pt_muon_poly": (_i32, [_vpp, _vpp, _vpp, _i32, _i64, _f32, _f32, _f32, _vp]),
+    "pt_muon_apply": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _vp]),
+    "pt_muon_apply_clip": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _vp, _f32, _vp, _vp]),
     "pt_rmsnorm_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
     "pt_rmsnorm_colsum_batch": (_i32, [_vp, _vp, _vp, _vp, _i32, _i64, _vp]),
     "pt_rmsnorm_bwd_splitk": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),

@@ -552,6 +552,223 @@ def grad_scale(grad, sq, max_norm, status=None):
                  clip=(sq, max_norm, status))
 
 
+# ------------------------------------------------------------------------------------ Muon
+# Everything of a Muon step (csrc/muon.hip) and the host scheduler of its Newton-Schulz iteration.
+# An item is (param, grad, momentum_buffer, x, lr_ratio): 2-D views with unit column stride; x is
+# the matrix's workspace image from muon_x_workspace ([up(R), up(C)] bf16, zero outside [R, C]),
+# where the scale kernel leaves X0, muon_newton_schulz leaves O and the apply kernel reads it.
+MUON_GROUP = 4   # pt_gemm_grouped / pt_muon_poly take at most 4 problems
+_MUON_DESC = {}
+_MUON_WS = {}    # (up(R), up(C), device index) -> the iteration's shared buffers
+_MUON_PART = {}  # device index -> f32 block partials of the momentum kernel
+
+
+def muon_lr_ratio(adjust_lr_fn, shape):
+    """torch.optim._muon._adjust_lr's ratio for a parameter shape: lr_adj = lr * ratio."""
+    R, C = int(shape[0]), int(shape[1])
+    if adjust_lr_fn is None or adjust_lr_fn == "original":
+        return math.sqrt(max(1, R / C))
+    if adjust_lr_fn == "match_rms_adamw":
+        return 0.2 * math.sqrt(max(R, C))
+    raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+
+
+def muon_x_workspace(shape, device):
+    """The zero-filled [up(R), up(C)] bf16 image of one [R, C] matrix (its X0 / O)."""
+    return torch.zeros(_up(shape[0]), _up(shape[1]), dtype=BF16, device=device)
+
+
+def muon_group_plan(shapes):
+    """Pure: [(shape, [indices])] -- the matrices of one shape, in order of first appearance, cut into
+    launches of at most MUON_GROUP problems."""
+    by_shape = {}
+    for i, s in enumerate(shapes):
+        by_shape.setdefault((int(s[0]), int(s[1])), []).append(i)
+    return [(s, idx[k:k + MUON_GROUP]) for s, idx in by_shape.items() for k in range(0, len(idx), MUON_GROUP)]
+
+
+def _f32_bits(x):
+    """The bit pattern of f32(x): a float field of a descriptor row built from int64s."""
+    return ctypes.c_uint32.from_buffer_copy(ctypes.c_float(float(x))).value
+
+
+def _muon_items_ok(items):
+    """The gradients' dtype code of a list of Muon items."""
+    _req(len(items) > 0, "muon: an empty tensor list")
+    gdt = None
+    for p, g, buf, x, _ in items:
+        _req(p.dim() == 2 and p.dtype == BF16 and p.is_cuda, "muon: 2-D bf16 device parameters")
+        _req(g.dtype in (BF16, torch.float32) and buf.dtype == g.dtype, "muon: bf16 or f32 gradients, buffers alike")
+        _req(x.dtype == BF16 and x.is_contiguous() and x.data_ptr() % 16 == 0 and
+             tuple(x.shape) == (_up(p.shape[0]), _up(p.shape[1])), "muon: x is muon_x_workspace(param.shape)")
+        for t in (p, g, buf):
+            _req(t.shape == p.shape and t.device == p.device and t.stride(1) == 1 and t.stride(0) >= p.shape[1],
+                 "muon: [R, C] views with unit column stride on one device")
+        d = 0 if g.dtype == BF16 else 1
+        _req(gdt in (None, d), "muon: the gradients of one launch share a dtype")
+        gdt = d
+    return gdt
+
+
+def _muon_desc(items):
+    """(device pt_muon_tensor table, device block_start, total blocks), cached per pointer set like
+    _adam_desc's.  sq_slot is the item's position."""
+    key = tuple((p.data_ptr(), g.data_ptr(), b.data_ptr(), x.data_ptr(), p.numel(), p.shape[1], p.stride(0),
+                 g.stride(0), b.stride(0), x.stride(0), _f32_bits(r) | (i << 32))
+                for i, (p, g, b, x, r) in enumerate(items))
+    ent = _MUON_DESC.get(key)
+    if ent is None:
+        dev = items[0][0].device
+        per = _C.lib().pt_muon_block_chunks()
+        blocks = [0]
+        for it in items:
+            blocks.append(blocks[-1] + -(-((it[0].numel() + 7) // 8) // per))
+        desc_h = torch.tensor([list(k) for k in key], dtype=torch.int64).pin_memory()
+        block_h = torch.tensor(blocks, dtype=torch.int64).pin_memory()
+        ent = (desc_h.to(dev, non_blocking=True), block_h.to(dev, non_blocking=True), blocks[-1])
+        if len(_MUON_DESC) > 64:
+            _MUON_DESC.clear()
+        _MUON_DESC[key] = ent
+    return ent
+
+
+def _muon_list(items, *extra):
+    desc, block_t, total = _muon_desc(items)
+    return (_ptr(desc), _ptr(block_t), len(items), int(total)) + extra
+
+
+def muon_momentum(items, momentum, nesterov, clip=None):
+    """buf = lerp(buf, g, 1 - momentum) in place for every item and sq[i] = sum u_i^2 (f32, over the
+    bf16 u = lerp(g, buf, momentum) | buf; bit-reproducible, independent of the item's position) --
+    one launch over the list plus the final sum.  clip = (global sq, max_norm, status): on the
+    clipped gradients; a non-finite global norm writes nothing (sq then stays the zeros it is handed).
+    Returns sq, [len(items)] f32."""
+    gdt = _muon_items_ok(items)
+    dev = items[0][0].device
+    lead = _muon_list(items, gdt)
+    i = _dev_index(dev)
+    part = _MUON_PART.get(i)
+    if part is None or part.numel() < lead[3]:
+        part = _MUON_PART[i] = torch.empty(max(lead[3], 4096), dtype=torch.float32, device=dev)
+    sq = (torch.zeros if clip else torch.empty)(len(items), dtype=torch.float32, device=dev)
+    tail = (float(1 - momentum), float(momentum), int(bool(nesterov)), _ptr(part), _ptr(sq))
+    _adam_launch("pt_muon_momentum" + ("_clip" if clip else ""), dev, lead + tail, clip=clip)
+    return sq
+
+
+def muon_scale(items, sq, momentum, nesterov, eps, clip=None):
+    """x_i[:R, :C] = bf16(u_i / max(sqrt(sq[i]), eps)), u recomputed from (g, buf): X0 of every item."""
+    gdt = _muon_items_ok(items)
+    dev = items[0][0].device
+    _req(sq.dtype == torch.float32 and sq.numel() == len(items) and sq.device == dev, "muon_scale: sq of muon_momentum")
+    _adam_launch("pt_muon_scale" + ("_clip" if clip else ""), dev,
+                 _muon_list(items, gdt) + (float(momentum), int(bool(nesterov)), _ptr(sq), float(eps)), clip=clip)
+
+
+def muon_apply(items, lr, weight_decay, clip=None):
+    """p = bf16(bf16(p * (1 - lr wd)) - lr * lr_ratio * x[:R, :C]) for every item."""
+    _muon_items_ok(items)
+    _adam_launch("pt_muon_apply" + ("_clip" if clip else ""), items[0][0].device,
+                 _muon_list(items) + (float(1 - lr * weight_decay), float(lr)), clip=clip)
+
+
+def muon_poly(As, Ss, Ps, a, b, c):
+    """P_i = bf16(a I + b A_i + c S_i) for up to 4 dense [m, m] matrices (A, P bf16; S f32)."""
+    _req(1 <= len(As) <= MUON_GROUP and len(As) == len(Ss) == len(Ps), "muon_poly: 1 to 4 matrices")
+    m = As[0].shape[0]
+    for A, S, P in zip(As, Ss, Ps):
+        _req(A.dtype == BF16 and P.dtype == BF16 and S.dtype == torch.float32, "muon_poly: A, P bf16 and S f32")
+        _req(all(tuple(t.shape) == (m, m) and t.is_contiguous() and t.is_cuda for t in (A, S, P)),
+             "muon_poly: dense [m, m] device matrices of one size")
+    rc = _C.lib().pt_muon_poly(_C.ptrarr([_ptr(t) for t in As]), _C.ptrarr([_ptr(t) for t in Ss]),
+                               _C.ptrarr([_ptr(t) for t in Ps]), len(As), m, float(a), float(b), float(c),
+                               _C.stream_ptr(As[0].device))
+    _C.check(rc, "pt_muon_poly")
+
+
+def _muon_ws(Rp, Cp, device):
+    key = (Rp, Cp, _dev_index(device))
+    ws = _MUON_WS.get(key)
+    if ws is None:
+        m = min(Rp, Cp)
+        ws = _MUON_WS[key] = dict(
+            T=[torch.zeros(MUON_GROUP, Rp, Cp, dtype=BF16, device=device) for _ in range(2)],
+            A=torch.zeros(MUON_GROUP, m, m, dtype=BF16, device=device),
+            S=torch.zeros(MUON_GROUP, m, m, dtype=torch.float32, device=device),
+            P=torch.zeros(MUON_GROUP, m, m, dtype=BF16, device=device))
+    return ws
+
+
+def _muon_gemm(label, probs, a_kcontig, b_kcontig, epilogue, mnk, dev):
+    M, N, K = mnk
+    n = len(probs)
+    arr = (_C.GemmProblem * n)(*probs)
+    rc = _timed(f"muon {label} {n}x{M}x{N}x{K}", 2.0 * n * M * N * K, float(n * _alg_bytes(M, N, K, epilogue)),
+                _C.lib().pt_gemm_grouped, arr, n, int(a_kcontig), int(b_kcontig), int(epilogue), -1, _C.stream_ptr(dev))
+    _C.check(rc, f"pt_gemm_grouped(muon {label}: {n} x M={M}, N={N}, K={K}, a_k={a_kcontig}, b_k={b_kcontig})")
+
+
+def muon_newton_schulz(xs, ns_coefficients, ns_steps, stages=None):
+    """The Newton-Schulz iteration of torch's _zeropower_via_newtonschulz on every image of xs
+    (muon_x_workspace buffers holding X0; O replaces it), ns_steps times, on the GEMM launch layer:
+
+        A = bf16(X X^T)   [m, m], m = the image's smaller side; X^T X where it has more rows than
+                          columns (the wgrad layout, no transpose; images are padded to the 64-grid)
+        S = f32(A A)
+        P' = bf16(a I + b A + c S)                       pt_muon_poly
+        X <- bf16(P' X)   (X P' for R > C)
+
+    Images of one shape run up to MUON_GROUP per launch (muon_group_plan) through pt_gemm_grouped
+    with the tile picked automatically; A, S, P' and two ping-pong X buffers are allocated once per
+    shape and shared by the groups.  Nothing synchronises with the host.  stages: a dict that
+    receives clones of the intermediates -- stages["X0"][i] and stages["iters"][k][name][i] for
+    name in A, S, P, X and image i (the padded buffers)."""
+    a, b, c = (float(v) for v in ns_coefficients)
+    ns_steps = int(ns_steps)
+    _req(0 <= ns_steps < 100, "muon_newton_schulz: 0 <= ns_steps < 100")
+    for x in xs:
+        _req(x.dtype == BF16 and x.dim() == 2 and x.is_contiguous() and x.is_cuda and _on_grid(*x.shape),
+             "muon_newton_schulz: dense bf16 images on the 64-grid (muon_x_workspace)")
+    if stages is not None:
+        stages["X0"] = [x.clone() for x in xs]
+        stages["iters"] = [{k: [None] * len(xs) for k in "ASPX"} for _ in range(ns_steps)]
+    for (Rp, Cp), idx in muon_group_plan([x.shape for x in xs]):
+        dev = xs[idx[0]].device
+        ws = _muon_ws(Rp, Cp, dev)
+        tall = Rp > Cp
+        m = min(Rp, Cp)
+        n = len(idx)
+        own = [xs[i] for i in idx]
+        A, S, P = ([ws[k][j] for j in range(n)] for k in "ASP")
+        for it in range(ns_steps):
+            src = own if it == 0 else [ws["T"][(it - 1) % 2][j] for j in range(n)]
+            last = it == ns_steps - 1
+            dst = own if last and it > 0 else [ws["T"][it % 2][j] for j in range(n)]
+            if tall:   # A = X^T X: both operands stored [K = R, m]
+                _muon_gemm("gram", [_problem(x, Cp, [x], [Cp], [0, m], 0, [g], [m], [0, m], m, m, Rp)
+                                    for x, g in zip(src, A)], 0, 0, EPI_BF16, (m, m, Rp), dev)
+            else:      # A = X X^T: the forward layout, X as activations and as weights
+                _muon_gemm("gram", [_problem(x, Cp, [x], [Cp], [0, m], 0, [g], [m], [0, m], m, m, Cp)
+                                    for x, g in zip(src, A)], 1, 1, EPI_BF16, (m, m, Cp), dev)
+            _muon_gemm("square", [_problem(g, m, [g], [m], [0, m], 0, [s], [m], [0, m], m, m, m)
+                                  for g, s in zip(A, S)], 1, 0, EPI_F32, (m, m, m), dev)
+            muon_poly(A, S, P, a, b, c)
+            if tall:   # X <- X P'
+                _muon_gemm("update", [_problem(x, Cp, [p], [m], [0, m], 0, [y], [Cp], [0, Rp], Rp, m, m)
+                                      for x, p, y in zip(src, P, dst)], 1, 0, EPI_BF16, (Rp, m, m), dev)
+            else:      # X <- P' X
+                _muon_gemm("update", [_problem(p, m, [x], [Cp], [0, Cp], 0, [y], [Cp], [0, m], m, Cp, m)
+                                      for x, p, y in zip(src, P, dst)], 1, 0, EPI_BF16, (m, Cp, m), dev)
+            if last and it == 0:   # a single iteration cannot write its own input: through T[0]
+                for o, d in zip(own, dst):
+                    o.copy_(d)
+            if stages is not None:
+                for k, ts in (("A", A), ("S", S), ("P", P), ("X", own if last else dst)):
+                    for i, t in zip(idx, ts):
+                        stages["iters"][it][k][i] = t.clone()
+    return xs
+
+
 # ------------------------------------------------------------------------------------ RoPE
 def rope_(x2d, nheads, head_dim, cos, sin, seq_len, inverse=False):
     """In-place rotate the first `nheads` heads of every row of x2d ([rows, row_stride] view)."""

@@ -17,6 +17,10 @@ f32 `master_param` and f32 moments in the state of every bf16 parameter, one mul
 AdamW(..., stochastic_rounding=True) is the recipe in between (opt-in; torch's layout): bf16 state, the
 update in f32 registers, and the three stores rounded up or down with probability equal to the
 discarded fraction, on counter-based random bits that a resumed run reproduces.
+
+Muon (torch.optim.Muon's interface; csrc/muon.hip + the GEMM launch layer) steps the decoder layers'
+2-D matrices; MuonAdamW pairs it with AdamW for everything else under one global gradient norm, and
+split_muon_params says which parameter goes where.
 """
 import itertools
 
@@ -242,6 +246,16 @@ class AdamW(torch.optim.Optimizer):
         return out
 
     def _step_clipped(self):
+        work, norm_batches = self._clip_work()
+        sq = _global_sq(norm_batches)
+        if sq is None:   # no gradients at all
+            return
+        self._launch_clipped(work, sq, self.max_grad_norm)
+
+    def _clip_work(self):
+        """(the step's batches, what _global_sq takes for their gradients); counts the step.  Split
+        from the launch so that a caller holding further parameters (MuonAdamW) can take ONE norm
+        over all of them and hand it to _launch_clipped."""
         work = [b for group in self.param_groups for b in self._batches(group)]
         norm_batches = []
         for _, kind, items in work:   # (param, what grad_sqnorm takes for it): see _global_sq
@@ -251,14 +265,19 @@ class AdamW(torch.optim.Optimizer):
             else:   # the gradient as the step will take it (_master_single, _sr_single)
                 dense = kind in (MASTER_SINGLE, SR_SINGLE)
                 norm_batches.append((False, [(it[ip], it[ig].contiguous() if dense else it[ig]) for it in items]))
-        sq = _global_sq(norm_batches)
-        if sq is None:   # no gradients at all
-            return
+        return work, norm_batches
+
+    def _launch_clipped(self, work, sq, max_norm, status=None):
+        """The clipped launches of _clip_work's batches on the squared norm sq.  status: the caller's
+        status word, which the caller then posts itself."""
         self.last_grad_norm = sq.sqrt().reshape(())
-        status = K.status_word(sq.device)   # one word, posted once: see kernels._clip_status
+        own = status is None
+        if own:
+            status = K.status_word(sq.device)   # one word, posted once: see kernels._clip_status
         for sc, kind, items in work:
-            _launch(kind, items, sc, clip=(sq, self.max_grad_norm, status))
-        K._status_posted(sq.device)
+            _launch(kind, items, sc, clip=(sq, max_norm, status))
+        if own:
+            K._status_posted(sq.device)
 
     @torch.no_grad()
     def sync_master_from_params(self):
@@ -377,3 +396,235 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
         K.grad_scale(g, sq, max_norm, status=status)
     K._status_posted(sq.device)
     return sq.sqrt().reshape(())
+
+
+# ------------------------------------------------------------------------------------ Muon
+_MUON_MATRICES = ("attention.q_proj.weight", "attention.k_proj.weight", "attention.v_proj.weight",
+                  "attention.out_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+
+
+def split_muon_params(model):
+    """(matrices, rest) of a Llama: `matrices` the decoder layers' q / k / v / out / gate / up / down
+    projection weights (what Muon orthogonalises), `rest` everything else -- the embedding,
+    final_proj, every norm weight (QK-norm's included) and the biases -- for AdamW.  By parameter
+    name, in named_parameters() order."""
+    matrices, rest = [], []
+    for name, p in model.named_parameters():
+        hidden = "decoder_layers." in name and name.endswith(_MUON_MATRICES) and p.dim() == 2
+        (matrices if hidden else rest).append(p)
+    return matrices, rest
+
+
+class Muon(torch.optim.Optimizer):
+    """torch.optim.Muon on the HIP kernels: the same constructor, defaults, param_groups keys and
+    state key (`momentum_buffer`), so a state_dict of one loads into the other.  Per 2-D bf16
+    parameter p [R, C] (csrc/muon.hip, kernels.muon_newton_schulz):
+
+        buf = lerp(buf, g, 1 - momentum); u = bf16(lerp(g, buf, momentum) | buf)
+        X0 = bf16(u / max(||u||_F, eps))          the norm in f32 on the device, never on the host
+        ns_steps x:  A = bf16(X X^T); S = f32(A A); P' = bf16(a I + b A + c S); X = bf16(P' X)
+        p = bf16(p (1 - lr wd)); p = bf16(p - lr_adj X)
+
+    The momentum, scale and apply kernels each run once over the whole list; the GEMMs of
+    same-shaped matrices run four to a launch.  Nothing synchronises with the host, nothing is
+    atomic: data-, context- and pipeline-parallel replicas compute identical bits.
+
+    use_main_grad=True (the added argument): a parameter with a `main_grad` attribute
+    (DataParallelBucket's accumulator, bf16 or f32) is stepped on that tensor and its p.grad is
+    ignored; the momentum buffer has the gradient's dtype.
+
+    Refused: parameters that are not 2-D or not floating point (ValueError, as torch); f32
+    parameters (NotImplementedError: the kernels store bf16); a parameter marked
+    `tensor_model_parallel` while tp > 1 (NotImplementedError: Newton-Schulz needs the whole
+    matrix, and a rank holds a block of it)."""
+
+    def __init__(self, params, lr=1e-3, weight_decay=0.1, momentum=0.95, nesterov=True,
+                 ns_coefficients=(3.4445, -4.7750, 2.0315), eps=1e-7, ns_steps=5, adjust_lr_fn=None,
+                 use_main_grad=False):
+        if not 0.0 <= lr:
+            raise ValueError(f"Learning rate should be >= 0 but is: {lr}")
+        if not 0.0 <= momentum:
+            raise ValueError(f"momentum should be >= 0 but is: {momentum}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"weight decay should be >= 0 but is: {weight_decay}")
+        if adjust_lr_fn is not None and adjust_lr_fn not in ("original", "match_rms_adamw"):
+            raise ValueError(f"Adjust learning rate function {adjust_lr_fn} is not supported")
+        if len(ns_coefficients) != 3:
+            raise ValueError("Coefficients must be a tuple of exactly 3 values")
+        if not 0 <= int(ns_steps) < 100:
+            raise ValueError("Number of steps must be less than 100 for computational efficiency")
+        defaults = dict(lr=lr, weight_decay=weight_decay, momentum=momentum, nesterov=nesterov,
+                        ns_coefficients=ns_coefficients, eps=eps, ns_steps=ns_steps, adjust_lr_fn=adjust_lr_fn)
+        super().__init__(params, defaults)
+        tp = pgm.current().tp_world_size
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.ndim != 2:
+                    raise ValueError(f"Muon only supports 2D parameters whereas we found a parameter with size: {p.size()}")
+                if p.dtype == torch.float32:
+                    raise NotImplementedError("picotron_amd.optim.Muon: f32 parameters are not supported (the kernels "
+                                              "store bf16); keep them on AdamW")
+                if p.dtype != torch.bfloat16:
+                    raise ValueError(f"picotron_amd.optim.Muon: bf16 parameters only, got {p.dtype}")
+                if tp > 1 and getattr(p, "tensor_model_parallel", False):
+                    raise NotImplementedError("picotron_amd.optim.Muon: a tensor-parallel shard (tp > 1): Newton-Schulz "
+                                              "needs the whole matrix")
+        self.use_main_grad = bool(use_main_grad)
+        self._x = {}   # parameter -> its workspace image (X0 / O); not optimizer state
+
+    def _grad(self, p):
+        if self.use_main_grad and getattr(p, "main_grad", None) is not None:
+            return p.main_grad
+        return p.grad
+
+    def _work(self):
+        """[(group, items, fix)] -- one list per param group and gradient dtype, items as kernels.muon_*
+        take them; fix: (parameter, dense copy) pairs to copy back after the apply (a parameter whose
+        column stride is not 1)."""
+        work = []
+        for group in self.param_groups:
+            lists = {}
+            for p in group["params"]:
+                g = self._grad(p)
+                if g is None:
+                    continue
+                if g.is_sparse:
+                    raise RuntimeError("Muon does not support sparse gradients")
+                if g.dtype not in (torch.bfloat16, torch.float32):
+                    raise ValueError(f"picotron_amd.optim.Muon: bf16 or f32 gradients, got {g.dtype}")
+                st = self.state[p]
+                if "momentum_buffer" not in st:
+                    st["momentum_buffer"] = torch.zeros(p.shape, dtype=g.dtype, device=p.device)
+                buf = st["momentum_buffer"]
+                if buf.dtype != g.dtype or buf.stride(1) != 1:   # a loaded state in another dtype
+                    buf = st["momentum_buffer"] = buf.to(g.dtype).contiguous()
+                x = self._x.get(p)
+                if x is None:
+                    x = self._x[p] = K.muon_x_workspace(p.shape, p.device)
+                pd = p if p.stride(1) == 1 and p.stride(0) >= p.shape[1] else p.detach().contiguous()
+                gd = g if g.stride(1) == 1 and g.stride(0) >= g.shape[1] else g.contiguous()
+                items, fix = lists.setdefault(g.dtype, ([], []))
+                items.append((pd, gd, buf, x, K.muon_lr_ratio(group["adjust_lr_fn"], p.shape)))
+                if pd is not p:
+                    fix.append((p, pd))
+            work.extend((group, items, fix) for items, fix in lists.values())
+        return work
+
+    @torch.no_grad()
+    def step(self, closure=None, stages=None):
+        """stages: a list that receives, per launched list (param group x gradient dtype), a dict of
+        the step's intermediates for the conformance tests -- `params`, `sq` and what
+        kernels.muon_newton_schulz(stages=) records."""
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        self._run(self._work(), None, stages)
+        return loss
+
+    def _run(self, work, clip, stages=None):
+        """clip = (global sq, max_norm, status word) from MuonAdamW, or None."""
+        for group, items, fix in work:
+            mu, nes = group["momentum"], group["nesterov"]
+            rec = None if stages is None else {"params": [it[0] for it in items]}
+            sq = K.muon_momentum(items, mu, nes, clip=clip)
+            K.muon_scale(items, sq, mu, nes, group["eps"], clip=clip)
+            K.muon_newton_schulz([it[3] for it in items], group["ns_coefficients"], group["ns_steps"], stages=rec)
+            K.muon_apply(items, group["lr"], group["weight_decay"], clip=clip)
+            if rec is not None:
+                rec["sq"] = sq
+                stages.append(rec)
+            for p, dense in fix:
+                p.copy_(dense)
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.Optimizer.load_state_dict, which casts every floating-point state tensor to the
+        parameter's dtype -- an f32 momentum buffer (use_main_grad with f32 accumulators) is put back
+        from the saved dict afterwards, bit for bit."""
+        saved = list(itertools.chain.from_iterable(g["params"] for g in state_dict["param_groups"]))
+        mine = list(itertools.chain.from_iterable(g["params"] for g in self.param_groups))
+        super().load_state_dict(state_dict)
+        for k, p in zip(saved, mine):
+            buf = state_dict["state"].get(k, {}).get("momentum_buffer")
+            if torch.is_tensor(buf) and buf.dtype == torch.float32:
+                self.state[p]["momentum_buffer"] = buf.detach().to(device=p.device, dtype=torch.float32, copy=True)
+
+    def _norm_batches(self, work):
+        """What _global_sq takes for the gradients of _work()'s lists."""
+        out = []
+        for _, items, _ in work:
+            listed = [it for it in items if it[1].dtype == torch.bfloat16 and _listable(it[1])]
+            ids = {id(it) for it in listed}
+            out.append((True, [(it[0], (it[1],) * 4) for it in listed]))
+            out.append((False, [(it[0], it[1].contiguous()) for it in items if id(it) not in ids]))
+        return [b for b in out if b[1]]
+
+
+class MuonAdamW:
+    """Muon for the hidden matrices and AdamW for the rest, as one optimizer object: step / zero_grad
+    / state_dict / load_state_dict, and `param_groups` = Muon's followed by AdamW's (the same dict
+    objects, so a schedule that writes group["lr"] drives both).  Not a torch.optim.Optimizer:
+    torch.optim.lr_scheduler classes take `.muon` and `.adamw`, one scheduler each, and a new param
+    group is added to the inner optimizer that is to own it (`param_groups` is rebuilt from the two on
+    every access).
+
+    MuonAdamW(model) splits with split_muon_params; MuonAdamW((matrices, rest)) takes a split.
+    muon= / adamw= are the keyword arguments of optim.Muon / optim.AdamW (every AdamW form stays
+    available: master_weights, stochastic_rounding, use_main_grad).  max_grad_norm=M: ONE global L2
+    norm over the gradients of both parts (and the model-parallel grid, grad_norm_plan); the same
+    device scalar feeds AdamW's clipped launches and Muon's clipped momentum kernel, so the whole
+    model is scaled by one coefficient; a non-finite norm skips the whole step on the device."""
+
+    def __init__(self, model_or_split, muon=None, adamw=None, max_grad_norm=None):
+        if isinstance(model_or_split, torch.nn.Module):
+            matrices, rest = split_muon_params(model_or_split)
+        else:
+            matrices, rest = (list(x) for x in model_or_split)
+        adamw = dict(adamw or {})
+        if "max_grad_norm" in adamw:
+            raise ValueError("MuonAdamW: max_grad_norm belongs to MuonAdamW itself (one norm over both parts)")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"invalid MuonAdamW max_grad_norm={max_grad_norm}: a positive number or None")
+        self.muon = Muon(matrices, **dict(muon or {}))
+        self.adamw = AdamW(rest, **adamw)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.last_grad_norm = None
+        self.last_grad_sq = None   # the [1] f32 device scalar both parts took their coefficient from
+
+    @property
+    def param_groups(self):
+        return self.muon.param_groups + self.adamw.param_groups
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if self.max_grad_norm is None:
+            self.muon.step()
+            self.adamw.step()
+            return loss
+        mwork = self.muon._work()
+        awork, abatches = self.adamw._clip_work()
+        sq = _global_sq(self.muon._norm_batches(mwork) + abatches)
+        if sq is None:   # no gradients at all
+            return loss
+        self.last_grad_sq = sq
+        self.last_grad_norm = sq.sqrt().reshape(())
+        status = K.status_word(sq.device)   # one word for the whole step, posted once
+        self.muon._run(mwork, (sq, self.max_grad_norm, status))
+        self.adamw._launch_clipped(awork, sq, self.max_grad_norm, status=status)
+        K._status_posted(sq.device)
+        return loss
+
+    def zero_grad(self, set_to_none=True):
+        self.muon.zero_grad(set_to_none=set_to_none)
+        self.adamw.zero_grad(set_to_none=set_to_none)
+
+    def state_dict(self):
+        return {"muon": self.muon.state_dict(), "adamw": self.adamw.state_dict()}
+
+    def load_state_dict(self, state_dict):
+        self.muon.load_state_dict(state_dict["muon"])
+        self.adamw.load_state_dict(state_dict["adamw"])
