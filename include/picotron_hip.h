@@ -106,6 +106,56 @@ int pt_swiglu_bwd(const void* dh, int64_t dh_stride, const void* g, int64_t g_st
                   int64_t u_stride, void* dg, int64_t dg_stride, void* du, int64_t du_stride, int64_t rows,
                   int64_t cols, hipStream_t stream);
 
+/* ---- mixture-of-experts routing ---------------------------------------------------------------
+ * Not in the reference (its MLP is dense, model.py:184-186): the routing of an MoE MLP (Mixtral,
+ * Qwen3-MoE, OLMoE) with a GShard / Switch capacity.  T tokens choose k of E experts; expert e owns
+ * rows [e C, (e + 1) C) of the [R = E C, H] expert buffers.  Item i = t k + j is token t's j-th
+ * choice (best first).  Every shape is static, nothing is read on the host, there are no atomics,
+ * and two runs give the same bits.  E <= 128, k <= min(E, 8), H % 64 == 0, any T >= 1 (beyond that
+ * PT_EUNSUPPORTED).  Checked before any launch, in this order: a NULL required pointer or a size
+ * < 1 PT_EINVAL; the limits above, or a count past 32 bits, PT_EUNSUPPORTED; a leading dimension
+ * below its row PT_EINVAL (logits) / a pointer off 16 bytes, a row stride off 8 elements or below H
+ * PT_EALIGN (the [*, H] rows).
+ *
+ * pt_moe_route: logits bf16 [T, ldl], the first E columns valid.  probs f32 [T, E] = the softmax of
+ * the stored values over all E; idx int32 [T, k] = the k largest STORED values, ties to the lower
+ * expert, best first; gate f32 [T, k] = probs[idx], divided by their sum when norm_topk;
+ * counts int32 [E] = the selections per expert (before any capacity); aux f32 [1] =
+ * E sum_e (counts[e] / (T k)) (mean_t probs[t, e]), the Switch load-balancing loss.  workspace:
+ * pt_moe_route_workspace(T, E) 4-byte words (negative: refused). */
+int pt_moe_route_workspace(int64_t T, int64_t E);
+int pt_moe_route(const void* logits, int64_t ldl, int64_t T, int64_t E, int64_t k, int norm_topk, int32_t* idx,
+                 float* gate, float* probs, int32_t* counts, float* aux, void* workspace, hipStream_t stream);
+/* pt_moe_plan: pos(i) = the number of items before i (flat order) with the same expert;
+ * slot int32 [T, k] = idx C + pos where pos < C, else -1 (dropped); src int32 [E C] = the item in
+ * that row, -1 for an empty row.  An idx outside [0, E) is dropped and not counted.  A prefix count
+ * over workgroups of pt_moe_plan_block() items, whose result does not depend on their scheduling.
+ * workspace: pt_moe_plan_workspace(T, E, k) int32 words. */
+int pt_moe_plan_block(void);
+int pt_moe_plan_workspace(int64_t T, int64_t E, int64_t k);
+int pt_moe_plan(const int32_t* idx, int64_t T, int64_t E, int64_t k, int64_t C, int32_t* slot, int32_t* src,
+                int32_t* workspace, hipStream_t stream);
+/* pt_moe_dispatch: xe[r, :] = x[src[r] / k, :] (a bit copy), zeros where src[r] is outside [0, T k). */
+int pt_moe_dispatch(const void* x, int64_t ldx, const int32_t* src, void* xe, int64_t ldxe, int64_t T, int64_t k,
+                    int64_t R, int64_t H, hipStream_t stream);
+/* pt_moe_combine: y[t, :] = bf16(residual[t, :] + sum_j gate[t, j] ye[slot[t, j], :]) over the items
+ * with slot in [0, R), accumulated in f32 in j order and rounded once.  gate NULL: weights of 1 (the
+ * backward of pt_moe_dispatch: dx[t] = sum_j dxe[slot[t, j]]); residual NULL: none. */
+int pt_moe_combine(const void* ye, int64_t ldye, const int32_t* slot, const float* gate, const void* residual,
+                   int64_t ldr, void* y, int64_t ldy, int64_t T, int64_t k, int64_t R, int64_t H, hipStream_t stream);
+/* pt_moe_combine_bwd: dye[r, :] = bf16(gate[src[r]] dy[src[r] / k, :]), zeros for empty rows;
+ * dgate[i] = sum_h dy[t, h] ye[slot[i], h] in f32, 0 for dropped items. */
+int pt_moe_combine_bwd(const void* dy, int64_t lddy, const void* ye, int64_t ldye, const int32_t* slot,
+                       const int32_t* src, const float* gate, void* dye, int64_t lddye, float* dgate, int64_t T,
+                       int64_t k, int64_t R, int64_t H, hipStream_t stream);
+/* pt_moe_route_bwd: dlogits bf16 [T, ldl] (columns E.. zero) from dgate [T, k] and the device scalar
+ * d_aux (NULL: 0), through the selection (idx fixed), the renormalisation (norm_topk) and the softmax:
+ * dp[t, idx_j] = (dgate_j - sum_i dgate_i gate_i) / sum_i p[idx_i] (or dgate_j), dp[t, e] +=
+ * d_aux E counts[e] / (T k) / T (counts carry no gradient), dlogit = p (dp - sum_e p dp). */
+int pt_moe_route_bwd(const float* dgate, const float* probs, const int32_t* idx, const int32_t* counts,
+                     const float* d_aux, int norm_topk, void* dlogits, int64_t ldl, int64_t T, int64_t E, int64_t k,
+                     hipStream_t stream);
+
 /* ---- residual add: out = bf16(x + r), n contiguous bf16 (n % 8 == 0, 16-B aligned) ------------
  * replaces picotron/model.py:208 `x + self.mlp(...)` where the sequence-parallel TP layer adds the
  * residual to its reduce-scattered MLP output (no GEMM epilogue can carry it there). */

@@ -57,6 +57,10 @@ from .cp_communications import ContextCommunicate, zigzag_exchange
 
 def apply_context_parallel(model):
     """context_parallel.py:10-12: sets CONTEXT_PARALLEL (read by every attention call)."""
+    from ..functional import has_moe   # (functional imports this module lazily: no cycle at import time)
+    if pgm.current().cp_world_size > 1 and has_moe(model):
+        raise NotImplementedError("apply_context_parallel: mixture-of-experts layers at cp > 1 (the capacity and the "
+                                  "aux loss are per rank)")
     os.environ["CONTEXT_PARALLEL"] = "1" if pgm.current().cp_world_size > 1 else "0"
     return model
 

@@ -1171,6 +1171,108 @@ class MLPFunction(torch.autograd.Function):
         return (dh.view(ctx.shape) if dh is not None else None), None, None, None
 
 
+# ------------------------------------------------------------------------ mixture-of-experts block
+def has_moe(model):
+    """True when `model` holds a mixture-of-experts MLP (model.MoE): the parallel engines that do not
+    carry one refuse it by this."""
+    return any(getattr(m, "_pt_moe", False) for m in model.modules())
+
+
+def _stage(stages, **tensors):
+    """Clones of a step's intermediates into the caller's `stages` dict (tests; None: nothing)."""
+    if stages is not None:
+        for name, t in tensors.items():
+            stages[name] = t.clone()
+
+
+def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None):
+    """h2 [T, H] -> (residual + sum_j gate_j Expert_{idx_j}(h2), aux, saved): router GEMM (bf16
+    logits), top-k on the stored logits, capacity slots (K.moe_capacity; items past an expert's C
+    rows are dropped and the residual carries the token), dispatch into the [E C, H] buffer, the
+    expert MLPs as grouped GEMMs, weighted combine with the residual in one rounding.  Static shapes,
+    nothing read on the host."""
+    T, E = h2.shape[0], len(wgs)
+    C = K.moe_capacity(T, E, k, capacity_factor)
+    logits = K.linear_fwd(h2, [router_w])
+    idx, gate, probs, counts, aux = K.moe_route(logits, k, norm_topk_prob)
+    slot, src = K.moe_plan(idx, E, C)
+    xe = K.moe_dispatch(h2, src, k)
+    gu, hh, ye = K.moe_experts_fwd(xe, wgs, wus, wds, C, fuse=_fuse())
+    out = K.moe_combine(ye, slot, gate, residual)
+    _stage(stages, h2=h2, logits=logits, idx=idx, gate=gate, probs=probs, counts=counts, aux=aux, slot=slot, src=src, xe=xe,
+           gu=gu, hh=hh, ye=ye, out=out)
+    return out, aux, (idx, gate, probs, counts, slot, src, xe, gu, hh, ye)
+
+
+def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob=True, need_dx=True, stages=None):
+    """Backward of moe_block_fwd's expert path and router: returns dh2 (the residual's gradient is
+    dout itself).  d_aux: the gradient of aux, an f32 device scalar or None.  Expert and router
+    weight gradients go to their sinks through wgrad_group / wgrad, MOE_GROUP experts to a launch, so
+    bf16 .grad, f32 main_grad, the DP notification and weight-gradient pairing behave as for a dense
+    layer (an expert's jobs pair on its own parameters; C is the same for every micro-batch)."""
+    idx, gate, probs, counts, slot, src, xe, gu, hh, ye = saved
+    E = len(wgs)
+    C = xe.shape[0] // E
+    rows = [slice(e * C, (e + 1) * C) for e in range(E)]
+    dye, dgate = K.moe_combine_bwd(dout, ye, slot, src, gate)
+    dgu, dhh = K.moe_experts_dgrad_down(dye, wds, gu, C, fuse=_fuse())
+    if dhh is not None:
+        _stage(stages, dhh=dhh)
+    for lo in range(0, E, K.MOE_GROUP):
+        wgrad_group([(dye[rows[e]], hh[rows[e]], [wds[e]]) for e in range(lo, min(E, lo + K.MOE_GROUP))])
+    dxe = K.moe_experts_dgrad_gate_up(dgu, wgs, wus, C) if need_dx else None
+    for lo in range(0, E, K.MOE_GROUP):
+        wgrad_group([(dgu[rows[e]], xe[rows[e]], [wgs[e], wus[e]]) for e in range(lo, min(E, lo + K.MOE_GROUP))])
+    dlogits = K.moe_route_bwd(dgate, probs, idx, counts, d_aux, norm_topk_prob)
+    dh = None
+    if need_dx:   # the router's dX rides as the residual of the dispatch backward: one rounding
+        dhr = K.linear_dgrad(dlogits, [router_w])
+        dh = K.moe_combine(dxe, slot, None, dhr)
+        _stage(stages, dxe=dxe, dh_router=dhr, dh=dh)
+    wgrad(dlogits, h2, [router_w])
+    _stage(stages, dye=dye, dgate=dgate, dgu=dgu, dlogits=dlogits)
+    return dh
+
+
+class MoEFunction(torch.autograd.Function):
+    """A mixture-of-experts MLP with its residual as one node:
+    apply(h2, residual, router_w, [wg_e], [wu_e], [wd_e], k, capacity_factor, norm_topk_prob)
+    -> (out = residual + MoE(h2), aux).  aux is the Switch load-balancing loss E sum_e f_e P_e with
+    f_e = the fraction of the T k selections that chose e (before dropping, no gradient) and P_e =
+    the mean router probability of e; HF Mixtral's load_balancing_loss_func is k times this value.
+    The expert weights travel in lists, which autograd does not see: like every weight here they get
+    their gradient written into their sink.  stages: a dict receiving clones of every intermediate of
+    the forward and, when the backward runs, of the backward (tests)."""
+
+    @staticmethod
+    def forward(ctx, h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None):
+        tp = TPContext.current()
+        if tp.world_size > 1:
+            raise NotImplementedError("mixture-of-experts layers under tensor parallelism (experts are not sharded)")
+        x2, r2 = _contig2d(h2), _contig2d(residual)
+        wgs, wus, wds = list(wgs), list(wus), list(wds)
+        out, aux, saved = moe_block_fwd(x2, r2, router_w, wgs, wus, wds, int(k), float(capacity_factor),
+                                        bool(norm_topk_prob), stages)
+        ctx.save_for_backward(x2, router_w, *saved, *wgs, *wus, *wds)
+        ctx.E, ctx.k, ctx.norm, ctx.shape, ctx.stages = len(wgs), int(k), bool(norm_topk_prob), h2.shape, stages
+        return out.view(h2.shape), aux.view(())
+
+    @staticmethod
+    def backward(ctx, dout, daux):
+        x2, router_w, *rest = ctx.saved_tensors
+        saved, ws = rest[:10], rest[10:]
+        E = ctx.E
+        wgs, wus, wds = ws[:E], ws[E:2 * E], ws[2 * E:]
+        if dout is None:
+            dout = torch.zeros(ctx.shape, dtype=x2.dtype, device=x2.device)
+        d2 = _contig2d(dout)
+        if daux is not None:
+            daux = daux.to(torch.float32).reshape(1).contiguous()
+        dh = moe_block_bwd(d2, daux, x2, saved, router_w, wgs, wus, wds, ctx.k, ctx.norm,
+                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages)
+        return (dh.view(ctx.shape) if dh is not None else None, dout if ctx.needs_input_grad[1] else None) + (None,) * 8
+
+
 # ------------------------------------------------------------------------ decoder layer
 class DecoderLayerFunction(torch.autograd.Function):
     """DecoderLayer.forward (model.py:204-209) as one autograd node:

@@ -876,6 +876,183 @@ def residual_add(x, r):
     return out
 
 
+# --------------------------------------------------------------------- mixture-of-experts routing
+MOE_MAX_EXPERTS, MOE_MAX_TOPK = 128, 8   # csrc/moe.hip: two experts per lane of a wave; k choices in registers
+# (kind, words, device index) -> the route / plan workspace.  Every MoE layer of a device shares them: a
+# workspace lives only between the launches of ONE moe_route / moe_plan call, so calls ordered on one stream
+# (the training loop's: forward and backward run on torch's current stream) cannot meet in it.  MoE calls
+# on two streams of one device at the same time are not supported (as for the Muon and gradient-norm
+# workspaces above).
+_MOE_WS = {}
+
+
+def moe_capacity(T, E, k, capacity_factor):
+    """Rows C each expert owns of the [E C, H] buffers: min(ceil64(T), max(64, ceil64(cf T k / E))).
+    Items past an expert's C are dropped.  cf >= E / k gives ceil64(T), which never drops (a token
+    picks an expert at most once): the dropless setting, at E / k times the GEMM work."""
+    T, E, k = int(T), int(E), int(k)
+    _req(T >= 1 and E >= 1 and 1 <= k <= E, "moe_capacity: T >= 1 and 1 <= k <= E")
+    _req(capacity_factor > 0 and math.isfinite(capacity_factor), "moe_capacity: a finite capacity_factor > 0")
+    return min(_up(T), max(GRID, _up(math.ceil(capacity_factor * T * k / E))))
+
+
+def _moe_sizes(E, k, what):
+    _req(1 <= E <= MOE_MAX_EXPERTS, f"{what}: 1 <= num_experts <= {MOE_MAX_EXPERTS}, got {E}")
+    _req(1 <= k <= min(E, MOE_MAX_TOPK), f"{what}: 1 <= k <= min(num_experts, {MOE_MAX_TOPK}), got {k}")
+
+
+def _moe_ws(kind, words, device):
+    key = (kind, int(words), _dev_index(device))
+    ws = _MOE_WS.get(key)
+    if ws is None:
+        ws = _MOE_WS[key] = torch.empty(int(words), dtype=torch.int32, device=device)
+    return ws
+
+
+def _moe_rows(t, H, name):
+    _req(t.dtype == BF16 and t.is_cuda and t.dim() == 2 and t.stride(1) == 1 and t.shape[1] == H,
+         f"{name}: bf16 row-major device view [rows, {H}]")
+
+
+def _moe_items(t, T, k, dtype, name):
+    _req(t.dtype == dtype and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (T, k),
+         f"{name}: contiguous {dtype} [{T}, {k}]")
+
+
+def moe_route(logits, k, norm_topk_prob=True):
+    """logits [T, E] bf16 (a row-major view; stride >= E) -> (idx int32 [T, k], gate f32 [T, k],
+    probs f32 [T, E], counts int32 [E], aux f32 [1]): the f32 softmax over all E stored values, the k
+    largest stored values (ties to the lower expert, best first), their probabilities (divided by
+    their sum under norm_topk_prob), the selections per expert and the Switch load-balancing loss
+    aux = E sum_e (counts_e / (T k)) mean_t probs[t, e] (HF Mixtral's value is k times this)."""
+    _req(logits.dtype == BF16 and logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1,
+         "moe_route: logits as a bf16 row-major device view [T, E]")
+    T, E = logits.shape
+    k = int(k)
+    _req(T >= 1, "moe_route: at least one token")
+    _moe_sizes(E, k, "moe_route")
+    dev = logits.device
+    lib = _C.lib()
+    idx = torch.empty(T, k, dtype=torch.int32, device=dev)
+    gate = torch.empty(T, k, dtype=torch.float32, device=dev)
+    probs = torch.empty(T, E, dtype=torch.float32, device=dev)
+    counts = torch.empty(E, dtype=torch.int32, device=dev)
+    aux = torch.empty(1, dtype=torch.float32, device=dev)
+    words = lib.pt_moe_route_workspace(T, E)
+    _C.check(0 if words > 0 else words, "pt_moe_route_workspace")
+    rc = lib.pt_moe_route(_ptr(logits), logits.stride(0), T, E, k, int(bool(norm_topk_prob)), _ptr(idx), _ptr(gate),
+                          _ptr(probs), _ptr(counts), _ptr(aux), _ptr(_moe_ws("route", words, dev)), _C.stream_ptr(dev))
+    _C.check(rc, "pt_moe_route")
+    return idx, gate, probs, counts, aux
+
+
+def moe_plan(idx, E, C):
+    """idx int32 [T, k] -> (slot int32 [T, k], src int32 [E C]).  Item i = t k + j takes position
+    pos = the number of earlier items with its expert; slot = e C + pos, or -1 when pos >= C (dropped);
+    src[slot] = i, -1 for the rows nobody fills."""
+    _req(idx.dim() == 2, "moe_plan: idx [T, k]")
+    T, k = idx.shape
+    E, C = int(E), int(C)
+    _moe_items(idx, T, k, torch.int32, "idx")
+    _req(T >= 1 and C >= 1, "moe_plan: at least one token and one row per expert")
+    _moe_sizes(E, k, "moe_plan")
+    dev = idx.device
+    lib = _C.lib()
+    slot = torch.empty(T, k, dtype=torch.int32, device=dev)
+    src = torch.empty(E * C, dtype=torch.int32, device=dev)
+    words = lib.pt_moe_plan_workspace(T, E, k)
+    _C.check(0 if words > 0 else words, "pt_moe_plan_workspace")
+    rc = lib.pt_moe_plan(_ptr(idx), T, E, k, C, _ptr(slot), _ptr(src), _ptr(_moe_ws("plan", words, dev)),
+                         _C.stream_ptr(dev))
+    _C.check(rc, "pt_moe_plan")
+    return slot, src
+
+
+def moe_dispatch(x, src, k, out=None):
+    """xe[r] = x[src[r] // k] (a bit copy of token rows into their experts' rows), zeros where
+    src[r] < 0.  x [T, H] bf16, H % 64 == 0 -> xe [len(src), H]."""
+    _req(x.dim() == 2, "moe_dispatch: x [T, H]")
+    T, H = x.shape
+    _moe_rows(x, H, "x")
+    _req(H % GRID == 0, f"moe_dispatch: H % {GRID} == 0")
+    _req(src.dtype == torch.int32 and src.is_cuda and src.dim() == 1 and src.is_contiguous(), "src: contiguous int32 [E C]")
+    R = src.shape[0]
+    xe = out if out is not None else torch.empty(R, H, dtype=BF16, device=x.device)
+    _moe_rows(xe, H, "out")
+    _req(xe.shape[0] == R, "out: one row per entry of src")
+    rc = _C.lib().pt_moe_dispatch(_ptr(x), x.stride(0), _ptr(src), _ptr(xe), xe.stride(0), T, int(k), R, H,
+                                  _C.stream_ptr(x.device))
+    _C.check(rc, "pt_moe_dispatch")
+    return xe
+
+
+def moe_combine(ye, slot, gate=None, residual=None):
+    """y[t] = bf16(residual[t] + sum_j gate[t, j] ye[slot[t, j]]) over the kept items (slot >= 0), f32
+    in j order, one rounding.  gate None: weights of 1 -- the backward of moe_dispatch,
+    dx[t] = sum_j dxe[slot[t, j]]."""
+    _req(ye.dim() == 2 and slot.dim() == 2, "moe_combine: ye [E C, H], slot [T, k]")
+    R, H = ye.shape
+    T, k = slot.shape
+    _moe_rows(ye, H, "ye")
+    _req(H % GRID == 0, f"moe_combine: H % {GRID} == 0")
+    _moe_items(slot, T, k, torch.int32, "slot")
+    if gate is not None:
+        _moe_items(gate, T, k, torch.float32, "gate")
+    if residual is not None:
+        _moe_rows(residual, H, "residual")
+        _req(residual.shape[0] == T, "residual: one row per token")
+    y = torch.empty(T, H, dtype=BF16, device=ye.device)
+    rc = _C.lib().pt_moe_combine(_ptr(ye), ye.stride(0), _ptr(slot), _ptr(gate), _ptr(residual),
+                                 residual.stride(0) if residual is not None else 0, _ptr(y), H, T, k, R, H,
+                                 _C.stream_ptr(ye.device))
+    _C.check(rc, "pt_moe_combine")
+    return y
+
+
+def moe_combine_bwd(dy, ye, slot, src, gate):
+    """Backward of moe_combine's weighted sum: (dye [E C, H] = bf16(gate[item] dy[token]) per filled
+    row, zeros for empty ones; dgate f32 [T, k] = <dy[t], ye[slot[t, j]]>, 0 for dropped items)."""
+    _req(ye.dim() == 2 and slot.dim() == 2, "moe_combine_bwd: ye [E C, H], slot [T, k]")
+    R, H = ye.shape
+    T, k = slot.shape
+    _moe_rows(ye, H, "ye")
+    _moe_rows(dy, H, "dy")
+    _req(H % GRID == 0, f"moe_combine_bwd: H % {GRID} == 0")
+    _req(dy.shape[0] == T, "dy: one row per token")
+    _moe_items(slot, T, k, torch.int32, "slot")
+    _moe_items(gate, T, k, torch.float32, "gate")
+    _req(src.dtype == torch.int32 and src.is_cuda and src.is_contiguous() and tuple(src.shape) == (R,),
+         "src: contiguous int32 [E C]")
+    dye = torch.empty(R, H, dtype=BF16, device=ye.device)
+    dgate = torch.empty(T, k, dtype=torch.float32, device=ye.device)
+    rc = _C.lib().pt_moe_combine_bwd(_ptr(dy), dy.stride(0), _ptr(ye), ye.stride(0), _ptr(slot), _ptr(src), _ptr(gate),
+                                     _ptr(dye), H, _ptr(dgate), T, k, R, H, _C.stream_ptr(ye.device))
+    _C.check(rc, "pt_moe_combine_bwd")
+    return dye, dgate
+
+
+def moe_route_bwd(dgate, probs, idx, counts, d_aux=None, norm_topk_prob=True):
+    """dlogits bf16 [T, E]: the backward of moe_route's gate (selection fixed at idx, renormalisation,
+    softmax) on dgate [T, k], plus d_aux (an f32 device scalar, read on the device; None: 0) times
+    the gradient of aux, which flows through the mean probabilities only."""
+    _req(probs.dim() == 2 and idx.dim() == 2, "moe_route_bwd: probs [T, E], idx [T, k]")
+    T, E = probs.shape
+    k = idx.shape[1]
+    _moe_sizes(E, k, "moe_route_bwd")
+    _moe_items(probs, T, E, torch.float32, "probs")
+    _moe_items(idx, T, k, torch.int32, "idx")
+    _moe_items(dgate, T, k, torch.float32, "dgate")
+    _req(counts.dtype == torch.int32 and counts.is_cuda and counts.is_contiguous() and counts.numel() == E,
+         "counts: contiguous int32 [E]")
+    if d_aux is not None:
+        _req(d_aux.dtype == torch.float32 and d_aux.is_cuda and d_aux.numel() == 1, "d_aux: an f32 device scalar")
+    dlogits = torch.empty(T, E, dtype=BF16, device=probs.device)
+    rc = _C.lib().pt_moe_route_bwd(_ptr(dgate), _ptr(probs), _ptr(idx), _ptr(counts), _ptr(d_aux),
+                                   int(bool(norm_topk_prob)), _ptr(dlogits), E, T, E, k, _C.stream_ptr(probs.device))
+    _C.check(rc, "pt_moe_route_bwd")
+    return dlogits
+
+
 # ---------------------------------------------------------------------------- device status
 STATUS_BAD_TARGET = 1   # PT_STATUS_BAD_TARGET (include/picotron_hip.h)
 STATUS_NONFINITE_GRAD = 2   # PT_STATUS_NONFINITE_GRAD
@@ -1833,6 +2010,107 @@ def linear_dgrad_swiglu(dy2d, wd, gu):
     _gemm(dy2d, dy2d.stride(0), 1, [wd], [I], [0, I], 0, 0, [dgu], [dgu.stride(0)], [0, T], T, I, H, EPI_SWIGLU_BWD,
           residual=gu, ldr=gu.stride(0))
     return dgu
+
+
+# ------------------------------------------------------------------ MoE expert GEMMs (grouped)
+# Expert e's tokens are rows [e C, (e + 1) C) of the [E C, *] buffers (moe_dispatch), C on the
+# 64-grid, so every expert is one plain same-layout problem: MOE_GROUP of them per pt_gemm_grouped
+# launch, the tile picked over the group.  The SwiGLU rides in the epilogues where the 8-phase tile
+# takes the shape (swiglu_fusable on C), else it is one strided call over the whole buffer; the two
+# forms give the same bits, as for the dense MLP.
+MOE_GROUP = 4   # pt_gemm_grouped takes at most 4 problems
+
+
+def _moe_gemm(label, probs, a_kcontig, b_kcontig, epilogue, mnk, dev):
+    M, N, K = mnk
+    for lo in range(0, len(probs), MOE_GROUP):
+        grp = probs[lo:lo + MOE_GROUP]
+        n = len(grp)
+        arr = (_C.GemmProblem * n)(*grp)
+        rc = _timed(f"moe {label} {n}x{M}x{N}x{K}", 2.0 * n * M * N * K, float(n * _alg_bytes(M, N, K, epilogue)),
+                    _C.lib().pt_gemm_grouped, arr, n, int(a_kcontig), int(b_kcontig), int(epilogue), -1,
+                    _C.stream_ptr(dev))
+        _C.check(rc, f"pt_gemm_grouped(moe {label}: {n} x M={M}, N={N}, K={K}, epi={epilogue})")
+
+
+def _moe_expert_shapes(buf, ws, C, what):
+    """E of an expert buffer [E C, cols] against its per-expert weights."""
+    _bf16_rowmajor(buf, what)
+    E = len(ws)
+    _req(E >= 1 and buf.shape[0] == E * C and buf.is_contiguous(), f"{what}: contiguous [E C, cols], E = {E}, C = {C}")
+    _req(C % GRID == 0 and buf.shape[1] % GRID == 0, f"{what}: C and the row width on the {GRID}-grid")
+    return E
+
+
+def _moe_weights(ws, shape, what):
+    for w in ws:
+        _req(w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == tuple(shape), f"{what}: contiguous bf16 {shape}")
+
+
+def moe_experts_fwd(xe, wgs, wus, wds, C, fuse=True):
+    """xe [E C, H] -> (gu [E C, 2I] = [x Wg_e^T | x Wu_e^T], hh [E C, I] = swiglu, ye [E C, H] =
+    hh Wd_e^T), each expert on its own C rows."""
+    E = _moe_expert_shapes(xe, wgs, C, "xe")
+    H, I = xe.shape[1], wgs[0].shape[0]
+    _req(len(wus) == E and len(wds) == E and I % GRID == 0, f"moe_experts_fwd: E weights each, I % {GRID} == 0")
+    _moe_weights(list(wgs) + list(wus), (I, H), "gate / up weights")
+    _moe_weights(wds, (H, I), "down weights")
+    dev = xe.device
+    gu = torch.empty(E * C, 2 * I, dtype=BF16, device=dev)
+    hh = torch.empty(E * C, I, dtype=BF16, device=dev)
+    ye = torch.empty(E * C, H, dtype=BF16, device=dev)
+    rows = [slice(e * C, (e + 1) * C) for e in range(E)]
+    if fuse and swiglu_fusable(C, I, H=H):
+        _moe_gemm("gate|up+swiglu", [_problem(xe[r], H, [wg, wu], [H, H], [0, I, 2 * I], 0, [hh[r], gu[r]], [I, 2 * I],
+                                              [0, C], C, 2 * I, H) for r, wg, wu in zip(rows, wgs, wus)],
+                  1, 1, EPI_SWIGLU_FWD, (C, 2 * I, H), dev)
+    else:
+        _moe_gemm("gate|up", [_problem(xe[r], H, [wg, wu], [H, H], [0, I, 2 * I], 0, [gu[r]], [2 * I], [0, C], C, 2 * I, H)
+                              for r, wg, wu in zip(rows, wgs, wus)], 1, 1, EPI_BF16, (C, 2 * I, H), dev)
+        swiglu_fwd(gu[:, :I], gu[:, I:], out=hh)
+    _moe_gemm("down", [_problem(hh[r], I, [wd], [I], [0, H], 0, [ye[r]], [H], [0, C], C, H, I)
+                       for r, wd in zip(rows, wds)], 1, 1, EPI_BF16, (C, H, I), dev)
+    return gu, hh, ye
+
+
+def moe_experts_dgrad_down(dye, wds, gu, C, fuse=True):
+    """dye [E C, H] -> (dgu [E C, 2I] = the SwiGLU backward of dhh = dye Wd_e on the saved gate|up,
+    dhh [E C, I] or None where the epilogue-fused form never stores it)."""
+    E = _moe_expert_shapes(dye, wds, C, "dye")
+    H, I = dye.shape[1], wds[0].shape[1]
+    _moe_weights(wds, (H, I), "down weights")
+    _bf16_rowmajor(gu, "gu")
+    _req(tuple(gu.shape) == (E * C, 2 * I) and gu.is_contiguous() and I % GRID == 0, "gu: contiguous [E C, 2I]")
+    dev = dye.device
+    dgu = torch.empty_like(gu)
+    rows = [slice(e * C, (e + 1) * C) for e in range(E)]
+    if fuse and swiglu_fusable(C, I, backward=True, H=H):
+        probs = []
+        for r, wd in zip(rows, wds):
+            pr = _problem(dye[r], H, [wd], [I], [0, I], 0, [dgu[r]], [2 * I], [0, C], C, I, H)
+            pr.residual, pr.ldr = _ptr(gu[r]), 2 * I
+            probs.append(pr)
+        _moe_gemm("down dX+swiglu", probs, 1, 0, EPI_SWIGLU_BWD, (C, I, H), dev)
+        return dgu, None
+    dhh = torch.empty(E * C, I, dtype=BF16, device=dev)
+    _moe_gemm("down dX", [_problem(dye[r], H, [wd], [I], [0, H], 1, [dhh[r]], [I], [0, C], C, I, H)
+                          for r, wd in zip(rows, wds)], 1, 0, EPI_BF16, (C, I, H), dev)
+    swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:])
+    return dgu, dhh
+
+
+def moe_experts_dgrad_gate_up(dgu, wgs, wus, C):
+    """dgu [E C, 2I] -> dxe [E C, H] = dg Wg_e + du Wu_e."""
+    E = _moe_expert_shapes(dgu, wgs, C, "dgu")
+    I, H = wgs[0].shape
+    _req(len(wus) == E and dgu.shape[1] == 2 * I, "moe_experts_dgrad_gate_up: dgu [E C, 2I], E weights each")
+    _moe_weights(list(wgs) + list(wus), (I, H), "gate / up weights")
+    dev = dgu.device
+    dxe = torch.empty(E * C, H, dtype=BF16, device=dev)
+    _moe_gemm("gate|up dX", [_problem(dgu[e * C:(e + 1) * C], 2 * I, [wg, wu], [H, H], [0, I, 2 * I], 1,
+                                      [dxe[e * C:(e + 1) * C]], [H], [0, C], C, H, 2 * I)
+                             for e, (wg, wu) in enumerate(zip(wgs, wus))], 1, 0, EPI_BF16, (C, H, 2 * I), dev)
+    return dxe
 
 
 def _splitk_enabled():

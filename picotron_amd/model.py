@@ -17,6 +17,7 @@ be called on their own (each is its own Function).  The token embedding is csrc/
 """
 import math
 import os
+import types
 
 import torch
 import torch.nn as nn
@@ -300,8 +301,64 @@ class MLP(nn.Module):
         return FN.MLPFunction.apply(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight)
 
 
+class MoE(nn.Module):
+    """A mixture-of-experts MLP (Mixtral / Qwen3-MoE / OLMoE; not in the reference): `router`
+    [num_experts, hidden] and `experts`, a ModuleList of MLP at config.moe_intermediate_size (default
+    intermediate_size) -- state_dict keys mlp.router.weight, mlp.experts.{e}.gate_proj.weight, ...
+    Every token takes its num_experts_per_tok best experts by router logit; expert e owns C rows
+    (kernels.moe_capacity with config.moe_capacity_factor, default 1.25; >= num_experts /
+    num_experts_per_tok never drops) and the items past them are dropped: the residual carries the
+    token.  norm_topk_prob (default True) divides the chosen probabilities by their sum.
+    forward(x, residual) returns residual + MoE(x) and leaves the Switch load-balancing loss of this
+    call in self.aux_loss (functional.MoEFunction).  DP only: tensor / sequence / context / pipeline
+    parallelism are refused."""
+    _pt_moe = True
+
+    def __init__(self, config) -> None:
+        super().__init__()
+        m = pgm.current()
+        if m.tp_world_size > 1:
+            raise NotImplementedError("num_experts > 0 under tensor / sequence parallelism (tp > 1): experts are not sharded")
+        if m.cp_world_size > 1:
+            raise NotImplementedError("num_experts > 0 under context parallelism (cp > 1): the capacity is per rank")
+        if m.pp_world_size > 1:
+            raise NotImplementedError("num_experts > 0 under pipeline parallelism: the aux loss does not cross stages")
+        self.num_experts = int(config.num_experts)
+        self.top_k = int(getattr(config, "num_experts_per_tok", 2))
+        self.capacity_factor = float(getattr(config, "moe_capacity_factor", 1.25))
+        self.norm_topk_prob = bool(getattr(config, "norm_topk_prob", True))
+        inter = getattr(config, "moe_intermediate_size", None) or config.intermediate_size
+        if not 1 <= self.num_experts <= K.MOE_MAX_EXPERTS or not 1 <= self.top_k <= min(self.num_experts, K.MOE_MAX_TOPK):
+            raise ValueError(f"MoE: 1 <= num_experts <= {K.MOE_MAX_EXPERTS} and 1 <= num_experts_per_tok <= "
+                             f"min(num_experts, {K.MOE_MAX_TOPK}); got {self.num_experts}, {self.top_k}")
+        if config.hidden_size % K.GRID or inter % K.GRID:
+            raise ValueError(f"MoE: hidden_size and moe_intermediate_size on the {K.GRID}-grid")
+        self.router = Linear(config.hidden_size, self.num_experts, bias=False)
+        expert = types.SimpleNamespace(hidden_size=config.hidden_size, intermediate_size=inter)
+        self.experts = nn.ModuleList([MLP(expert) for _ in range(self.num_experts)])
+        self.aux_loss = None
+        self.stages = None   # a dict here receives clones of every call's intermediates (MoEFunction's stages=)
+        _init_uniform_fan_in(self.router.weight)
+
+    def reset_parameters(self):
+        _init_uniform_fan_in(self.router.weight)
+        for e in self.experts:
+            e.reset_parameters()
+
+    def forward(self, x, residual=None):
+        if residual is None:
+            residual = torch.zeros_like(x)
+        out, self.aux_loss = FN.MoEFunction.apply(
+            x, residual, self.router.weight, [e.gate_proj.weight for e in self.experts],
+            [e.up_proj.weight for e in self.experts], [e.down_proj.weight for e in self.experts], self.top_k,
+            self.capacity_factor, self.norm_topk_prob, self.stages)
+        return out
+
+
 class DecoderLayer(nn.Module):
-    """model.py:188-209: RMSNorm -> Attention -> residual -> RMSNorm -> MLP -> residual."""
+    """model.py:188-209: RMSNorm -> Attention -> residual -> RMSNorm -> MLP -> residual.  With
+    config.num_experts > 0 the MLP is a MoE and the layer is composed from the separate nodes
+    (RMSNormFunction -> AttentionFunction -> AddRMSNormFunction -> MoEFunction)."""
 
     def __init__(self, config, layer_idx):
         super().__init__()
@@ -309,7 +366,7 @@ class DecoderLayer(nn.Module):
         self.input_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.attention = Attention(config, layer_idx=layer_idx)
-        self.mlp = MLP(config)
+        self.mlp = MoE(config) if (getattr(config, "num_experts", 0) or 0) > 0 else MLP(config)
         self.layer_idx = layer_idx
         head_dim = config.hidden_size // config.num_attention_heads
         self._rope_args = (config.max_position_embeddings, head_dim, config.rope_theta)
@@ -358,6 +415,15 @@ class DecoderLayer(nn.Module):
         qk = at.qk_norm_args()   # (): no QK-norm; else its two weights, in the layer norms' flavour
         if qk and qk[2:] != (_norm_eps(n1), _norm_mode(n1)):
             raise ValueError("DecoderLayer: q_norm / k_norm must be the layer norms' flavour")
+        if isinstance(mlp, MoE):
+            if sp or zz:
+                raise NotImplementedError("a mixture-of-experts layer on a sharded residual stream (tp / cp > 1)")
+            eps, mode = _norm_eps(n1), _norm_mode(n1)
+            h1 = FN.RMSNormFunction.apply(x, n1.weight, eps, mode)
+            a = FN.AttentionFunction.apply(h1, *at.weights(), cos, sin, at.num_local_heads, at.num_local_kv_heads,
+                                           at.head_dim, band, *qk)
+            h2, z = FN.AddRMSNormFunction.apply(a, x, n2.weight, eps, mode)
+            return mlp(h2, z)
         return FN.DecoderLayerFunction.apply(
             x, n1.weight, n2.weight, *at.weights(), mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
             cos, sin, _norm_eps(n1), _norm_mode(n1), at.num_local_heads, at.num_local_kv_heads, at.head_dim, zz, sp,
@@ -435,8 +501,14 @@ class Llama(nn.Module):
             else:
                 # (ids of the full rows: a token-row shard of the stream has no band of its own)
                 band = FN.make_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids, window)
+        aux = None
         for layer in self.decoder_layers:
             x = layer(x) if band is None else layer(x, document_ids=band)
+            if isinstance(layer.mlp, MoE):
+                aux = layer.mlp.aux_loss if aux is None else aux + layer.mlp.aux_loss
+        # the sum of the MoE layers' load-balancing losses of this forward (a tensor with grad; None
+        # for dense models): train_step(moe_aux_loss=coef) adds coef times it to the loss
+        self.moe_aux_loss = aux
         x = self.final_norm(x)
         return lm_head(self.final_proj, x)
 

@@ -401,16 +401,19 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 # ------------------------------------------------------------------------------------ Muon
 _MUON_MATRICES = ("attention.q_proj.weight", "attention.k_proj.weight", "attention.v_proj.weight",
                   "attention.out_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+_MUON_EXPERT_MATRICES = ("gate_proj.weight", "up_proj.weight", "down_proj.weight")   # under mlp.experts.{e}.
 
 
 def split_muon_params(model):
     """(matrices, rest) of a Llama: `matrices` the decoder layers' q / k / v / out / gate / up / down
-    projection weights (what Muon orthogonalises), `rest` everything else -- the embedding,
-    final_proj, every norm weight (QK-norm's included) and the biases -- for AdamW.  By parameter
-    name, in named_parameters() order."""
+    projection weights (what Muon orthogonalises; of a mixture-of-experts layer every expert's
+    mlp.experts.{e}.gate / up / down), `rest` everything else -- the embedding, final_proj, every norm
+    weight (QK-norm's included), an MoE layer's mlp.router.weight and the biases -- for AdamW.  By
+    parameter name, in named_parameters() order."""
     matrices, rest = [], []
     for name, p in model.named_parameters():
-        hidden = "decoder_layers." in name and name.endswith(_MUON_MATRICES) and p.dim() == 2
+        expert = ".mlp.experts." in name and name.endswith(_MUON_EXPERT_MATRICES)
+        hidden = "decoder_layers." in name and (name.endswith(_MUON_MATRICES) or expert) and p.dim() == 2
         (matrices if hidden else rest).append(p)
     return matrices, rest
 

@@ -44,6 +44,9 @@ class PipelineParallel(nn.Module):
 
     def __init__(self, model, config):
         super().__init__()
+        from ..functional import has_moe
+        if has_moe(model):
+            raise NotImplementedError("PipelineParallel: mixture-of-experts layers (their aux loss does not cross stages)")
         m = pgm.process_group_manager
         self.layer_distribution = self.distribute_layers(config.num_hidden_layers)
         self.embedding = model.embedding if m.pp_is_first_stage else nn.Identity()

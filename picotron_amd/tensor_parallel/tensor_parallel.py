@@ -23,6 +23,9 @@ from .tp_communications import (GatherFromModelParallelRegion, ReduceFromModelPa
 
 
 def apply_tensor_parallel(model):
+    if FN.has_moe(model):
+        raise NotImplementedError("apply_tensor_parallel: mixture-of-experts layers are not sharded (tp / sequence "
+                                  "parallelism with num_experts > 0)")
     def _replace_module(_module, _linear_proj_name, _style, args={}):
         assert _style in ["column", "row", "vocab"]
         linear_layer = getattr(_module, _linear_proj_name)

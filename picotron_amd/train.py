@@ -83,7 +83,12 @@ class SyntheticMicroBatchDataLoader:
                 "hidden_states": None}
 
 
-def train_step(model, data_loader, device, on_microbatch=None, read_loss=True, z_loss=0.0):
+def _moe_module(model):
+    """The module whose forward leaves `moe_aux_loss` (model.Llama), through a data-parallel wrapper."""
+    return model.module if hasattr(model, "module") and not hasattr(model, "decoder_layers") else model
+
+
+def train_step(model, data_loader, device, on_microbatch=None, read_loss=True, z_loss=0.0, moe_aux_loss=0.0):
     """train.py:29-55 with the fused HIP cross-entropy; returns the accumulated loss (float).
     on_microbatch(i): optional hook called before micro-batch i (bench.py samples its GEMM timing).
     read_loss=False: return the loss as a device scalar instead, so that the caller can enqueue the
@@ -97,7 +102,17 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True, z
     z_loss > 0: the auxiliary z-loss  z_loss * logsumexp(logits)^2  per token is part of every
     micro-batch's loss (functional.cross_entropy's keyword) and of the returned loss; the step's z
     part, sum_i z_part_i / grad_acc, is left as an f32 device scalar in `model.z_loss_part` (None when
-    z_loss == 0) -- reading it is the caller's synchronisation, not this function's."""
+    z_loss == 0) -- reading it is the caller's synchronisation, not this function's.
+    moe_aux_loss > 0 (a mixture-of-experts model): coef * model.moe_aux_loss / grad_acc -- the sum of
+    the MoE layers' Switch load-balancing losses of the micro-batch's forward -- is added to every
+    micro-batch's loss before its backward, and to the returned loss; the step's aux part,
+    sum_i aux_i / grad_acc (without the coefficient), is left as an f32 device scalar in
+    `model.moe_aux_part` (None when moe_aux_loss == 0)."""
+    moe_coef = float(moe_aux_loss)
+    if not moe_coef >= 0.0 or moe_coef == float("inf"):
+        raise ValueError(f"train_step: moe_aux_loss must be a finite coefficient >= 0, got {moe_aux_loss}")
+    moe_on = moe_coef > 0
+    acc_aux = torch.zeros((), dtype=torch.float32, device=device) if moe_on else None
     acc_loss = torch.zeros((), dtype=torch.float32, device=device)
     z_on = K.z_coef(z_loss) > 0
     acc_z = torch.zeros((), dtype=torch.float32, device=device) if z_on else None
@@ -127,6 +142,12 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True, z
                 acc_z += z_part / ga
             else:
                 loss = FN.cross_entropy(outputs, target_ids, reduction="mean") / ga
+            if moe_on:
+                aux = _moe_module(model).moe_aux_loss
+                if aux is None:
+                    raise ValueError("train_step: moe_aux_loss > 0 needs a model with mixture-of-experts layers")
+                loss = loss + aux * (moe_coef / ga)
+                acc_aux += aux.detach() / ga
             # micro-batches (2 j, 2 j + 1) share their weight-gradient launches (functional.WgradPairing):
             # the first defers, the second launches K = 2 T GEMMs; an odd last micro-batch on its own
             if pairing:
@@ -138,6 +159,7 @@ def train_step(model, data_loader, device, on_microbatch=None, read_loss=True, z
             FN.wgrad_pairing(None)
             FN.flush_wgrad_pairs()
     model.z_loss_part = acc_z
+    model.moe_aux_part = acc_aux
     return read_step_loss(acc_loss, device) if read_loss else acc_loss
 
 
@@ -205,6 +227,8 @@ class GraphedTrainStep:
     def __init__(self, model, data_loader, device, warmup=2, z_loss=0.0):
         if not GraphedTrainStep.supported(model):
             raise ValueError("GraphedTrainStep: data-parallel wrappers, CP and PP are not captured")
+        if FN.has_moe(model):
+            raise NotImplementedError("GraphedTrainStep: mixture-of-experts layers (moe_aux_loss is not captured)")
         self.model, self.loader, self.device = model, data_loader, torch.device(device)
         self.warmup = max(1, warmup)
         self.graph = None
