@@ -27,11 +27,20 @@
 // One 256-thread workgroup per row; the row is held in registers (NC 16-byte chunks per
 // thread) so HBM sees exactly one read and one write of the logits: 4*V bytes per row, the
 // roofline figure in DESIGN.md.  Rows longer than 256*8*32 elements take the two-pass variant.
+//
+// What the kernels share is written once: ms_merge (the online (max, sum-exp) merge), block_ms (the
+// block reduction of such pairs), merge_tile_stats (the lm_head GEMM's tile statistics of a row),
+// Target / store_row_loss (a row's target, its NaN-on-bad-target LSE and status bit; its loss and z
+// part) and grad_chunk (eight gradient elements, in either of the two exp roundings).  On the host, with_z picks
+// the Z instantiation and logits_ok / stats_ok hold the argument checks several entry points make.
 #include "common.h"
+
+#include <type_traits>
 
 namespace {
 
 constexpr int kThreads = 256;
+constexpr float kLog2e = 1.4426950408889634f;
 
 __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) {
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
@@ -45,13 +54,54 @@ __device__ __forceinline__ float block_reduce(float v, float* red, bool is_max) 
   return r;
 }
 
-// z lse^2: two f32 multiplies, and the loss's sum kept a separate rounding (no contraction)
+// (m, s = sum exp(x - m)) <- its merge with (om, os); a side that has seen nothing finite (max -inf)
+// adds 0, not exp(-inf - -inf)
+__device__ __forceinline__ void ms_merge(float& m, float& s, float om, float os) {
+  const float nm = fmaxf(m, om);
+  s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
+  m = nm;
+}
+
+// the block's (m, s) pairs: merged across each wave by shuffles, one pair per wave left in red / red2
+// (a barrier), which block_ms_total then combines in wave order
+__device__ __forceinline__ void block_ms(float m, float s, float* red, float* red2) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) ms_merge(m, s, __shfl_xor(m, o, 64), __shfl_xor(s, o, 64));
+  if (lane == 0) { red[wid] = m; red2[wid] = s; }
+  __syncthreads();
+}
+__device__ __forceinline__ void block_ms_total(const float* red, const float* red2, float& M, float& S) {
+  M = red[0];
+  for (int i = 1; i < kThreads / 64; ++i) M = fmaxf(M, red[i]);
+  S = 0.f;
+  for (int i = 0; i < kThreads / 64; ++i) S += red2[i] * __expf(red[i] - M);
+}
+
+// a row's target: valid = not ignore_index; bad = valid and outside [0, V)
+struct Target {
+  int64_t t;
+  bool valid, bad;
+  __device__ __forceinline__ Target(const int64_t* __restrict__ tgt, int64_t row, int64_t ignore_index, int64_t V)
+      : t(tgt[row]), valid(t != ignore_index), bad(valid && (t < 0 || t >= V)) {}
+  // the target's logit in the row x (0 where there is none to read)
+  __device__ __forceinline__ float logit(const uint16_t* __restrict__ x) const { return (valid && !bad) ? bf2f(x[t]) : 0.f; }
+  // lse = m + log s; NaN for a bad target
+  __device__ __forceinline__ float lse(float m, float s) const { return bad ? __builtin_nanf("") : m + __logf(s); }
+  // a bad target's status bit (torch's device-side assert, without the trap)
+  __device__ __forceinline__ void report(int* __restrict__ status) const {
+    if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
+  }
+};
+
+// the loss of a row (0 for an ignored one) and its z part z lse^2: two f32 multiplies, and the loss's
+// sum kept a separate rounding (no contraction)
 template <bool Z>
 __device__ __forceinline__ void store_row_loss(float* __restrict__ row_loss, float* __restrict__ row_z, int64_t row,
-                                               bool valid, float lse, float xt, float z) {
+                                               const Target& tg, float lse, float xt, float z) {
 #pragma clang fp contract(off)
-  float loss = valid ? lse - xt : 0.f, rz = 0.f;
-  if (Z && valid) {
+  float loss = tg.valid ? lse - xt : 0.f, rz = 0.f;
+  if (Z && tg.valid) {
     rz = z * (lse * lse);
     loss = loss + rz;
   }
@@ -65,6 +115,21 @@ __device__ __forceinline__ float z_factor(bool valid, float lse, float z) {
   return (Z && valid) ? fmaf(2.f * z, lse, 1.f) : 1.f;
 }
 
+// chunk c of a gradient row: d[8c + j] = (p_j cz - onehot) g, with p_j = exp(x_j - lse) in one of two
+// roundings: EXP2 false: __expf(x_j - a), a = lse;  EXP2 true: exp2(fma(x_j, log2e, a)), a = -lse log2e
+template <bool Z, bool EXP2>
+__device__ __forceinline__ void grad_chunk(const bf16x8& v, uint16_t* d, int c, int64_t t, float a, float cz, float g) {
+  float f[8];
+  unpack8(v, f);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float p = EXP2 ? __builtin_amdgcn_exp2f(fmaf(f[j], kLog2e, a)) : __expf(f[j] - a);
+    if (Z) p *= cz;
+    f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
+  }
+  st8(d + c * 8, pack8(f));
+}
+
 template <int NC, bool Z>
 __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict__ logits, int64_t ls,
                                                       const int64_t* __restrict__ tgt, uint16_t* dlogits,
@@ -76,12 +141,10 @@ __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict
   const int64_t row = blockIdx.x;
   const uint16_t* x = logits + row * ls;
   const int nch = V >> 3;
-  const int64_t t = tgt[row];
-  const bool valid = t != ignore_index;
-  const bool bad = valid && (t < 0 || t >= V);
+  const Target tg(tgt, row, ignore_index, V);
   // read the target logit before any barrier: later writes may overwrite x in place
-  const float xt = (threadIdx.x == 0 && valid && !bad) ? bf2f(x[t]) : 0.f;
-  if (bad && threadIdx.x == 0 && status) status[0] = PT_STATUS_BAD_TARGET;
+  const float xt = threadIdx.x == 0 ? tg.logit(x) : 0.f;
+  if (threadIdx.x == 0) tg.report(status);
   bf16x8 v[NC];
   float mx = -INFINITY;
 #pragma unroll
@@ -108,26 +171,16 @@ __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict
     }
   }
   se = block_reduce(se, red, false);
-  const float lse = bad ? __builtin_nanf("") : mx + __logf(se);
-  const float g = valid ? scale * (inv_count ? *inv_count : 1.0f) : 0.f;
-  if (threadIdx.x == 0) store_row_loss<Z>(row_loss, row_z, row, valid, lse, xt, z);
+  const float lse = tg.lse(mx, se);
+  const float g = tg.valid ? scale * (inv_count ? *inv_count : 1.0f) : 0.f;
+  if (threadIdx.x == 0) store_row_loss<Z>(row_loss, row_z, row, tg, lse, xt, z);
   if (!dlogits) return;  // loss-only (forward) launch
-  const float cz = z_factor<Z>(valid, lse, z);
+  const float cz = z_factor<Z>(tg.valid, lse, z);
   uint16_t* d = dlogits + row * ds;
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
     const int c = threadIdx.x + i * kThreads;
-    if (c < nch) {
-      float f[8];
-      unpack8(v[i], f);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float p = __expf(f[j] - lse);
-        if (Z) p *= cz;
-        f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
-      }
-      st8(d + c * 8, pack8(f));
-    }
+    if (c < nch) grad_chunk<Z, false>(v[i], d, c, tg.t, lse, cz, g);
   }
 }
 
@@ -157,44 +210,21 @@ __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __re
     for (int j = 0; j < 8; ++j) s += __expf(f[j] - cm);
     m = cm;
   }
-  // combine (m, s) pairs across the block
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-    const float nm = fmaxf(m, om);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
-    m = nm;
+  block_ms(m, s, red, red2);
+  float M, S;
+  block_ms_total(red, red2, M, S);
+  const Target tg(tgt, row, ignore_index, V);
+  const float lse = tg.lse(M, S);
+  const float g = tg.valid ? scale * (inv_count ? *inv_count : 1.0f) : 0.f;
+  if (threadIdx.x == 0) {
+    store_row_loss<Z>(row_loss, row_z, row, tg, lse, tg.logit(x), z);
+    tg.report(status);
   }
-  if (lane == 0) { red[wid] = m; red2[wid] = s; }
-  __syncthreads();
-  float M = red[0];
-  for (int i = 1; i < kThreads / 64; ++i) M = fmaxf(M, red[i]);
-  float S = 0.f;
-  for (int i = 0; i < kThreads / 64; ++i) S += red2[i] * __expf(red[i] - M);
-  const int64_t t = tgt[row];
-  const bool valid = t != ignore_index;
-  const bool bad = valid && (t < 0 || t >= V);
-  const float lse = bad ? __builtin_nanf("") : M + __logf(S);
-  const float g = valid ? scale * (inv_count ? *inv_count : 1.0f) : 0.f;
-  if (threadIdx.x == 0)
-    store_row_loss<Z>(row_loss, row_z, row, valid, lse, (valid && !bad) ? bf2f(x[t]) : 0.f, z);
-  if (bad && threadIdx.x == 0 && status) status[0] = PT_STATUS_BAD_TARGET;
   __syncthreads();  // x[t] read before any in-place write
   if (!dlogits) return;
-  const float cz = z_factor<Z>(valid, lse, z);
+  const float cz = z_factor<Z>(tg.valid, lse, z);
   uint16_t* d = dlogits + row * ds;
-  for (int c = threadIdx.x; c < nch; c += kThreads) {
-    float f[8];
-    unpack8(ld8(x + c * 8), f);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float p = __expf(f[j] - lse);
-      if (Z) p *= cz;
-      f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
-    }
-    st8(d + c * 8, pack8(f));
-  }
+  for (int c = threadIdx.x; c < nch; c += kThreads) grad_chunk<Z, false>(ld8(x + c * 8), d, c, tg.t, lse, cz, g);
 }
 
 // ---- streaming pair: the autograd forward saves the row LSE so the backward needs no reduction
@@ -204,7 +234,6 @@ __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __re
 // register-resident ce_kernel above caps occupancy at ~4 waves per SIMD for V = 49152).
 // bwd: purely elementwise  dl = (exp(x - lse_row) - onehot) * g,  4 chunks in flight per thread.
 constexpr int kUnroll = 4;
-constexpr float kLog2e = 1.4426950408889634f;
 
 template <bool Z>
 __global__ __launch_bounds__(kThreads) void ce_fwd_stream_kernel(const uint16_t* __restrict__ logits, int64_t ls,
@@ -251,71 +280,55 @@ __global__ __launch_bounds__(kThreads) void ce_fwd_stream_kernel(const uint16_t*
     }
     m = cm;
   }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
-    const float nm = fmaxf(m, om);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (om == -INFINITY ? 0.f : os * __expf(om - nm));
-    m = nm;
-  }
-  if (lane == 0) { red[wid] = m; red2[wid] = s; }
-  __syncthreads();
+  block_ms(m, s, red, red2);
   if (threadIdx.x == 0) {
-    float M = red[0];
-    for (int i = 1; i < kThreads / 64; ++i) M = fmaxf(M, red[i]);
-    float S = 0.f;
-    for (int i = 0; i < kThreads / 64; ++i) S += red2[i] * __expf(red[i] - M);
-    const int64_t t = tgt[row];
-    const bool valid = t != ignore_index;
-    const bool bad = valid && (t < 0 || t >= V);
-    const float lse = bad ? __builtin_nanf("") : M + __logf(S);
-    row_lse[row] = lse;
-    store_row_loss<Z>(row_loss, row_z, row, valid, lse, (valid && !bad) ? bf2f(x[t]) : 0.f, z);
-    if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
+    float M, S;
+    block_ms_total(red, red2, M, S);
+    const Target tg(tgt, row, ignore_index, V);
+    const float lse = row_lse[row] = tg.lse(M, S);
+    store_row_loss<Z>(row_loss, row_z, row, tg, lse, tg.logit(x), z);
+    tg.report(status);
   }
 }
 
-// Forward from the lm_head GEMM's statistics (gemm.hip EPI_CE_STATS): float2 stats[b][row] =
-// (m_b, s_b = sum exp(x - m_b)) over the nblk column tiles -> lse = M + log(sum_b s_b exp(m_b - M)),
-// M = max_b m_b; row_loss = lse - x[t].  A block = 32 rows x 8 tile groups: each lane merges every
-// 8th tile of its row online (32 lanes read 256 contiguous bytes of one tile's pairs), then the 8
-// partial merges of a row are combined in a fixed order.  The [rows, V] logits are not read again
-// (only x[t]).
+// The lm_head GEMM's statistics (gemm.hip EPI_CE_STATS): float2 stats[b][row] = (m_b, s_b = sum exp(x -
+// m_b)) over the nblk column tiles, merged to the row's (m, s).  A block = 32 rows x 8 tile groups: each
+// lane merges every 8th tile of its row online (32 lanes read 256 contiguous bytes of one tile's pairs),
+// then the 8 partial merges of a row are combined in a fixed order by the thread that gets `true`.
 constexpr int kStatRows = 32, kStatGroups = 8;
+__device__ __forceinline__ bool merge_tile_stats(const float2* __restrict__ stats, int nblk, int64_t rows, int64_t& row,
+                                                 float& m, float& s) {
+  __shared__ float2 part[kStatGroups][kStatRows];
+  const int r = threadIdx.x % kStatRows, grp = threadIdx.x / kStatRows;
+  row = (int64_t)blockIdx.x * kStatRows + r;
+  m = -INFINITY, s = 0.f;
+  if (row < rows) {
+    for (int b = grp; b < nblk; b += kStatGroups) {
+      const float2 p = stats[(int64_t)b * rows + row];
+      ms_merge(m, s, p.x, p.y);
+    }
+  }
+  part[grp][r] = make_float2(m, s);
+  __syncthreads();
+  if (grp != 0 || row >= rows) return false;
+  for (int g = 1; g < kStatGroups; ++g) ms_merge(m, s, part[g][r].x, part[g][r].y);
+  return true;
+}
+
+// Forward from those statistics: lse = m + log s, row_loss = lse - x[t].  The [rows, V] logits are not
+// read again (only x[t]).
 template <bool Z>
 __global__ __launch_bounds__(kStatRows * kStatGroups) void ce_fwd_stats_kernel(
     const uint16_t* __restrict__ logits, int64_t ls, const int64_t* __restrict__ tgt,
     const float2* __restrict__ stats, int nblk, float* __restrict__ row_loss, float* __restrict__ row_lse,
     int64_t rows, int V, int64_t ignore_index, int* __restrict__ status, float z, float* __restrict__ row_z) {
-  __shared__ float2 part[kStatGroups][kStatRows];
-  const int r = threadIdx.x % kStatRows, grp = threadIdx.x / kStatRows;
-  const int64_t row = (int64_t)blockIdx.x * kStatRows + r;
-  float m = -INFINITY, s = 0.f;
-  if (row < rows) {
-    for (int b = grp; b < nblk; b += kStatGroups) {
-      const float2 p = stats[(int64_t)b * rows + row];
-      const float nm = fmaxf(m, p.x);
-      s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (p.x == -INFINITY ? 0.f : p.y * __expf(p.x - nm));
-      m = nm;
-    }
-  }
-  part[grp][r] = make_float2(m, s);
-  __syncthreads();
-  if (grp == 0 && row < rows) {
-    for (int g = 1; g < kStatGroups; ++g) {
-      const float2 p = part[g][r];
-      const float nm = fmaxf(m, p.x);
-      s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (p.x == -INFINITY ? 0.f : p.y * __expf(p.x - nm));
-      m = nm;
-    }
-    const int64_t t = tgt[row];
-    const bool valid = t != ignore_index;
-    const bool bad = valid && (t < 0 || t >= V);
-    const float lse = bad ? __builtin_nanf("") : m + __logf(s);
-    row_lse[row] = lse;
-    store_row_loss<Z>(row_loss, row_z, row, valid, lse, (valid && !bad) ? bf2f(logits[row * ls + t]) : 0.f, z);
-    if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
+  int64_t row;
+  float m, s;
+  if (merge_tile_stats(stats, nblk, rows, row, m, s)) {
+    const Target tg(tgt, row, ignore_index, V);
+    const float lse = row_lse[row] = tg.lse(m, s);
+    store_row_loss<Z>(row_loss, row_z, row, tg, lse, tg.logit(logits + row * ls), z);
+    tg.report(status);
   }
 }
 
@@ -384,17 +397,7 @@ __global__ __launch_bounds__(kThreads) void ce_bwd_stream_kernel(const uint16_t*
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       const int c = c0 + u * kThreads;
-      if (c < nch) {
-        float f[8];
-        unpack8(v[u], f);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          float p = __builtin_amdgcn_exp2f(fmaf(f[j], kLog2e, nl2));
-          if (Z) p *= cz;
-          f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
-        }
-        st8(d + c * 8, pack8(f));
-      }
+      if (c < nch) grad_chunk<Z, true>(v[u], d, c, t, nl2, cz, g);
     }
   }
 }
@@ -408,27 +411,9 @@ __global__ __launch_bounds__(kStatRows * kStatGroups) void ce_vp_partial_kernel(
     const uint16_t* __restrict__ logits, int64_t ls, const int64_t* __restrict__ tgt,
     const float2* __restrict__ stats, int nblk, float4* __restrict__ part_out, int64_t rows, int Vs,
     int64_t vocab_lo) {
-  __shared__ float2 part[kStatGroups][kStatRows];
-  const int r = threadIdx.x % kStatRows, grp = threadIdx.x / kStatRows;
-  const int64_t row = (int64_t)blockIdx.x * kStatRows + r;
-  float m = -INFINITY, s = 0.f;
-  if (row < rows) {
-    for (int b = grp; b < nblk; b += kStatGroups) {   // ce_fwd_stats_kernel's merge
-      const float2 p = stats[(int64_t)b * rows + row];
-      const float nm = fmaxf(m, p.x);
-      s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (p.x == -INFINITY ? 0.f : p.y * __expf(p.x - nm));
-      m = nm;
-    }
-  }
-  part[grp][r] = make_float2(m, s);
-  __syncthreads();
-  if (grp == 0 && row < rows) {
-    for (int g = 1; g < kStatGroups; ++g) {
-      const float2 p = part[g][r];
-      const float nm = fmaxf(m, p.x);
-      s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (p.x == -INFINITY ? 0.f : p.y * __expf(p.x - nm));
-      m = nm;
-    }
+  int64_t row;
+  float m, s;
+  if (merge_tile_stats(stats, nblk, rows, row, m, s)) {
     const int64_t t = tgt[row] - vocab_lo;
     const bool own = t >= 0 && t < Vs;
     part_out[row] = make_float4(m, s, own ? bf2f(logits[row * ls + t]) : 0.f, own ? 1.f : 0.f);
@@ -448,18 +433,39 @@ __global__ __launch_bounds__(256) void ce_vp_combine_kernel(const float4* __rest
   float m = -INFINITY, s = 0.f, xt = 0.f;
   for (int q = 0; q < tp; ++q) {
     const float4 p = parts[(int64_t)q * rows + row];
-    const float nm = fmaxf(m, p.x);
-    s = (m == -INFINITY ? 0.f : s * __expf(m - nm)) + (p.x == -INFINITY ? 0.f : p.y * __expf(p.x - nm));
-    m = nm;
+    ms_merge(m, s, p.x, p.y);
     xt += p.z;
   }
-  const int64_t t = tgt[row];
-  const bool valid = t != ignore_index;
-  const bool bad = valid && (t < 0 || t >= V);
-  const float lse = bad ? __builtin_nanf("") : m + __logf(s);
-  row_lse[row] = lse;
-  store_row_loss<Z>(row_loss, row_z, row, valid, lse, xt, z);
-  if (bad && status) status[0] = PT_STATUS_BAD_TARGET;
+  const Target tg(tgt, row, ignore_index, V);
+  const float lse = row_lse[row] = tg.lse(m, s);
+  store_row_loss<Z>(row_loss, row_z, row, tg, lse, xt, z);
+  tg.report(status);
+}
+
+// ------------------------------------------------------------------------------------ host side
+// z_coef of the _z entry points: finite and >= 0 (NaN fails the comparison)
+bool z_ok(float z) { return z >= 0.f && z < __builtin_inff(); }
+
+// f(std::bool_constant<Z>) with Z = the z term is on: the kernels' compile-time switch
+template <class F>
+void with_z(float z_coef, F&& f) {
+  if (z_coef > 0.f) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// what the forms that stream [rows, vocab] logits check after their null pointers and sizes: 8-element
+// widths and strides, 16-byte bases (dlogits' when it is given), then the kernels' int32 indices
+int logits_ok(const void* logits, int64_t logits_stride, const void* dlogits, int64_t dlogits_stride, int64_t rows,
+              int64_t vocab) {
+  if ((vocab & 7) || (logits_stride & 7) || (dlogits && (dlogits_stride & 7))) return PT_EALIGN;
+  if (!pt_aligned16(logits) || (dlogits && !pt_aligned16(dlogits))) return PT_EALIGN;
+  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
+  return PT_OK;
+}
+
+// the lm_head GEMM's statistics: nblk > 0 tiles that divide the vocabulary, 16-byte aligned pairs
+bool stats_ok(const float* stats, int64_t nblk, int64_t vocab) {
+  return stats && nblk > 0 && vocab % nblk == 0 && pt_aligned16(stats);
 }
 
 }  // namespace
@@ -467,8 +473,8 @@ __global__ __launch_bounds__(256) void ce_vp_combine_kernel(const float4* __rest
 extern "C" int pt_cross_entropy_vp_partial(const void* logits, int64_t logits_stride, const int64_t* targets,
                                            const float* stats, int64_t nblk, float* part, int64_t rows,
                                            int64_t vocab_shard, int64_t vocab_lo, hipStream_t stream) {
-  if (!logits || !targets || !stats || !part || rows <= 0 || vocab_shard <= 0 || nblk <= 0) return PT_EINVAL;
-  if (vocab_shard % nblk || !pt_aligned16(stats) || !pt_aligned16(part)) return PT_EINVAL;
+  if (!logits || !targets || !part || rows <= 0 || vocab_shard <= 0) return PT_EINVAL;
+  if (!stats_ok(stats, nblk, vocab_shard) || !pt_aligned16(part)) return PT_EINVAL;
   if (rows > INT32_MAX || vocab_shard > INT32_MAX) return PT_EUNSUPPORTED;
   const unsigned grid = (unsigned)((rows + kStatRows - 1) / kStatRows);
   ce_vp_partial_kernel<<<grid, kStatRows * kStatGroups, 0, stream>>>((const uint16_t*)logits, logits_stride, targets,
@@ -478,9 +484,6 @@ extern "C" int pt_cross_entropy_vp_partial(const void* logits, int64_t logits_st
   return PT_OK;
 }
 
-// z_coef of the _z entry points: finite and >= 0 (NaN fails the comparison)
-static bool z_ok(float z) { return z >= 0.f && z < __builtin_inff(); }
-
 // Every rank's parts -> row_loss / row_lse (+ z lse^2 in row_loss and, optionally, row_z [rows]).
 extern "C" int pt_cross_entropy_vp_combine_z(const float* parts, int64_t tp, const int64_t* targets, float* row_loss,
                                              float* row_lse, int64_t rows, int64_t vocab, int64_t ignore_index,
@@ -489,10 +492,11 @@ extern "C" int pt_cross_entropy_vp_combine_z(const float* parts, int64_t tp, con
   if (!parts || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0 || tp <= 0) return PT_EINVAL;
   if (!pt_aligned16(parts)) return PT_EALIGN;
   const unsigned grid = (unsigned)((rows + 255) / 256);
-#define PT_CE(Z) ce_vp_combine_kernel<Z><<<grid, 256, 0, stream>>>((const float4*)parts, (int)tp, targets, row_loss, row_lse, rows, vocab, ignore_index, status, z_coef, row_z)
-  if (z_coef > 0.f) PT_CE(true);
-  else PT_CE(false);
-#undef PT_CE
+  with_z(z_coef, [&](auto Z) {
+    ce_vp_combine_kernel<decltype(Z)::value><<<grid, 256, 0, stream>>>((const float4*)parts, (int)tp, targets, row_loss,
+                                                                     row_lse, rows, vocab, ignore_index, status, z_coef,
+                                                                     row_z);
+  });
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -513,13 +517,12 @@ extern "C" int pt_cross_entropy_bwd_lse_shard_z(const void* logits, int64_t logi
   if (!z_ok(z_coef)) return PT_EINVAL;
   if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab_shard <= 0) return PT_EINVAL;
   if (scale_stride != 0 && scale_stride != 1) return PT_EINVAL;
-  if ((vocab_shard & 7) || (logits_stride & 7) || (dlogits_stride & 7)) return PT_EALIGN;
-  if (!pt_aligned16(logits) || !pt_aligned16(dlogits)) return PT_EALIGN;
-  if (rows > INT32_MAX || vocab_shard > INT32_MAX) return PT_EUNSUPPORTED;
-#define PT_CE(Z) ce_bwd_stream_kernel<Z><<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, row_lse, (uint16_t*)dlogits, dlogits_stride, (int)vocab_shard, scale, scale_stride, ignore_index, vocab_lo, z_coef)
-  if (z_coef > 0.f) PT_CE(true);
-  else PT_CE(false);
-#undef PT_CE
+  if (const int rc = logits_ok(logits, logits_stride, dlogits, dlogits_stride, rows, vocab_shard)) return rc;
+  with_z(z_coef, [&](auto Z) {
+    ce_bwd_stream_kernel<decltype(Z)::value><<<(unsigned)rows, kThreads, 0, stream>>>(
+        (const uint16_t*)logits, logits_stride, targets, row_lse, (uint16_t*)dlogits, dlogits_stride, (int)vocab_shard,
+        scale, scale_stride, ignore_index, vocab_lo, z_coef);
+  });
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -539,12 +542,12 @@ extern "C" int pt_cross_entropy_fwd_lse_z(const void* logits, int64_t logits_str
                                           hipStream_t stream) {
   if (!z_ok(z_coef)) return PT_EINVAL;
   if (!logits || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0) return PT_EINVAL;
-  if ((vocab & 7) || (logits_stride & 7) || !pt_aligned16(logits)) return PT_EALIGN;
-  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
-#define PT_CE(Z) ce_fwd_stream_kernel<Z><<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, row_loss, row_lse, (int)vocab, ignore_index, status, z_coef, row_z)
-  if (z_coef > 0.f) PT_CE(true);
-  else PT_CE(false);
-#undef PT_CE
+  if (const int rc = logits_ok(logits, logits_stride, nullptr, 0, rows, vocab)) return rc;
+  with_z(z_coef, [&](auto Z) {
+    ce_fwd_stream_kernel<decltype(Z)::value><<<(unsigned)rows, kThreads, 0, stream>>>(
+        (const uint16_t*)logits, logits_stride, targets, row_loss, row_lse, (int)vocab, ignore_index, status, z_coef,
+        row_z);
+  });
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -580,25 +583,16 @@ extern "C" int pt_cross_entropy_fwd_bwd_z(const void* logits, int64_t logits_str
                                           int* status, float z_coef, float* row_z, hipStream_t stream) {
   if (!z_ok(z_coef)) return PT_EINVAL;
   if (!logits || !targets || !row_loss || rows <= 0 || vocab <= 0) return PT_EINVAL;
-  if ((vocab & 7) || (logits_stride & 7) || (dlogits && (dlogits_stride & 7))) return PT_EALIGN;
-  if (!pt_aligned16(logits) || (dlogits && !pt_aligned16(dlogits))) return PT_EALIGN;
-  if (rows > INT32_MAX || vocab > INT32_MAX) return PT_EUNSUPPORTED;
-  const auto* L = (const uint16_t*)logits;
-  auto* D = (uint16_t*)dlogits;
-  const int nc = (int)((vocab / 8 + kThreads - 1) / kThreads);
-  const dim3 grid((unsigned)rows);
-  const bool zon = z_coef > 0.f;
-#define PT_CE_ARGS <<<grid, kThreads, 0, stream>>>(L, logits_stride, targets, D, dlogits_stride, row_loss, (int)vocab, scale, inv_count, ignore_index, status, z_coef, row_z)
-#define PT_CE(N) do { if (zon) ce_kernel<N, true> PT_CE_ARGS; else ce_kernel<N, false> PT_CE_ARGS; } while (0)
-  if (nc <= 4) PT_CE(4);
-  else if (nc <= 8) PT_CE(8);
-  else if (nc <= 16) PT_CE(16);
-  else if (nc <= 24) PT_CE(24);
-  else if (nc <= 32) PT_CE(32);
-  else if (zon) ce_kernel_2pass<true> PT_CE_ARGS;
-  else ce_kernel_2pass<false> PT_CE_ARGS;
-#undef PT_CE
-#undef PT_CE_ARGS
+  if (const int rc = logits_ok(logits, logits_stride, dlogits, dlogits_stride, rows, vocab)) return rc;
+  const int nc = (int)((vocab / 8 + kThreads - 1) / kThreads);   // 16-byte chunks per thread
+  with_z(z_coef, [&](auto Z) {
+    constexpr bool kZ = decltype(Z)::value;
+    auto* kernel = nc <= 4 ? ce_kernel<4, kZ> : nc <= 8 ? ce_kernel<8, kZ> : nc <= 16 ? ce_kernel<16, kZ>
+                 : nc <= 24 ? ce_kernel<24, kZ> : nc <= 32 ? ce_kernel<32, kZ> : ce_kernel_2pass<kZ>;
+    kernel<<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, (uint16_t*)dlogits,
+                                                    dlogits_stride, row_loss, (int)vocab, scale, inv_count, ignore_index,
+                                                    status, z_coef, row_z);
+  });
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -619,13 +613,14 @@ extern "C" int pt_cross_entropy_fwd_stats_z(const void* logits, int64_t logits_s
                                             int64_t rows, int64_t vocab, int64_t ignore_index, int* status,
                                             float z_coef, float* row_z, hipStream_t stream) {
   if (!z_ok(z_coef)) return PT_EINVAL;
-  if (!logits || !targets || !stats || !row_loss || !row_lse || rows <= 0 || vocab <= 0 || nblk <= 0) return PT_EINVAL;
-  if (vocab % nblk || !pt_aligned16(stats)) return PT_EINVAL;
+  if (!logits || !targets || !row_loss || !row_lse || rows <= 0 || vocab <= 0) return PT_EINVAL;
+  if (!stats_ok(stats, nblk, vocab)) return PT_EINVAL;
   const unsigned grid = (unsigned)((rows + kStatRows - 1) / kStatRows);
-#define PT_CE(Z) ce_fwd_stats_kernel<Z><<<grid, kStatRows * kStatGroups, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, (const float2*)stats, (int)nblk, row_loss, row_lse, rows, (int)vocab, ignore_index, status, z_coef, row_z)
-  if (z_coef > 0.f) PT_CE(true);
-  else PT_CE(false);
-#undef PT_CE
+  with_z(z_coef, [&](auto Z) {
+    ce_fwd_stats_kernel<decltype(Z)::value><<<grid, kStatRows * kStatGroups, 0, stream>>>(
+        (const uint16_t*)logits, logits_stride, targets, (const float2*)stats, (int)nblk, row_loss, row_lse, rows,
+        (int)vocab, ignore_index, status, z_coef, row_z);
+  });
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

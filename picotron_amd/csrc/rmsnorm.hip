@@ -16,26 +16,21 @@
 // Rows are grid-strided over a grid sized so that every block is resident at once (at the layer's
 // 4096 rows: one row per wave, all loads in flight from the start); the register budget is kept
 // at <= 128 VGPRs for that (see the backward's second pass).
+//
+// Rows wider than 4096 columns take the wide kernels, which stream the row twice instead of holding
+// it.  The two families spell out the same per-chunk arithmetic: as shared inline helpers it compiles
+// to other register counts (profiles/row_refactor_helper_trials.log); they share ld8_split.
+// The host computes one Plan per shape (which family, waves per block, grids); every entry point
+// launches from it, and the two backward entry points are one body.
 #include "common.h"
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 namespace {
 
 constexpr int kCUs = 256;
-
-// launch shape: waves per block and blocks per CU (grid cap) of the forward and backward kernels.
-// Measured at T 4096 (tools/norm_bench.py, profiles/r02_norm_bench.log, r02_notes.md): forward 4
-// waves x 4 blocks per CU; backward 16 waves x 1 block per CU (backward + column sum 17.5-18.4 us vs
-// 19.2 with 8 x 2: one 1024-thread block per CU halves the partial rows), 4 waves for the 8-chunk
-// rows (cols > 2048: 16 waves of those would not fit the LDS row buffers and spill).
-// Below 4096 rows (the TP sequence-parallel shards: T / tp rows per rank, 512 at TP = 8) those
-// shapes leave most CUs idle -- 32 backward blocks of 16 waves for 512 rows, 10.4 us -- so the
-// blocks shrink with the rows until they cover the 256 CUs: 16 / 4 / 2 waves per backward block at
-// >= 4096 / >= 1024 / fewer rows, and 4 / 1 waves per forward block at >= 4096 / fewer rows.
-constexpr int kFwdWpb = 4, kFwdBpc = 4, kBwdBpc = 1;
-constexpr int fwd_wpb(int64_t rows) { return rows >= 4096 ? kFwdWpb : 1; }
-constexpr int bwd_wpb(int nch, int64_t rows) { return nch == 8 ? (rows >= 1024 ? 4 : 2) : (rows >= 4096 ? 16 : rows >= 1024 ? 4 : 2); }
 
 template <int NCH>
 __device__ __forceinline__ void load_row(const uint16_t* __restrict__ p, int lane, int nchunk, bf16x8 (&v)[NCH]) {
@@ -122,19 +117,21 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(min_wa
 // SPLIT: dy arrives as the two f32 K halves of a split-K dX GEMM (gemm.hip splitk_sum2_kernel's
 // inputs) and is formed here as bf16(p0 + p1) -- the sum pass's own rounding -- so the bf16 dy is
 // never written and re-read (dy_p1 = the second half; dy = the first, as float)
+__device__ __forceinline__ bf16x8 ld8_split(const float* __restrict__ p0, const float* __restrict__ p1) {
+  const float4 a0 = *(const float4*)p0, a1 = *(const float4*)(p0 + 4);
+  const float4 b0 = *(const float4*)p1, b1 = *(const float4*)(p1 + 4);
+  float f[8] = {a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w,
+                a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w};
+  return pack8(f);
+}
+
 template <int NCH>
 __device__ __forceinline__ void load_split_row(const float* __restrict__ p0, const float* __restrict__ p1, int lane,
                                                int nchunk, bf16x8 (&v)[NCH]) {
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     const int c = lane + i * PT_WAVE;
-    if (c < nchunk) {
-      const float4 a0 = *(const float4*)(p0 + c * 8), a1 = *(const float4*)(p0 + c * 8 + 4);
-      const float4 b0 = *(const float4*)(p1 + c * 8), b1 = *(const float4*)(p1 + c * 8 + 4);
-      float f[8] = {a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w,
-                    a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w};
-      v[i] = pack8(f);
-    }
+    if (c < nchunk) v[i] = ld8_split(p0 + c * 8, p1 + c * 8);
   }
 }
 
@@ -246,7 +243,6 @@ __global__ __launch_bounds__(WPB * 64) __attribute__((amdgpu_waves_per_eu(min_wa
 // (planar, as above), combined per block in a fixed order: one partial row per block.
 constexpr int kWideWpb = 4;   // waves per block; 2 above 8192 columns (LDS: WPB x cols x 4 B)
 constexpr int kWideMax = 16384;
-inline int wide_wpb(int cols) { return cols > 8192 ? 2 : kWideWpb; }
 
 __global__ __launch_bounds__(kWideWpb * 64) void rmsnorm_fwd_wide_kernel(
     const uint16_t* __restrict__ x, const uint16_t* __restrict__ res, const uint16_t* __restrict__ w,
@@ -306,13 +302,7 @@ __global__ __launch_bounds__(kWideWpb * 64) void rmsnorm_bwd_wide_kernel(
   }
   auto load_dy = [&](int64_t row, int c, float (&d)[8]) {
     if constexpr (SPLIT) {
-      const float* p0 = (const float*)dy + row * cols + c * 8;
-      const float* p1 = dy_p1 + row * cols + c * 8;
-      const float4 a0 = *(const float4*)p0, a1 = *(const float4*)(p0 + 4);
-      const float4 b0 = *(const float4*)p1, b1 = *(const float4*)(p1 + 4);
-      float f[8] = {a0.x + b0.x, a0.y + b0.y, a0.z + b0.z, a0.w + b0.w,
-                    a1.x + b1.x, a1.y + b1.y, a1.z + b1.z, a1.w + b1.w};
-      unpack8(pack8(f), d);   // bf16(p0 + p1): the split-K sum pass's own rounding
+      unpack8(ld8_split((const float*)dy + row * cols + c * 8, dy_p1 + row * cols + c * 8), d);
     } else {
       unpack8(ld8(dy + row * cols + c * 8), d);
     }
@@ -363,28 +353,6 @@ __global__ __launch_bounds__(kWideWpb * 64) void rmsnorm_bwd_wide_kernel(
     for (int k = 0; k < wpb; ++k) s += red[k * cols + at];
     dw_partial[(int64_t)blockIdx.x * cols + col] = s;
   }
-}
-
-int wide_grid(int64_t rows, int wpb, int bpc) {
-  const int64_t g = (rows + wpb - 1) / wpb, cap = (int64_t)kCUs * bpc;
-  return (int)(g < cap ? g : cap);
-}
-
-void launch_bwd_wide(bool split, int grid, hipStream_t s, const uint16_t* DY, const uint16_t* Z, const uint16_t* W,
-                     const float* rstd, const uint16_t* DR, uint16_t* DX, float* part, int64_t rows, int cols,
-                     int mode, const float* P1) {
-  const int wpb = wide_wpb(cols);
-  const size_t lds = (size_t)wpb * cols * sizeof(float);
-  static bool attr[2] = {false, false};
-  if (!attr[split]) {
-    (void)hipFuncSetAttribute(split ? (const void*)rmsnorm_bwd_wide_kernel<true> : (const void*)rmsnorm_bwd_wide_kernel<false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr[split] = true;
-  }
-  if (split)
-    rmsnorm_bwd_wide_kernel<true><<<grid, wpb * 64, lds, s>>>(DY, Z, W, rstd, DR, DX, part, rows, cols, mode, P1);
-  else
-    rmsnorm_bwd_wide_kernel<false><<<grid, wpb * 64, lds, s>>>(DY, Z, W, rstd, DR, DX, part, rows, cols, mode, P1);
 }
 
 // dw[col] = sum_p partial[p][col]  -- fixed summation order, deterministic.  One block per 32
@@ -465,57 +433,140 @@ __global__ __launch_bounds__(kCsThreads) void colsum_batch_kernel(const ColsumBa
   colsum_block(b.partial[i], b.nparts[i], cols, b.out[i], b.sink[i]);
 }
 
-int nch_for(int cols) {
-  const int chunks = cols / 8;
-  if (chunks <= 64) return 1;
-  if (chunks <= 128) return 2;
-  if (chunks <= 256) return 4;
-  if (chunks <= 512) return 8;
-  return -1;
-}
+// ------------------------------------------------------------------------------------ host side
+// launch shape: waves per block and blocks per CU (grid cap) of the forward and backward kernels.
+// Measured at T 4096 (tools/norm_bench.py, profiles/r02_norm_bench.log, r02_notes.md): forward 4
+// waves x 4 blocks per CU; backward 16 waves x 1 block per CU (backward + column sum 17.5-18.4 us vs
+// 19.2 with 8 x 2: one 1024-thread block per CU halves the partial rows), 4 waves for the 8-chunk
+// rows (cols > 2048: 16 waves of those would not fit the LDS row buffers and spill).
+// Below 4096 rows (the TP sequence-parallel shards: T / tp rows per rank, 512 at TP = 8) those
+// shapes leave most CUs idle -- 32 backward blocks of 16 waves for 512 rows, 10.4 us -- so the
+// blocks shrink with the rows until they cover the 256 CUs: 16 / 4 / 2 waves per backward block at
+// >= 4096 / >= 1024 / fewer rows, and 4 / 1 waves per forward block at >= 4096 / fewer rows.
+// The wide kernels: 4 waves per block (2 above 8192 columns), 4 forward / 1 backward blocks per CU.
+constexpr int kFwdWpb = 4, kFwdBpc = 4, kBwdBpc = 1;
+constexpr int max_bwd_wpb(int nch) { return nch == 8 ? 4 : 16; }
 
 int grid_for(int64_t rows, int wpb, int bpc) {
   const int64_t g = (rows + wpb - 1) / wpb, cap = (int64_t)kCUs * bpc;
   return (int)(g < cap ? g : cap);
 }
 
-template <int NCH>
-void launch_fwd(hipStream_t s, const uint16_t* X, const uint16_t* R, const uint16_t* W, uint16_t* Y,
-                uint16_t* Z, float* rstd, int64_t rows, int cols, float eps, int mode) {
-  if (fwd_wpb(rows) == kFwdWpb)
-    rmsnorm_fwd_kernel<NCH, kFwdWpb><<<grid_for(rows, kFwdWpb, kFwdBpc), kFwdWpb * 64, 0, s>>>(X, R, W, Y, Z, rstd,
-                                                                                              rows, cols, eps, mode);
-  else
-    rmsnorm_fwd_kernel<NCH, 1><<<grid_for(rows, 1, kFwdBpc * kFwdWpb), 64, 0, s>>>(X, R, W, Y, Z, rstd, rows, cols,
-                                                                                  eps, mode);
+// How a [rows, cols] norm is launched; the one place that decides it.
+struct Plan {
+  int nch;                 // 16-byte chunks per lane of the register-resident kernels; 0: the wide kernels
+  bool too_wide;           // more columns than the wide kernels take
+  int fwd_wpb, fwd_grid;   // waves per block and blocks of the forward
+  int bwd_wpb, bwd_grid;   // ... of the backward: one dW partial row per block
+};
+
+Plan plan_for(int64_t rows, int cols) {
+  const int chunks = cols / 8;
+  Plan p{};
+  p.nch = chunks <= 64 ? 1 : chunks <= 128 ? 2 : chunks <= 256 ? 4 : chunks <= 512 ? 8 : 0;
+  p.too_wide = !p.nch && cols > kWideMax;
+  if (p.nch) {
+    p.fwd_wpb = rows >= 4096 ? kFwdWpb : 1;
+    p.fwd_grid = grid_for(rows, p.fwd_wpb, kFwdBpc * kFwdWpb / p.fwd_wpb);
+    const int wpb = rows >= 4096 ? 16 : rows >= 1024 ? 4 : 2;
+    p.bwd_wpb = wpb < max_bwd_wpb(p.nch) ? wpb : max_bwd_wpb(p.nch);
+  } else {
+    p.fwd_wpb = kWideWpb;
+    p.fwd_grid = grid_for(rows, kWideWpb, 4);
+    p.bwd_wpb = cols > 8192 ? 2 : kWideWpb;
+  }
+  p.bwd_grid = grid_for(rows, p.bwd_wpb, kBwdBpc);
+  return p;
 }
+
+template <int N>
+using Int = std::integral_constant<int, N>;
+
+// f(Int<NCH>) for a register-resident plan's chunk count
+template <class F>
+void with_nch(int nch, F&& f) {
+  switch (nch) {
+    case 1: f(Int<1>{}); break;
+    case 2: f(Int<2>{}); break;
+    case 4: f(Int<4>{}); break;
+    case 8: f(Int<8>{}); break;
+  }
+}
+
+struct BwdArgs {
+  const uint16_t *dy, *z, *w;
+  const float* rstd;
+  const uint16_t* dres;
+  uint16_t* dx;
+  float* part;
+  int64_t rows;
+  int cols, mode;
+  const float* dy_p1;
+};
 
 // LDS: wpb * cols * 4 (128 KiB at 16 waves x 2048 columns)
 template <int NCH, int WPB, bool SPLIT>
-void launch_bwd_w(int grid, hipStream_t s, const uint16_t* DY, const uint16_t* Z, const uint16_t* W,
-                  const float* rstd, const uint16_t* DR, uint16_t* DX, float* part, int64_t rows, int cols, int mode,
-                  const float* P1) {
-  const size_t lds = (size_t)WPB * cols * sizeof(float);
+void launch_bwd_w(int grid, hipStream_t s, const BwdArgs& a) {
+  const size_t lds = (size_t)WPB * a.cols * sizeof(float);
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute((const void*)rmsnorm_bwd_kernel<NCH, WPB, SPLIT>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  rmsnorm_bwd_kernel<NCH, WPB, SPLIT><<<grid, WPB * 64, lds, s>>>(DY, Z, W, rstd, DR, DX, part, rows, cols, mode, P1);
+  rmsnorm_bwd_kernel<NCH, WPB, SPLIT><<<grid, WPB * 64, lds, s>>>(a.dy, a.z, a.w, a.rstd, a.dres, a.dx, a.part, a.rows,
+                                                                  a.cols, a.mode, a.dy_p1);
 }
 
-template <int NCH, bool SPLIT = false>
-void launch_bwd(int grid, hipStream_t s, const uint16_t* DY, const uint16_t* Z, const uint16_t* W,
-                const float* rstd, const uint16_t* DR, uint16_t* DX, float* part, int64_t rows, int cols, int mode,
-                const float* P1 = nullptr) {
-  switch (bwd_wpb(NCH, rows)) {
-    case 16:
-      if constexpr (NCH != 8) launch_bwd_w<NCH, 16, SPLIT>(grid, s, DY, Z, W, rstd, DR, DX, part, rows, cols, mode, P1);
-      break;
-    case 4: launch_bwd_w<NCH, 4, SPLIT>(grid, s, DY, Z, W, rstd, DR, DX, part, rows, cols, mode, P1); break;
-    default: launch_bwd_w<NCH, 2, SPLIT>(grid, s, DY, Z, W, rstd, DR, DX, part, rows, cols, mode, P1); break;
+// the plan's waves per block as a template argument: only the counts max_bwd_wpb(NCH) allows exist
+template <int NCH, bool SPLIT>
+void launch_bwd(const Plan& p, hipStream_t s, const BwdArgs& a) {
+  if constexpr (max_bwd_wpb(NCH) >= 16)
+    if (p.bwd_wpb == 16) return launch_bwd_w<NCH, 16, SPLIT>(p.bwd_grid, s, a);
+  if (p.bwd_wpb == 4) return launch_bwd_w<NCH, 4, SPLIT>(p.bwd_grid, s, a);
+  launch_bwd_w<NCH, 2, SPLIT>(p.bwd_grid, s, a);
+}
+
+template <bool SPLIT>
+void launch_bwd_wide(const Plan& p, hipStream_t s, const BwdArgs& a) {
+  const size_t lds = (size_t)p.bwd_wpb * a.cols * sizeof(float);
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)rmsnorm_bwd_wide_kernel<SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+    attr = true;
   }
+  rmsnorm_bwd_wide_kernel<SPLIT><<<p.bwd_grid, p.bwd_wpb * 64, lds, s>>>(a.dy, a.z, a.w, a.rstd, a.dres, a.dx, a.part,
+                                                                         a.rows, a.cols, a.mode, a.dy_p1);
+}
+
+// pt_rmsnorm_bwd (dy_p1 NULL: dy is bf16) and pt_rmsnorm_bwd_splitk (dy, dy_p1: the two f32 halves)
+template <bool SPLIT>
+int rmsnorm_bwd(const void* dy, const float* dy_p1, const void* z, const void* weight, const float* rstd,
+                const void* dres, void* dx, void* dweight, float* dw_partial, int64_t rows, int64_t cols, int mode,
+                hipStream_t stream) {
+  if (!dy || (SPLIT && !dy_p1) || !z || !weight || !rstd || !dx || !dw_partial || rows <= 0 || cols <= 0 || (cols & 7))
+    return PT_EINVAL;
+  if (!pt_aligned16(dy) || (SPLIT && !pt_aligned16(dy_p1)) || !pt_aligned16(z) || !pt_aligned16(dx) ||
+      (dres && !pt_aligned16(dres)))
+    return PT_EALIGN;
+  const Plan p = plan_for(rows, (int)cols);
+  if (p.too_wide) return PT_EUNSUPPORTED;
+  const int nmode = mode & 3;
+  if (nmode > 1 || (mode & PT_DW_ACC_BF16 && mode & PT_DW_ACC_F32)) return PT_EINVAL;
+  const BwdArgs a{(const uint16_t*)dy, (const uint16_t*)z, (const uint16_t*)weight, rstd, (const uint16_t*)dres,
+                  (uint16_t*)dx,       dw_partial,         rows,                    (int)cols, nmode, dy_p1};
+  if (p.nch)
+    with_nch(p.nch, [&](auto N) { launch_bwd<decltype(N)::value, SPLIT>(p, stream, a); });
+  else
+    launch_bwd_wide<SPLIT>(p, stream, a);
+  PT_CHECK_LAUNCH();
+  if (dweight) {
+    colsum_kernel<<<(int)((cols + kCsCols - 1) / kCsCols), kCsThreads, 0, stream>>>(
+        dw_partial, p.bwd_grid, (int)cols, dweight, mode & (PT_DW_ACC_BF16 | PT_DW_ACC_F32));
+    PT_CHECK_LAUNCH();
+  }
+  return PT_OK;
 }
 
 }  // namespace
@@ -523,12 +574,9 @@ void launch_bwd(int grid, hipStream_t s, const uint16_t* DY, const uint16_t* Z, 
 extern "C" {
 
 int pt_rmsnorm_bwd_partials(int64_t rows, int cols) {
-  const int nch = nch_for(cols);
-  if (nch < 0) {
-    if (cols > kWideMax || (cols & 7)) return PT_EUNSUPPORTED;
-    return wide_grid(rows, wide_wpb(cols), 1);   // the wide-row backward: one partial row per block
-  }
-  return grid_for(rows, bwd_wpb(nch, rows), kBwdBpc);  // one partial row per bwd block
+  const Plan p = plan_for(rows, cols);
+  if (!p.nch && (p.too_wide || (cols & 7))) return PT_EUNSUPPORTED;
+  return p.bwd_grid;   // one partial row per backward block
 }
 
 int pt_rmsnorm_fwd(const void* x, const void* residual, const void* weight, void* y, void* z_out,
@@ -537,22 +585,23 @@ int pt_rmsnorm_fwd(const void* x, const void* residual, const void* weight, void
   if (residual && !z_out) return PT_EINVAL;
   if (!pt_aligned16(x) || !pt_aligned16(weight) || !pt_aligned16(y)) return PT_EALIGN;
   if (residual && (!pt_aligned16(residual) || !pt_aligned16(z_out))) return PT_EALIGN;
+  const Plan p = plan_for(rows, (int)cols);
+  if (p.too_wide) return PT_EUNSUPPORTED;
   const auto* X = (const uint16_t*)x;
   const auto* R = (const uint16_t*)residual;
   const auto* W = (const uint16_t*)weight;
   auto* Y = (uint16_t*)y;
   auto* Z = (uint16_t*)z_out;
-  switch (nch_for((int)cols)) {
-    case 1: launch_fwd<1>(stream, X, R, W, Y, Z, rstd, rows, (int)cols, eps, mode); break;
-    case 2: launch_fwd<2>(stream, X, R, W, Y, Z, rstd, rows, (int)cols, eps, mode); break;
-    case 4: launch_fwd<4>(stream, X, R, W, Y, Z, rstd, rows, (int)cols, eps, mode); break;
-    case 8: launch_fwd<8>(stream, X, R, W, Y, Z, rstd, rows, (int)cols, eps, mode); break;
-    default:
-      if (cols > kWideMax) return PT_EUNSUPPORTED;
-      rmsnorm_fwd_wide_kernel<<<wide_grid(rows, kWideWpb, 4), kWideWpb * 64, 0, stream>>>(X, R, W, Y, Z, rstd, rows,
-                                                                                         (int)cols, eps, mode);
-      break;
-  }
+  auto launch = [&](auto* kernel) {
+    kernel<<<p.fwd_grid, p.fwd_wpb * 64, 0, stream>>>(X, R, W, Y, Z, rstd, rows, (int)cols, eps, mode);
+  };
+  if (!p.nch)
+    launch(rmsnorm_fwd_wide_kernel);
+  else
+    with_nch(p.nch, [&](auto N) {
+      constexpr int NCH = decltype(N)::value;
+      launch(p.fwd_wpb == kFwdWpb ? rmsnorm_fwd_kernel<NCH, kFwdWpb> : rmsnorm_fwd_kernel<NCH, 1>);
+    });
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -560,34 +609,7 @@ int pt_rmsnorm_fwd(const void* x, const void* residual, const void* weight, void
 int pt_rmsnorm_bwd(const void* dy, const void* z, const void* weight, const float* rstd, const void* dres,
                    void* dx, void* dweight, float* dw_partial, int64_t rows, int64_t cols, int mode,
                    hipStream_t stream) {
-  if (!dy || !z || !weight || !rstd || !dx || !dw_partial || rows <= 0 || cols <= 0 || (cols & 7))
-    return PT_EINVAL;
-  if (!pt_aligned16(dy) || !pt_aligned16(z) || !pt_aligned16(dx) || (dres && !pt_aligned16(dres)))
-    return PT_EALIGN;
-  const int nch = nch_for((int)cols);
-  if (nch < 0 && cols > kWideMax) return PT_EUNSUPPORTED;
-  const int nmode = mode & 3;
-  if (nmode > 1 || (mode & PT_DW_ACC_BF16 && mode & PT_DW_ACC_F32)) return PT_EINVAL;
-  const int grid = nch < 0 ? wide_grid(rows, wide_wpb((int)cols), 1) : grid_for(rows, bwd_wpb(nch, rows), kBwdBpc);
-  const auto* DY = (const uint16_t*)dy;
-  const auto* Z = (const uint16_t*)z;
-  const auto* W = (const uint16_t*)weight;
-  const auto* DR = (const uint16_t*)dres;
-  auto* DX = (uint16_t*)dx;
-  switch (nch) {
-    case 1: launch_bwd<1>(grid, stream, DY, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode); break;
-    case 2: launch_bwd<2>(grid, stream, DY, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode); break;
-    case 4: launch_bwd<4>(grid, stream, DY, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode); break;
-    case 8: launch_bwd<8>(grid, stream, DY, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode); break;
-    default: launch_bwd_wide(false, grid, stream, DY, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode, nullptr);
-  }
-  PT_CHECK_LAUNCH();
-  if (dweight) {
-    colsum_kernel<<<(int)((cols + kCsCols - 1) / kCsCols), kCsThreads, 0, stream>>>(
-        dw_partial, grid, (int)cols, dweight, mode & (PT_DW_ACC_BF16 | PT_DW_ACC_F32));
-    PT_CHECK_LAUNCH();
-  }
-  return PT_OK;
+  return rmsnorm_bwd<false>(dy, nullptr, z, weight, rstd, dres, dx, dweight, dw_partial, rows, cols, mode, stream);
 }
 
 // pt_rmsnorm_bwd with dy = bf16(dy_p0 + dy_p1): the two f32 K halves [rows, cols] (contiguous) of a
@@ -596,35 +618,7 @@ int pt_rmsnorm_bwd(const void* dy, const void* z, const void* weight, const floa
 int pt_rmsnorm_bwd_splitk(const float* dy_p0, const float* dy_p1, const void* z, const void* weight,
                           const float* rstd, const void* dres, void* dx, void* dweight, float* dw_partial,
                           int64_t rows, int64_t cols, int mode, hipStream_t stream) {
-  if (!dy_p0 || !dy_p1 || !z || !weight || !rstd || !dx || !dw_partial || rows <= 0 || cols <= 0 || (cols & 7))
-    return PT_EINVAL;
-  if (!pt_aligned16(dy_p0) || !pt_aligned16(dy_p1) || !pt_aligned16(z) || !pt_aligned16(dx) ||
-      (dres && !pt_aligned16(dres)))
-    return PT_EALIGN;
-  const int nch = nch_for((int)cols);
-  if (nch < 0 && cols > kWideMax) return PT_EUNSUPPORTED;
-  const int nmode = mode & 3;
-  if (nmode > 1 || (mode & PT_DW_ACC_BF16 && mode & PT_DW_ACC_F32)) return PT_EINVAL;
-  const int grid = nch < 0 ? wide_grid(rows, wide_wpb((int)cols), 1) : grid_for(rows, bwd_wpb(nch, rows), kBwdBpc);
-  const auto* P0 = (const uint16_t*)dy_p0;  // reinterpreted as float inside the SPLIT kernel
-  const auto* Z = (const uint16_t*)z;
-  const auto* W = (const uint16_t*)weight;
-  const auto* DR = (const uint16_t*)dres;
-  auto* DX = (uint16_t*)dx;
-  switch (nch) {
-    case 1: launch_bwd<1, true>(grid, stream, P0, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode, dy_p1); break;
-    case 2: launch_bwd<2, true>(grid, stream, P0, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode, dy_p1); break;
-    case 4: launch_bwd<4, true>(grid, stream, P0, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode, dy_p1); break;
-    case 8: launch_bwd<8, true>(grid, stream, P0, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode, dy_p1); break;
-    default: launch_bwd_wide(true, grid, stream, P0, Z, W, rstd, DR, DX, dw_partial, rows, (int)cols, nmode, dy_p1);
-  }
-  PT_CHECK_LAUNCH();
-  if (dweight) {
-    colsum_kernel<<<(int)((cols + kCsCols - 1) / kCsCols), kCsThreads, 0, stream>>>(
-        dw_partial, grid, (int)cols, dweight, mode & (PT_DW_ACC_BF16 | PT_DW_ACC_F32));
-    PT_CHECK_LAUNCH();
-  }
-  return PT_OK;
+  return rmsnorm_bwd<true>(dy_p0, dy_p1, z, weight, rstd, dres, dx, dweight, dw_partial, rows, cols, mode, stream);
 }
 
 // dweight[i] (+)= column sums of partials[i] ([nparts[i], cols] f32, from pt_rmsnorm_bwd called with

@@ -1143,6 +1143,35 @@ def z_coef(z_loss):
     return z
 
 
+def _ce_native(name, device, args, z=0.0, row_z=None, what=None):
+    """One CE native call on torch's current stream: name(*args, stream) when z == 0; with z > 0 its _z
+    namesake, which takes z (and row_z [rows] f32, where the entry point writes one) between args and
+    the stream."""
+    if z > 0:
+        name, args = name + "_z", (*args, z) if row_z is None else (*args, z, _ptr(row_z))
+    rc = getattr(_C.lib(), name)(*args, _C.stream_ptr(device))
+    _C.check(rc, what or name)
+
+
+def _ce_fwd_args(rows, targets, stats=None, vocab=None):
+    """The forward forms' shared checks: int64 targets [rows] (returned contiguous) and, where given,
+    the lm_head GEMM's statistics f32 [nblk, rows, 2] with nblk dividing vocab."""
+    _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
+    if stats is not None:
+        _req(stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3 and stats.shape[1:] == (rows, 2)
+             and vocab % stats.shape[0] == 0, "stats: f32 [nblk, rows, 2]")
+    return targets.contiguous()
+
+
+def _ce_bwd_args(rows, targets, row_lse, scale_dev):
+    """The LSE backward forms' shared checks: an f32 scale (one element or [rows]) and the saved f32
+    row_lse [rows]; returns (targets, scale_dev) contiguous."""
+    targets = targets.contiguous()
+    _req(scale_dev.dtype == torch.float32 and scale_dev.numel() in (1, rows), "scale: f32 device scalar or [rows]")
+    _req(row_lse.dtype == torch.float32 and row_lse.is_contiguous() and row_lse.numel() == rows, "row_lse: f32 [rows]")
+    return targets, scale_dev.contiguous()
+
+
 def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace=True, z_loss=0.0):
     """logits [rows, V] bf16, targets [rows] int64.  Returns (loss (f32 scalar tensor, mean over
     valid rows, *not* multiplied by scale), dlogits (aliases logits when inplace), inv_count); with
@@ -1155,35 +1184,25 @@ def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace
     inv_count = (1.0 / valid.sum().clamp_min(1).to(torch.float32)).reshape(1)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     dlogits = logits if inplace else torch.empty_like(logits)
-    if z > 0:
-        row_z = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        rc = _C.lib().pt_cross_entropy_fwd_bwd_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits),
-                                                 dlogits.stride(0), _ptr(row_loss), rows, vocab, float(scale),
-                                                 _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device)),
-                                                 z, _ptr(row_z), _C.stream_ptr(logits.device))
-        _C.check(rc, "pt_cross_entropy_fwd_bwd_z")
-        _status_posted(logits.device)
-        return row_loss.sum() * inv_count[0], dlogits, inv_count, row_z.sum() * inv_count[0]
-    rc = _C.lib().pt_cross_entropy_fwd_bwd(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits),
-                                           dlogits.stride(0), _ptr(row_loss), rows, vocab, float(scale),
-                                           _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device)), _C.stream_ptr(logits.device))
-    _C.check(rc, "pt_cross_entropy_fwd_bwd")
+    row_z = torch.empty(rows, dtype=torch.float32, device=logits.device) if z > 0 else None
+    _ce_native("pt_cross_entropy_fwd_bwd", logits.device,
+               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits), dlogits.stride(0), _ptr(row_loss), rows,
+                vocab, float(scale), _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device))), z, row_z)
     _status_posted(logits.device)
     loss = row_loss.sum() * inv_count[0]
-    return loss, dlogits, inv_count
+    return (loss, dlogits, inv_count) if row_z is None else (loss, dlogits, inv_count, row_z.sum() * inv_count[0])
 
 
 def cross_entropy_loss(logits, targets, ignore_index=-100):
     """Forward only: (mean loss f32 scalar tensor, inv_count [1] f32) -- one read of the logits."""
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
-    _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
-    targets = targets.contiguous()
+    targets = _ce_fwd_args(rows, targets)
     inv_count = (1.0 / (targets != ignore_index).sum().clamp_min(1).to(torch.float32)).reshape(1)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    rc = _C.lib().pt_cross_entropy_fwd_bwd(_ptr(logits), logits.stride(0), _ptr(targets), None, 0, _ptr(row_loss),
-                                           rows, vocab, 1.0, None, int(ignore_index), _ptr(status_word(logits.device)), _C.stream_ptr(logits.device))
-    _C.check(rc, "pt_cross_entropy_fwd_bwd(loss)")
+    _ce_native("pt_cross_entropy_fwd_bwd", logits.device,
+               (_ptr(logits), logits.stride(0), _ptr(targets), None, 0, _ptr(row_loss), rows, vocab, 1.0, None,
+                int(ignore_index), _ptr(status_word(logits.device))), what="pt_cross_entropy_fwd_bwd(loss)")
     _status_posted(logits.device)
     return row_loss.sum() * inv_count[0], inv_count
 
@@ -1211,10 +1230,14 @@ def _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction):
     return _ce_mean(row_loss, targets, ignore_index, out_dtype, reduce_sum=reduction == "sum")
 
 
-def _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction):
-    """_ce_reduce of the row losses and, in f32, of their z parts: (loss, inv_count, z_part)."""
+def _ce_lse_result(row_loss, row_lse, row_z, targets, ignore_index, out_dtype, reduction):
+    """What the forward forms that save the LSE return: (loss, inv_count, row_lse) by _ce_reduce and, when
+    there is a z part (row_z), its f32 reduction as a fourth element."""
+    # no clamp: every target ignored gives 0 * inf = nan, as F.cross_entropy's mean does (grads 0)
     loss, inv_count = _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction)
-    return loss, inv_count, _ce_reduce(row_z, targets, ignore_index, torch.float32, reduction)[0]
+    if row_z is None:
+        return loss, inv_count, row_lse
+    return loss, inv_count, row_lse, _ce_reduce(row_z, targets, ignore_index, torch.float32, reduction)[0]
 
 
 def cross_entropy_loss_lse(logits, targets, ignore_index=-100, out_dtype=torch.float32, reduction="mean", z_loss=0.0):
@@ -1224,27 +1247,15 @@ def cross_entropy_loss_lse(logits, targets, ignore_index=-100, out_dtype=torch.f
     z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
-    _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
-    targets = targets.contiguous()
+    targets = _ce_fwd_args(rows, targets)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     row_lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    if z > 0:
-        row_z = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        rc = _C.lib().pt_cross_entropy_fwd_lse_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_loss),
-                                                 _ptr(row_lse), rows, vocab, int(ignore_index),
-                                                 _ptr(status_word(logits.device)), z, _ptr(row_z),
-                                                 _C.stream_ptr(logits.device))
-        _C.check(rc, "pt_cross_entropy_fwd_lse_z")
-        _status_posted(logits.device)
-        loss, inv_count, z_part = _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction)
-        return loss, inv_count, row_lse, z_part
-    rc = _C.lib().pt_cross_entropy_fwd_lse(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_loss),
-                                           _ptr(row_lse), rows, vocab, int(ignore_index), _ptr(status_word(logits.device)), _C.stream_ptr(logits.device))
-    _C.check(rc, "pt_cross_entropy_fwd_lse")
+    row_z = torch.empty(rows, dtype=torch.float32, device=logits.device) if z > 0 else None
+    _ce_native("pt_cross_entropy_fwd_lse", logits.device,
+               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_loss), _ptr(row_lse), rows, vocab,
+                int(ignore_index), _ptr(status_word(logits.device))), z, row_z)
     _status_posted(logits.device)
-    # no clamp: every target ignored gives 0 * inf = nan, as F.cross_entropy's mean does (grads 0)
-    loss, inv_count = _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction)
-    return loss, inv_count, row_lse
+    return _ce_lse_result(row_loss, row_lse, row_z, targets, ignore_index, out_dtype, reduction)
 
 
 def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-100, z_loss=0.0):
@@ -1254,22 +1265,11 @@ def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-10
     z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
-    targets = targets.contiguous()
-    _req(scale_dev.dtype == torch.float32 and scale_dev.numel() in (1, rows), "scale: f32 device scalar or [rows]")
-    _req(row_lse.dtype == torch.float32 and row_lse.is_contiguous() and row_lse.numel() == rows, "row_lse: f32 [rows]")
-    scale_dev = scale_dev.contiguous()
+    targets, scale_dev = _ce_bwd_args(rows, targets, row_lse, scale_dev)
     dl = torch.empty(rows, vocab, dtype=BF16, device=logits.device)
-    if z > 0:
-        rc = _C.lib().pt_cross_entropy_bwd_lse_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse),
-                                                 _ptr(dl), dl.stride(0), rows, vocab, _ptr(scale_dev),
-                                                 int(scale_dev.numel() != 1), int(ignore_index), z,
-                                                 _C.stream_ptr(logits.device))
-        _C.check(rc, "pt_cross_entropy_bwd_lse_z")
-        return dl
-    rc = _C.lib().pt_cross_entropy_bwd_lse(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse), _ptr(dl),
-                                           dl.stride(0), rows, vocab, _ptr(scale_dev), int(scale_dev.numel() != 1),
-                                           int(ignore_index), _C.stream_ptr(logits.device))
-    _C.check(rc, "pt_cross_entropy_bwd_lse")
+    _ce_native("pt_cross_entropy_bwd_lse", logits.device,
+               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vocab,
+                _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index)), z)
     return dl
 
 
@@ -1282,10 +1282,9 @@ def cross_entropy_grad(logits, targets, scale_dev, ignore_index=-100):
     scale_dev = scale_dev.contiguous()
     dl = torch.empty(rows, vocab, dtype=BF16, device=logits.device)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    rc = _C.lib().pt_cross_entropy_fwd_bwd(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dl), dl.stride(0),
-                                           _ptr(row_loss), rows, vocab, 1.0, _ptr(scale_dev), int(ignore_index),
-                                           _ptr(status_word(logits.device)), _C.stream_ptr(logits.device))
-    _C.check(rc, "pt_cross_entropy_fwd_bwd(grad)")
+    _ce_native("pt_cross_entropy_fwd_bwd", logits.device,
+               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dl), dl.stride(0), _ptr(row_loss), rows, vocab, 1.0,
+                _ptr(scale_dev), int(ignore_index), _ptr(status_word(logits.device))), what="pt_cross_entropy_fwd_bwd(grad)")
     _status_posted(logits.device)
     return dl
 
@@ -1860,30 +1859,15 @@ def cross_entropy_loss_lse_stats(logits, targets, stats, ignore_index=-100, out_
     z = z_coef(z_loss)
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
-    _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
-    _req(stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3 and stats.shape[1:] == (rows, 2)
-         and vocab % stats.shape[0] == 0, "stats: f32 [nblk, rows, 2]")
-    targets = targets.contiguous()
+    targets = _ce_fwd_args(rows, targets, stats, vocab)
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     row_lse = torch.empty(rows, dtype=torch.float32, device=logits.device)
-    if z > 0:
-        row_z = torch.empty(rows, dtype=torch.float32, device=logits.device)
-        rc = _C.lib().pt_cross_entropy_fwd_stats_z(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(stats),
-                                                   stats.shape[0], _ptr(row_loss), _ptr(row_lse), rows, vocab,
-                                                   int(ignore_index), _ptr(status_word(logits.device)), z,
-                                                   _ptr(row_z), _C.stream_ptr(logits.device))
-        _C.check(rc, "pt_cross_entropy_fwd_stats_z")
-        _status_posted(logits.device)
-        loss, inv_count, z_part = _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction)
-        return loss, inv_count, row_lse, z_part
-    rc = _C.lib().pt_cross_entropy_fwd_stats(_ptr(logits), logits.stride(0), _ptr(targets), _ptr(stats),
-                                             stats.shape[0], _ptr(row_loss), _ptr(row_lse), rows, vocab,
-                                             int(ignore_index), _ptr(status_word(logits.device)),
-                                             _C.stream_ptr(logits.device))
-    _C.check(rc, "pt_cross_entropy_fwd_stats")
+    row_z = torch.empty(rows, dtype=torch.float32, device=logits.device) if z > 0 else None
+    _ce_native("pt_cross_entropy_fwd_stats", logits.device,
+               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(stats), stats.shape[0], _ptr(row_loss), _ptr(row_lse),
+                rows, vocab, int(ignore_index), _ptr(status_word(logits.device))), z, row_z)
     _status_posted(logits.device)
-    loss, inv_count = _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction)
-    return loss, inv_count, row_lse
+    return _ce_lse_result(row_loss, row_lse, row_z, targets, ignore_index, out_dtype, reduction)
 
 
 def cross_entropy_vp_partial(logits_shard, targets, stats, vocab_lo):
@@ -1892,15 +1876,11 @@ def cross_entropy_vp_partial(logits_shard, targets, stats, vocab_lo):
     the lm_head GEMM's statistics (linear_ce_stats) -- the logits are read at x[target] only."""
     _bf16_rowmajor(logits_shard, "logits")
     rows, vs = logits_shard.shape
-    _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
-    _req(stats.dtype == torch.float32 and stats.is_contiguous() and stats.dim() == 3 and stats.shape[1:] == (rows, 2)
-         and vs % stats.shape[0] == 0, "stats: f32 [nblk, rows, 2]")
-    targets = targets.contiguous()
+    targets = _ce_fwd_args(rows, targets, stats, vs)
     part = torch.empty(rows, 4, dtype=torch.float32, device=logits_shard.device)
-    rc = _C.lib().pt_cross_entropy_vp_partial(_ptr(logits_shard), logits_shard.stride(0), _ptr(targets), _ptr(stats),
-                                              stats.shape[0], _ptr(part), rows, vs, int(vocab_lo),
-                                              _C.stream_ptr(logits_shard.device))
-    _C.check(rc, "pt_cross_entropy_vp_partial")
+    _ce_native("pt_cross_entropy_vp_partial", logits_shard.device,
+               (_ptr(logits_shard), logits_shard.stride(0), _ptr(targets), _ptr(stats), stats.shape[0], _ptr(part), rows, vs,
+                int(vocab_lo)))
     return part
 
 
@@ -1913,26 +1893,15 @@ def cross_entropy_vp_combine(parts, targets, vocab, ignore_index=-100, out_dtype
     _req(parts.dtype == torch.float32 and parts.is_contiguous() and parts.dim() == 3 and parts.shape[2] == 4,
          "parts: f32 [tp, rows, 4]")
     tp, rows = parts.shape[0], parts.shape[1]
-    _req(targets.dtype == torch.int64 and targets.numel() == rows, "targets: int64 [rows]")
-    targets = targets.contiguous()
+    targets = _ce_fwd_args(rows, targets)
     row_loss = torch.empty(rows, dtype=torch.float32, device=parts.device)
     row_lse = torch.empty(rows, dtype=torch.float32, device=parts.device)
-    if z > 0:
-        row_z = torch.empty(rows, dtype=torch.float32, device=parts.device)
-        rc = _C.lib().pt_cross_entropy_vp_combine_z(_ptr(parts), tp, _ptr(targets), _ptr(row_loss), _ptr(row_lse), rows,
-                                                    int(vocab), int(ignore_index), _ptr(status_word(parts.device)), z,
-                                                    _ptr(row_z), _C.stream_ptr(parts.device))
-        _C.check(rc, "pt_cross_entropy_vp_combine_z")
-        _status_posted(parts.device)
-        loss, inv_count, z_part = _ce_reduce_z(row_loss, row_z, targets, ignore_index, out_dtype, reduction)
-        return loss, inv_count, row_lse, z_part
-    rc = _C.lib().pt_cross_entropy_vp_combine(_ptr(parts), tp, _ptr(targets), _ptr(row_loss), _ptr(row_lse), rows,
-                                              int(vocab), int(ignore_index), _ptr(status_word(parts.device)),
-                                              _C.stream_ptr(parts.device))
-    _C.check(rc, "pt_cross_entropy_vp_combine")
+    row_z = torch.empty(rows, dtype=torch.float32, device=parts.device) if z > 0 else None
+    _ce_native("pt_cross_entropy_vp_combine", parts.device,
+               (_ptr(parts), tp, _ptr(targets), _ptr(row_loss), _ptr(row_lse), rows, int(vocab), int(ignore_index),
+                _ptr(status_word(parts.device))), z, row_z)
     _status_posted(parts.device)
-    loss, inv_count = _ce_reduce(row_loss, targets, ignore_index, out_dtype, reduction)
-    return loss, inv_count, row_lse
+    return _ce_lse_result(row_loss, row_lse, row_z, targets, ignore_index, out_dtype, reduction)
 
 
 def cross_entropy_grad_lse_shard(logits_shard, targets, row_lse, scale_dev, vocab_lo, ignore_index=-100, z_loss=0.0):
@@ -1941,23 +1910,11 @@ def cross_entropy_grad_lse_shard(logits_shard, targets, row_lse, scale_dev, voca
     z = z_coef(z_loss)
     _bf16_rowmajor(logits_shard, "logits")
     rows, vs = logits_shard.shape
-    targets = targets.contiguous()
-    _req(scale_dev.dtype == torch.float32 and scale_dev.numel() in (1, rows), "scale: f32 device scalar or [rows]")
-    _req(row_lse.dtype == torch.float32 and row_lse.is_contiguous() and row_lse.numel() == rows, "row_lse: f32 [rows]")
-    scale_dev = scale_dev.contiguous()
+    targets, scale_dev = _ce_bwd_args(rows, targets, row_lse, scale_dev)
     dl = torch.empty(rows, vs, dtype=BF16, device=logits_shard.device)
-    if z > 0:
-        rc = _C.lib().pt_cross_entropy_bwd_lse_shard_z(_ptr(logits_shard), logits_shard.stride(0), _ptr(targets),
-                                                       _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vs, int(vocab_lo),
-                                                       _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index),
-                                                       z, _C.stream_ptr(logits_shard.device))
-        _C.check(rc, "pt_cross_entropy_bwd_lse_shard_z")
-        return dl
-    rc = _C.lib().pt_cross_entropy_bwd_lse_shard(_ptr(logits_shard), logits_shard.stride(0), _ptr(targets),
-                                                 _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vs, int(vocab_lo),
-                                                 _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index),
-                                                 _C.stream_ptr(logits_shard.device))
-    _C.check(rc, "pt_cross_entropy_bwd_lse_shard")
+    _ce_native("pt_cross_entropy_bwd_lse_shard", logits_shard.device,
+               (_ptr(logits_shard), logits_shard.stride(0), _ptr(targets), _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vs,
+                int(vocab_lo), _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index)), z)
     return dl
 
 
