@@ -135,6 +135,32 @@ int pt_moe_plan_block(void);
 int pt_moe_plan_workspace(int64_t T, int64_t E, int64_t k);
 int pt_moe_plan(const int32_t* idx, int64_t T, int64_t E, int64_t k, int64_t C, int32_t* slot, int32_t* src,
                 int32_t* workspace, hipStream_t stream);
+/* The dropless layout: expert e's items on rows [seg[e], seg[e] + n_e) of one packed buffer, in flat
+ * item order (pt_moe_plan's rank), every seg[e] a multiple of pt_moe_seg_align() = 128.
+ * pt_moe_dropless_rows(T, E, k) = 128 ((T k + 127 E) / 128) rows hold any routing.  pt_moe_plan_dropless:
+ * slot int32 [T, k] (the row of each item, -1 for an idx outside [0, E)), src int32 [R] (the item of each
+ * row, -1 on padding rows and the unused tail), seg int32 [E + 1] (seg[E] = the rows in use),
+ * tile_expert int32 [R / 128] (-1 past seg[E]).  No atomics; workspace as pt_moe_plan. */
+int pt_moe_seg_align(void);
+int pt_moe_dropless_rows(int64_t T, int64_t E, int64_t k);
+int pt_moe_plan_dropless(const int32_t* idx, int64_t T, int64_t E, int64_t k, int64_t R, int32_t* slot, int32_t* src,
+                         int32_t* seg, int32_t* tile_expert, int32_t* workspace, hipStream_t stream);
+/* The segment GEMMs of that layout (csrc/gemm.hip): one launch for every expert, the expert of a
+ * 128-row tile and its pointers read on the device.  pt_moe_seg_table fills the host image of the
+ * per-expert table (E rows of 4 int64: p0[e], p1[e] or 0, ld, 0) the caller uploads once per set of
+ * pointers.  form 0: C[r, :] = A[r, :] . W_e^T, W_e [N, K] as p0 (columns [0, split)) | p1; form 1:
+ * C[r, :] = A[r, :] . W_e, W_e [K, N] as p0 (k < split) ; p1; tiles of expert -1 store zeros.  form 2:
+ * sink_e [N, K] (op)= A[seg[e] : seg[e + 1], :N]^T . B[seg[e] : seg[e + 1], :K], the sink as p0 (rows
+ * [0, split)) ; p1, epilogue 0-3; an empty expert stores zeros or (accumulating) leaves the sink as it
+ * is, a null p0 skips the expert.  PT_EUNSUPPORTED: R, N or (form 2) K off the 128-grid, K off the
+ * 64-grid, split off the tile grid, E > 128; PT_EALIGN: pointers off 16 bytes, ld off 8 elements.
+ * The table lives on the device, so the launch cannot look into it: a launch with split below the full
+ * extent reads p1 of every expert it runs, and pt_moe_seg_table refuses (PT_EINVAL) a two-pointer table
+ * with a null p1 beside a non-null p0. */
+int pt_moe_seg_table(const void* const* p0, const void* const* p1, int64_t ld, int64_t E, int64_t* out);
+int pt_moe_gemm_seg(int form, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                    const int64_t* table, const int32_t* seg, const int32_t* tile_expert, int64_t R,
+                    int64_t N, int64_t K, int64_t split, int64_t E, int epilogue, hipStream_t stream);
 /* pt_moe_dispatch: xe[r, :] = x[src[r] / k, :] (a bit copy), zeros where src[r] is outside [0, T k). */
 int pt_moe_dispatch(const void* x, int64_t ldx, const int32_t* src, void* xe, int64_t ldxe, int64_t T, int64_t k,
                     int64_t R, int64_t H, hipStream_t stream);

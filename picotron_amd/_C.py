@@ -93,6 +93,12 @@ SIGNATURES = {
     "pt_moe_plan_block": (_i32, []),
     "pt_moe_plan_workspace": (_i32, [_i64, _i64, _i64]),
     "pt_moe_plan": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "pt_moe_seg_align": (_i32, []),
+    "pt_moe_dropless_rows": (_i32, [_i64, _i64, _i64]),
+    "pt_moe_plan_dropless": (_i32, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pt_moe_seg_table": (_i32, [_vpp, _vpp, _i64, _i64, _i64p]),
+    "pt_moe_gemm_seg": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64,
+                               _i32, _vp]),
     "pt_moe_dispatch": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "pt_moe_combine": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "pt_moe_combine_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),

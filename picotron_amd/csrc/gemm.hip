@@ -2102,3 +2102,263 @@ int pt_gemm_pick_tile(int64_t M, int64_t N, const int64_t* mseg, int nmseg, cons
 }
 
 }  // extern "C"
+
+// ==================================================================== segment GEMMs (dropless MoE)
+// The expert GEMMs of the dropless mixture-of-experts layout (csrc/moe.hip, pt_moe_plan_dropless):
+// all experts' rows packed back to back in one [R, *] buffer, expert e on rows [seg[e], seg[e + 1]),
+// every seg[e] a multiple of 128.  The M-tile is 128 rows, so a tile never straddles two experts and
+// no kernel masks a row.  One launch covers every expert: a workgroup reads its tile's expert from
+// the device (tile_expert[tile_m], forms 0 / 1) or takes it from its tile id (form 2), and its
+// weight / sink pointers and leading dimension from a per-expert device table -- nothing of the
+// routing is a kernel argument, nothing is read on the host.
+//
+//   form 0  Y[r, :]  = X[r, :] . W_e^T      W K-contiguous [N, K], up to two pointers along N
+//   form 1  dX[r, :] = dY[r, :] . W_e       W N-contiguous [K, N], up to two pointers along K
+//   form 2  dW_e [Nout, Kin] (op)= dY[seg[e] : seg[e + 1], :]^T . X[seg[e] : seg[e + 1], :]
+//           the sink split along Nout into up to two pointers; only the K-loop length is data
+//
+// One body, a 128 x (128 NB) workgroup tile (NB = 2 where N is on the 256-grid): 8 waves as 2 (M) x
+// 4 (N), each a 64 x (32 NB) output.  A K-tile is 1 + NB images of 128 rows / columns x 64 k, 16 KiB
+// each, staged by LDS-DMA into a three-deep ring (NB = 2: 144 KiB, what one resident workgroup has
+// beside its epilogue staging, which reuses the ring): K-tile t + 2 is issued at the top of K-tile t
+// into the buffer K-tile t - 1 left at the closing barrier, and the one counted wait per K-tile
+// retires t + 1 with t + 2 in flight.  Per K-tile and wave: 2 (1 + NB) DMA instructions, 16 fragment
+// reads, 16 NB MFMAs, one barrier.  Tile order: XCD remap, then every N-tile of kSegGroupM
+// consecutive M-tiles, so an expert's weight panel and its rows meet in one XCD's L2.
+// Forms 0 / 1 run the static worst-case grid; a tile past seg[E] (expert -1) runs no K loop and
+// stores zeros.  Form 2 with an empty expert stores zeros (EPI_BF16 / EPI_F32) or leaves the sink
+// untouched (the accumulating epilogues); a null sink pointer skips the expert (a frozen parameter).
+namespace {
+
+constexpr int kSegAlign = 128;
+constexpr int kSegMaxE = 128;    // csrc/moe.hip's kMaxE
+constexpr int kSegGroupM = 4;
+constexpr int kSegRing = 3;
+constexpr int kSegTableWords = 4;   // per expert: pointer 0, pointer 1, leading dimension, unused
+
+struct SegArgs {
+  const uint16_t* A;   // forms 0 / 1: the packed rows [R, K]; form 2: dY [R, Nout] (read as dY^T)
+  int64_t lda;
+  const uint16_t* B;   // form 2: X [R, Kin]
+  int64_t ldb;
+  uint16_t* C;         // forms 0 / 1: the packed output [R, N]
+  int64_t ldc;
+  const int64_t* table;
+  const int32_t* seg;
+  const int32_t* tile_expert;
+  int N, K;            // output columns, contraction (form 2: Kin, unused)
+  int split;           // form 0: the N boundary of the two weight pointers; 1: the K one; 2: the Nout one
+  int tiles_m, tiles_n;
+};
+
+template <int FORM, int NB, int EPI>
+__global__ __launch_bounds__(512) void moe_gemm_seg_kernel(const SegArgs s) {
+  constexpr bool AK = FORM != 2, BKC = FORM == 0;
+  constexpr int BN = 128 * NB, TN = BN / 4, FN = TN / 16;
+  constexpr int IMG = 128 * BK * 2, BUF = (1 + NB) * IMG, NS = kSegRing;
+  constexpr int OPS = 2 * (1 + NB);   // DMA instructions per wave and K-tile
+  extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+  lds_u8* smem = (lds_u8*)smem_raw;
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const int pid = xcd_remap(blockIdx.x, gridDim.x);
+  int tile_m, tile_n, e;
+  if (FORM == 2) {
+    const int per = s.tiles_m * s.tiles_n;
+    e = pid / per;
+    raster_tile(pid - e * per, s.tiles_m, s.tiles_n, kSegGroupM, tile_m, tile_n);
+  } else {
+    raster_tile(pid, s.tiles_m, s.tiles_n, kSegGroupM, tile_m, tile_n);
+    e = __builtin_amdgcn_readfirstlane(s.tile_expert[tile_m]);
+  }
+  const int m0 = tile_m * 128, n0 = tile_n * BN;
+  if (FORM != 2 && e < 0) {   // the unused tail: defined, and the same from run to run
+    constexpr int CPR = BN / 8;
+    for (int i = tid; i < 128 * CPR; i += 512)
+      st8(s.C + (int64_t)(m0 + i / CPR) * s.ldc + n0 + (i % CPR) * 8, bf16x8{{0u, 0u, 0u, 0u}});
+    return;
+  }
+  const int64_t* row = s.table + (int64_t)e * kSegTableWords;
+  const uint16_t* p0 = (const uint16_t*)pt_uniform_u64((uint64_t)row[0]);
+  const uint16_t* p1 = (const uint16_t*)pt_uniform_u64((uint64_t)row[1]);
+  const int64_t ldt = (int64_t)pt_uniform_u64((uint64_t)row[2]);
+  int r0 = 0, nk = s.K / BK;
+  if (FORM == 2) {
+    if (!p0) return;
+    r0 = __builtin_amdgcn_readfirstlane(s.seg[e]);
+    nk = (__builtin_amdgcn_readfirstlane(s.seg[e + 1]) - r0) / BK;
+    if (nk == 0 && (EPI == EPI_BF16_ACC || EPI == EPI_F32_ACC)) return;   // sink + 0: not a bit of it changes
+  }
+  const int64_t lda = s.lda, ldb = FORM == 2 ? s.ldb : ldt;
+  // K-tile t's images: A at (m0, 64 t); B at (64 t, n0), from the pointer its segment selects
+  const uint16_t* Ab0 = FORM == 2 ? s.A + (int64_t)r0 * lda + m0 : s.A + (int64_t)m0 * lda;
+  const uint16_t* Bb0 = FORM == 0   ? (n0 < s.split ? p0 + (int64_t)n0 * ldb : p1 + (int64_t)(n0 - s.split) * ldb)
+                        : FORM == 1 ? p0 + n0
+                                    : s.B + (int64_t)r0 * ldb + n0;
+  // form 1: from k = split on, element (k, n) is pointer 1's (k - split, n): one element delta
+  const int64_t b_d1 = FORM == 1 && p1 ? ((int64_t)(intptr_t)p1 - (int64_t)(intptr_t)p0) / 2 - (int64_t)s.split * ldb : 0;
+  const int ksplit = FORM == 1 && p1 ? s.split : INT_MAX;
+  uint32_t vA[2], vB[2];
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    vA[it] = himg_voff<AK, 128>(it * 8 + wave, lane, lda, 0);
+    vB[it] = himg_voff<BKC, 128>(it * 8 + wave, lane, ldb, 0);
+  }
+  auto stage = [&](int t, int buf) {
+    lds_u8* dst = smem + buf * BUF;
+    const uint16_t* ap = AK ? Ab0 + t * BK : Ab0 + (int64_t)t * BK * lda;
+    const uint16_t* bp = (BKC ? Bb0 + t * BK : Bb0 + (int64_t)t * BK * ldb) + (t * BK >= ksplit ? b_d1 : 0);
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      glds16_asm(ap, vA[it], dst + (it * 8 + wave) * 1024);
+#pragma unroll
+      for (int h = 0; h < NB; ++h)
+        glds16_asm(BKC ? bp + (int64_t)h * 128 * ldb : bp + h * 128, vB[it], dst + (1 + h) * IMG + (it * 8 + wave) * 1024);
+    }
+  };
+
+  f32x4_t acc[4][FN];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+
+  auto ktile = [&](int t, auto bufc) {
+    constexpr int buf = decltype(bufc)::value;
+    const lds_u8* sA = smem + buf * BUF;
+    const lds_u8* sB = sA + IMG + (wn * TN / 128) * IMG;
+    if (t + 2 < nk) stage(t + 2, (buf + 2) % NS);
+#pragma unroll
+    for (int ss = 0; ss < 2; ++ss) {
+      bf16x8_t af[4], bf[FN];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) af[i] = read_frag<128, AK>(sA, wm * 64 + i * 16, ss, lane);
+#pragma unroll
+      for (int j = 0; j < FN; ++j) bf[j] = read_frag<128, BKC>(sB, (wn * TN) % 128 + j * 16, ss, lane);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) acc[i][j] = mfma16(af[i], bf[j], acc[i][j]);
+    }
+    // K-tile t + 1 landed before the next K-tile's reads; t + 2 (just issued) may stay in flight
+    if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    phase_bar();
+  };
+
+  if (nk > 0) {
+    stage(0, 0);
+    if (nk > 1) {
+      stage(1, 1);
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(OPS) : "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    phase_bar();
+    int t = 0;
+    for (; t + 2 < nk; t += 3) {
+      ktile(t, std::integral_constant<int, 0>{});
+      ktile(t + 1, std::integral_constant<int, 1>{});
+      ktile(t + 2, std::integral_constant<int, 2>{});
+    }
+    if (t < nk) ktile(t, std::integral_constant<int, 0>{});
+    if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
+  }
+
+  // the common epilogue on one unsegmented sink: this tile's pointer and local row
+  GemmArgs ga{};
+  ga.ncseg = 1;
+  int ml = m0;
+  if (FORM == 2) {
+    const bool hi = m0 >= s.split;
+    ga.C[0] = hi ? (void*)p1 : (void*)p0;
+    ga.ldc[0] = ldt;
+    ml = hi ? m0 - s.split : m0;
+  } else {
+    ga.C[0] = s.C;
+    ga.ldc[0] = s.ldc;
+  }
+  epilogue<64, TN, EPI>(ga, acc, smem + wave * (64 * (TN * 2 + 16)), ml, n0, wm, wn, lane);
+}
+
+template <int FORM, int NB, int EPI>
+int launch_seg(const SegArgs& s, int grid, hipStream_t stream) {
+  return launch_kernel<moe_gemm_seg_kernel<FORM, NB, EPI>, kSegRing * (1 + NB) * 128 * BK * 2>(grid, 512, stream, s);
+}
+template <int FORM, int EPI>
+int launch_seg_nb(const SegArgs& s, int nb, int grid, hipStream_t stream) {
+  return nb == 2 ? launch_seg<FORM, 2, EPI>(s, grid, stream) : launch_seg<FORM, 1, EPI>(s, grid, stream);
+}
+
+bool seg_ld_ok(int64_t ld, int64_t width) { return ld >= width && (ld & 7) == 0 && ld <= (1 << 22); }
+
+}  // namespace
+
+extern "C" {
+
+int pt_moe_seg_align(void) { return kSegAlign; }
+
+// The per-expert device table's host image: E rows of {p0[e], p1[e] (or null), ld, 0}.
+int pt_moe_seg_table(const void* const* p0, const void* const* p1, int64_t ld, int64_t E, int64_t* out) {
+  if (!p0 || !out || E < 1 || ld < 1) return PT_EINVAL;
+  if (p1)   // two pointers per expert: a launch with split < full reads both of every expert it runs
+    for (int64_t e = 0; e < E; ++e)
+      if (p0[e] && !p1[e]) return PT_EINVAL;
+  if (E > kSegMaxE) return PT_EUNSUPPORTED;
+  if (ld & 7) return PT_EALIGN;
+  for (int64_t e = 0; e < E; ++e) {
+    const void* q1 = p1 ? p1[e] : nullptr;
+    if (!pt_aligned16(p0[e]) || !pt_aligned16(q1)) return PT_EALIGN;
+    out[e * kSegTableWords + 0] = (int64_t)(intptr_t)p0[e];
+    out[e * kSegTableWords + 1] = (int64_t)(intptr_t)q1;
+    out[e * kSegTableWords + 2] = ld;
+    out[e * kSegTableWords + 3] = 0;
+  }
+  return PT_OK;
+}
+
+// form 0 / 1: A = the packed rows [R, K], C = the packed output [R, N] (bf16), B unused; table = the
+// experts' weights ([N, K] K-contiguous / [K, N] N-contiguous, `split` the boundary of their two
+// pointers along N / K, = N / K with one).  form 2: A = dY [R, N] (N = Nout), B = X [R, K] (K = Kin),
+// C unused; table = the sinks [Nout, Kin] split along Nout at `split`; epilogue 0-3.
+// R, N on the 128-grid, K on the 64-grid (form 2: Kin on the 128-grid), split on the tile's grid.
+int pt_moe_gemm_seg(int form, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
+                    const int64_t* table, const int32_t* seg, const int32_t* tile_expert, int64_t R,
+                    int64_t N, int64_t K, int64_t split, int64_t E, int epilogue, hipStream_t stream) {
+  if (form < 0 || form > 2 || !A || !table || !seg || R < 1 || N < 1 || K < 1 || E < 1) return PT_EINVAL;
+  if (form == 2 ? !B : (!C || !tile_expert)) return PT_EINVAL;
+  if (epilogue < EPI_BF16 || epilogue > EPI_F32_ACC || (form != 2 && epilogue != EPI_BF16)) return PT_EINVAL;
+  if (E > kSegMaxE || R > (1 << 30) || N > (1 << 22) || K > (1 << 22)) return PT_EUNSUPPORTED;
+  const int64_t full = form == 1 ? K : N;
+  if (split < 1 || split > full) return PT_EINVAL;
+  // the output tile: form 0 / 1 rows x N; form 2 Nout x Kin
+  const int64_t cols = form == 2 ? K : N;
+  if (R % kSegAlign || N % 128 || cols % 128 || K % BK) return PT_EUNSUPPORTED;
+  const int nb = cols % 256 == 0 && (form != 0 || split % 256 == 0) ? 2 : 1;
+  if (split % (form == 1 ? BK : form == 0 ? 128 * nb : 128)) return PT_EUNSUPPORTED;
+  if (!pt_aligned16(A) || !pt_aligned16(table) || !seg_ld_ok(lda, form == 2 ? N : K))
+    return PT_EALIGN;
+  if (form == 2 ? (!pt_aligned16(B) || !seg_ld_ok(ldb, K)) : (!pt_aligned16(C) || !seg_ld_ok(ldc, N))) return PT_EALIGN;
+  SegArgs s{};
+  s.A = (const uint16_t*)A, s.lda = lda;
+  s.B = (const uint16_t*)B, s.ldb = ldb;
+  s.C = (uint16_t*)C, s.ldc = ldc;
+  s.table = table, s.seg = seg, s.tile_expert = tile_expert;
+  s.N = (int)N, s.K = (int)K, s.split = (int)split;
+  s.tiles_m = (int)((form == 2 ? N : R) / 128);
+  s.tiles_n = (int)(cols / (128 * nb));
+  const int64_t grid = (int64_t)s.tiles_m * s.tiles_n * (form == 2 ? E : 1);
+  if (grid > INT32_MAX) return PT_EUNSUPPORTED;
+  if (form == 0) return launch_seg_nb<0, EPI_BF16>(s, nb, (int)grid, stream);
+  if (form == 1) return launch_seg_nb<1, EPI_BF16>(s, nb, (int)grid, stream);
+  switch (epilogue) {
+    case EPI_BF16: return launch_seg_nb<2, EPI_BF16>(s, nb, (int)grid, stream);
+    case EPI_BF16_ACC: return launch_seg_nb<2, EPI_BF16_ACC>(s, nb, (int)grid, stream);
+    case EPI_F32: return launch_seg_nb<2, EPI_F32>(s, nb, (int)grid, stream);
+    default: return launch_seg_nb<2, EPI_F32_ACC>(s, nb, (int)grid, stream);
+  }
+}
+
+}  // extern "C"

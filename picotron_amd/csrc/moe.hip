@@ -214,6 +214,61 @@ __global__ __launch_bounds__(256) void moe_plan_place_kernel(const int32_t* __re
   }
 }
 
+// ---- dropless plan ---------------------------------------------------------------------------------
+// The same rank and scan passes, then segments instead of capacity slots: expert e's items take rows
+// [seg[e], seg[e] + n_e) of one packed buffer in flat item order, every seg[e] a multiple of kSegAlign
+// (the segment GEMMs' M-tile: csrc/gemm.hip), so a 128-row tile belongs to one expert.  R rows are
+// allocated (the bound of kernels.moe_dropless_rows); seg[E] of them are in use.
+constexpr int kSegAlign = 128;
+
+// one workgroup: thread 0 adds the aligned totals in expert order, then every thread labels tiles
+__global__ __launch_bounds__(kMaxE) void moe_plan_seg_kernel(const int32_t* __restrict__ hist, int nblk, int E,
+                                                             int ntiles, int32_t* __restrict__ seg,
+                                                             int32_t* __restrict__ tile_expert) {
+  __shared__ int sh_seg[kMaxE + 1];
+  if (threadIdx.x == 0) {
+    int run = 0;
+    for (int e = 0; e < E; ++e) {
+      sh_seg[e] = run;
+      run += (hist[(int64_t)nblk * E + e] + kSegAlign - 1) / kSegAlign * kSegAlign;
+    }
+    sh_seg[E] = run;
+  }
+  __syncthreads();
+  for (int e = threadIdx.x; e <= E; e += kMaxE) seg[e] = sh_seg[e];
+  for (int t = threadIdx.x; t < ntiles; t += kMaxE) {
+    const int r = t * kSegAlign;
+    int own = -1;   // the one expert with seg[e] <= r < seg[e + 1]; none past seg[E]
+    for (int e = 0; e < E; ++e)
+      if (r >= sh_seg[e] && r < sh_seg[e + 1]) own = e;
+    tile_expert[t] = own;
+  }
+}
+
+__global__ __launch_bounds__(256) void moe_plan_place_seg_kernel(const int32_t* __restrict__ idx,
+                                                                 const int32_t* __restrict__ hist,
+                                                                 const int32_t* __restrict__ seg,
+                                                                 const int32_t* __restrict__ tile_expert, int N, int E,
+                                                                 int R, int nblk, int32_t* __restrict__ slot,
+                                                                 int32_t* __restrict__ src) {
+  const int64_t n = N > R ? N : R;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    if (i < N) {
+      const int e = idx[i];
+      int s = -1;
+      if ((unsigned)e < (unsigned)E) {
+        s = seg[e] + hist[(int64_t)(i / kPlanBlock) * E + e] + slot[i];
+        src[s] = (int)i;
+      }
+      slot[i] = s;
+    }
+    if (i < R) {   // padding rows and the unused tail (disjoint from the rows written above)
+      const int e = tile_expert[i / kSegAlign];
+      if (e < 0 || (int)i - seg[e] >= hist[(int64_t)nblk * E + e]) src[i] = -1;
+    }
+  }
+}
+
 // ---- the row kernels: one thread per 8 columns -----------------------------------------------------
 __global__ __launch_bounds__(256) void moe_dispatch_kernel(const uint16_t* __restrict__ x, int64_t ldx,
                                                            const int32_t* __restrict__ src,
@@ -423,6 +478,35 @@ int pt_moe_plan(const int32_t* idx, int64_t T, int64_t E, int64_t k, int64_t C, 
   PT_CHECK_LAUNCH();
   const int64_t n = N > E * C ? N : E * C;
   moe_plan_place_kernel<<<stream_grid(n), 256, 0, stream>>>(idx, workspace, N, (int)E, (int)C, nblk, slot, src);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_moe_dropless_rows(int64_t T, int64_t E, int64_t k) {
+  const int rc = sizes_ok(T, E, k);
+  if (rc != PT_OK) return rc;
+  const int64_t rows = (T * k + E * (kSegAlign - 1)) / kSegAlign * kSegAlign;
+  return rows > kI32 ? PT_EUNSUPPORTED : (int)rows;
+}
+
+// slot [T, k], src [R], seg [E + 1], tile_expert [R / 128]; R >= pt_moe_dropless_rows, on the 128-grid
+int pt_moe_plan_dropless(const int32_t* idx, int64_t T, int64_t E, int64_t k, int64_t R, int32_t* slot, int32_t* src,
+                         int32_t* seg, int32_t* tile_expert, int32_t* workspace, hipStream_t stream) {
+  if (!idx || !slot || !src || !seg || !tile_expert || !workspace) return PT_EINVAL;
+  const int rc = sizes_ok(T, E, k);
+  if (rc != PT_OK) return rc;
+  if (R % kSegAlign || R < pt_moe_dropless_rows(T, E, k)) return PT_EINVAL;
+  if (R > kI32 || (plan_blocks(T * k) + 1) * E > kI32) return PT_EUNSUPPORTED;
+  const int N = (int)(T * k), nblk = (int)plan_blocks(T * k);
+  moe_plan_rank_kernel<<<nblk, kPlanBlock, 0, stream>>>(idx, N, (int)E, slot, workspace);
+  PT_CHECK_LAUNCH();
+  moe_plan_scan_kernel<<<1, kMaxE, 0, stream>>>(workspace, nblk, (int)E);
+  PT_CHECK_LAUNCH();
+  moe_plan_seg_kernel<<<1, kMaxE, 0, stream>>>(workspace, nblk, (int)E, (int)(R / kSegAlign), seg, tile_expert);
+  PT_CHECK_LAUNCH();
+  const int64_t n = N > R ? N : R;
+  moe_plan_place_seg_kernel<<<stream_grid(n), 256, 0, stream>>>(idx, workspace, seg, tile_expert, N, (int)E, (int)R, nblk,
+                                                                slot, src);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

@@ -1192,6 +1192,8 @@ def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, nor
     expert MLPs as grouped GEMMs, weighted combine with the residual in one rounding.  Static shapes,
     nothing read on the host."""
     T, E = h2.shape[0], len(wgs)
+    if capacity_factor is None:
+        return _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages)
     C = K.moe_capacity(T, E, k, capacity_factor)
     logits = K.linear_fwd(h2, [router_w])
     idx, gate, probs, counts, aux = K.moe_route(logits, k, norm_topk_prob)
@@ -1204,12 +1206,69 @@ def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, nor
     return out, aux, (idx, gate, probs, counts, slot, src, xe, gu, hh, ye)
 
 
-def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob=True, need_dx=True, stages=None):
+def _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages):
+    """moe_block_fwd with capacity_factor None: no item is dropped.  The experts' rows are packed back to
+    back in [R, *] buffers (K.moe_plan_dropless: R = K.moe_dropless_rows, a static bound; segments on the
+    128-grid) and every product is one segment-GEMM launch over all experts."""
+    E = len(wgs)
+    logits = K.linear_fwd(h2, [router_w])
+    idx, gate, probs, counts, aux = K.moe_route(logits, k, norm_topk_prob)
+    slot, src, seg, tile_expert = K.moe_plan_dropless(idx, E)
+    xe = K.moe_dispatch(h2, src, k)
+    gu, hh, ye = K.moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert)
+    out = K.moe_combine(ye, slot, gate, residual)
+    _stage(stages, h2=h2, logits=logits, idx=idx, gate=gate, probs=probs, counts=counts, aux=aux, slot=slot, src=src, xe=xe,
+           gu=gu, hh=hh, ye=ye, out=out, seg=seg, tile_expert=tile_expert)
+    return out, aux, (idx, gate, probs, counts, slot, src, xe, gu, hh, ye, seg, tile_expert)
+
+
+def _wgrad_seg(dy, x, params_per_expert, seg, notify=True):
+    """The weight gradients of every expert, dW_e = dy[rows of e]^T x[rows of e], through _resolve_sinks
+    into one segment launch per (sink epilogue, column range of dy) -- one launch when every sink takes
+    the same epilogue; the owners are told once every launch is queued, as for a dense layer.  Not
+    through pair_jobs: the contraction length differs per micro-batch, so these jobs never pair and
+    never defer."""
+    E = len(params_per_expert)
+    groups, told = {}, []
+    for e, params in enumerate(params_per_expert):
+        for dyv, _, sinks, epi, ready in _resolve_sinks([(dy, x, params)])[0]:
+            g = groups.setdefault((epi, dyv.data_ptr(), dyv.shape[1], len(sinks)), (dyv, [None] * E))
+            g[1][e] = sinks
+            told.extend(ready)
+    for (epi, _, _, _), (dyv, sinks) in groups.items():
+        K.moe_experts_wgrad_seg(dyv, x, sinks, seg, epi)
+    if notify:
+        _notify(told)
+
+
+def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages):
+    idx, gate, probs, counts, slot, src, xe, gu, hh, ye, seg, tile_expert = saved
+    dye, dgate = K.moe_combine_bwd(dout, ye, slot, src, gate)
+    dgu, dhh = K.moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert)
+    _stage(stages, dhh=dhh)
+    _wgrad_seg(dye, hh, [[w] for w in wds], seg)
+    dxe = K.moe_experts_dgrad_gate_up_seg(dgu, wgs, wus, seg, tile_expert) if need_dx else None
+    _wgrad_seg(dgu, xe, [[wg, wu] for wg, wu in zip(wgs, wus)], seg)
+    dlogits = K.moe_route_bwd(dgate, probs, idx, counts, d_aux, norm_topk_prob)
+    dh = None
+    if need_dx:
+        dhr = K.linear_dgrad(dlogits, [router_w])
+        dh = K.moe_combine(dxe, slot, None, dhr)
+        _stage(stages, dxe=dxe, dh_router=dhr, dh=dh)
+    wgrad(dlogits, h2, [router_w])
+    _stage(stages, dye=dye, dgate=dgate, dgu=dgu, dlogits=dlogits)
+    return dh
+
+
+def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob=True, need_dx=True, stages=None,
+                  dropless=False):
     """Backward of moe_block_fwd's expert path and router: returns dh2 (the residual's gradient is
     dout itself).  d_aux: the gradient of aux, an f32 device scalar or None.  Expert and router
     weight gradients go to their sinks through wgrad_group / wgrad, MOE_GROUP experts to a launch, so
     bf16 .grad, f32 main_grad, the DP notification and weight-gradient pairing behave as for a dense
     layer (an expert's jobs pair on its own parameters; C is the same for every micro-batch)."""
+    if dropless:   # `saved` of moe_block_fwd(capacity_factor=None): with its segments
+        return _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages)
     idx, gate, probs, counts, slot, src, xe, gu, hh, ye = saved
     E = len(wgs)
     C = xe.shape[0] // E
@@ -1237,7 +1296,7 @@ def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_
 class MoEFunction(torch.autograd.Function):
     """A mixture-of-experts MLP with its residual as one node:
     apply(h2, residual, router_w, [wg_e], [wu_e], [wd_e], k, capacity_factor, norm_topk_prob)
-    -> (out = residual + MoE(h2), aux).  aux is the Switch load-balancing loss E sum_e f_e P_e with
+    -> (out = residual + MoE(h2), aux).  capacity_factor None: dropless (segment GEMMs over packed rows).  aux is the Switch load-balancing loss E sum_e f_e P_e with
     f_e = the fraction of the T k selections that chose e (before dropping, no gradient) and P_e =
     the mean router probability of e; HF Mixtral's load_balancing_loss_func is k times this value.
     The expert weights travel in lists, which autograd does not see: like every weight here they get
@@ -1251,17 +1310,19 @@ class MoEFunction(torch.autograd.Function):
             raise NotImplementedError("mixture-of-experts layers under tensor parallelism (experts are not sharded)")
         x2, r2 = _contig2d(h2), _contig2d(residual)
         wgs, wus, wds = list(wgs), list(wus), list(wds)
-        out, aux, saved = moe_block_fwd(x2, r2, router_w, wgs, wus, wds, int(k), float(capacity_factor),
+        out, aux, saved = moe_block_fwd(x2, r2, router_w, wgs, wus, wds, int(k),
+                                        None if capacity_factor is None else float(capacity_factor),
                                         bool(norm_topk_prob), stages)
         ctx.save_for_backward(x2, router_w, *saved, *wgs, *wus, *wds)
         ctx.E, ctx.k, ctx.norm, ctx.shape, ctx.stages = len(wgs), int(k), bool(norm_topk_prob), h2.shape, stages
+        ctx.dropless, ctx.nsaved = capacity_factor is None, len(saved)
         return out.view(h2.shape), aux.view(())
 
     @staticmethod
     def backward(ctx, dout, daux):
         x2, router_w, *rest = ctx.saved_tensors
-        saved, ws = rest[:10], rest[10:]
         E = ctx.E
+        saved, ws = rest[:ctx.nsaved], rest[ctx.nsaved:]
         wgs, wus, wds = ws[:E], ws[E:2 * E], ws[2 * E:]
         if dout is None:
             dout = torch.zeros(ctx.shape, dtype=x2.dtype, device=x2.device)
@@ -1269,7 +1330,7 @@ class MoEFunction(torch.autograd.Function):
         if daux is not None:
             daux = daux.to(torch.float32).reshape(1).contiguous()
         dh = moe_block_bwd(d2, daux, x2, saved, router_w, wgs, wus, wds, ctx.k, ctx.norm,
-                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages)
+                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages, dropless=ctx.dropless)
         return (dh.view(ctx.shape) if dh is not None else None, dout if ctx.needs_input_grad[1] else None) + (None,) * 8
 
 

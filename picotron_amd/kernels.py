@@ -968,6 +968,44 @@ def moe_plan(idx, E, C):
     return slot, src
 
 
+MOE_SEG_ALIGN = 128   # pt_moe_seg_align(): the segment GEMMs' M-tile; every expert's first row is a multiple
+
+
+def moe_dropless_rows(T, E, k):
+    """Rows of the packed dropless buffers: MOE_SEG_ALIGN * ((T k + E (MOE_SEG_ALIGN - 1)) // MOE_SEG_ALIGN),
+    an upper bound of sum_e ceil128(n_e) for any routing -- a static shape, nothing read on the host."""
+    T, E, k = int(T), int(E), int(k)
+    _req(T >= 1 and E >= 1 and 1 <= k <= E, "moe_dropless_rows: T >= 1 and 1 <= k <= E")
+    A = MOE_SEG_ALIGN
+    return A * ((T * k + E * (A - 1)) // A)
+
+
+def moe_plan_dropless(idx, E):
+    """idx int32 [T, k] -> (slot int32 [T, k], src int32 [R], seg int32 [E + 1], tile_expert int32
+    [R / 128]), R = moe_dropless_rows(T, E, k).  Expert e's items take rows [seg[e], seg[e] + n_e) in flat
+    item order, every seg[e] a multiple of MOE_SEG_ALIGN; src is -1 on padding rows and the unused tail
+    (from seg[E] on), tile_expert -1 there.  Nothing is dropped."""
+    _req(idx.dim() == 2, "moe_plan_dropless: idx [T, k]")
+    T, k = idx.shape
+    E = int(E)
+    _moe_items(idx, T, k, torch.int32, "idx")
+    _req(T >= 1, "moe_plan_dropless: at least one token")
+    _moe_sizes(E, k, "moe_plan_dropless")
+    R = moe_dropless_rows(T, E, k)
+    dev = idx.device
+    lib = _C.lib()
+    slot = torch.empty(T, k, dtype=torch.int32, device=dev)
+    src = torch.empty(R, dtype=torch.int32, device=dev)
+    seg = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    tile_expert = torch.empty(R // MOE_SEG_ALIGN, dtype=torch.int32, device=dev)
+    words = lib.pt_moe_plan_workspace(T, E, k)
+    _C.check(0 if words > 0 else words, "pt_moe_plan_workspace")
+    rc = lib.pt_moe_plan_dropless(_ptr(idx), T, E, k, R, _ptr(slot), _ptr(src), _ptr(seg), _ptr(tile_expert),
+                                  _ptr(_moe_ws("plan", words, dev)), _C.stream_ptr(dev))
+    _C.check(rc, "pt_moe_plan_dropless")
+    return slot, src, seg, tile_expert
+
+
 def moe_dispatch(x, src, k, out=None):
     """xe[r] = x[src[r] // k] (a bit copy of token rows into their experts' rows), zeros where
     src[r] < 0.  x [T, H] bf16, H % 64 == 0 -> xe [len(src), H]."""
@@ -2068,6 +2106,133 @@ def moe_experts_dgrad_gate_up(dgu, wgs, wus, C):
                                       [dxe[e * C:(e + 1) * C]], [H], [0, C], C, H, 2 * I)
                              for e, (wg, wu) in enumerate(zip(wgs, wus))], 1, 0, EPI_BF16, (C, H, 2 * I), dev)
     return dxe
+
+
+# ------------------------------------------------------------------ MoE expert GEMMs (dropless)
+# The packed layout of moe_plan_dropless: one pt_moe_gemm_seg launch per product covers every expert;
+# the kernel finds a tile's expert in tile_expert and its pointers in a per-expert device table.  A table
+# is uploaded once per distinct set of pointers and cached (as _moe_ws caches workspaces).  Weights, f32
+# main_grad buffers and .grad tensors that are zeroed in place keep their storage over a run, so their
+# tables are uploaded once.  A .grad that is freed every step (zero_grad(set_to_none=True)) is a new
+# allocation: its table is found again only where torch's caching allocator hands back the same blocks --
+# usual in a steady training loop, not guaranteed and not measured; a miss costs one 4 E-word upload.
+_MOE_SEG_TABLES = {}
+_MOE_SEG_TABLES_MAX = 1024   # (full: emptied; live pointer sets come back with their next launch)
+
+
+def moe_seg_table_host(p0, p1, ld):
+    """The host image (int64 [E, 4]) of a per-expert table from pointer lists (p1 None: one pointer each);
+    pt_moe_seg_table's refusals raise."""
+    E = len(p0)
+    a0 = (ctypes.c_void_p * max(E, 1))(*p0)
+    a1 = (ctypes.c_void_p * max(E, 1))(*p1) if p1 is not None else None
+    host = torch.empty(max(E, 1), 4, dtype=torch.int64)
+    rc = _C.lib().pt_moe_seg_table(a0, a1, int(ld), E, ctypes.cast(host.data_ptr(), ctypes.POINTER(ctypes.c_int64)))
+    _C.check(rc, f"pt_moe_seg_table(E={E}, ld={ld})")
+    return host
+
+
+def _moe_seg_table(p0, p1, ld, dev):
+    key = (tuple(p0), tuple(p1) if p1 is not None else None, int(ld), _dev_index(dev))
+    t = _MOE_SEG_TABLES.get(key)
+    if t is None:
+        if len(_MOE_SEG_TABLES) >= _MOE_SEG_TABLES_MAX:
+            _MOE_SEG_TABLES.clear()
+        t = _MOE_SEG_TABLES[key] = moe_seg_table_host(p0, p1, ld).to(dev)
+    return t
+
+
+def moe_gemm_seg(form, a, table, seg, tile_expert, N, K, split, E, b=None, out=None, epilogue=EPI_BF16, label="seg"):
+    """One pt_moe_gemm_seg launch (include/picotron_hip.h).  form 0 / 1: a [R, K] -> out [R, N] (allocated
+    when None); form 2: a = dY [R, N], b = X [R, K] into the table's sinks."""
+    _bf16_rowmajor(a, "a")
+    R = a.shape[0]
+    dev = a.device
+    if form != 2 and out is None:
+        out = torch.empty(R, N, dtype=BF16, device=dev)
+    flops = 2.0 * R * N * K
+    rc = _timed(f"moe {label} form{form} {R}x{N}x{K}", flops, float(2 * R * (N + K) + 2 * E * N * K),
+                _C.lib().pt_moe_gemm_seg, int(form), _ptr(a), a.stride(0), _ptr(b) if b is not None else None,
+                b.stride(0) if b is not None else 0, _ptr(out) if out is not None else None,
+                out.stride(0) if out is not None else 0, _ptr(table), _ptr(seg),
+                _ptr(tile_expert) if tile_expert is not None else None, R, int(N), int(K), int(split), int(E), int(epilogue),
+                _C.stream_ptr(dev))
+    _C.check(rc, f"pt_moe_gemm_seg(moe {label}: form {form}, R={R}, N={N}, K={K}, split={split}, E={E}, epi={epilogue})")
+    return out
+
+
+def _moe_seg_shapes(buf, ws, seg, tile_expert, what):
+    _bf16_rowmajor(buf, what)
+    E, R = len(ws), buf.shape[0]
+    _req(E >= 1 and R % MOE_SEG_ALIGN == 0 and buf.is_contiguous(), f"{what}: contiguous [R, cols], R % {MOE_SEG_ALIGN} == 0")
+    for t, n, name in ((seg, E + 1, "seg"), (tile_expert, R // MOE_SEG_ALIGN, "tile_expert")):
+        _req(t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (n,), f"{name}: int32 [{n}]")
+    return E
+
+
+def moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert):
+    """The dropless form of moe_experts_fwd: xe [R, H] -> (gu [R, 2I], hh [R, I], ye [R, H]), one
+    launch per product for all experts; the SwiGLU is the row kernel over the whole buffer."""
+    E = _moe_seg_shapes(xe, wgs, seg, tile_expert, "xe")
+    H, I = xe.shape[1], wgs[0].shape[0]
+    _req(len(wus) == E and len(wds) == E, "moe_experts_fwd_seg: E weights each")
+    _moe_weights(list(wgs) + list(wus), (I, H), "gate / up weights")
+    _moe_weights(wds, (H, I), "down weights")
+    dev = xe.device
+    tgu = _moe_seg_table([_ptr(w) for w in wgs], [_ptr(w) for w in wus], H, dev)
+    gu = moe_gemm_seg(0, xe, tgu, seg, tile_expert, 2 * I, H, I, E, label="gate|up")
+    hh = torch.empty(xe.shape[0], I, dtype=BF16, device=dev)
+    swiglu_fwd(gu[:, :I], gu[:, I:], out=hh)
+    td = _moe_seg_table([_ptr(w) for w in wds], None, I, dev)
+    ye = moe_gemm_seg(0, hh, td, seg, tile_expert, H, I, H, E, label="down")
+    return gu, hh, ye
+
+
+def moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert):
+    """dye [R, H] -> (dgu [R, 2I], dhh [R, I] = dye Wd_e), the dropless form of moe_experts_dgrad_down."""
+    E = _moe_seg_shapes(dye, wds, seg, tile_expert, "dye")
+    H, I = dye.shape[1], wds[0].shape[1]
+    _moe_weights(wds, (H, I), "down weights")
+    _bf16_rowmajor(gu, "gu")
+    _req(tuple(gu.shape) == (dye.shape[0], 2 * I) and gu.is_contiguous(), "gu: contiguous [R, 2I]")
+    td = _moe_seg_table([_ptr(w) for w in wds], None, I, dye.device)
+    dhh = moe_gemm_seg(1, dye, td, seg, tile_expert, I, H, H, E, label="down dX")
+    dgu = torch.empty_like(gu)
+    swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:])
+    return dgu, dhh
+
+
+def moe_experts_dgrad_gate_up_seg(dgu, wgs, wus, seg, tile_expert):
+    """dgu [R, 2I] -> dxe [R, H] = dg Wg_e + du Wu_e in one launch."""
+    E = _moe_seg_shapes(dgu, wgs, seg, tile_expert, "dgu")
+    I, H = wgs[0].shape
+    _req(len(wus) == E and dgu.shape[1] == 2 * I, "moe_experts_dgrad_gate_up_seg: dgu [R, 2I], E weights each")
+    _moe_weights(list(wgs) + list(wus), (I, H), "gate / up weights")
+    tgu = _moe_seg_table([_ptr(w) for w in wgs], [_ptr(w) for w in wus], H, dgu.device)
+    return moe_gemm_seg(1, dgu, tgu, seg, tile_expert, H, 2 * I, I, E, label="gate|up dX")
+
+
+def moe_experts_wgrad_seg(dy, x, sinks, seg, epilogue):
+    """Every expert's weight gradient in one launch: sinks[e] = [sink] or [sink_lo, sink_hi] (the row
+    halves of dY^T's product, e.g. gate and up) or None (the expert is skipped); sink_e (op)=
+    dy[seg[e] : seg[e + 1]]^T x[seg[e] : seg[e + 1]]."""
+    _bf16_rowmajor(dy, "dy")
+    _bf16_rowmajor(x, "x")
+    E, (R, Nout), Kin = len(sinks), dy.shape, x.shape[1]
+    _req(x.shape[0] == R and R % MOE_SEG_ALIGN == 0, f"moe_experts_wgrad_seg: dy and x [R, *], R % {MOE_SEG_ALIGN} == 0")
+    _req(seg.dtype == torch.int32 and seg.is_cuda and seg.is_contiguous() and tuple(seg.shape) == (E + 1,), f"seg: int32 [{E + 1}]")
+    live = [s for s in sinks if s is not None]
+    _req(len(live) > 0 and len({len(s) for s in live}) == 1 and len(live[0]) in (1, 2), "sinks: one or two per expert")
+    parts = len(live[0])
+    want = torch.float32 if epilogue in (EPI_F32, EPI_F32_ACC) else BF16
+    for s in live:
+        for t in s:
+            _req(t.dtype == want and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (Nout // parts, Kin),
+                 f"sink: contiguous {want} [{Nout // parts}, {Kin}]")
+    p0 = [_ptr(s[0]) if s is not None else None for s in sinks]
+    p1 = [_ptr(s[1]) if s is not None else None for s in sinks] if parts == 2 else None
+    table = _moe_seg_table(p0, p1, Kin, dy.device)
+    moe_gemm_seg(2, dy, table, seg, None, Nout, Kin, Nout // parts, E, b=x, epilogue=epilogue, label="dW")
 
 
 def _splitk_enabled():

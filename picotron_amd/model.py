@@ -308,7 +308,9 @@ class MoE(nn.Module):
     Every token takes its num_experts_per_tok best experts by router logit; expert e owns C rows
     (kernels.moe_capacity with config.moe_capacity_factor, default 1.25; >= num_experts /
     num_experts_per_tok never drops) and the items past them are dropped: the residual carries the
-    token.  norm_topk_prob (default True) divides the chosen probabilities by their sum.
+    token.  config.moe_dropless = True (default False) drops nothing instead: the experts' rows are packed
+    back to back and run as segment GEMMs (kernels.moe_plan_dropless); moe_capacity_factor is then ignored.
+    norm_topk_prob (default True) divides the chosen probabilities by their sum.
     forward(x, residual) returns residual + MoE(x) and leaves the Switch load-balancing loss of this
     call in self.aux_loss (functional.MoEFunction).  DP only: tensor / sequence / context / pipeline
     parallelism are refused."""
@@ -327,12 +329,15 @@ class MoE(nn.Module):
         self.top_k = int(getattr(config, "num_experts_per_tok", 2))
         self.capacity_factor = float(getattr(config, "moe_capacity_factor", 1.25))
         self.norm_topk_prob = bool(getattr(config, "norm_topk_prob", True))
+        self.dropless = bool(getattr(config, "moe_dropless", False))
         inter = getattr(config, "moe_intermediate_size", None) or config.intermediate_size
         if not 1 <= self.num_experts <= K.MOE_MAX_EXPERTS or not 1 <= self.top_k <= min(self.num_experts, K.MOE_MAX_TOPK):
             raise ValueError(f"MoE: 1 <= num_experts <= {K.MOE_MAX_EXPERTS} and 1 <= num_experts_per_tok <= "
                              f"min(num_experts, {K.MOE_MAX_TOPK}); got {self.num_experts}, {self.top_k}")
         if config.hidden_size % K.GRID or inter % K.GRID:
             raise ValueError(f"MoE: hidden_size and moe_intermediate_size on the {K.GRID}-grid")
+        if self.dropless and (config.hidden_size % K.MOE_SEG_ALIGN or inter % K.MOE_SEG_ALIGN):
+            raise ValueError(f"MoE: moe_dropless needs hidden_size and moe_intermediate_size on the {K.MOE_SEG_ALIGN}-grid")
         self.router = Linear(config.hidden_size, self.num_experts, bias=False)
         expert = types.SimpleNamespace(hidden_size=config.hidden_size, intermediate_size=inter)
         self.experts = nn.ModuleList([MLP(expert) for _ in range(self.num_experts)])
@@ -351,7 +356,7 @@ class MoE(nn.Module):
         out, self.aux_loss = FN.MoEFunction.apply(
             x, residual, self.router.weight, [e.gate_proj.weight for e in self.experts],
             [e.up_proj.weight for e in self.experts], [e.down_proj.weight for e in self.experts], self.top_k,
-            self.capacity_factor, self.norm_topk_prob, self.stages)
+            None if self.dropless else self.capacity_factor, self.norm_topk_prob, self.stages)
         return out
 
 

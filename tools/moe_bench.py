@@ -9,6 +9,7 @@ capture is refused), the best of three replays per round, of
 then the expert GEMMs per launch label under a GemmProbe.  No threshold: the log is the record.
 python tools/moe_bench.py [--tokens 4096] [--hidden 2048] [--dense-inter 8192] [--rounds 3] [--reps 4]"""
 import argparse
+import hashlib
 import json
 import os
 import sys
@@ -52,6 +53,32 @@ def weights(n, rows, cols, gen):
     return ws
 
 
+def dropless_rounds(a, h2, res, dout, rw, wgs, wus, wds, E, k, I):
+    """Forward and backward of the block dropless, at factor 1.25 and at E / k, alternating in every round;
+    tflops counts the items each setting keeps (dropless and E / k: all T k)."""
+    T, H = h2.shape
+    d_aux = torch.full((1,), 0.01, device="cuda")
+    runs = []
+    for name, cf in (("dropless", None), ("cf 1.25", 1.25), ("cf E/k", E / k)):
+        saved = FN.moe_block_fwd(h2, res, rw, wgs, wus, wds, k, cf)[2]
+        kept = int((saved[4] >= 0).sum())
+        out(what="setting", E=E, k=k, setting=name, rows=saved[6].shape[0], kept=kept, dropped=T * k - kept)
+        runs.append((name + " forward", lambda cf=cf: FN.moe_block_fwd(h2, res, rw, wgs, wus, wds, k, cf), 6 * kept * H * I))
+        runs.append((name + " backward", lambda saved=saved, cf=cf: FN.moe_block_bwd(dout, d_aux, h2, saved, rw, wgs, wus, wds, k,
+                                                                                     dropless=cf is None), 12 * kept * H * I))
+    for rnd in range(a.rounds):
+        for name, fn, flop in (runs if rnd % 2 == 0 else runs[::-1]):
+            us, how = time_us(fn, a.reps)
+            out(block=name, E=E, k=k, round=rnd, us=round(us, 1), tflops=round(flop / us / 1e6, 1), timed=how)
+    for _ in range(2):   # the second pass is the warm one
+        with K.GemmProbe() as probe:
+            s2 = FN.moe_block_fwd(h2, res, rw, wgs, wus, wds, k, None)[2]
+            FN.moe_block_bwd(dout, d_aux, h2, s2, rw, wgs, wus, wds, k, dropless=True)
+            labels = probe.by_label()
+    for label, (launches, ms, tf) in labels.items():
+        out(gemm=label, E=E, k=k, launches=launches, total_ms=ms, tflops=tf)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=4096)
@@ -59,6 +86,8 @@ def main():
     ap.add_argument("--dense-inter", type=int, default=8192)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--reps", type=int, default=4)
+    ap.add_argument("--dropless", action="store_true",
+                    help="the block at capacity_factor None (segment GEMMs), 1.25 and E / k (never drops), interleaved")
     a = ap.parse_args()
     T, H = a.tokens, a.hidden
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -74,6 +103,11 @@ def main():
         out(what="case", E=E, k=k, T=T, H=H, I_moe=I, I_dense=k * I, C=C, rows=R)
         rw = weights(1, E, H, gen)[0]
         wgs, wus, wds = weights(E, I, H, gen), weights(E, I, H, gen), weights(E, H, I, gen)
+        if a.dropless:
+            dropless_rounds(a, h2, res, dout, rw, wgs, wus, wds, E, k, I)
+            del wgs, wus, wds
+            torch.cuda.empty_cache()
+            continue
         logits = K.linear_fwd(h2, [rw])
         idx, gate, probs, counts, aux = K.moe_route(logits, k)
         slot, src = K.moe_plan(idx, E, C)
@@ -121,6 +155,8 @@ def main():
             out(gemm=label, E=E, k=k, launches=launches, total_ms=ms, tflops=tf)
         del wgs, wus, wds, dg, du, dd, saved, dsaved, s2
         torch.cuda.empty_cache()
+    import socket
+    out(what="box", id=hashlib.sha1(socket.gethostname().encode()).hexdigest()[:8])
     out(what="status", value=K.device_status(torch.device("cuda")))
 
 
