@@ -181,6 +181,35 @@ int pt_moe_combine_bwd(const void* dy, int64_t lddy, const void* ye, int64_t ldy
 int pt_moe_route_bwd(const float* dgate, const float* probs, const int32_t* idx, const int32_t* counts,
                      const float* d_aux, int norm_topk, void* dlogits, int64_t ldl, int64_t T, int64_t E, int64_t k,
                      hipStream_t stream);
+/* The sigmoid router (DeepSeek-V2/V3, Moonlight, GLM-4.5, Kimi-K2): scores instead of a softmax, a
+ * per-expert selection bias, group-limited top-k, a routed scaling factor.  All in f32 from the stored
+ * bf16 logits: s[t, e] = 1 / (1 + exp(-logit)), key[t, e] = s[t, e] + bias[e] (bias f32 [E], NULL:
+ * zeros).  The E experts form n_group contiguous groups of E / n_group; a group's score is the sum of
+ * its two largest keys, and the topk_group groups with the largest score stay (ties to the lower
+ * group; n_group 1: no limit).  idx int32 [T, k] = the k largest keys inside the kept groups, ties to
+ * the lower expert, best first; a NaN key orders as -inf.  gate f32 [T, k] = s[idx] -- the score, not
+ * the key -- divided by (sum_i s[idx_i] + 1e-20) when norm_topk, then times scale.  probs f32 [T, E] =
+ * s; counts as pt_moe_route; aux = E sum_e (counts[e] / (T k)) mean_t q[t, e] with q = s / sum_e s,
+ * the Switch loss on normalised scores.  load int32 [E] (NULL: none): load[e] += counts[e], what
+ * pt_moe_bias_update consumes.  Beyond the preamble's limits (E <= 128 -- a 256-expert router is not
+ * covered -- and k <= min(E, 8)), PT_EUNSUPPORTED unless n_group divides E, 1 <= topk_group <=
+ * n_group <= 16, E / n_group >= 2 when n_group > 1, and k <= topk_group E / n_group; n_group or
+ * topk_group < 1 is a size < 1.  workspace: pt_moe_route_workspace(T, E) words.
+ * pt_moe_route_sigmoid_bwd: dlogits bf16 [T, ldl] (columns E.. zero), idx, bias and counts carrying
+ * no gradient: with S = sum_i s[idx_i] + 1e-20, ds[idx_j] = (scale dgate_j - sum_i dgate_i gate_i) / S
+ * under norm_topk, else scale dgate_j; ds[e] += (dq_e - sum_e' q_e' dq_e') / sum_e' s_e' with dq_e =
+ * d_aux E counts[e] / (T k) / T (d_aux a device scalar, NULL: 0); dlogit = ds s (1 - s), one rounding.
+ * pt_moe_bias_update (one workgroup; E <= 128): bias[e] += rate sign(sum_e' load[e'] - E load[e]),
+ * compared in int64 (exact: an expert at the mean keeps its bias), then load[e] = 0 -- the
+ * auxiliary-loss-free balancing step, once per layer and optimizer step. */
+int pt_moe_route_sigmoid(const void* logits, int64_t ldl, const float* bias, int64_t T, int64_t E, int64_t k,
+                         int64_t n_group, int64_t topk_group, int norm_topk, float scale, int32_t* idx, float* gate,
+                         float* probs, int32_t* counts, float* aux, int32_t* load, void* workspace,
+                         hipStream_t stream);
+int pt_moe_route_sigmoid_bwd(const float* dgate, const float* probs, const int32_t* idx, const float* gate,
+                             const int32_t* counts, const float* d_aux, int norm_topk, float scale, void* dlogits,
+                             int64_t ldl, int64_t T, int64_t E, int64_t k, hipStream_t stream);
+int pt_moe_bias_update(float* bias, int32_t* load, int64_t E, float rate, hipStream_t stream);
 
 /* ---- residual add: out = bf16(x + r), n contiguous bf16 (n % 8 == 0, 16-B aligned) ------------
  * replaces picotron/model.py:208 `x + self.mlp(...)` where the sequence-parallel TP layer adds the

@@ -103,6 +103,10 @@ SIGNATURES = {
     "pt_moe_combine": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _vp]),
     "pt_moe_combine_bwd": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     "pt_moe_route_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "pt_moe_route_sigmoid": (_i32, [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp]),
+    "pt_moe_route_sigmoid_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _vp, _i64, _i64, _i64, _i64, _vp]),
+    "pt_moe_bias_update": (_i32, [_vp, _vp, _i64, _f32, _vp]),
     "pt_cross_entropy_fwd_bwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _f32, _vp, _i64, _vp, _vp]),
     "pt_cross_entropy_fwd_lse": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),
     "pt_cross_entropy_bwd_lse": (_i32, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp]),

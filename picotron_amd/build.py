@@ -37,7 +37,12 @@ def sources():
 # per-source code-generation flags.  attention: MFMA results in VGPRs (gfx950's unified register
 # file) instead of AGPRs -- the softmax reads every S / dP accumulator, and the AGPR form cost a
 # v_accvgpr_read per element plus registers (fwd 156 -> 124 VGPRs: 3 -> 4 waves per SIMD).
-FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+# moe: no packed-f32 VALU forms (v_pk_add / mul / fma_f32): the routing kernels gain nothing from them
+# -- a row kernel waits on HBM, the routers on lane moves -- and every result then comes from the
+# plain f32 instructions whose rounding the tests pin down (the feature is a device one: the host
+# pass notes that it does not know it).
+FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+              "moe.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _compile(src, obj, extra):

@@ -14,13 +14,18 @@
 //   combine_bwd  dye[r] = bf16(gate[src[r]] dy[src[r] / k]);  dgate[i] = <dy[t], ye[slot[i]]> in f32
 //   route_bwd    dlogits = the backward of softmax, selection and renormalisation, plus the aux term
 //
+// A second router, DeepSeek-V3 / Moonlight / GLM-4.5 / Kimi-K2 style (route_sigmoid, its backward and
+// bias_update, below the softmax router's backward): sigmoid scores, a selection bias that moves the
+// choice but not the gate, group-limited top-k, a routed scaling factor, and the auxiliary-loss-free
+// bias step on the observed load.  Everything downstream of idx / gate is shared.
+//
 // No atomics anywhere: sums over tokens go through per-workgroup partials added in index order, the
 // prefix count of `plan` through a per-workgroup histogram scanned by one thread per expert -- two
 // runs give the same bits, and no result depends on how workgroups are scheduled.  The row kernels
 // move O(T k H) bytes in 16-byte accesses and do nothing else.
 //
 // Top to bottom: route (+ its final sum), plan (three passes), the row kernels, route_bwd, the
-// extern "C" entries with their host-side validation.
+// sigmoid router (route, backward, bias step), the extern "C" entries with their host-side validation.
 #include "common.h"
 #include <limits.h>
 #include <math.h>
@@ -109,11 +114,11 @@ __global__ __launch_bounds__(256) void moe_route_kernel(const uint16_t* __restri
 }
 
 // counts[e], and aux = E sum_e f_e P_e: thread e adds the partial rows in workgroup order, thread 0
-// the E terms in expert order
+// the E terms in expert order.  load (the sigmoid router's; NULL: none): load[e] += counts[e].
 __global__ __launch_bounds__(kMaxE) void moe_route_final_kernel(const float* __restrict__ part_p,
                                                                 const int32_t* __restrict__ part_c, int nblk, int T,
                                                                 int E, int k, int32_t* __restrict__ counts,
-                                                                float* __restrict__ aux) {
+                                                                float* __restrict__ aux, int32_t* __restrict__ load) {
   __shared__ float term[kMaxE];
   const int e = threadIdx.x;
   float P = 0.0f;
@@ -124,6 +129,7 @@ __global__ __launch_bounds__(kMaxE) void moe_route_final_kernel(const float* __r
       c += part_c[(int64_t)b * E + e];
     }
     counts[e] = c;
+    if (load) load[e] += c;
   }
   term[e] = e < E ? ((float)c / ((float)T * (float)k)) * (P / (float)T) : 0.0f;
   __syncthreads();
@@ -403,6 +409,217 @@ __global__ __launch_bounds__(256) void moe_route_bwd_kernel(const float* __restr
   }
 }
 
+// ---- sigmoid route ---------------------------------------------------------------------------------
+// s = sigmoid(logit), key = s + bias[e]; the Kg of G contiguous expert groups with the largest sum of
+// their two best keys stay, idx = the k best keys inside them, gate = scale s[idx] (/ their sum).
+// One wave per token, lane l holds experts l and l + 64 as in the softmax router, but nothing here is
+// a round of wave argmax.  Per token:
+//   1. every group's two best keys at once: a segmented inclusive scan of (best, second) pairs along
+//      the lanes, one per register slot, log2(E / G) steps of two lane shifts -- lane l merges lane
+//      l - o only while that lane is still inside its group, so the groups need no alignment and no
+//      power-of-two size; the last lane of a group ends up with its pair (a group across the 64-lane
+//      seam: one pair per slot, merged on arrival)
+//   2. lane g < G fetches group g's pair; its rank among the G scores is a count over G lane
+//      broadcasts through scalar registers (v_readlane), and one ballot of rank < Kg is the kept mask
+//   3. the top-k the same way: (key, expert) packed into one ordered integer per candidate, 0 for an
+//      expert of a dropped group, and a candidate's rank is the number of larger integers among E
+//      lane broadcasts.  The integers are distinct, so the ranks are, and rank r < k IS position r of
+//      idx: every chosen lane stores its own entry, best first, with no selection rounds.
+// The cost is E broadcasts and compares per token instead of k rounds of a 6-step argmax, and the
+// group pass is 2 log2(E / G) + 4 lane moves.  A NaN key orders as -inf (it loses to every number and
+// ties, by index, with other -inf keys), as in the softmax router.
+constexpr int kMaxG = 16;
+
+// the IEEE order of non-NaN floats as unsigned integers
+__device__ __forceinline__ uint32_t ord_key(float v) {
+  const uint32_t b = __float_as_uint(v);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// (ordered key, expert) -> the selection order in one integer: larger key first, then the lower expert
+__device__ __forceinline__ uint64_t cand(uint32_t ok, int e) { return ((uint64_t)ok << 32) | (uint32_t)(kMaxE - 1 - e); }
+__device__ __forceinline__ uint32_t lane_bcast(uint32_t v, int l) {   // l wave-uniform
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, l);
+}
+// (a, b) = the two largest of {a, b, pa, pb}, a >= b; no NaNs reach here
+__device__ __forceinline__ void top2_merge(float& a, float& b, float pa, float pb) {
+  const float lo = fminf(a, pa);
+  a = fmaxf(a, pa);
+  b = fmaxf(lo, fmaxf(b, pb));
+}
+// the segmented scan of step 1 over one register slot; pos = the expert's position inside its group
+__device__ __forceinline__ void group_top2_scan(float& a, float& b, int pos, int lane, int gs) {
+  for (int o = 1; o < gs && o < 64; o <<= 1) {   // wave-uniform
+    const float pa = __shfl_up(a, o, 64), pb = __shfl_up(b, o, 64);
+    if (lane >= o && pos >= o) top2_merge(a, b, pa, pb);
+  }
+}
+
+__global__ __launch_bounds__(256) void moe_route_sigmoid_kernel(
+    const uint16_t* __restrict__ logits, int64_t ldl, const float* __restrict__ bias, int T, int E, int k, int G, int Kg,
+    int norm, float scale, int32_t* __restrict__ idx, float* __restrict__ gate, float* __restrict__ probs,
+    float* __restrict__ part_p, int32_t* __restrict__ part_c) {
+  __shared__ float sh_p[4][kMaxE];
+  __shared__ int sh_c[4][kMaxE];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int e0 = lane, e1 = lane + 64;
+  const bool has0 = e0 < E, has1 = e1 < E;
+  const int gs = E / G;                      // experts per group
+  const int g0 = e0 / gs, g1 = e1 / gs;      // (G == 1: 0 for every expert there is)
+  const int pos0 = e0 - g0 * gs, pos1 = e1 - g1 * gs;
+  // lane g < G: where group g's pair ends, per slot
+  const int eF = lane * gs, eL = eF + gs - 1;
+  const bool in0 = lane < G && eF < 64, in1 = lane < G && eL >= 64;
+  const int l0 = (eL < 63 ? eL : 63) & 63, l1 = (eL - 64) & 63;
+  const float b0 = (bias && has0) ? bias[e0] : 0.0f, b1 = (bias && has1) ? bias[e1] : 0.0f;
+  const int n0 = E < 64 ? E : 64, n1 = E - n0;
+  float qs0 = 0.0f, qs1 = 0.0f;
+  int c0 = 0, c1 = 0;
+  const int t0 = blockIdx.x * kRouteTokens + w * (kRouteTokens / 4);
+  for (int i = 0; i < kRouteTokens / 4; ++i) {
+    const int t = t0 + i;   // wave-uniform
+    if (t >= T) break;
+    const uint16_t* row = logits + (int64_t)t * ldl;
+    // the accurate expf and an IEEE division: the scores are saved for the backward
+    const float s0 = has0 ? 1.0f / (1.0f + expf(-bf2f(row[e0]))) : 0.0f;
+    const float s1 = has1 ? 1.0f / (1.0f + expf(-bf2f(row[e1]))) : 0.0f;
+    if (has0) probs[(int64_t)t * E + e0] = s0;
+    if (has1) probs[(int64_t)t * E + e1] = s1;
+    const float tot = wave_sum(s0 + s1);
+    qs0 += s0 / tot;   // the aux loss runs on the normalised scores
+    qs1 += s1 / tot;
+    float k0 = (s0 + b0) + 0.0f, k1 = (s1 + b1) + 0.0f;   // (+ 0: no -0 in the integer order)
+    k0 = (has0 && k0 == k0) ? k0 : -INFINITY;
+    k1 = (has1 && k1 == k1) ? k1 : -INFINITY;
+    uint32_t kept = 1u;
+    if (G > 1) {
+      float a0 = k0, m0 = -INFINITY, a1 = k1, m1 = -INFINITY;
+      group_top2_scan(a0, m0, pos0, lane, gs);
+      if (E > 64) group_top2_scan(a1, m1, pos1, lane, gs);
+      float ga = -INFINITY, gb = -INFINITY;
+      const float f0 = __shfl(a0, l0, 64), f1 = __shfl(m0, l0, 64);
+      if (in0) top2_merge(ga, gb, f0, f1);
+      if (E > 64) {
+        const float h0 = __shfl(a1, l1, 64), h1 = __shfl(m1, l1, 64);
+        if (in1) top2_merge(ga, gb, h0, h1);
+      }
+      float score = ga + gb;
+      score = (lane < G && score == score) ? score : -INFINITY;
+      int rank = 0;
+      for (int j = 0; j < G; ++j) {
+        const float sj = __uint_as_float(lane_bcast(__float_as_uint(score), j));
+        rank += better(sj, j, score, lane) ? 1 : 0;
+      }
+      kept = (uint32_t)__ballot(lane < G && rank < Kg);
+    }
+    const bool v0 = has0 && ((kept >> g0) & 1u), v1 = has1 && ((kept >> g1) & 1u);
+    const uint32_t o0 = v0 ? ord_key(k0) : 0u, o1 = v1 ? ord_key(k1) : 0u;   // an ordered -inf is > 0
+    const uint64_t m0c = cand(o0, e0), m1c = cand(o1, e1);
+    int r0 = 0, r1 = 0;
+    for (int j = 0; j < n0; ++j) {
+      const uint64_t c = cand(lane_bcast(o0, j), j);
+      r0 += c > m0c ? 1 : 0;
+      r1 += c > m1c ? 1 : 0;
+    }
+    for (int j = 0; j < n1; ++j) {
+      const uint64_t c = cand(lane_bcast(o1, j), j + 64);
+      r0 += c > m0c ? 1 : 0;
+      r1 += c > m1c ? 1 : 0;
+    }
+    const bool sel0 = v0 && r0 < k, sel1 = v1 && r1 < k;   // k <= Kg E / G candidates: exactly k chosen
+    float mul = scale;
+    if (norm) mul = scale / (wave_sum((sel0 ? s0 : 0.0f) + (sel1 ? s1 : 0.0f)) + 1e-20f);
+    if (sel0) {
+      idx[(int64_t)t * k + r0] = e0;
+      gate[(int64_t)t * k + r0] = s0 * mul;
+    }
+    if (sel1) {
+      idx[(int64_t)t * k + r1] = e1;
+      gate[(int64_t)t * k + r1] = s1 * mul;
+    }
+    c0 += sel0 ? 1 : 0;
+    c1 += sel1 ? 1 : 0;
+  }
+  sh_p[w][e0] = qs0; sh_p[w][e1] = qs1;
+  sh_c[w][e0] = c0;  sh_c[w][e1] = c1;
+  __syncthreads();
+  if ((int)threadIdx.x < E) {
+    const int e = threadIdx.x;
+    part_p[(int64_t)blockIdx.x * E + e] = ((sh_p[0][e] + sh_p[1][e]) + sh_p[2][e]) + sh_p[3][e];
+    part_c[(int64_t)blockIdx.x * E + e] = sh_c[0][e] + sh_c[1][e] + sh_c[2][e] + sh_c[3][e];
+  }
+}
+
+// One wave per token.  S = sum_i s[idx_i] + 1e-20, gate_j = scale s[idx_j] / S (norm) or scale s[idx_j]:
+//   ds[idx_j] = (scale dgate_j - sum_i dgate_i gate_i) / S   |   scale dgate_j
+//   ds[e]    += (dq_e - sum_e' q_e' dq_e') / sum_e' s_e',  dq_e = d_aux E f_e / T, q = s / sum s
+//   dlogit[e] = ds[e] s[e] (1 - s[e])
+__global__ __launch_bounds__(256) void moe_route_sigmoid_bwd_kernel(
+    const float* __restrict__ dgate, const float* __restrict__ probs, const int32_t* __restrict__ idx,
+    const float* __restrict__ gate, const int32_t* __restrict__ counts, const float* __restrict__ d_aux, int norm,
+    float scale, uint16_t* __restrict__ dlogits, int64_t ldl, int T, int E, int k) {
+  const int lane = threadIdx.x & 63;
+  const int e0 = lane, e1 = lane + 64;
+  const bool has0 = e0 < E, has1 = e1 < E;
+  const float da = d_aux ? d_aux[0] : 0.0f;
+  const float fk = (float)T * (float)k;
+  const float a0 = has0 ? da * (float)E * ((float)counts[e0] / fk) / (float)T : 0.0f;
+  const float a1 = has1 ? da * (float)E * ((float)counts[e1] / fk) / (float)T : 0.0f;
+  for (int t = blockIdx.x * 4 + (threadIdx.x >> 6); t < T; t += gridDim.x * 4) {
+    const float s0 = has0 ? probs[(int64_t)t * E + e0] : 0.0f;
+    const float s1 = has1 ? probs[(int64_t)t * E + e1] : 0.0f;
+    int my_e = -1;
+    float my_d = 0.0f, my_g = 0.0f, my_s = 0.0f;   // lane j: the j-th choice
+    if (lane < k) {
+      my_e = idx[(int64_t)t * k + lane];
+      my_d = dgate[(int64_t)t * k + lane];
+      my_g = gate[(int64_t)t * k + lane];
+      if ((unsigned)my_e < (unsigned)E) my_s = probs[(int64_t)t * E + my_e];
+    }
+    if (norm) {
+      const float S = wave_sum(my_s) + 1e-20f;
+      const float dot = wave_sum(my_d * my_g);
+      my_d = (scale * my_d - dot) / S;
+    } else {
+      my_d = scale * my_d;
+    }
+    float ds0 = 0.0f, ds1 = 0.0f;
+    if (da != 0.0f) {   // wave-uniform
+      const float tot = wave_sum(s0 + s1);
+      const float inner = wave_sum(fmaf(s0 / tot, a0, (s1 / tot) * a1));
+      ds0 = (a0 - inner) / tot;
+      ds1 = (a1 - inner) / tot;
+    }
+    for (int j = 0; j < k; ++j) {
+      const int e = (int)lane_bcast((uint32_t)my_e, j);
+      const float d = __uint_as_float(lane_bcast(__float_as_uint(my_d), j));
+      if (e == e0) ds0 += d;
+      if (e == e1) ds1 += d;
+    }
+    uint16_t* row = dlogits + (int64_t)t * ldl;
+    if (has0) row[e0] = f2bf(ds0 * (s0 * (1.0f - s0)));
+    if (has1) row[e1] = f2bf(ds1 * (s1 * (1.0f - s1)));
+    for (int64_t c = E + lane; c < ldl; c += 64) row[c] = 0;   // the padded columns
+  }
+}
+
+// The auxiliary-loss-free balancing step, one workgroup: bias[e] += rate sign(sum load - E load[e])
+// (int64: exact, a tie leaves the bias as it is), then load[e] = 0.
+__global__ __launch_bounds__(kMaxE) void moe_bias_update_kernel(float* __restrict__ bias, int32_t* __restrict__ load,
+                                                                int E, float rate) {
+  __shared__ int sh_load[kMaxE];
+  const int e = threadIdx.x;
+  const int mine = e < E ? load[e] : 0;
+  sh_load[e] = mine;
+  __syncthreads();
+  if (e >= E) return;
+  int64_t total = 0;
+  for (int i = 0; i < E; ++i) total += sh_load[i];
+  const int64_t d = total - (int64_t)E * mine;
+  if (d > 0) bias[e] += rate;
+  if (d < 0) bias[e] -= rate;
+  load[e] = 0;
+}
+
 // ---- host side -------------------------------------------------------------------------------------
 constexpr int64_t kI32 = 2147483647;
 
@@ -410,6 +627,13 @@ constexpr int64_t kI32 = 2147483647;
 int sizes_ok(int64_t T, int64_t E, int64_t k) {
   if (T < 1 || E < 1 || k < 1) return PT_EINVAL;
   if (E > kMaxE || k > kMaxK || k > E || T * k > kI32) return PT_EUNSUPPORTED;
+  return PT_OK;
+}
+// the sigmoid router's groups (sizes >= 1 checked by the caller): G | E, 1 <= Kg <= G <= 16, groups of
+// two or more when there is more than one, and k candidates left inside the kept groups
+int groups_ok(int64_t E, int64_t k, int64_t G, int64_t Kg) {
+  if (G > kMaxG || Kg > G || E % G) return PT_EUNSUPPORTED;
+  if ((G > 1 && E / G < 2) || k > Kg * (E / G)) return PT_EUNSUPPORTED;
   return PT_OK;
 }
 // a row kernel's: R expert rows of H columns besides the T k items
@@ -451,7 +675,7 @@ int pt_moe_route(const void* logits, int64_t ldl, int64_t T, int64_t E, int64_t 
   moe_route_kernel<<<nblk, 256, 0, stream>>>((const uint16_t*)logits, ldl, (int)T, (int)E, (int)k, norm_topk ? 1 : 0,
                                              idx, gate, probs, part_p, part_c);
   PT_CHECK_LAUNCH();
-  moe_route_final_kernel<<<1, kMaxE, 0, stream>>>(part_p, part_c, nblk, (int)T, (int)E, (int)k, counts, aux);
+  moe_route_final_kernel<<<1, kMaxE, 0, stream>>>(part_p, part_c, nblk, (int)T, (int)E, (int)k, counts, aux, nullptr);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }
@@ -565,6 +789,54 @@ int pt_moe_route_bwd(const float* dgate, const float* probs, const int32_t* idx,
   const int grid = (int)(want < PT_STREAM_GRID_CAP * 2 ? want : PT_STREAM_GRID_CAP * 2);
   moe_route_bwd_kernel<<<grid, 256, 0, stream>>>(dgate, probs, idx, counts, d_aux, norm_topk ? 1 : 0,
                                                  (uint16_t*)dlogits, ldl, (int)T, (int)E, (int)k);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_moe_route_sigmoid(const void* logits, int64_t ldl, const float* bias, int64_t T, int64_t E, int64_t k,
+                         int64_t n_group, int64_t topk_group, int norm_topk, float scale, int32_t* idx, float* gate,
+                         float* probs, int32_t* counts, float* aux, int32_t* load, void* workspace,
+                         hipStream_t stream) {
+  if (!logits || !idx || !gate || !probs || !counts || !aux || !workspace || n_group < 1 || topk_group < 1)
+    return PT_EINVAL;
+  const int rc = sizes_ok(T, E, k);
+  if (rc != PT_OK) return rc;
+  const int gc = groups_ok(E, k, n_group, topk_group);
+  if (gc != PT_OK) return gc;
+  if (ldl < E) return PT_EINVAL;
+  if (T * ldl > kI32 * 2 || 2 * route_blocks(T) * E > kI32) return PT_EUNSUPPORTED;
+  const int nblk = (int)route_blocks(T);
+  float* part_p = (float*)workspace;
+  int32_t* part_c = (int32_t*)workspace + (int64_t)nblk * E;
+  moe_route_sigmoid_kernel<<<nblk, 256, 0, stream>>>((const uint16_t*)logits, ldl, bias, (int)T, (int)E, (int)k,
+                                                     (int)n_group, (int)topk_group, norm_topk ? 1 : 0, scale, idx, gate,
+                                                     probs, part_p, part_c);
+  PT_CHECK_LAUNCH();
+  moe_route_final_kernel<<<1, kMaxE, 0, stream>>>(part_p, part_c, nblk, (int)T, (int)E, (int)k, counts, aux, load);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_moe_route_sigmoid_bwd(const float* dgate, const float* probs, const int32_t* idx, const float* gate,
+                             const int32_t* counts, const float* d_aux, int norm_topk, float scale, void* dlogits,
+                             int64_t ldl, int64_t T, int64_t E, int64_t k, hipStream_t stream) {
+  if (!dgate || !probs || !idx || !gate || !counts || !dlogits) return PT_EINVAL;
+  const int rc = sizes_ok(T, E, k);
+  if (rc != PT_OK) return rc;
+  if (ldl < E) return PT_EINVAL;
+  if (T * ldl > kI32 * 2) return PT_EUNSUPPORTED;
+  const int64_t want = (T + 3) / 4;
+  const int grid = (int)(want < PT_STREAM_GRID_CAP * 2 ? want : PT_STREAM_GRID_CAP * 2);
+  moe_route_sigmoid_bwd_kernel<<<grid, 256, 0, stream>>>(dgate, probs, idx, gate, counts, d_aux, norm_topk ? 1 : 0, scale,
+                                                         (uint16_t*)dlogits, ldl, (int)T, (int)E, (int)k);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+int pt_moe_bias_update(float* bias, int32_t* load, int64_t E, float rate, hipStream_t stream) {
+  if (!bias || !load || E < 1) return PT_EINVAL;
+  if (E > kMaxE) return PT_EUNSUPPORTED;
+  moe_bias_update_kernel<<<1, kMaxE, 0, stream>>>(bias, load, (int)E, rate);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

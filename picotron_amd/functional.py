@@ -24,6 +24,7 @@ notify the gradient owner through `param._pt_grad_ready`.
 """
 import math
 import os
+import typing
 import weakref
 
 import torch
@@ -1153,12 +1154,15 @@ def mlp_block_bwd(dm, h2, saved, wg, wu, wd, tp, need_dx=True, keep_parts=False,
 
 
 class MLPFunction(torch.autograd.Function):
-    """MLP.forward (model.py:184-186): gate|up in one GEMM, SwiGLU, down_proj."""
+    """MLP.forward (model.py:184-186): gate|up in one GEMM, SwiGLU, down_proj.  residual (x's shape; None:
+    none): out = residual + MLP(x), added in the down_proj epilogue -- how an MoE layer's shared experts
+    enter its residual stream; its gradient is dm itself."""
 
     @staticmethod
-    def forward(ctx, x, wg, wu, wd):
+    def forward(ctx, x, wg, wu, wd, residual=None):
         h2 = _contig2d(x)
-        m, saved = mlp_block_fwd(h2, wg, wu, wd, TPContext.current())
+        m, saved = mlp_block_fwd(h2, wg, wu, wd, TPContext.current(),
+                                 residual=None if residual is None else _contig2d(residual))
         ctx.save_for_backward(h2, *saved, wg, wu, wd)
         ctx.shape = x.shape
         return m.view(*x.shape[:-1], -1)
@@ -1168,7 +1172,8 @@ class MLPFunction(torch.autograd.Function):
         h2, gu, hh, wg, wu, wd = ctx.saved_tensors
         dh = mlp_block_bwd(_contig2d(dm), h2, (gu, hh), wg, wu, wd, TPContext.current(),
                            need_dx=ctx.needs_input_grad[0])
-        return (dh.view(ctx.shape) if dh is not None else None), None, None, None
+        dres = dm if len(ctx.needs_input_grad) > 4 and ctx.needs_input_grad[4] else None
+        return (dh.view(ctx.shape) if dh is not None else None), None, None, None, dres
 
 
 # ------------------------------------------------------------------------ mixture-of-experts block
@@ -1185,7 +1190,33 @@ def _stage(stages, **tensors):
             stages[name] = t.clone()
 
 
-def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None):
+class MoERouter(typing.NamedTuple):
+    """The router variant of an MoE block, its one trailing argument (None: the softmax router).  This one
+    is the sigmoid router of kernels.moe_route_sigmoid: bias f32 [E] or None (the selection bias), n_group /
+    topk_group (group-limited top-k; 1 / 1: no limit), scale (the routed scaling factor) and load int32 [E]
+    or None (every forward adds its selections per expert: what update_moe_router_bias consumes)."""
+    bias: typing.Optional[torch.Tensor] = None
+    n_group: int = 1
+    topk_group: int = 1
+    scale: float = 1.0
+    load: typing.Optional[torch.Tensor] = None
+
+
+def _moe_route(logits, k, norm_topk_prob, router):
+    if router is None:
+        return K.moe_route(logits, k, norm_topk_prob)
+    return K.moe_route_sigmoid(logits, k, norm_topk_prob, router.bias, router.n_group, router.topk_group, router.scale,
+                               router.load)
+
+
+def _moe_route_bwd(dgate, probs, idx, gate, counts, d_aux, norm_topk_prob, router):
+    if router is None:
+        return K.moe_route_bwd(dgate, probs, idx, counts, d_aux, norm_topk_prob)
+    return K.moe_route_sigmoid_bwd(dgate, probs, idx, gate, counts, d_aux, norm_topk_prob, router.scale)
+
+
+def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None,
+                  router=None):
     """h2 [T, H] -> (residual + sum_j gate_j Expert_{idx_j}(h2), aux, saved): router GEMM (bf16
     logits), top-k on the stored logits, capacity slots (K.moe_capacity; items past an expert's C
     rows are dropped and the residual carries the token), dispatch into the [E C, H] buffer, the
@@ -1193,10 +1224,10 @@ def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, nor
     nothing read on the host."""
     T, E = h2.shape[0], len(wgs)
     if capacity_factor is None:
-        return _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages)
+        return _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages, router)
     C = K.moe_capacity(T, E, k, capacity_factor)
     logits = K.linear_fwd(h2, [router_w])
-    idx, gate, probs, counts, aux = K.moe_route(logits, k, norm_topk_prob)
+    idx, gate, probs, counts, aux = _moe_route(logits, k, norm_topk_prob, router)
     slot, src = K.moe_plan(idx, E, C)
     xe = K.moe_dispatch(h2, src, k)
     gu, hh, ye = K.moe_experts_fwd(xe, wgs, wus, wds, C, fuse=_fuse())
@@ -1206,13 +1237,13 @@ def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, nor
     return out, aux, (idx, gate, probs, counts, slot, src, xe, gu, hh, ye)
 
 
-def _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages):
+def _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages, router=None):
     """moe_block_fwd with capacity_factor None: no item is dropped.  The experts' rows are packed back to
     back in [R, *] buffers (K.moe_plan_dropless: R = K.moe_dropless_rows, a static bound; segments on the
     128-grid) and every product is one segment-GEMM launch over all experts."""
     E = len(wgs)
     logits = K.linear_fwd(h2, [router_w])
-    idx, gate, probs, counts, aux = K.moe_route(logits, k, norm_topk_prob)
+    idx, gate, probs, counts, aux = _moe_route(logits, k, norm_topk_prob, router)
     slot, src, seg, tile_expert = K.moe_plan_dropless(idx, E)
     xe = K.moe_dispatch(h2, src, k)
     gu, hh, ye = K.moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert)
@@ -1241,7 +1272,8 @@ def _wgrad_seg(dy, x, params_per_expert, seg, notify=True):
         _notify(told)
 
 
-def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages):
+def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages,
+                            router=None):
     idx, gate, probs, counts, slot, src, xe, gu, hh, ye, seg, tile_expert = saved
     dye, dgate = K.moe_combine_bwd(dout, ye, slot, src, gate)
     dgu, dhh = K.moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert)
@@ -1249,7 +1281,7 @@ def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, 
     _wgrad_seg(dye, hh, [[w] for w in wds], seg)
     dxe = K.moe_experts_dgrad_gate_up_seg(dgu, wgs, wus, seg, tile_expert) if need_dx else None
     _wgrad_seg(dgu, xe, [[wg, wu] for wg, wu in zip(wgs, wus)], seg)
-    dlogits = K.moe_route_bwd(dgate, probs, idx, counts, d_aux, norm_topk_prob)
+    dlogits = _moe_route_bwd(dgate, probs, idx, gate, counts, d_aux, norm_topk_prob, router)
     dh = None
     if need_dx:
         dhr = K.linear_dgrad(dlogits, [router_w])
@@ -1261,14 +1293,15 @@ def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, 
 
 
 def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob=True, need_dx=True, stages=None,
-                  dropless=False):
+                  dropless=False, router=None):
     """Backward of moe_block_fwd's expert path and router: returns dh2 (the residual's gradient is
     dout itself).  d_aux: the gradient of aux, an f32 device scalar or None.  Expert and router
     weight gradients go to their sinks through wgrad_group / wgrad, MOE_GROUP experts to a launch, so
     bf16 .grad, f32 main_grad, the DP notification and weight-gradient pairing behave as for a dense
     layer (an expert's jobs pair on its own parameters; C is the same for every micro-batch)."""
     if dropless:   # `saved` of moe_block_fwd(capacity_factor=None): with its segments
-        return _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages)
+        return _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages,
+                                       router)
     idx, gate, probs, counts, slot, src, xe, gu, hh, ye = saved
     E = len(wgs)
     C = xe.shape[0] // E
@@ -1282,7 +1315,7 @@ def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_
     dxe = K.moe_experts_dgrad_gate_up(dgu, wgs, wus, C) if need_dx else None
     for lo in range(0, E, K.MOE_GROUP):
         wgrad_group([(dgu[rows[e]], xe[rows[e]], [wgs[e], wus[e]]) for e in range(lo, min(E, lo + K.MOE_GROUP))])
-    dlogits = K.moe_route_bwd(dgate, probs, idx, counts, d_aux, norm_topk_prob)
+    dlogits = _moe_route_bwd(dgate, probs, idx, gate, counts, d_aux, norm_topk_prob, router)
     dh = None
     if need_dx:   # the router's dX rides as the residual of the dispatch backward: one rounding
         dhr = K.linear_dgrad(dlogits, [router_w])
@@ -1299,12 +1332,14 @@ class MoEFunction(torch.autograd.Function):
     -> (out = residual + MoE(h2), aux).  capacity_factor None: dropless (segment GEMMs over packed rows).  aux is the Switch load-balancing loss E sum_e f_e P_e with
     f_e = the fraction of the T k selections that chose e (before dropping, no gradient) and P_e =
     the mean router probability of e; HF Mixtral's load_balancing_loss_func is k times this value.
+    router: a MoERouter picks the sigmoid router (its P_e: the mean normalised score); None the softmax one.
     The expert weights travel in lists, which autograd does not see: like every weight here they get
     their gradient written into their sink.  stages: a dict receiving clones of every intermediate of
     the forward and, when the backward runs, of the backward (tests)."""
 
     @staticmethod
-    def forward(ctx, h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None):
+    def forward(ctx, h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None,
+                router=None):
         tp = TPContext.current()
         if tp.world_size > 1:
             raise NotImplementedError("mixture-of-experts layers under tensor parallelism (experts are not sharded)")
@@ -1312,8 +1347,9 @@ class MoEFunction(torch.autograd.Function):
         wgs, wus, wds = list(wgs), list(wus), list(wds)
         out, aux, saved = moe_block_fwd(x2, r2, router_w, wgs, wus, wds, int(k),
                                         None if capacity_factor is None else float(capacity_factor),
-                                        bool(norm_topk_prob), stages)
+                                        bool(norm_topk_prob), stages, router)
         ctx.save_for_backward(x2, router_w, *saved, *wgs, *wus, *wds)
+        ctx.router = router
         ctx.E, ctx.k, ctx.norm, ctx.shape, ctx.stages = len(wgs), int(k), bool(norm_topk_prob), h2.shape, stages
         ctx.dropless, ctx.nsaved = capacity_factor is None, len(saved)
         return out.view(h2.shape), aux.view(())
@@ -1330,8 +1366,37 @@ class MoEFunction(torch.autograd.Function):
         if daux is not None:
             daux = daux.to(torch.float32).reshape(1).contiguous()
         dh = moe_block_bwd(d2, daux, x2, saved, router_w, wgs, wus, wds, ctx.k, ctx.norm,
-                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages, dropless=ctx.dropless)
-        return (dh.view(ctx.shape) if dh is not None else None, dout if ctx.needs_input_grad[1] else None) + (None,) * 8
+                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages, dropless=ctx.dropless, router=ctx.router)
+        return (dh.view(ctx.shape) if dh is not None else None, dout if ctx.needs_input_grad[1] else None) + (None,) * 9
+
+
+def update_moe_router_bias(model, group=None):
+    """The auxiliary-loss-free balancing step of every sigmoid-routed MoE layer with moe_bias_update_rate > 0;
+    call it once per optimizer step.  The layers' `load` buffers (the selections per expert since the last
+    call) are summed over the data-parallel group first -- `group`, or the process grid's cp x dp group when
+    it has more than one rank -- as ONE stacked tensor, so every replica takes the same step; then one
+    pt_moe_bias_update launch per layer moves e_score_correction_bias by +-rate and clears load.  Nothing to
+    do (no launch, no collective) for a model without such a layer."""
+    layers = [m for m in model.modules() if getattr(m, "_pt_moe", False) and getattr(m, "bias_update_rate", 0.0) > 0.0]
+    if not layers:
+        return
+    if group is None and dist.is_available() and dist.is_initialized():
+        from . import process_group_manager as pgm
+        m = pgm.process_group_manager
+        if m is not None and getattr(m, "cp_dp_world_size", 1) > 1:
+            group = m.cp_dp_group
+    if group is not None and dist.get_world_size(group) > 1:
+        loads = torch.stack([l.load for l in layers])
+        if dist.get_backend(group) == "gloo":   # (gloo reduces host tensors)
+            host = loads.cpu()
+            dist.all_reduce(host, group=group)
+            loads = host.to(loads.device)
+        else:
+            dist.all_reduce(loads, group=group)
+        for l, row in zip(layers, loads):
+            l.load.copy_(row)
+    for l in layers:
+        K.moe_bias_update(l.e_score_correction_bias, l.load, l.bias_update_rate)
 
 
 # ------------------------------------------------------------------------ decoder layer

@@ -1091,6 +1091,93 @@ def moe_route_bwd(dgate, probs, idx, counts, d_aux=None, norm_topk_prob=True):
     return dlogits
 
 
+MOE_MAX_GROUPS = 16   # csrc/moe.hip: the kept-group mask of the sigmoid router
+
+
+def moe_group_limits(E, k, n_group, topk_group):
+    """None when (E, k, n_group, topk_group) is a grouping the sigmoid router takes, else the limits as a
+    sentence (moe_route_sigmoid raises it; model.MoE puts it into its ValueError)."""
+    E, k, G, Kg = int(E), int(k), int(n_group), int(topk_group)
+    ok = (1 <= Kg <= G <= MOE_MAX_GROUPS and E % G == 0 and (G == 1 or E // G >= 2) and k <= Kg * (E // G))
+    return None if ok else (f"1 <= topk_group <= n_group <= {MOE_MAX_GROUPS}, n_group divides num_experts, groups of at "
+                            f"least 2 experts, k <= topk_group * num_experts / n_group; got num_experts {E}, k {k}, "
+                            f"n_group {G}, topk_group {Kg}")
+
+
+def _moe_expert_vec(t, E, dtype, name):
+    _req(t.dtype == dtype and t.is_cuda and t.is_contiguous() and t.numel() == E, f"{name}: contiguous {dtype} [{E}]")
+
+
+def moe_route_sigmoid(logits, k, norm_topk_prob=True, bias=None, n_group=1, topk_group=1, scale=1.0, load=None):
+    """The sigmoid router (DeepSeek-V3 style) with moe_route's outputs: s = sigmoid(logits) in f32 (returned
+    as probs), key = s + bias (f32 [E]; None: zeros); of n_group contiguous expert groups the topk_group with
+    the largest sum of their two best keys stay, idx = the k best keys inside them (ties to the lower
+    expert, best first), gate = s[idx] (not the key), divided by (their sum + 1e-20) under norm_topk_prob,
+    times scale.  aux is the Switch loss on s / sum_e s.  load (int32 [E] or None): load += counts, for
+    moe_bias_update."""
+    _req(logits.dtype == BF16 and logits.is_cuda and logits.dim() == 2 and logits.stride(1) == 1,
+         "moe_route_sigmoid: logits as a bf16 row-major device view [T, E]")
+    T, E = logits.shape
+    k = int(k)
+    _req(T >= 1, "moe_route_sigmoid: at least one token")
+    _moe_sizes(E, k, "moe_route_sigmoid")
+    bad = moe_group_limits(E, k, n_group, topk_group)
+    _req(bad is None, f"moe_route_sigmoid: {bad}")
+    if bias is not None:
+        _moe_expert_vec(bias, E, torch.float32, "bias")
+    if load is not None:
+        _moe_expert_vec(load, E, torch.int32, "load")
+    dev = logits.device
+    lib = _C.lib()
+    idx = torch.empty(T, k, dtype=torch.int32, device=dev)
+    gate = torch.empty(T, k, dtype=torch.float32, device=dev)
+    probs = torch.empty(T, E, dtype=torch.float32, device=dev)
+    counts = torch.empty(E, dtype=torch.int32, device=dev)
+    aux = torch.empty(1, dtype=torch.float32, device=dev)
+    words = lib.pt_moe_route_workspace(T, E)
+    _C.check(0 if words > 0 else words, "pt_moe_route_workspace")
+    rc = lib.pt_moe_route_sigmoid(_ptr(logits), logits.stride(0), _ptr(bias), T, E, k, int(n_group), int(topk_group),
+                                  int(bool(norm_topk_prob)), float(scale), _ptr(idx), _ptr(gate), _ptr(probs),
+                                  _ptr(counts), _ptr(aux), _ptr(load), _ptr(_moe_ws("route", words, dev)),
+                                  _C.stream_ptr(dev))
+    _C.check(rc, "pt_moe_route_sigmoid")
+    return idx, gate, probs, counts, aux
+
+
+def moe_route_sigmoid_bwd(dgate, probs, idx, gate, counts, d_aux=None, norm_topk_prob=True, scale=1.0):
+    """dlogits bf16 [T, E]: the backward of moe_route_sigmoid's gate (selection fixed at idx; the bias and
+    the counts carry no gradient) on dgate [T, k], plus d_aux (an f32 device scalar or None) times the
+    gradient of aux through the normalised scores, through s (1 - s)."""
+    _req(probs.dim() == 2 and idx.dim() == 2, "moe_route_sigmoid_bwd: probs [T, E], idx [T, k]")
+    T, E = probs.shape
+    k = idx.shape[1]
+    _moe_sizes(E, k, "moe_route_sigmoid_bwd")
+    _moe_items(probs, T, E, torch.float32, "probs")
+    _moe_items(idx, T, k, torch.int32, "idx")
+    _moe_items(dgate, T, k, torch.float32, "dgate")
+    _moe_items(gate, T, k, torch.float32, "gate")
+    _moe_expert_vec(counts, E, torch.int32, "counts")
+    if d_aux is not None:
+        _req(d_aux.dtype == torch.float32 and d_aux.is_cuda and d_aux.numel() == 1, "d_aux: an f32 device scalar")
+    dlogits = torch.empty(T, E, dtype=BF16, device=probs.device)
+    rc = _C.lib().pt_moe_route_sigmoid_bwd(_ptr(dgate), _ptr(probs), _ptr(idx), _ptr(gate), _ptr(counts), _ptr(d_aux),
+                                           int(bool(norm_topk_prob)), float(scale), _ptr(dlogits), E, T, E, k,
+                                           _C.stream_ptr(probs.device))
+    _C.check(rc, "pt_moe_route_sigmoid_bwd")
+    return dlogits
+
+
+def moe_bias_update(bias, load, rate):
+    """The auxiliary-loss-free balancing step, in place: bias[e] += rate * sign(sum(load) - E * load[e]) (an
+    expert under the mean load gains, one over it loses, one at it keeps its bias), then load = 0."""
+    E = bias.numel()
+    _req(1 <= E <= MOE_MAX_EXPERTS, f"moe_bias_update: 1 <= num_experts <= {MOE_MAX_EXPERTS}, got {E}")
+    _moe_expert_vec(bias, E, torch.float32, "bias")
+    _moe_expert_vec(load, E, torch.int32, "load")
+    rc = _C.lib().pt_moe_bias_update(_ptr(bias), _ptr(load), E, float(rate), _C.stream_ptr(bias.device))
+    _C.check(rc, "pt_moe_bias_update")
+
+
 # ---------------------------------------------------------------------------- device status
 STATUS_BAD_TARGET = 1   # PT_STATUS_BAD_TARGET (include/picotron_hip.h)
 STATUS_NONFINITE_GRAD = 2   # PT_STATUS_NONFINITE_GRAD

@@ -313,8 +313,22 @@ class MoE(nn.Module):
     norm_topk_prob (default True) divides the chosen probabilities by their sum.
     forward(x, residual) returns residual + MoE(x) and leaves the Switch load-balancing loss of this
     call in self.aux_loss (functional.MoEFunction).  DP only: tensor / sequence / context / pipeline
-    parallelism are refused."""
+    parallelism are refused.
+
+    config.moe_scoring_func = "sigmoid" (default "softmax") is the DeepSeek-V2/V3 / Moonlight / GLM-4.5 /
+    Kimi-K2 router (kernels.moe_route_sigmoid): sigmoid scores; a persistent f32 buffer
+    `e_score_correction_bias` [num_experts] added to the scores for the choice only (HF's key
+    mlp.gate.e_score_correction_bias is mlp.e_score_correction_bias here, as mlp.gate.weight is
+    mlp.router.weight; it stays f32 whatever dtype the module is cast to); n_group / topk_group (default
+    1 / 1) keep the top-k inside the topk_group best of n_group contiguous expert groups;
+    routed_scaling_factor (default 1.0) multiplies the gates.  moe_bias_update_rate > 0 (default 0.0) also
+    registers a non-persistent int32 `load` [num_experts] that every forward adds its selections to, for
+    functional.update_moe_router_bias, the auxiliary-loss-free balancing step.  n_shared_experts = n > 0
+    (either router; DeepSeek, Llama-4) adds `shared_experts`, a dense MLP of width n *
+    moe_intermediate_size every token passes through: residual + shared(x) leaves its down_proj epilogue
+    and is the residual of the routed experts' combine."""
     _pt_moe = True
+    _F32_BUFFER = "e_score_correction_bias"
 
     def __init__(self, config) -> None:
         super().__init__()
@@ -338,9 +352,33 @@ class MoE(nn.Module):
             raise ValueError(f"MoE: hidden_size and moe_intermediate_size on the {K.GRID}-grid")
         if self.dropless and (config.hidden_size % K.MOE_SEG_ALIGN or inter % K.MOE_SEG_ALIGN):
             raise ValueError(f"MoE: moe_dropless needs hidden_size and moe_intermediate_size on the {K.MOE_SEG_ALIGN}-grid")
+        self.scoring_func = str(getattr(config, "moe_scoring_func", "softmax"))
+        self.n_group = int(getattr(config, "n_group", 1) or 1)
+        self.topk_group = int(getattr(config, "topk_group", 1) or 1)
+        self.routed_scaling_factor = float(getattr(config, "routed_scaling_factor", 1.0))
+        self.n_shared_experts = int(getattr(config, "n_shared_experts", 0) or 0)
+        self.bias_update_rate = float(getattr(config, "moe_bias_update_rate", 0.0))
+        if self.scoring_func not in ("softmax", "sigmoid"):
+            raise ValueError(f'MoE: moe_scoring_func is "softmax" or "sigmoid", got {self.scoring_func!r}')
+        if self.scoring_func == "softmax" and ((self.n_group, self.topk_group) != (1, 1) or self.bias_update_rate != 0.0
+                                               or self.routed_scaling_factor != 1.0):
+            raise ValueError('MoE: n_group, topk_group, routed_scaling_factor and moe_bias_update_rate belong to '
+                             'moe_scoring_func = "sigmoid" (the softmax router takes 1, 1, 1.0 and 0.0)')
+        bad = K.moe_group_limits(self.num_experts, self.top_k, self.n_group, self.topk_group)
+        if bad is not None:
+            raise ValueError(f"MoE: {bad}")
+        if self.n_shared_experts < 0 or not (self.bias_update_rate >= 0.0 and math.isfinite(self.bias_update_rate)):
+            raise ValueError("MoE: n_shared_experts >= 0 and a finite moe_bias_update_rate >= 0")
         self.router = Linear(config.hidden_size, self.num_experts, bias=False)
         expert = types.SimpleNamespace(hidden_size=config.hidden_size, intermediate_size=inter)
         self.experts = nn.ModuleList([MLP(expert) for _ in range(self.num_experts)])
+        if self.n_shared_experts:
+            self.shared_experts = MLP(types.SimpleNamespace(hidden_size=config.hidden_size,
+                                                            intermediate_size=self.n_shared_experts * inter))
+        if self.scoring_func == "sigmoid":
+            self.register_buffer(self._F32_BUFFER, torch.zeros(self.num_experts, dtype=torch.float32))
+            if self.bias_update_rate > 0.0:
+                self.register_buffer("load", torch.zeros(self.num_experts, dtype=torch.int32), persistent=False)
         self.aux_loss = None
         self.stages = None   # a dict here receives clones of every call's intermediates (MoEFunction's stages=)
         _init_uniform_fan_in(self.router.weight)
@@ -349,14 +387,36 @@ class MoE(nn.Module):
         _init_uniform_fan_in(self.router.weight)
         for e in self.experts:
             e.reset_parameters()
+        if self.n_shared_experts:
+            self.shared_experts.reset_parameters()
+
+    def _apply(self, fn, recurse=True):
+        # .to(bfloat16) / .half() cast every floating buffer; the selection bias is compared in f32 and moved
+        # by steps far below bf16's spacing, so it keeps its f32 values and follows the device only
+        keep = self._buffers.get(self._F32_BUFFER)
+        super()._apply(fn, recurse)
+        moved = self._buffers.get(self._F32_BUFFER)
+        if keep is not None and moved is not None and moved.dtype != torch.float32:
+            self._buffers[self._F32_BUFFER] = keep.to(device=moved.device)
+        return self
+
+    def router_variant(self):
+        """MoEFunction's trailing argument: None for the softmax router, else a functional.MoERouter."""
+        if self.scoring_func == "softmax":
+            return None
+        return FN.MoERouter(self.e_score_correction_bias, self.n_group, self.topk_group, self.routed_scaling_factor,
+                            self.load if self.bias_update_rate > 0.0 and self.training else None)
 
     def forward(self, x, residual=None):
-        if residual is None:
+        if self.n_shared_experts:   # residual + shared(x) out of the dense block's down_proj epilogue
+            sh = self.shared_experts
+            residual = FN.MLPFunction.apply(x, sh.gate_proj.weight, sh.up_proj.weight, sh.down_proj.weight, residual)
+        elif residual is None:
             residual = torch.zeros_like(x)
         out, self.aux_loss = FN.MoEFunction.apply(
             x, residual, self.router.weight, [e.gate_proj.weight for e in self.experts],
             [e.up_proj.weight for e in self.experts], [e.down_proj.weight for e in self.experts], self.top_k,
-            None if self.dropless else self.capacity_factor, self.norm_topk_prob, self.stages)
+            None if self.dropless else self.capacity_factor, self.norm_topk_prob, self.stages, self.router_variant())
         return out
 
 

@@ -7,7 +7,10 @@ capture is refused), the best of three replays per round, of
     the dense block (mlp_block_fwd / mlp_block_bwd) at the same active FLOPs, I_dense = k * I_moe,
 
 then the expert GEMMs per launch label under a GemmProbe.  No threshold: the log is the record.
-python tools/moe_bench.py [--tokens 4096] [--hidden 2048] [--dense-inter 8192] [--rounds 3] [--reps 4]"""
+--router sigmoid adds the sigmoid router (kernels.moe_route_sigmoid: no groups at E = 8, 4 of 8 groups at
+E = 64, a selection bias, scale 2.5) beside the softmax one in the same interleaved rounds: its route and
+route_bwd kernels, and the whole block forward and backward.
+python tools/moe_bench.py [--tokens 4096] [--hidden 2048] [--dense-inter 8192] [--rounds 3] [--reps 4] [--router sigmoid]"""
 import argparse
 import hashlib
 import json
@@ -88,6 +91,8 @@ def main():
     ap.add_argument("--reps", type=int, default=4)
     ap.add_argument("--dropless", action="store_true",
                     help="the block at capacity_factor None (segment GEMMs), 1.25 and E / k (never drops), interleaved")
+    ap.add_argument("--router", choices=("softmax", "sigmoid"), default="softmax",
+                    help="sigmoid: also time the sigmoid router's kernels and the block with it, interleaved")
     a = ap.parse_args()
     T, H = a.tokens, a.hidden
     gen = torch.Generator(device="cuda").manual_seed(0)
@@ -126,6 +131,17 @@ def main():
             ("combine_bwd", lambda: K.moe_combine_bwd(dout, ye, slot, src, gate), 2 * kept * H * 2 + R * H * 2 + T * k * 12 + R * 4),
             ("route_bwd", lambda: K.moe_route_bwd(dgate, probs, idx, counts, d_aux), T * E * 6 + T * k * 8),
         ]
+        router = None
+        if a.router == "sigmoid":
+            G, Kg = (1, 1) if E < 64 else (8, 4)
+            router = FN.MoERouter(torch.randn(E, device="cuda", generator=gen) * 0.1, G, Kg, 2.5, None)
+            sg = K.moe_route_sigmoid(logits, k, True, router.bias, G, Kg, 2.5)
+            out(what="sigmoid routing", n_group=G, topk_group=Kg, counts_max=int(sg[3].max()), aux=round(sg[4].item(), 4))
+            parts += [
+                ("route (sigmoid)", lambda: K.moe_route_sigmoid(logits, k, True, router.bias, G, Kg, 2.5), T * E * 6 + T * k * 8),
+                ("route_bwd (sigmoid)", lambda: K.moe_route_sigmoid_bwd(dgate, sg[2], sg[0], sg[1], sg[3], d_aux, True, 2.5),
+                 T * E * 6 + T * k * 12),
+            ]
         for rnd in range(a.rounds):
             for name, fn, nbytes in (parts if rnd % 2 == 0 else parts[::-1]):
                 us, how = time_us(fn, a.reps)
@@ -142,6 +158,15 @@ def main():
             ("dense block forward", lambda: FN.mlp_block_fwd(h2, dg, du, dd, tp, residual=res), 6 * T * H * dI),
             ("dense block backward", lambda: FN.mlp_block_bwd(dout, h2, dsaved, dg, du, dd, tp), 12 * T * H * dI),
         ]
+        if router is not None:   # (its own routing: the kept items differ, so the tflops column is the softmax block's only)
+            ssaved = FN.moe_block_fwd(h2, res, rw, wgs, wus, wds, k, 1.25, router=router)[2]
+            skept = int((ssaved[4] >= 0).sum())
+            blocks += [
+                ("moe block forward (sigmoid)", lambda: FN.moe_block_fwd(h2, res, rw, wgs, wus, wds, k, 1.25, router=router),
+                 6 * skept * H * I),
+                ("moe block backward (sigmoid)", lambda: FN.moe_block_bwd(dout, d_aux, h2, ssaved, rw, wgs, wus, wds, k,
+                                                                          router=router), 12 * skept * H * I),
+            ]
         for rnd in range(a.rounds):
             for name, fn, flop in (blocks if rnd % 2 == 0 else blocks[::-1]):
                 us, how = time_us(fn, a.reps)
