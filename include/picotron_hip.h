@@ -765,6 +765,42 @@ int pt_attn_bwd_block_band(const void* q, const int64_t* q_str, const void* k, c
                            int64_t D, float scale, int causal, int grad_f32, int64_t lse_ld, int parts,
                            const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream);
 
+/* ---- multi-head latent attention (csrc/attention_mla.hip) -------------------------------------
+ * Causal flash attention in MLA's training form: q / k heads are [d_nope | d_rope] = 128 + 64 wide,
+ * v / o heads d_v = 128 wide, and the rotary part of k is one row per token shared by every head.
+ * q [B, S, H, 192], k_nope / v / o / dout [B, S, H, 128]: base pointer + (batch, seq, head) strides in
+ * elements, d contiguous; k_pe [B, S, 64]: base pointer + (batch, seq) strides.  The broadcast k is
+ * never formed.  lse f32 [B, H, S] dense.  bf16, f32 softmax, Sq == Sk = S, one k/v head per q head.
+ * PT_EINVAL: dims other than 128 / 64 / 128, S % 128 != 0, a NULL pointer, a row stride below the
+ * row's width or at or above 2^24; PT_EALIGN: a pointer off 16 bytes or a stride off 8 elements.
+ * A refused call launches nothing.  No atomics: equal inputs give equal bits.
+ * pt_mla_attn_bwd: delta_out f32 [B, H, S] receives D = rowsum(dO * O) (formed by the dQ kernel).
+ *   dq [B, S, H, 192], dk_nope and dv [B, S, H, 128] are bf16 strided views (e.g. column slices of the
+ *   d(kv_b output) buffer); the rotary columns of every head's dK go to dkpe_ws, f32 [B, S, H, 64]
+ *   dense, for pt_mla_dkpe_reduce.  dq and dkpe_ws are gradients of the ROTATED q / k_pe.
+ * pt_mla_rope: rotates in place (pt_rope's rotate-half arithmetic, position = row % seq_len, tables
+ *   [seq_len, table_stride] bf16 of which the first d_rope / 2 columns are read) columns
+ *   [192 h + 128, 192 h + 192) of each of `rows` rows of q, h < H, and, when k_pe is not NULL, the
+ *   64-wide k_pe row.  inverse = 1 rotates by -theta (the backward of both).
+ * pt_mla_dkpe_reduce: dk_pe[row] = bf16(rotate by -theta (sum over h = 0 .. H - 1, in that order, of
+ *   ws[row, h, :])): f32 sums, one rounding. */
+int pt_mla_attn_fwd(const void* q, const int64_t* q_str, const void* k_nope, const int64_t* kn_str, const void* k_pe,
+                    const int64_t* kpe_str, const void* v, const int64_t* v_str, void* o, const int64_t* o_str,
+                    float* lse, int64_t B, int64_t H, int64_t S, int64_t d_nope, int64_t d_rope, int64_t d_v,
+                    float scale, hipStream_t stream);
+int pt_mla_attn_bwd(const void* q, const int64_t* q_str, const void* k_nope, const int64_t* kn_str, const void* k_pe,
+                    const int64_t* kpe_str, const void* v, const int64_t* v_str, const void* o, const int64_t* o_str,
+                    const void* dout, const int64_t* do_str, const float* lse, float* delta_out, void* dq,
+                    const int64_t* dq_str, void* dk_nope, const int64_t* dkn_str, void* dv, const int64_t* dv_str,
+                    float* dkpe_ws, int64_t B, int64_t H, int64_t S, int64_t d_nope, int64_t d_rope, int64_t d_v,
+                    float scale, hipStream_t stream);
+int pt_mla_rope(void* q, int64_t q_row_stride, int64_t H, void* k_pe, int64_t kpe_row_stride, int64_t rows,
+                const void* cos_table, const void* sin_table, int64_t seq_len, int64_t table_stride, int64_t d_nope,
+                int64_t d_rope, int inverse, hipStream_t stream);
+int pt_mla_dkpe_reduce(const float* ws, int64_t H, void* dk_pe, int64_t dkpe_row_stride, int64_t rows,
+                       const void* cos_table, const void* sin_table, int64_t seq_len, int64_t table_stride,
+                       int64_t d_rope, hipStream_t stream);
+
 /* ---- measurement variants ------------------------------------------------------------------
  * Not a reference interface: selects between kernel forms with identical results, for A/B runs and
  * the bit-identity tests.  The library reads no environment; the host sets these (picotron_amd/

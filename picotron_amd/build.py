@@ -42,6 +42,7 @@ def sources():
 # plain f32 instructions whose rounding the tests pin down (the feature is a device one: the host
 # pass notes that it does not know it).
 FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
+              "attention_mla.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],   # the same scheme, the same reason
               "moe.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 

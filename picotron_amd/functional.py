@@ -1082,6 +1082,81 @@ class AttentionFunction(torch.autograd.Function):
         return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 14
 
 
+# ------------------------------------------------------------------------ multi-head latent attention
+class MLAttentionFunction(torch.autograd.Function):
+    """Multi-head latent attention (DeepSeek-V2/V3, Moonlight, Kimi-K2) as one node:
+    q = q_b(norm(q_a x)) (or q_proj x) [T, H * 192]; kv_a x = [c | k_pe] [T, r_kv + 64];
+    kv_b(norm(c)) = per head [k_nope | v] [T, H * 256]; the rotary columns of q's heads and the k_pe
+    row rotated in place (kernels.mla_rope_); kernels.mla_attn_fwd on those buffers' strided views (no
+    broadcast k, no copies but the norm's contiguous c); out_proj.  Softmax scale 192^-0.5.
+    wq: (q_proj,) or (q_a_proj, q_a_layernorm, q_b_proj).  Every GEMM is kernels.linear_*; the weight
+    gradients go through wgrad / norm_bwd into .grad or main_grad."""
+
+    @staticmethod
+    def forward(ctx, x, wq, w_kva, w_kvn, w_kvb, wo, cos, sin, nh, eps, mode):
+        B, S, _ = x.shape
+        T, r_kv = B * S, w_kvn.shape[0]
+        dq, dn, dv = K.MLA_NOPE + K.MLA_ROPE, K.MLA_NOPE, K.MLA_V
+        h2 = _contig2d(x)
+        qa = qn = q_rstd = None
+        if len(wq) == 3:
+            qa = K.linear_fwd(h2, [wq[0]])
+            qn, q_rstd, _ = K.rmsnorm_fwd(qa, wq[1], eps, mode)
+            q = K.linear_fwd(qn, [wq[2]])
+        else:
+            q = K.linear_fwd(h2, [wq[0]])
+        kva = K.linear_fwd(h2, [w_kva])
+        c = kva[:, :r_kv].contiguous()   # the norm kernels take contiguous rows
+        cn, kv_rstd, _ = K.rmsnorm_fwd(c, w_kvn, eps, mode)
+        kvb = K.linear_fwd(cn, [w_kvb])
+        K.mla_rope_(q, nh, kva[:, r_kv:], cos, sin, S)
+        kvb4 = kvb.view(B, S, nh, dn + dv)
+        o, lse = K.mla_attn_fwd(q.view(B, S, nh, dq), kvb4[..., :dn], kva.view(B, S, -1)[..., r_kv:], kvb4[..., dn:],
+                                dq ** -0.5)
+        a = K.linear_fwd(o.view(T, nh * dv), [wo])
+        ctx.save_for_backward(h2, q, kva, c, cn, kv_rstd, kvb, o, lse, cos, sin, w_kva, w_kvn, w_kvb, wo, *wq,
+                              *((qa, qn, q_rstd) if len(wq) == 3 else ()))
+        ctx.dims, ctx.norm, ctx.nq = (B, S, nh), (eps, mode), len(wq)
+        return a.view(B, S, -1)
+
+    @staticmethod
+    def backward(ctx, da):
+        h2, q, kva, c, cn, kv_rstd, kvb, o, lse, cos, sin, w_kva, w_kvn, w_kvb, wo, *rest = ctx.saved_tensors
+        wq, q_saved = rest[:ctx.nq], rest[ctx.nq:]
+        (B, S, nh), (eps, mode) = ctx.dims, ctx.norm
+        T, r_kv = B * S, w_kvn.shape[0]
+        dq_w, dn, dv_w = K.MLA_NOPE + K.MLA_ROPE, K.MLA_NOPE, K.MLA_V
+        da = _contig2d(da)
+        do2 = K.linear_dgrad(da, [wo])
+        wgrad(da, o.view(T, nh * dv_w), [wo])
+        # the attention backward stores straight into the projections' gradient buffers
+        dq = torch.empty_like(q)
+        dkvb = torch.empty_like(kvb)
+        dkva = torch.empty_like(kva)
+        kvb4, dkvb4 = kvb.view(B, S, nh, dn + dv_w), dkvb.view(B, S, nh, dn + dv_w)
+        K.mla_attn_bwd(do2.view(B, S, nh, dv_w), q.view(B, S, nh, dq_w), kvb4[..., :dn], kva.view(B, S, -1)[..., r_kv:],
+                       kvb4[..., dn:], o, lse, dq_w ** -0.5, cos, sin, dq=dq.view(B, S, nh, dq_w),
+                       dk_nope=dkvb4[..., :dn], dk_pe=dkva.view(B, S, -1)[..., r_kv:], dv=dkvb4[..., dn:])
+        K.mla_rope_(dq, nh, None, cos, sin, S, inverse=True)
+        # k / v side: kv_b, the latent norm, kv_a
+        dcn = K.linear_dgrad(dkvb, [w_kvb])
+        wgrad(dkvb, cn, [w_kvb])
+        dkva[:, :r_kv].copy_(norm_bwd(dcn, c, w_kvn, kv_rstd, mode, need_dw=ctx.needs_input_grad[3]))
+        wgrad(dkva, h2, [w_kva])
+        need_dx = ctx.needs_input_grad[0]
+        dh = K.linear_dgrad(dkva, [w_kva]) if need_dx else None
+        # q side
+        if ctx.nq == 3:
+            qa, qn, q_rstd = q_saved
+            dqn = K.linear_dgrad(dq, [wq[2]])
+            wgrad(dq, qn, [wq[2]])
+            dq = norm_bwd(dqn, qa, wq[1], q_rstd, mode)
+        wgrad(dq, h2, [wq[0]])
+        if need_dx:
+            dh = K.linear_dgrad(dq, [wq[0]], out=dh, accumulate=True)
+        return (dh.view(B, S, -1) if need_dx else None,) + (None,) * 10
+
+
 # ------------------------------------------------------------------------ MLP block
 def mlp_block_fwd(h2, wg, wu, wd, tp, residual=None, reduce=True):
     """h2 [T,H] -> down(silu(gate) * up) (+ residual, entering the tp sum once, from tp rank 0;
@@ -1181,6 +1256,11 @@ def has_moe(model):
     """True when `model` holds a mixture-of-experts MLP (model.MoE): the parallel engines that do not
     carry one refuse it by this."""
     return any(getattr(m, "_pt_moe", False) for m in model.modules())
+
+
+def has_mla(model):
+    """True when `model` holds a multi-head latent attention block (model.MLAttention)."""
+    return any(getattr(m, "_pt_mla", False) for m in model.modules())
 
 
 def _stage(stages, **tensors):

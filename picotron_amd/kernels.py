@@ -3061,3 +3061,119 @@ def _attn_bwd_band(dout, q, k, v, out, lse, scale, causal, dq, dk, dv, grad_f32,
                                    _C.stream_ptr(q.device))
     _C.check(rc, "pt_attn_bwd_band")
     return dq, dk, dv, delta
+
+
+# ------------------------------------------------------------- multi-head latent attention (MLA)
+# csrc/attention_mla.hip: q / k heads [128 nope | 64 rope], v / o heads 128 wide, k's rope part one row
+# per token shared by every head.  No padding path: S must sit on the 128-row blocks.
+MLA_NOPE, MLA_ROPE, MLA_V = 128, 64, 128
+
+
+def _mla_dims_ok(nope, rope, vdim, what):
+    if (nope, rope, vdim) != (MLA_NOPE, MLA_ROPE, MLA_V):
+        raise NotImplementedError(f"{what}: the MLA kernels take qk_nope_head_dim / qk_rope_head_dim / v_head_dim = "
+                                  f"{MLA_NOPE} / {MLA_ROPE} / {MLA_V}, got {nope} / {rope} / {vdim}")
+
+
+def _mla_str2(t):
+    return _C.i64arr([t.stride(0), t.stride(1)])
+
+
+def _mla_inputs(q, k_nope, k_pe, v, what):
+    _req(q.dim() == 4 and k_nope.dim() == 4 and v.dim() == 4 and k_pe.dim() == 3, f"{what}: q / k_nope / v are "
+         "[B, S, H, d] views and k_pe is [B, S, 64]")
+    B, S, H, dq = q.shape
+    _mla_dims_ok(dq - MLA_ROPE, k_pe.shape[-1], v.shape[-1], what)
+    _req(tuple(k_nope.shape) == (B, S, H, MLA_NOPE) and tuple(v.shape) == (B, S, H, MLA_V)
+         and tuple(k_pe.shape) == (B, S, MLA_ROPE), f"{what}: k_nope / v [B, S, H, 128] and k_pe [B, S, 64] must match q")
+    for t, name in ((q, "q"), (k_nope, "k_nope"), (k_pe, "k_pe"), (v, "v")):
+        _req(t.dtype == BF16 and t.is_cuda and t.stride(-1) == 1, f"{what}: {name} must be a bf16 device view with d contiguous")
+    if S % ATTN_Q_BLOCK:
+        raise NotImplementedError(f"{what}: S = {S} is off the {ATTN_Q_BLOCK}-row blocks (MLA has no padding path)")
+    return B, S, H
+
+
+def _mla_tables(cos, sin, S, what):
+    _req(cos.dtype == BF16 and sin.dtype == BF16 and cos.is_cuda and cos.dim() == 2 and cos.stride(1) == 1
+         and sin.stride() == cos.stride() and cos.shape[0] >= S and cos.shape[1] >= MLA_ROPE // 2,
+         f"{what}: bf16 [S, 64] cos / sin tables with equal strides")
+
+
+def mla_workspace(B, S, H, device):
+    """The backward's scratch: (delta f32 [B, H, S], the per-head rotary dK rows f32 [B, S, H, 64])."""
+    return (torch.empty(B, H, S, dtype=torch.float32, device=device),
+            torch.empty(B, S, H, MLA_ROPE, dtype=torch.float32, device=device))
+
+
+def mla_rope_(q2d, nheads, k_pe2d, cos, sin, seq_len, inverse=False):
+    """In place: rotate columns [192 h + 128, 192 h + 192) of every row of q2d ([rows, >= 192 nheads] view)
+    and, when given, every row of k_pe2d ([rows, 64] view); position = row % seq_len."""
+    _req(q2d.dtype == BF16 and q2d.is_cuda and q2d.dim() == 2 and q2d.stride(1) == 1
+         and q2d.shape[1] >= nheads * (MLA_NOPE + MLA_ROPE), "mla_rope: q is a bf16 row-major [rows, H * 192] view")
+    rows = q2d.shape[0]
+    if k_pe2d is not None:
+        _req(k_pe2d.dtype == BF16 and k_pe2d.is_cuda and tuple(k_pe2d.shape) == (rows, MLA_ROPE)
+             and k_pe2d.stride(1) == 1, "mla_rope: k_pe is a bf16 [rows, 64] view")
+    _mla_tables(cos, sin, seq_len, "mla_rope")
+    rc = _C.lib().pt_mla_rope(_ptr(q2d), q2d.stride(0), nheads, _ptr(k_pe2d), 0 if k_pe2d is None else k_pe2d.stride(0),
+                              rows, _ptr(cos), _ptr(sin), seq_len, cos.stride(0), MLA_NOPE, MLA_ROPE,
+                              1 if inverse else 0, _C.stream_ptr(q2d.device))
+    _C.check(rc, "pt_mla_rope")
+    return q2d
+
+
+def mla_attn_fwd(q, k_nope, k_pe, v, scale, out=None, lse=None):
+    """Causal MLA attention.  q [B,S,H,192], k_nope / v [B,S,H,128], k_pe [B,S,64] (strided views, rope
+    already applied).  Returns (out [B,S,H,128] bf16, lse [B,H,S] f32)."""
+    B, S, H = _mla_inputs(q, k_nope, k_pe, v, "mla_attn_fwd")
+    if out is None:
+        out = torch.empty(B, S, H, MLA_V, dtype=BF16, device=q.device)
+    if lse is None:
+        lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+    _req(out.dtype == BF16 and tuple(out.shape) == (B, S, H, MLA_V), "mla_attn_fwd: out is bf16 [B, S, H, 128]")
+    _req(lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, S) and lse.is_contiguous(), "mla_attn_fwd: dense f32 lse")
+    rc = _C.lib().pt_mla_attn_fwd(_ptr(q), _str3(q), _ptr(k_nope), _str3(k_nope), _ptr(k_pe), _mla_str2(k_pe), _ptr(v),
+                                  _str3(v), _ptr(out), _str3(out), _ptr(lse), B, H, S, MLA_NOPE, MLA_ROPE, MLA_V,
+                                  float(scale), _C.stream_ptr(q.device))
+    _C.check(rc, "pt_mla_attn_fwd")
+    return out, lse
+
+
+def mla_attn_bwd(dout, q, k_nope, k_pe, v, out, lse, scale, cos, sin, dq=None, dk_nope=None, dk_pe=None, dv=None,
+                 ws=None):
+    """Backward of mla_attn_fwd.  Returns (dq, dk_nope, dk_pe, dv), all bf16; dk_nope / dv / dk_pe may be
+    strided views (column slices of the projections' gradient buffers).  dq is the gradient of the
+    ROTATED q (mla_rope_(..., inverse=True) takes it back); dk_pe is summed over heads in head order and
+    already rotated back with the cos / sin tables.  ws: mla_workspace(B, S, H, device)."""
+    B, S, H = _mla_inputs(q, k_nope, k_pe, v, "mla_attn_bwd")
+    dev = q.device
+    _mla_tables(cos, sin, S, "mla_attn_bwd")
+    if dq is None:
+        dq = torch.empty(B, S, H, MLA_NOPE + MLA_ROPE, dtype=BF16, device=dev)
+    if dk_nope is None:
+        dk_nope = torch.empty(B, S, H, MLA_NOPE, dtype=BF16, device=dev)
+    if dv is None:
+        dv = torch.empty(B, S, H, MLA_V, dtype=BF16, device=dev)
+    if dk_pe is None:
+        dk_pe = torch.empty(B, S, MLA_ROPE, dtype=BF16, device=dev)
+    delta, dkpe_ws = ws if ws is not None else mla_workspace(B, S, H, dev)
+    for t, shape, name in ((dout, (B, S, H, MLA_V), "dout"), (out, (B, S, H, MLA_V), "out"),
+                           (dq, (B, S, H, MLA_NOPE + MLA_ROPE), "dq"), (dk_nope, (B, S, H, MLA_NOPE), "dk_nope"),
+                           (dv, (B, S, H, MLA_V), "dv"), (dk_pe, (B, S, MLA_ROPE), "dk_pe")):
+        _req(t.dtype == BF16 and t.is_cuda and tuple(t.shape) == shape and t.stride(-1) == 1,
+             f"mla_attn_bwd: {name} must be a bf16 {list(shape)} view with d contiguous")
+    _req(B == 1 or dk_pe.stride(0) == S * dk_pe.stride(1), "mla_attn_bwd: dk_pe rows evenly spaced over (b, s)")
+    _req(lse.dtype == torch.float32 and tuple(lse.shape) == (B, H, S) and lse.is_contiguous(), "mla_attn_bwd: dense f32 lse")
+    _req(delta.dtype == torch.float32 and delta.is_contiguous() and delta.numel() == B * H * S
+         and dkpe_ws.dtype == torch.float32 and dkpe_ws.is_contiguous() and dkpe_ws.numel() == B * S * H * MLA_ROPE,
+         "mla_attn_bwd: ws is mla_workspace(B, S, H, device)")
+    stream = _C.stream_ptr(dev)
+    rc = _C.lib().pt_mla_attn_bwd(_ptr(q), _str3(q), _ptr(k_nope), _str3(k_nope), _ptr(k_pe), _mla_str2(k_pe), _ptr(v),
+                                  _str3(v), _ptr(out), _str3(out), _ptr(dout), _str3(dout), _ptr(lse), _ptr(delta),
+                                  _ptr(dq), _str3(dq), _ptr(dk_nope), _str3(dk_nope), _ptr(dv), _str3(dv),
+                                  _ptr(dkpe_ws), B, H, S, MLA_NOPE, MLA_ROPE, MLA_V, float(scale), stream)
+    _C.check(rc, "pt_mla_attn_bwd")
+    rc = _C.lib().pt_mla_dkpe_reduce(_ptr(dkpe_ws), H, _ptr(dk_pe), dk_pe.stride(1), B * S, _ptr(cos), _ptr(sin), S,
+                                     cos.stride(0), MLA_ROPE, stream)
+    _C.check(rc, "pt_mla_dkpe_reduce")
+    return dq, dk_nope, dk_pe, dv

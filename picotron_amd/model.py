@@ -283,6 +283,73 @@ class Attention(nn.Module):
                                           *self.qk_norm_args())
 
 
+class MLAttention(nn.Module):
+    """Multi-head latent attention (DeepSeek-V2/V3, Moonlight, Kimi-K2; not in the reference), chosen by
+    DecoderLayer when config.kv_lora_rank > 0.  HF's field and parameter names: q_lora_rank (None: one
+    q_proj; else q_a_proj -> q_a_layernorm -> q_b_proj), kv_lora_rank, qk_nope_head_dim, qk_rope_head_dim,
+    v_head_dim; kv_a_proj_with_mqa [kv_lora_rank + rope, hidden], kv_a_layernorm, kv_b_proj
+    [H * (nope + v), kv_lora_rank], out_proj (HF's o_proj) [hidden, H * v].  The rotary pairing is this
+    project's rotate-half (HF's interleaved checkpoints need their q / kv_a rope rows permuted); softmax
+    scale (nope + rope)^-0.5, no YaRN mscale.  The kernels take dims 128 / 64 / 128; data parallelism only."""
+    _pt_mla = True
+
+    def __init__(self, config, layer_idx):
+        super().__init__()
+        m = pgm.current()
+        for name, n in (("tensor (tp", m.tp_world_size), ("context (cp", m.cp_world_size), ("pipeline (pp", m.pp_world_size)):
+            if n > 1:
+                raise NotImplementedError(f"kv_lora_rank > 0 under {name} > 1) parallelism: the latent projections "
+                                          "are not sharded and the MLA kernels have no ring or stage form")
+        if getattr(config, "qk_norm", False):
+            raise NotImplementedError("qk_norm with kv_lora_rank > 0: MLA norms the latents, not the heads")
+        if getattr(config, "sliding_window", None) is not None:
+            raise NotImplementedError("sliding_window with kv_lora_rank > 0: the MLA kernels are plain causal")
+        self.num_heads = config.num_attention_heads
+        self.q_lora_rank = getattr(config, "q_lora_rank", None) or None
+        self.kv_lora_rank = int(config.kv_lora_rank)
+        self.qk_nope_head_dim = int(getattr(config, "qk_nope_head_dim", K.MLA_NOPE))
+        self.qk_rope_head_dim = int(getattr(config, "qk_rope_head_dim", K.MLA_ROPE))
+        self.v_head_dim = int(getattr(config, "v_head_dim", K.MLA_V))
+        K._mla_dims_ok(self.qk_nope_head_dim, self.qk_rope_head_dim, self.v_head_dim, "MLAttention")
+        if self.kv_lora_rank % 8 or (self.q_lora_rank or 8) % 8:
+            raise ValueError("MLAttention: kv_lora_rank and q_lora_rank must be multiples of 8")
+        hidden, H, dq = config.hidden_size, self.num_heads, self.qk_nope_head_dim + self.qk_rope_head_dim
+        RMSNorm = TritonRMSNorm if _flash() else LlamaRMSNorm
+        if self.q_lora_rank is None:
+            self.q_proj = Linear(hidden, H * dq, bias=False)
+        else:
+            self.q_a_proj = Linear(hidden, self.q_lora_rank, bias=False)
+            self.q_a_layernorm = RMSNorm(self.q_lora_rank, eps=config.rms_norm_eps)
+            self.q_b_proj = Linear(self.q_lora_rank, H * dq, bias=False)
+        self.kv_a_proj_with_mqa = Linear(hidden, self.kv_lora_rank + self.qk_rope_head_dim, bias=False)
+        self.kv_a_layernorm = RMSNorm(self.kv_lora_rank, eps=config.rms_norm_eps)
+        self.kv_b_proj = Linear(self.kv_lora_rank, H * (self.qk_nope_head_dim + self.v_head_dim), bias=False)
+        self.out_proj = Linear(H * self.v_head_dim, hidden, bias=False)
+        self.layer_idx = layer_idx
+        self.sliding_window = None
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        for mod in self.children():
+            if isinstance(mod, Linear):
+                _init_uniform_fan_in(mod.weight)
+            else:
+                mod.reset_parameters()
+
+    def q_weights(self):
+        if self.q_lora_rank is None:
+            return (self.q_proj.weight,)
+        return self.q_a_proj.weight, self.q_a_layernorm.weight, self.q_b_proj.weight
+
+    def forward(self, x, cos, sin, attention_mask=None, position_ids=None, document_ids=None):
+        if document_ids is not None:
+            raise NotImplementedError("document_ids with kv_lora_rank > 0: the MLA kernels are plain causal")
+        n = self.kv_a_layernorm
+        return FN.MLAttentionFunction.apply(x, self.q_weights(), self.kv_a_proj_with_mqa.weight, n.weight,
+                                            self.kv_b_proj.weight, self.out_proj.weight, cos, sin, self.num_heads,
+                                            _norm_eps(n), _norm_mode(n))
+
+
 class MLP(nn.Module):
     """model.py:164-186 (parameter order up, gate, down as in the reference)."""
 
@@ -430,10 +497,12 @@ class DecoderLayer(nn.Module):
         RMSNorm = TritonRMSNorm if _flash() else LlamaRMSNorm
         self.input_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
         self.post_attention_layernorm = RMSNorm(config.hidden_size, eps=config.rms_norm_eps)
-        self.attention = Attention(config, layer_idx=layer_idx)
+        mla = (getattr(config, "kv_lora_rank", None) or 0) > 0
+        self.attention = MLAttention(config, layer_idx=layer_idx) if mla else Attention(config, layer_idx=layer_idx)
         self.mlp = MoE(config) if (getattr(config, "num_experts", 0) or 0) > 0 else MLP(config)
         self.layer_idx = layer_idx
-        head_dim = config.hidden_size // config.num_attention_heads
+        # (MLA rotates its qk_rope_head_dim columns only)
+        head_dim = self.attention.qk_rope_head_dim if mla else config.hidden_size // config.num_attention_heads
         self._rope_args = (config.max_position_embeddings, head_dim, config.rope_theta)
         self.cos, self.sin = get_cos_sin(config.max_position_embeddings, head_dim=head_dim, base=config.rope_theta)
         self.cos, self.sin = context_parallel.update_rope_for_context_parallel(self.cos, self.sin)
@@ -471,6 +540,16 @@ class DecoderLayer(nn.Module):
         st = getattr(self, "_pt_sp_state", None)
         sp = st.chunks if (self.tp_sequence_parallel and st is not None and st.local_len and
                            st.local_len == x.shape[1]) else 0
+        if isinstance(at, MLAttention):   # composed from separate nodes, as the MoE path below
+            if sp or zz:
+                raise NotImplementedError("a multi-head latent attention layer on a sharded residual stream (tp / cp > 1)")
+            eps, mode = _norm_eps(n1), _norm_mode(n1)
+            h1 = FN.RMSNormFunction.apply(x, n1.weight, eps, mode)
+            a = at(h1, cos, sin, document_ids=document_ids)
+            h2, z = FN.AddRMSNormFunction.apply(a, x, n2.weight, eps, mode)
+            if isinstance(mlp, MoE):
+                return mlp(h2, z)
+            return FN.MLPFunction.apply(h2, mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight, z)
         band = document_ids if isinstance(document_ids, (K.AttnBand, context_parallel.CPBand)) else None
         if band is None and (document_ids is not None or at.sliding_window is not None):
             if sp or (zz and not FN.ring_enabled()):

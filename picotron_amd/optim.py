@@ -400,7 +400,10 @@ def clip_grad_norm_(parameters, max_norm, norm_type=2.0, error_if_nonfinite=Fals
 
 # ------------------------------------------------------------------------------------ Muon
 _MUON_MATRICES = ("attention.q_proj.weight", "attention.k_proj.weight", "attention.v_proj.weight",
-                  "attention.out_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight")
+                  "attention.out_proj.weight", "mlp.gate_proj.weight", "mlp.up_proj.weight", "mlp.down_proj.weight",
+                  # multi-head latent attention (model.MLAttention)
+                  "attention.q_a_proj.weight", "attention.q_b_proj.weight", "attention.kv_a_proj_with_mqa.weight",
+                  "attention.kv_b_proj.weight")
 _MUON_EXPERT_MATRICES = ("gate_proj.weight", "up_proj.weight", "down_proj.weight")   # under mlp.experts.{e}.
 
 

@@ -229,6 +229,9 @@ class GraphedTrainStep:
             raise ValueError("GraphedTrainStep: data-parallel wrappers, CP and PP are not captured")
         if FN.has_moe(model):
             raise NotImplementedError("GraphedTrainStep: mixture-of-experts layers (moe_aux_loss is not captured)")
+        if FN.has_mla(model):
+            raise NotImplementedError("GraphedTrainStep: multi-head latent attention layers (their backward allocates "
+                                      "and copies outside what the capture was measured for)")
         self.model, self.loader, self.device = model, data_loader, torch.device(device)
         self.warmup = max(1, warmup)
         self.graph = None
