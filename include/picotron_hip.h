@@ -733,6 +733,40 @@ int pt_attn_bwd_band(const void* q, const int64_t* q_str, const void* k, const i
                      int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, const void* rope_cos,
                      const void* rope_sin, int64_t rope_stride, const int32_t* kv_lo, const int32_t* q_hi,
                      hipStream_t stream);
+/* Attention sinks (gpt-oss; the "softmax off by one"; trained StreamingLLM sinks): every query row's
+ * softmax runs over its visible keys and one more column whose score is the learned logit of the
+ * row's query head, sinks[h] (bf16 [H], read as f32; one per QUERY head, also under GQA), and whose
+ * value vector is zero:  m = max(max_j s_j, sink), l = sum_j exp(s_j - m) + exp(sink - m),
+ * o = sum_j exp(s_j - m) v_j / l, and the stored lse = m + log l includes the sink.
+ * pt_attn_fwd_sink = pt_attn_fwd (causal = 1, merge = 0, dense lse) and pt_attn_fwd_band_sink =
+ * pt_attn_fwd_band with that column; the same shapes (Sq == Sk, S % 128 == 0, D in {64, 128}, else
+ * PT_EUNSUPPORTED); a NULL pointer, sinks included, is PT_EINVAL; sinks off 4 bytes PT_EALIGN (the kernels
+ * read the logit as the aligned dword that holds it, on the scalar path).  A sink
+ * of -inf gives pt_attn_fwd's / pt_attn_fwd_band's bits.  Always the regular launch: the few-head
+ * split forms are not used.  A refused call launches nothing.
+ * The backward of q / k / v is pt_attn_bwd / pt_attn_bwd_fused_delta / pt_attn_bwd_band unchanged,
+ * on the sink-including lse.  pt_attn_sink_bwd forms the sink gradient from that lse and the delta
+ * (rowsum(dO * O)) those calls take or leave, both f32 [B, H, Sq] with (b, h) rows lse_ld / delta_ld
+ * elements apart (0: dense):  dsinks[h] = -sum_{b, i} exp(sinks[h] - lse[b, h, i]) delta[b, h, i],
+ * in two stages without atomics (per-workgroup f32 partials over fixed 1024-row ranges in ws, then
+ * one add per head in index order: equal inputs give equal bits), through the gradient sink
+ * sink_mode: 0 store bf16, PT_DW_ACC_BF16, PT_DW_ACC_F32 as pt_rmsnorm_bwd's, PT_DW_STORE_F32 dsinks
+ * is f32, = the sum.  ws: pt_attn_sink_bwd_partials(B, H, Sq) f32 (negative: refused -- a size < 1
+ * PT_EINVAL; B or H above 65535, Sq above 2^31 - 1025, or a count past 32 bits, PT_EUNSUPPORTED).  Checked before any
+ * launch, in this order: a NULL pointer or an unknown sink_mode PT_EINVAL; the sizes as above; a row
+ * stride below Sq PT_EINVAL; lse / delta / ws (or an f32 dsinks) off 4 bytes, sinks (or a bf16 dsinks)
+ * off 2 bytes PT_EALIGN. */
+#define PT_DW_STORE_F32 16
+int pt_attn_fwd_sink(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, void* o, const int64_t* o_str, float* lse, const void* sinks, int64_t B,
+                     int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, hipStream_t stream);
+int pt_attn_fwd_band_sink(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                          const int64_t* v_str, void* o, const int64_t* o_str, float* lse, const void* sinks,
+                          int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale,
+                          const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream);
+int pt_attn_sink_bwd_partials(int64_t B, int64_t H, int64_t Sq);
+int pt_attn_sink_bwd(const float* lse, const float* delta, const void* sinks, void* dsinks, float* ws, int64_t B,
+                     int64_t H, int64_t Sq, int64_t lse_ld, int64_t delta_ld, int sink_mode, hipStream_t stream);
 /* Block bands: the band of one block of a context-parallel schedule (a rank's queries against one
  * owner's keys), where the block is rectangular and usually not causal.  Key j of the block is
  * visible to query i of batch row b iff kv_lo[b, i] <= j, and also j <= i when causal = 1 (the

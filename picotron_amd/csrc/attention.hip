@@ -31,6 +31,17 @@
 // accumulation and parts.  A query row without a visible key leaves its merge accumulator and
 // running LSE untouched (merge = 0: o = 0, lse = -inf) and adds 0 to dQ / dK / dV; a query block
 // whose first row has kv_lo = Sk runs no tile.
+// Sinks (pt_attn_fwd_sink / pt_attn_fwd_band_sink; the SINK instantiations of the forward body): a
+// learned logit sinks[h] (bf16 [H], one per query head, read as f32) joins every row's softmax as one
+// more column whose value vector is zero (gpt-oss; "softmax off by one"; trained StreamingLLM sinks):
+//   m = max(max_j s_j, sink), l = sum_j exp(s_j - m) + exp(sink - m), o = sum_j exp(s_j - m) v_j / l,
+// and the stored lse = m + log l includes the sink.  The column is the INITIAL STATE of the online
+// softmax -- running max = sink (log2 units), running sum = 1 -- so the tile loop carries it without
+// an instruction of its own.  With that lse P = exp(s - lse) is the right probability and rowsum(dO * O)
+// still equals sum_j P_j dP_j (the sink's value is zero): dQ / dK / dV come from the backward kernels
+// unchanged.  dsinks[h] = -sum_{b, i} exp(sinks[h] - lse[b, h, i]) delta[b, h, i] is formed from the
+// lse and the delta workspace the backward leaves (pt_attn_sink_bwd), in two stages without atomics.
+// Causal, merge = 0, dense lse; never the few-head split forms (the sink would enter once per item).
 //
 // Fragment scheme (all v_mfma_f32_32x32x16_bf16): scores are computed "key on the row",
 // S^T = K . Q^T, so a lane owns one query column and softmax statistics are lane-local (plus one
@@ -397,9 +408,19 @@ constexpr int dq_stages() { return D == 64 ? 4 : 2; }
 // at the tile of kv_lo of its first row (the block minimum: kv_lo is non-decreasing); a wave skips
 // tiles wholly below the bound of its first row and masks keys below a lane's own bound on tiles that
 // reach under the bound of its last row.
-template <int D, int NWK, bool BAND = false>
+// a * b + c as a rounded product and a sum, whatever the surrounding code contracts
+__device__ __forceinline__ float mul_then_add(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
+// SINK (causal, merge = 0, no split items): the row's softmax has one more column, the head's sink
+// logit with a zero value vector, as the initial state of the online softmax (see the header).  sinks
+// (bf16 [H]) is the sink kernels' own second argument: AttnArgs, and with it the code of every other
+// kernel, stays as it was.
+template <int D, int NWK, bool BAND = false, bool SINK = false>
 __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_or_hk, int b, int kt_lo = 0,
-                                               int kt_hi = -1, int item = -1) {
+                                               int kt_hi = -1, int item = -1, const uint16_t* sinks = nullptr) {
   constexpr int DT = D / 32, KS = D / 16;
   constexpr int TILE_B = KT * D * 2;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
@@ -442,6 +463,30 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
 #pragma unroll
   for (int i = 0; i < DT; ++i) o[i] = zero16();
   float m = -INFINITY, l = 0.f;
+  if constexpr (SINK) {
+    // the sink column before the first tile: its exponent (log2 units, as mt below) is the running
+    // max and its probability exp2(0) = 1 the running sum -- on one of the two lanes that share a
+    // query row (xor32_sum adds both halves at the end).  A sink of -inf is the plain initial state
+    // (m = -inf, l = 0) and gives the plain kernel's bits.
+    // The logit comes in on the scalar path: the aligned dword that holds sinks[h] (sinks is 4-byte
+    // aligned), one s_load the compiler tracks with lgkmcnt.  As a 2-byte vector load its first use
+    // got a compiler-placed vmcnt(0) behind the Q barrier, which drained the K/V tiles the d64
+    // prologue's counted waits leave in flight (+4 % at d64 S1024).  Only the last head of an odd H,
+    // whose dword would reach past the array, takes the vector load -- consumed here, before the first
+    // stage() has anything in flight.  l follows the scaled value, so a finite sink whose product
+    // overflows to -inf is the plain state too.
+    typedef __attribute__((address_space(4))) const uint32_t sink_word;
+    const int hu = __builtin_amdgcn_readfirstlane(h);
+    float sg;
+    if ((hu | 1) < a.H) {
+      const uint32_t w = ((sink_word*)sinks)[hu >> 1];
+      sg = (hu & 1) ? hi_bf(w) : lo_bf(w);
+    } else {
+      sg = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(bf2f(sinks[hu]))));
+    }
+    m = sg * kLog2e;
+    l = (lane < 32 && m != -INFINITY) ? 1.f : 0.f;
+  }
 
   constexpr int NS = fwd_stages<D, NWK>(), OPS = 2 * (KT * D * 2 / 1024) / NWK;
   auto stage = [&](int kt, int buf) {
@@ -617,7 +662,10 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
   const float inv_l = empty ? 0.f : 1.0f / l;
   // (band d64: spelled as the fma this expression is contracted to in the causal d64 kernel -- the
   // d128 kernels keep a multiply and an add -- so a band that masks nothing gives the causal bits)
-  const float lse = (BAND && D == 64) ? __builtin_fmaf(m, kLn2, __logf(l)) : m * kLn2 + __logf(l);
+  // (sink: both forms spelled out -- the fma at d64, a rounded product and a sum at d128 -- so that a
+  // sink of -inf gives the plain kernels' lse bits whatever this instantiation would contract)
+  const float lse = SINK ? (D == 64 ? __builtin_fmaf(m, kLn2, __logf(l)) : mul_then_add(m, kLn2, __logf(l)))
+                         : (BAND && D == 64) ? __builtin_fmaf(m, kLn2, __logf(l)) : m * kLn2 + __logf(l);
   float* lse_p = a.lse + ((int64_t)b * a.H + h) * a.lse_ld + myq;
   if (!a.merge) {
     uint16_t* orow = a.o.row<uint16_t>(b, myq, h);
@@ -676,6 +724,27 @@ __global__ __launch_bounds__(NWK * 64) void attn_fwd_band_kernel(AttnArgs a) {
   for (int pass = 0; pass <= a.pair; ++pass) {
     if (pass) __syncthreads();
     attn_fwd_block<D, NWK, true>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b);
+  }
+}
+
+// the sink forms of the two kernels above (separate kernels: those compile to what they did)
+template <int D, int NWK>
+__global__ __launch_bounds__(NWK * 64) void attn_fwd_sink_kernel(AttnArgs a, const uint16_t* sinks) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_fwd_block<D, NWK, false, true>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b, 0, -1, -1, sinks);
+  }
+}
+
+template <int D, int NWK>
+__global__ __launch_bounds__(NWK * 64) void attn_fwd_band_sink_kernel(AttnArgs a, const uint16_t* sinks) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_fwd_block<D, NWK, true, true>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b, 0, -1, -1, sinks);
   }
 }
 
@@ -805,6 +874,60 @@ __global__ __launch_bounds__(256) void attn_delta_kernel(View4<const uint16_t> d
     for (int j = 0; j < 8; ++j) acc += x[j] * y[j];
     for (int off = lpr >> 1; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
     if (c == 0) delta[((int64_t)b * H + h) * ld + qq] = acc;
+  }
+}
+
+// ================================================================ dsinks = -sum exp(sink - lse) delta
+// Stage 1: workgroup (c, h, b) takes rows [c kSinkRows, (c + 1) kSinkRows) of lse / delta row (b, h):
+// thread t the rows t, t + 256, ... of the range in that order (coalesced 4-byte loads, 8 bytes per
+// attention row in all), a butterfly over the wave, the four waves' sums added in wave order; its f32
+// partial goes to partial[(h B + b) nchunk + c].  Stage 2: thread h adds head h's B nchunk partials in
+// index order and hands the negated sum to the gradient sink.  No atomics, every order fixed: two
+// runs give the same bits.  expf, not the fast form: the kernel waits on its loads either way.
+constexpr int kSinkRows = 1024;
+__global__ __launch_bounds__(256) void attn_sink_bwd_partial_kernel(const float* __restrict__ lse,
+                                                                    const float* __restrict__ delta,
+                                                                    const uint16_t* __restrict__ sinks,
+                                                                    float* __restrict__ partial, int B, int Sq,
+                                                                    int64_t lse_ld, int64_t delta_ld) {
+  __shared__ float red[4];
+  const int c = blockIdx.x, h = blockIdx.y, b = blockIdx.z, H = gridDim.y, nchunk = gridDim.x;
+  const float sg = bf2f(sinks[h]);
+  const float* lrow = lse + ((int64_t)b * H + h) * lse_ld;
+  const float* drow = delta + ((int64_t)b * H + h) * delta_ld;
+  float x[kSinkRows / 256], y[kSinkRows / 256];
+#pragma unroll
+  for (int i = 0; i < kSinkRows / 256; ++i) {   // every load before the first exp
+    const int r = c * kSinkRows + i * 256 + (int)threadIdx.x;
+    x[i] = r < Sq ? lrow[r] : INFINITY;   // exp(sink - inf) = 0: rows past the end add nothing
+    y[i] = r < Sq ? drow[r] : 0.f;
+  }
+  float acc = 0.f;
+#pragma unroll
+  for (int i = 0; i < kSinkRows / 256; ++i) acc += expf(sg - x[i]) * y[i];
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partial[((int64_t)h * B + b) * nchunk + c] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// sink_mode: 0 store bf16, PT_DW_ACC_BF16 (autograd's grad + bf16(new)), PT_DW_ACC_F32, PT_DW_STORE_F32
+__global__ __launch_bounds__(64) void attn_sink_bwd_reduce_kernel(const float* __restrict__ partial, int n, int H,
+                                                                  void* __restrict__ out, int sink_mode) {
+  const int h = blockIdx.x * blockDim.x + threadIdx.x;
+  if (h >= H) return;
+  float acc = 0.f;
+  for (int i = 0; i < n; ++i) acc += partial[(int64_t)h * n + i];
+  const float g = -acc;
+  if (sink_mode == PT_DW_ACC_F32) {
+    ((float*)out)[h] += g;
+  } else if (sink_mode == PT_DW_STORE_F32) {
+    ((float*)out)[h] = g;
+  } else if (sink_mode == PT_DW_ACC_BF16) {
+    uint16_t* o = (uint16_t*)out;
+    o[h] = f2bf(bf2f(o[h]) + round_bf(g));
+  } else {
+    ((uint16_t*)out)[h] = f2bf(g);
   }
 }
 
@@ -1588,10 +1711,16 @@ int fill_common(AttnArgs& a, const Problem& p) {
 }
 
 template <int D, int NWK>
-void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream) {
+void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream, const uint16_t* sinks) {
   // (d64: the Q image shares the last ring stage)
-  launch(a.kv_lo ? attn_fwd_band_kernel<D, NWK> : attn_fwd_kernel<D, NWK>, grid, NWK * 64,
-         fwd_stages<D, NWK>() * 2 * KT * D * 2, stream, a);
+  const int smem = fwd_stages<D, NWK>() * 2 * KT * D * 2;
+  if (sinks) {   // the sink forms: the same grid, block and LDS, the sinks as a second argument
+    auto kern = a.kv_lo ? attn_fwd_band_sink_kernel<D, NWK> : attn_fwd_sink_kernel<D, NWK>;
+    set_smem(kern, smem);
+    kern<<<grid, NWK * 64, smem, stream>>>(a, sinks);
+    return;
+  }
+  launch(a.kv_lo ? attn_fwd_band_kernel<D, NWK> : attn_fwd_kernel<D, NWK>, grid, NWK * 64, smem, stream, a);
 }
 
 // the backward's operands beyond Problem; what an entry point does not have stays zero
@@ -1700,7 +1829,8 @@ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline int64_t split_tile_bytes(int64_t items, int64_t width) { return align256(items * NW * 32 * width * 4); }
 
 // the forward's launch (pt_attn_fwd, pt_attn_fwd_band): fills and checks the common part, picks the form
-int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream);
+// (sinks: the sink forms, pt_attn_fwd_sink / pt_attn_fwd_band_sink)
+int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uint16_t* sinks = nullptr);
 
 }  // namespace
 
@@ -1737,6 +1867,71 @@ int pt_attn_fwd_band(const void* q, const int64_t* q_str, const void* k, const i
   a.lse = lse;
   a.kv_lo = kv_lo; a.q_hi = q_hi;
   return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1}, stream);
+}
+
+// pt_attn_fwd (causal, merge = 0, dense lse) / pt_attn_fwd_band with the per-head sink logit sinks
+// (bf16 [H]) as one more softmax column (see the header); lse includes it.  Always the regular launch.
+int pt_attn_fwd_sink(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, void* o, const int64_t* o_str, float* lse, const void* sinks, int64_t B,
+                     int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, hipStream_t stream) {
+  if (!q || !k || !v || !o || !lse || !sinks) return PT_EINVAL;
+  if (Sq != Sk) return PT_EUNSUPPORTED;
+  if ((uintptr_t)sinks & 3u) return PT_EALIGN;   // read as aligned dwords
+  AttnArgs a{};
+  a.lse_ld = Sq;
+  a.o = view(o, o_str);
+  a.lse = lse;
+  return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1}, stream,
+                         (const uint16_t*)sinks);
+}
+
+int pt_attn_fwd_band_sink(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                          const int64_t* v_str, void* o, const int64_t* o_str, float* lse, const void* sinks,
+                          int64_t B, int64_t H, int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale,
+                          const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream) {
+  if (!q || !k || !v || !o || !lse || !sinks || !kv_lo || !q_hi) return PT_EINVAL;
+  if (Sq != Sk) return PT_EUNSUPPORTED;
+  if ((uintptr_t)sinks & 3u) return PT_EALIGN;   // read as aligned dwords
+  AttnArgs a{};
+  a.lse_ld = Sq;
+  a.o = view(o, o_str);
+  a.lse = lse;
+  a.kv_lo = kv_lo; a.q_hi = q_hi;
+  return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1}, stream,
+                         (const uint16_t*)sinks);
+}
+
+// f32 partials pt_attn_sink_bwd needs in its workspace (negative: refused)
+int pt_attn_sink_bwd_partials(int64_t B, int64_t H, int64_t Sq) {
+  if (B <= 0 || H <= 0 || Sq <= 0) return PT_EINVAL;
+  if (B > 65535 || H > 65535 || Sq > INT32_MAX - kSinkRows) return PT_EUNSUPPORTED;   // grid dims, 32-bit row index
+  const int64_t n = B * H * ((Sq + kSinkRows - 1) / kSinkRows);
+  return n > INT32_MAX ? PT_EUNSUPPORTED : (int)n;
+}
+
+// dsinks [H] from the forward's lse and the backward's delta (both f32 [B, H, Sq], rows lse_ld /
+// delta_ld apart, 0: dense), through the gradient sink sink_mode: 0 store bf16, PT_DW_ACC_BF16,
+// PT_DW_ACC_F32, PT_DW_STORE_F32.  ws: pt_attn_sink_bwd_partials f32.
+int pt_attn_sink_bwd(const float* lse, const float* delta, const void* sinks, void* dsinks, float* ws, int64_t B,
+                     int64_t H, int64_t Sq, int64_t lse_ld, int64_t delta_ld, int sink_mode, hipStream_t stream) {
+  if (!lse || !delta || !sinks || !dsinks || !ws) return PT_EINVAL;
+  if (sink_mode != 0 && sink_mode != PT_DW_ACC_BF16 && sink_mode != PT_DW_ACC_F32 && sink_mode != PT_DW_STORE_F32)
+    return PT_EINVAL;
+  const int np = pt_attn_sink_bwd_partials(B, H, Sq);
+  if (np < 0) return np;
+  if ((lse_ld != 0 && lse_ld < Sq) || (delta_ld != 0 && delta_ld < Sq)) return PT_EINVAL;
+  const bool f32_out = sink_mode == PT_DW_ACC_F32 || sink_mode == PT_DW_STORE_F32;
+  if (((uintptr_t)lse & 3u) || ((uintptr_t)delta & 3u) || ((uintptr_t)ws & 3u) || ((uintptr_t)sinks & 1u) ||
+      ((uintptr_t)dsinks & (f32_out ? 3u : 1u)))
+    return PT_EALIGN;
+  const int nchunk = (int)((Sq + kSinkRows - 1) / kSinkRows);
+  attn_sink_bwd_partial_kernel<<<dim3((unsigned)nchunk, (unsigned)H, (unsigned)B), 256, 0, stream>>>(
+      lse, delta, (const uint16_t*)sinks, ws, (int)B, (int)Sq, lse_ld ? lse_ld : Sq, delta_ld ? delta_ld : Sq);
+  PT_CHECK_LAUNCH();
+  attn_sink_bwd_reduce_kernel<<<(unsigned)((H + 63) / 64), 64, 0, stream>>>(ws, (int)(B * nchunk), (int)H, dsinks,
+                                                                            sink_mode);
+  PT_CHECK_LAUNCH();
+  return PT_OK;
 }
 
 // pt_attn_bwd_fused_delta under a band (bf16 gradients, dense lse; the optional fused RoPE inverse)
@@ -1797,7 +1992,7 @@ int pt_attn_bwd_block_band(const void* q, const int64_t* q_str, const void* k, c
 
 namespace {
 
-int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream) {
+int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uint16_t* sinks) {
   const int64_t B = p.B, H = p.H, Sq = p.Sq, D = p.D;
   const int causal = p.causal;
   int rc = fill_common(a, p);
@@ -1808,9 +2003,9 @@ int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream) {
   const int nqb = (int)(Sq / (nwk * 32));
   a.pair = causal && nqb % 2 == 0 && pair_enabled();
   const dim3 grid((unsigned)(a.pair ? nqb / 2 : nqb), (unsigned)H, (unsigned)B);
-  if (D == 64) launch_fwd<64, NW>(a, grid, stream);
-  else if (nwk == 8) launch_fwd<128, 8>(a, grid, stream);
-  else launch_fwd<128, NW>(a, grid, stream);
+  if (D == 64) launch_fwd<64, NW>(a, grid, stream, sinks);
+  else if (nwk == 8) launch_fwd<128, 8>(a, grid, stream, sinks);
+  else launch_fwd<128, NW>(a, grid, stream, sinks);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

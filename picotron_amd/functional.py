@@ -925,17 +925,42 @@ class QKNorm:
                                       "zero-padding path would have to norm over the real head_dim")
 
 
-def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None):
+def require_sinks(sh, tp, sp=False):
+    """Refuse, before any launch, what the attention sinks do not do."""
+    if tp.world_size > 1 or sp:
+        raise NotImplementedError("attention sinks under tensor parallelism (tp > 1): the per-head logits and "
+                                  "their gradient are not sharded with the heads")
+    if ring_enabled():
+        raise NotImplementedError("attention sinks under context parallelism (cp > 1): across the ring's steps "
+                                  "the sink must enter the softmax exactly once")
+    if sh.d not in ATTN_HEAD_DIMS:
+        raise NotImplementedError(f"attention sinks with head_dim {sh.d}: the sink kernels take 64 / 128")
+
+
+def sinks_bwd(lse, delta, sinks):
+    """The sinks' gradient from the attention backward's lse and delta, into the parameter's sink as a
+    norm weight's goes (bf16 .grad store / accumulate, or main_grad); a frozen parameter gets none."""
+    if not sinks.requires_grad:
+        return
+    buf, sink = _norm_dw_sink(sinks)
+    K.attn_sink_bwd(lse, delta, sinks, out=buf, sink=sink)
+    _grad_ready(sinks)
+
+
+def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None, sinks=None):
     """RoPE on q|k in place (model.py:136-137; skipped when the projection epilogue already
     rotated them: roped), then causal flash attention (model.py:154) or the ring
     (model.py:148-151).  Returns (o [B,S,nh,d] bf16, lse f32 [B,nh,S]).
     qkn (a QKNorm): q|k are normed per head and rotated by one kernel into their own [T, q|k] buffer
     -- qkv keeps the raw projection, which the norm's backward needs -- and attention reads q, k from
-    that buffer and v from qkv; returns (o, lse, qk, rstd [T, nh + nkv] f32)."""
+    that buffer and v from qkv; returns (o, lse, qk, rstd [T, nh + nkv] f32).
+    sinks (bf16 [nh]): the per-head sink logits of kernels.attn_fwd; lse then includes the sink."""
+    if sinks is not None:
+        require_sinks(sh, TPContext.current())
     if qkn is not None:
         qkn.require(sh, TPContext.current())
         qk, rstd = K.qk_norm_rope_fwd(qkv, sh.nh, sh.nkv, sh.d, qkn.wq, qkn.wk, qkn.eps, qkn.mode, cos, sin, sh.S)
-        o, lse = K.attn_fwd(sh.q(qk), sh.k(qk), sh.v(qkv), scale, True, band=sh.band)
+        o, lse = K.attn_fwd(sh.q(qk), sh.k(qk), sh.v(qkv), scale, True, band=sh.band, sinks=sinks)
         return o, lse, qk, rstd
     if sh.d not in ATTN_HEAD_DIMS and not ring_enabled():
         _req_head_dim(sh.d, roped)
@@ -945,21 +970,25 @@ def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None):
     if ring_enabled():
         from .context_parallel.context_parallel import ring_attention_tokens
         return ring_attention_tokens(qkv, sh, scale, True, resident=sh.zz)
-    return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True, band=sh.band)
+    return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True, band=sh.band, sinks=sinks)
 
 
-def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=None):
+def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=None, sinks=None):
     """dq|dk|dv written into one [T, q|k|v] buffer, then the inverse rotation of dq|dk.
     qkn / normed = (qk, rstd) of attention_core_fwd: attention ran on the normed, rotated qk (v from
     qkv); after the inverse rotation dq|dk are the gradient of the norm's output, and its backward
     runs in place on those columns from the raw q|k in qkv.  The two [d] weight gradients go the
-    layer norms' way (norm_dw_from_partial); a frozen weight gets none."""
+    layer norms' way (norm_dw_from_partial); a frozen weight gets none.
+    sinks: lse includes the sink, so dq|dk|dv are the same kernels'; the sinks' own gradient is formed
+    from lse and the delta those kernels leave (sinks_bwd)."""
     if qkn is not None:
         qk, rstd = normed
         dqkv = torch.empty_like(qkv)
         rope = (cos, sin) if _fuse() else None   # the RoPE backward fused into the dq / dk stores, or after
-        K.attn_bwd(do, sh.q(qk), sh.k(qk), sh.v(qkv), o, lse, scale, True,
-                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band)
+        *_, delta = K.attn_bwd(do, sh.q(qk), sh.k(qk), sh.v(qkv), o, lse, scale, True,
+                               dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band)
+        if sinks is not None:
+            sinks_bwd(lse, delta, sinks)
         if rope is None:
             K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
         need = (qkn.wq.requires_grad, qkn.wk.requires_grad)
@@ -975,35 +1004,39 @@ def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=No
         from .context_parallel.context_parallel import ring_attention_tokens_bwd
         ring_attention_tokens_bwd(do, qkv, o, lse, sh, scale, True, dqkv, resident=sh.zz)
         K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
-    elif _fuse():  # the RoPE backward is fused into the dq / dk stores
-        K.attn_bwd(do, sh.q(qkv), sh.k(qkv), sh.v(qkv), o, lse, scale, True,
-                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=(cos, sin), band=sh.band)
     else:
-        K.attn_bwd(do, sh.q(qkv), sh.k(qkv), sh.v(qkv), o, lse, scale, True,
-                   dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), band=sh.band)
-        K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
+        rope = (cos, sin) if _fuse() else None   # the RoPE backward fused into the dq / dk stores, or after
+        *_, delta = K.attn_bwd(do, sh.q(qkv), sh.k(qkv), sh.v(qkv), o, lse, scale, True,
+                               dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band)
+        if rope is None:
+            K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
+        if sinks is not None:
+            sinks_bwd(lse, delta, sinks)
     return dqkv
 
 
-def attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, tp, reduce=True, qkn=None):
+def attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, tp, reduce=True, qkn=None, sinks=None):
     """h2 [T,H] -> (a [T,H], saved).  Row-parallel out_proj: a = sum over tp of o W_o^T (reduce=False:
     this rank's partial, for the sequence-parallel reduce-scatter).
     qkn (a QKNorm): the plain q|k|v GEMM (the norm sits between the projection and the rotation, so
     the RoPE-epilogue GEMM cannot run), then the fused norm + RoPE kernel; saved grows by the normed,
-    rotated [T, q|k] and rstd [T, nh + nkv] f32."""
+    rotated [T, q|k] and rstd [T, nh + nkv] f32.
+    sinks (bf16 [nh]): the attention sinks (attention_core_fwd)."""
     scale = 1.0 / math.sqrt(sh.d)
+    if sinks is not None:
+        require_sinks(sh, tp, not reduce)
     if qkn is not None:
         qkn.require(sh, tp, not reduce)
         qkv = K.linear_fwd(h2, [wq, wk, wv])
-        o, lse, qk, rstd = attention_core_fwd(qkv, sh, cos, sin, scale, qkn=qkn)
+        o, lse, qk, rstd = attention_core_fwd(qkv, sh, cos, sin, scale, qkn=qkn, sinks=sinks)
         a = K.linear_fwd(o.view(sh.T, sh.wq), [wo])
         return a, (qkv, o, lse, qk, rstd)
     if _fuse() and K.rope_fusable(h2.shape[0], sh.d, sh.S, (wq.shape[0], wk.shape[0], wv.shape[0])):   # RoPE of q|k in the projection's epilogue
         qkv = K.linear_fwd_rope(h2, [wq, wk, wv], cos, sin, sh.S, sh.nh + sh.nkv, sh.d)
-        o, lse = attention_core_fwd(qkv, sh, cos, sin, scale, roped=True)
+        o, lse = attention_core_fwd(qkv, sh, cos, sin, scale, roped=True, sinks=sinks)
     else:
         qkv = K.linear_fwd(h2, [wq, wk, wv])
-        o, lse = attention_core_fwd(qkv, sh, cos, sin, scale)
+        o, lse = attention_core_fwd(qkv, sh, cos, sin, scale, sinks=sinks)
     a = K.linear_fwd(o.view(sh.T, sh.wq), [wo])
     if reduce:
         tp.all_reduce(a)
@@ -1015,7 +1048,7 @@ def _dual_qkv_enabled():
 
 
 def attn_block_bwd(da, h2, saved, wq, wk, wv, wo, cos, sin, sh, tp, need_dx=True, keep_parts=False, sp=False,
-                   rs_out=None, notify=True, qkn=None):
+                   rs_out=None, notify=True, qkn=None, sinks=None):
     """keep_parts: the q|k|v dX may come back as K.SplitKParts (two f32 K halves) for a following
     rmsnorm backward to sum.  sp: the column-parallel dX is reduce-scattered onto this rank's token
     rows (sequence parallelism) instead of all-reduced.  rs_out: one token chunk of the chunked
@@ -1025,7 +1058,8 @@ def attn_block_bwd(da, h2, saved, wq, wk, wv, wo, cos, sin, sh, tp, need_dx=True
     qkv, o, lse, *normed = saved   # normed: (qk, rstd) of a QK-norm forward, else nothing
     scale = 1.0 / math.sqrt(sh.d)
     do2 = K.linear_dgrad(da, [wo])
-    dqkv = attention_core_bwd(do2.view(sh.B, sh.S, sh.nh, sh.d), qkv, o, lse, sh, cos, sin, scale, qkn, normed)
+    dqkv = attention_core_bwd(do2.view(sh.B, sh.S, sh.nh, sh.d), qkv, o, lse, sh, cos, sin, scale, qkn, normed,
+                              sinks)
     if need_dx and tp.world_size == 1 and _dual_qkv_enabled():
         # tp = 1 (no all-reduce to overlap): the q|k|v dX as two split-K halves (128 + 128 tiles of
         # 256x256, summed by the input norm's backward -- or by the sum pass without keep_parts) in
@@ -1059,27 +1093,31 @@ class AttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wq, wk, wv, wo, cos, sin, nh, nkv, d, band=None, wqn=None, wkn=None, qk_eps=None,
-                qk_mode=None):
+                qk_mode=None, sinks=None):
         B, S, _ = x.shape
         sh = AttnShape(B, S, nh, nkv, d, band=band)
         qkn = QKNorm.of(wqn, wkn, qk_eps, qk_mode)
         if qkn is not None:
             qkn.require(sh, TPContext.current())
+        if sinks is not None:
+            require_sinks(sh, TPContext.current())
         h2 = _contig2d(x)
-        a, saved = attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, TPContext.current(), qkn=qkn)
-        ctx.save_for_backward(h2, *saved[:3], wq, wk, wv, wo, cos, sin,
+        a, saved = attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, TPContext.current(), qkn=qkn, sinks=sinks)
+        # (the sinks first of the optional tensors: the QK-norm's four follow as before)
+        ctx.save_for_backward(h2, *saved[:3], wq, wk, wv, wo, cos, sin, *(() if sinks is None else (sinks,)),
                               *((*saved[3:], wqn, wkn) if qkn is not None else ()))
-        ctx.sh, ctx.qk = sh, (qk_eps, qk_mode)
+        ctx.sh, ctx.qk, ctx.has_sinks = sh, (qk_eps, qk_mode), sinks is not None
         return a.view(B, S, -1)
 
     @staticmethod
     def backward(ctx, da):
         h2, qkv, o, lse, wq, wk, wv, wo, cos, sin, *rest = ctx.saved_tensors
         sh = ctx.sh
+        sinks = rest.pop(0) if ctx.has_sinks else None   # its gradient goes straight into its sink (sinks_bwd)
         qkn = QKNorm(rest[2], rest[3], *ctx.qk) if rest else None   # rest: qk, rstd, q_norm, k_norm weights
         dh = attn_block_bwd(_contig2d(da), h2, (qkv, o, lse, *rest[:2]), wq, wk, wv, wo, cos, sin, sh,
-                            TPContext.current(), need_dx=ctx.needs_input_grad[0], qkn=qkn)
-        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 14
+                            TPContext.current(), need_dx=ctx.needs_input_grad[0], qkn=qkn, sinks=sinks)
+        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 15
 
 
 # ------------------------------------------------------------------------ multi-head latent attention

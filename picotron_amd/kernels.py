@@ -2776,16 +2776,36 @@ def _band_for(band, q, k, causal, what):
     return band.padded(_attn_padded_len(Sq))
 
 
-def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None):
+def _sinks_for(sinks, H, device, what):
+    """The checks every sink call shares: one bf16 logit per query head, contiguous, on the device."""
+    _req(isinstance(sinks, torch.Tensor) and sinks.dtype == BF16, f"{what}: sinks must be a bfloat16 tensor")
+    _req(tuple(sinks.shape) == (H,) and sinks.is_contiguous(),
+         f"{what}: sinks must be a contiguous [num query heads] = [{H}] tensor, got {tuple(sinks.shape)}")
+    _req(sinks.device == device, f"{what}: sinks on {sinks.device}, the queries on {device}")
+    _req(sinks.data_ptr() % 4 == 0, f"{what}: sinks must be 4-byte aligned (the kernels read them as dwords)")
+
+
+def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None, sinks=None):
     """q [B,Sq,H,D], k/v [B,Sk,Hkv,D] (token-major views).  Returns (out, lse[B,H,Sq] f32).
     merge=True: `out` is an f32 accumulator and `lse` the running LSE; this block is merged in.
     lse may be the Sq-column slice of a longer [B, H, S] LSE (rows evenly spaced).
     band (an AttnBand): document-masked / sliding-window causal attention; causal only, no merge,
     dense lse; the few-head split forms are not taken.
     band (an AttnBlockBand): one block of a context-parallel schedule; causal or not, merge, a strided
-    lse; Sq and Sk on the 128-row blocks."""
+    lse; Sq and Sk on the 128-row blocks.
+    sinks (bf16 [H], one learned logit per query head): every row's softmax gets one more column with
+    that score and a zero value vector, and lse includes it (attention.hip, "Sinks"); causal, with an
+    AttnBand or without, dense lse; the few-head split forms are not taken.  The backward is attn_bwd
+    on this lse, unchanged, plus attn_sink_bwd for the sinks' own gradient."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if sinks is not None:
+        if merge or isinstance(band, AttnBlockBand):
+            raise NotImplementedError("attn_fwd: sinks with merge=True or an AttnBlockBand (context-parallel blocks): "
+                                      "across the ring's steps the sink must enter the softmax exactly once")
+        _sinks_for(sinks, H, q.device, "attn_fwd")
+        _req(bool(causal) and Sq == Sk, "attn_fwd: sinks take causal attention with Sq == Sk")
+        _req(lse is None or _lse_ld(lse, B, H, Sq) == Sq, "attn_fwd: sinks take a dense lse")
     if isinstance(band, AttnBlockBand):
         _block_band_for(band, q, k, causal, "attn_fwd")
         _req(not merge or (out is not None and lse is not None), "attn_fwd: merge=True needs out and lse")
@@ -2804,7 +2824,8 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None)
         bp = _band_for(band, q, k, causal, "attn_fwd")
         _req(lse is None or _lse_ld(lse, B, H, Sq) == Sq, "attn_fwd: a band takes a dense lse")
         if bp is not band:   # S off the 128-row blocks: the padded path below, pad rows their own documents
-            op, lp = attn_fwd(_pad_seq(q, bp.S), _pad_seq(k, bp.S), _pad_seq(v, bp.S), scale, True, band=bp)
+            op, lp = attn_fwd(_pad_seq(q, bp.S), _pad_seq(k, bp.S), _pad_seq(v, bp.S), scale, True, band=bp,
+                              sinks=sinks)
             if out is None:
                 out = op[:, :Sq].contiguous()
             else:
@@ -2818,6 +2839,12 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None)
             out = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device)
         if lse is None:
             lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+        if sinks is not None:
+            rc = _C.lib().pt_attn_fwd_band_sink(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out),
+                                                _str3(out), _ptr(lse), _ptr(sinks), B, H, HKV, Sq, Sk, D, float(scale),
+                                                _ptr(band.kv_lo), _ptr(band.q_hi), _C.stream_ptr(q.device))
+            _C.check(rc, "pt_attn_fwd_band_sink")
+            return out, lse
         rc = _C.lib().pt_attn_fwd_band(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
                                        _ptr(lse), B, H, HKV, Sq, Sk, D, float(scale), _ptr(band.kv_lo),
                                        _ptr(band.q_hi), _C.stream_ptr(q.device))
@@ -2825,7 +2852,7 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None)
         return out, lse
     if not merge and _attn_off_block(causal, Sq, Sk, lse, B, H):
         Sp = _attn_padded_len(Sq)
-        op, lp = attn_fwd(_pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp), scale, True)
+        op, lp = attn_fwd(_pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp), scale, True, sinks=sinks)
         if out is None:
             out = op[:, :Sq].contiguous()
         else:
@@ -2839,6 +2866,12 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None)
         out = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device)
     if lse is None:
         lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+    if sinks is not None:   # always the regular launch (each split work item would take the sink again)
+        rc = _C.lib().pt_attn_fwd_sink(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                       _ptr(lse), _ptr(sinks), B, H, HKV, Sq, Sk, D, float(scale),
+                                       _C.stream_ptr(q.device))
+        _C.check(rc, "pt_attn_fwd_sink")
+        return out, lse
     ld = _lse_ld(lse, B, H, Sq)
     ws = _attn_split_ws(B, H, HKV, Sq, Sk, D, causal, 0, q.device) if (not merge and ld == Sq) else None
     if ws is not None:   # few heads (a TP shard): split work items + merge (pt_attn_split_plan)
@@ -2873,6 +2906,36 @@ def attn_delta(dout, out, delta=None):
                                     _C.stream_ptr(out.device))
     _C.check(rc, "pt_attn_bwd_delta")
     return delta
+
+
+DW_STORE_F32 = 16   # pt_attn_sink_bwd: an f32 gradient stored, not accumulated (include/picotron_hip.h)
+
+
+def attn_sink_bwd(lse, delta, sinks, out=None, sink=0):
+    """The gradient of attn_fwd's sinks, [H]: -sum_{b, i} exp(sinks[h] - lse[b, h, i]) delta[b, h, i], from
+    the forward's lse and the delta attn_bwd returns (f32 [B, H, Sq], dense or row-strided, each with
+    its own stride).  Two launches, no atomics: equal inputs give equal bits.  out / sink: the buffer
+    the gradient goes to -- 0 store bf16 (a new tensor when out is None), DW_ACC_BF16 accumulate into a
+    bf16 .grad, DW_ACC_F32 accumulate into an f32 main_grad, DW_STORE_F32 store f32."""
+    _req(lse.dim() == 3, "attn_sink_bwd: lse must be f32 [B, H, Sq]")
+    B, H, Sq = lse.shape
+    _sinks_for(sinks, H, lse.device, "attn_sink_bwd")
+    _req(sink in (0, DW_ACC_BF16, DW_ACC_F32, DW_STORE_F32), "attn_sink_bwd: unknown gradient sink")
+    odt = torch.float32 if sink in (DW_ACC_F32, DW_STORE_F32) else BF16
+    if out is None:
+        _req(sink in (0, DW_STORE_F32), "attn_sink_bwd: an accumulating sink needs its buffer")
+        out = torch.empty(H, dtype=odt, device=lse.device)
+    _req(out.dtype == odt and tuple(out.shape) == (H,) and out.is_contiguous() and out.device == lse.device,
+         f"attn_sink_bwd: the gradient buffer must be a contiguous {odt} [{H}] tensor on {lse.device}")
+    ld, dld = _lse_ld(lse, B, H, Sq), _lse_ld(delta, B, H, Sq, "delta")
+    lib = _C.lib()
+    n = lib.pt_attn_sink_bwd_partials(B, H, Sq)
+    _C.check(min(n, 0), "pt_attn_sink_bwd_partials")
+    ws = torch.empty(n, dtype=torch.float32, device=lse.device)
+    rc = lib.pt_attn_sink_bwd(_ptr(lse), _ptr(delta), _ptr(sinks), _ptr(out), _ptr(ws), B, H, Sq, ld, dld, int(sink),
+                              _C.stream_ptr(lse.device))
+    _C.check(rc, "pt_attn_sink_bwd")
+    return out
 
 
 def attn_bwd_part(dout, q, k, v, lse, delta, scale, causal, dq=None, dk=None, dv=None, grad_f32=True, band=None):

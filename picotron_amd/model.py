@@ -209,8 +209,29 @@ def _init_uniform_fan_in(tensor):
 
 
 # ---------------------------------------------------------------------------- blocks
+LAYER_TYPES = ("sliding_attention", "full_attention")
+
+
+def layer_types(config):
+    """config.layer_types (HF's field: one of LAYER_TYPES per layer; gpt-oss alternates them) checked
+    against num_hidden_layers, or None when the config has none.  With it config.sliding_window
+    applies to the layers named "sliding_attention" only."""
+    lt = getattr(config, "layer_types", None)
+    if lt is None:
+        return None
+    lt = list(lt)
+    if len(lt) != config.num_hidden_layers:
+        raise ValueError(f"layer_types: {len(lt)} entries for num_hidden_layers = {config.num_hidden_layers}")
+    for name in lt:
+        if name not in LAYER_TYPES:
+            raise ValueError(f"layer_types: {name!r} is not one of {LAYER_TYPES}")
+    return lt
+
+
 class Attention(nn.Module):
-    """model.py:88-162."""
+    """model.py:88-162.  config.attention_sinks = True (gpt-oss; not in the reference) adds `sinks`
+    [num_attention_heads] bf16 (HF's self_attn.sinks is attention.sinks here): one learned logit per
+    query head that joins every row's softmax as a column with a zero value vector (kernels.attn_fwd)."""
 
     def __init__(self, config, layer_idx):
         super().__init__()
@@ -230,6 +251,22 @@ class Attention(nn.Module):
         self.layer_idx = layer_idx
         # Mistral-style sliding-window attention: a token sees the last `sliding_window` keys (None: all)
         self.sliding_window = getattr(config, "sliding_window", None)
+        lt = layer_types(config)
+        if lt is not None and lt[layer_idx] == "full_attention":
+            self.sliding_window = None
+        self.attention_sinks = bool(getattr(config, "attention_sinks", False))
+        if self.attention_sinks:
+            if m.tp_world_size > 1:
+                raise NotImplementedError("attention_sinks under tensor parallelism (tp > 1): the per-head logits "
+                                          "and their gradient are not sharded with the heads")
+            if m.cp_world_size > 1:
+                raise NotImplementedError("attention_sinks under context parallelism (cp > 1): across the ring's "
+                                          "steps the sink must enter the softmax exactly once")
+            if self.head_dim not in FN.ATTN_HEAD_DIMS:
+                raise NotImplementedError(f"attention_sinks with head_dim {self.head_dim}: the sink kernels take "
+                                          "64 / 128")
+            self.sinks = nn.Parameter(torch.empty(self.num_heads, dtype=torch.bfloat16))
+            self.sinks_std = float(getattr(config, "initializer_range", 0.02))
         # QK-norm (config.qk_norm; Qwen3 / OLMo-2 / Gemma-3 / Chameleon): an RMSNorm of the layer norms'
         # flavour over each q head's and each k head's head_dim values, between the projection and
         # RoPE; one [head_dim] weight for the q heads, one for the k heads (Qwen3's layout)
@@ -252,6 +289,8 @@ class Attention(nn.Module):
         if self.qk_norm:
             self.q_norm.reset_parameters()
             self.k_norm.reset_parameters()
+        if self.attention_sinks:   # HF's gpt-oss: normal(0, initializer_range)
+            nn.init.normal_(self.sinks, mean=0.0, std=self.sinks_std)
 
     def weights(self):
         return self.q_proj.weight, self.k_proj.weight, self.v_proj.weight, self.out_proj.weight
@@ -263,6 +302,14 @@ class Attention(nn.Module):
         if _norm_mode(self.q_norm) != _norm_mode(self.k_norm) or _norm_eps(self.q_norm) != _norm_eps(self.k_norm):
             raise ValueError("Attention: q_norm and k_norm must be the same flavour")
         return self.q_norm.weight, self.k_norm.weight, _norm_eps(self.q_norm), _norm_mode(self.q_norm)
+
+    def tail_args(self):
+        """AttentionFunction's arguments after the band: the QK-norm's four (None without one) and the
+        sinks -- or nothing when the layer has neither."""
+        qk = self.qk_norm_args()
+        if not self.attention_sinks:
+            return qk
+        return (qk or (None,) * 4) + (self.sinks,)
 
     def band(self, x, document_ids):
         """The kernels.AttnBand of this forward (None: plain causal): document_ids a [B, S] integer
@@ -280,7 +327,7 @@ class Attention(nn.Module):
         positions reset per document would give the same attention; position_ids stays unused."""
         return FN.AttentionFunction.apply(x, *self.weights(), cos, sin, self.num_local_heads,
                                           self.num_local_kv_heads, self.head_dim, self.band(x, document_ids),
-                                          *self.qk_norm_args())
+                                          *self.tail_args())
 
 
 class MLAttention(nn.Module):
@@ -304,6 +351,8 @@ class MLAttention(nn.Module):
             raise NotImplementedError("qk_norm with kv_lora_rank > 0: MLA norms the latents, not the heads")
         if getattr(config, "sliding_window", None) is not None:
             raise NotImplementedError("sliding_window with kv_lora_rank > 0: the MLA kernels are plain causal")
+        if getattr(config, "attention_sinks", False):
+            raise NotImplementedError("attention_sinks with kv_lora_rank > 0: the MLA kernels have no sink form")
         self.num_heads = config.num_attention_heads
         self.q_lora_rank = getattr(config, "q_lora_rank", None) or None
         self.kv_lora_rank = int(config.kv_lora_rank)
@@ -559,15 +608,17 @@ class DecoderLayer(nn.Module):
         qk = at.qk_norm_args()   # (): no QK-norm; else its two weights, in the layer norms' flavour
         if qk and qk[2:] != (_norm_eps(n1), _norm_mode(n1)):
             raise ValueError("DecoderLayer: q_norm / k_norm must be the layer norms' flavour")
-        if isinstance(mlp, MoE):
+        if isinstance(mlp, MoE) or at.attention_sinks:   # composed from the separate nodes
             if sp or zz:
                 raise NotImplementedError("a mixture-of-experts layer on a sharded residual stream (tp / cp > 1)")
             eps, mode = _norm_eps(n1), _norm_mode(n1)
             h1 = FN.RMSNormFunction.apply(x, n1.weight, eps, mode)
             a = FN.AttentionFunction.apply(h1, *at.weights(), cos, sin, at.num_local_heads, at.num_local_kv_heads,
-                                           at.head_dim, band, *qk)
+                                           at.head_dim, band, *at.tail_args())
             h2, z = FN.AddRMSNormFunction.apply(a, x, n2.weight, eps, mode)
-            return mlp(h2, z)
+            if isinstance(mlp, MoE):
+                return mlp(h2, z)
+            return FN.MLPFunction.apply(h2, mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight, z)
         return FN.DecoderLayerFunction.apply(
             x, n1.weight, n2.weight, *at.weights(), mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
             cos, sin, _norm_eps(n1), _norm_mode(n1), at.num_local_heads, at.num_local_kv_heads, at.head_dim, zz, sp,
@@ -608,6 +659,7 @@ class Llama(nn.Module):
         self.max_position_embeddings = config.max_position_embeddings
         self.num_layers = config.num_hidden_layers
         self.model_config = config
+        layer_types(config)   # (refused here, before any layer is built)
         self.embedding = Embedding(self.vocab_size, self.hidden_size)
         self.decoder_layers = nn.ModuleList([DecoderLayer(config, layer_idx=i) for i in range(self.num_layers)])
         self.final_proj = Linear(self.hidden_size, self.vocab_size, bias=False)
@@ -634,19 +686,28 @@ class Llama(nn.Module):
         RoPE scores depend on i - j only, so per-document positions would give the same attention.
         Under context parallelism (cp > 1) document_ids is this rank's [B, S_local] chunk, sliced like
         input_ids (the shards are all-gathered over the cp group once), or the full [B, cp * S_local]
-        rows; one context_parallel.CPBand is built and handed to every layer."""
+        rows; one context_parallel.CPBand is built and handed to every layer.
+        With config.layer_types the window belongs to the "sliding_attention" layers only: at most two
+        bands per forward, one per window a layer has (its own sliding_window, or none)."""
         x = self.embedding(input_ids)
-        band = None
-        window = getattr(self.model_config, "sliding_window", None)
-        if document_ids is not None or window is not None:
-            if FN.ring_enabled():   # (a cp group of one rank, or a plain AttnBand: refused there)
-                band = context_parallel.make_cp_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids,
-                                                     window)
-            else:
-                # (ids of the full rows: a token-row shard of the stream has no band of its own)
-                band = FN.make_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids, window)
+        bands = {}
+
+        def band_of(window):
+            if document_ids is None and window is None:
+                return None
+            if window not in bands:
+                if FN.ring_enabled():   # (a cp group of one rank, or a plain AttnBand: refused there)
+                    bands[window] = context_parallel.make_cp_band(input_ids.shape[0], input_ids.shape[1], x.device,
+                                                                  document_ids, window)
+                else:
+                    # (ids of the full rows: a token-row shard of the stream has no band of its own)
+                    bands[window] = FN.make_band(input_ids.shape[0], input_ids.shape[1], x.device, document_ids,
+                                                 window)
+            return bands[window]
+
         aux = None
         for layer in self.decoder_layers:
+            band = band_of(layer.attention.sliding_window)
             x = layer(x) if band is None else layer(x, document_ids=band)
             if isinstance(layer.mlp, MoE):
                 aux = layer.mlp.aux_loss if aux is None else aux + layer.mlp.aux_loss

@@ -232,6 +232,9 @@ class GraphedTrainStep:
         if FN.has_mla(model):
             raise NotImplementedError("GraphedTrainStep: multi-head latent attention layers (their backward allocates "
                                       "and copies outside what the capture was measured for)")
+        if any(getattr(m, "attention_sinks", False) for m in model.modules()):
+            raise NotImplementedError("GraphedTrainStep: attention sinks (their layers run as separate autograd nodes "
+                                      "and the sinks' gradient pass allocates its workspace: not shown to capture)")
         self.model, self.loader, self.device = model, data_loader, torch.device(device)
         self.warmup = max(1, warmup)
         self.graph = None
