@@ -835,6 +835,29 @@ int pt_mla_dkpe_reduce(const float* ws, int64_t H, void* dk_pe, int64_t dkpe_row
                        const void* cos_table, const void* sin_table, int64_t seq_len, int64_t table_stride,
                        int64_t d_rope, hipStream_t stream);
 
+/* ---- head dim 256 attention (csrc/attention_d256.hip) -----------------------------------------
+ * Causal flash attention at head dim 256 (the pt_attn_* entries above keep refusing it): bf16 in and
+ * out, f32 softmax and accumulation, Sq == Sk = S, GQA with query head h on kv head h / (H / HKV).
+ * q / o / dout / dq [B, S, H, 256] and k / v / dk / dv [B, S, HKV, 256]: base pointer + (batch, seq, head)
+ * strides in elements, d contiguous (e.g. column slices of one [T, (H + 2 HKV) * 256] buffer).  lse and
+ * delta_out f32 [B, H, S] dense.  scale > 0 is the caller's (nothing assumes 256^-0.5).
+ * Checked in this order, before any launch: a NULL pointer, a size < 1 or scale <= 0 PT_EINVAL;
+ * S % 128 != 0, H % HKV != 0, or a count past 32 bits (B or H > 65535, B H S >= 2^31, a seq stride
+ * >= 2^24) PT_EUNSUPPORTED; a negative batch stride, or a seq or head stride below 256, PT_EINVAL; a
+ * pointer off 16 bytes or a stride off 8 elements PT_EALIGN.  A refused call launches nothing.
+ * No atomics: equal inputs give equal bits.
+ * pt_attn_d256_bwd: two launches.  The dQ kernel forms D = rowsum(dO * O) and writes it to delta_out;
+ *   the dK/dV kernel reads it and walks the query heads of each kv head's group in head order.  dq, dk,
+ *   dv are bf16 stores (no accumulation, no fused RoPE inverse). */
+int pt_attn_d256_fwd(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H, int64_t HKV,
+                     int64_t S, float scale, hipStream_t stream);
+int pt_attn_d256_bwd(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                     const int64_t* v_str, const void* o, const int64_t* o_str, const void* dout, const int64_t* do_str,
+                     const float* lse, float* delta_out, void* dq, const int64_t* dq_str, void* dk,
+                     const int64_t* dk_str, void* dv, const int64_t* dv_str, int64_t B, int64_t H, int64_t HKV, int64_t S,
+                     float scale, hipStream_t stream);
+
 /* ---- measurement variants ------------------------------------------------------------------
  * Not a reference interface: selects between kernel forms with identical results, for A/B runs and
  * the bit-identity tests.  The library reads no environment; the host sets these (picotron_amd/

@@ -153,6 +153,9 @@ SIGNATURES = {
                                _vp]),
     "pt_mla_rope": (_i32, [_vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp]),
     "pt_mla_dkpe_reduce": (_i32, [_vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp]),
+    "pt_attn_d256_fwd": (_i32, [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _i64, _i64, _i64, _f32, _vp]),
+    "pt_attn_d256_bwd": (_i32, [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _i64p, _vp,
+                                _i64p, _vp, _i64p, _i64, _i64, _i64, _i64, _f32, _vp]),
     "pt_lse_merge": (_i32, [_vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp]),
     "pt_gemm_ce_stats": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp]),
     "pt_cross_entropy_fwd_stats": (_i32, [_vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp]),

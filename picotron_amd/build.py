@@ -43,6 +43,7 @@ def sources():
 # pass notes that it does not know it).
 FILE_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               "attention_mla.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],   # the same scheme, the same reason
+              "attention_d256.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"],
               "moe.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 

@@ -804,6 +804,9 @@ class AttnShape:
             if ring_enabled() != isinstance(band, CPBand):
                 raise NotImplementedError("document masking / sliding-window attention under context parallelism "
                                           "takes a CPBand (context_parallel.make_cp_band), and a CPBand only there")
+            if d == ATTN_D256:
+                raise NotImplementedError("document masking / sliding-window attention with head_dim 256: the "
+                                          "head dim 256 kernels are plain causal")
 
     def q(self, t):
         return t[:, :self.wq].view(self.B, self.S, self.nh, self.d)
@@ -841,6 +844,9 @@ def make_band(B, S, device, document_ids=None, window=None):
 # rotary half separately -- [x1 | 0 | x2 | 0] -- so that RoPE's (d, d + d/2) pairs stay pairs and the
 # padded columns add nothing to q . k or to o (the scale stays 1/sqrt(d) of the real d).
 ATTN_HEAD_DIMS = (64, 128)
+# head dim 256 has attention kernels of its own (kernels.ATTN_D256): the kernel-width path, plain causal
+# only -- no padding up to it, no QK-norm, sinks, band or ring (those go by ATTN_HEAD_DIMS)
+ATTN_D256 = K.ATTN_D256
 
 
 def _head_pad_dim(d):
@@ -896,7 +902,18 @@ def _attention_core_bwd_padded(do, qkv, o, lse, sh, cos, sin, scale):
 
 def _req_head_dim(d, roped):
     if _head_pad_dim(d) is None or d % 2 or roped:
-        raise RuntimeError(f"attention: head_dim {d} -- the kernels take 64 / 128 and pad even dims below 128")
+        raise RuntimeError(f"attention: head_dim {d} -- the kernels take 64 / 128 / 256 and pad even dims below 128")
+
+
+def _req_d256(sh):
+    """Refuse, before any launch, what the head dim 256 kernels do not do (QK-norm and sinks refuse
+    themselves: QKNorm.require, require_sinks)."""
+    if ring_enabled():
+        raise NotImplementedError("attention with head_dim 256 under context parallelism: the ring merges blocks, "
+                                  "and the head dim 256 kernels have no merge form")
+    if sh.band is not None:
+        raise NotImplementedError("document masking / sliding-window attention with head_dim 256: the head dim "
+                                  "256 kernels are plain causal")
 
 
 class QKNorm:
@@ -962,7 +979,9 @@ def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None, sinks=No
         qk, rstd = K.qk_norm_rope_fwd(qkv, sh.nh, sh.nkv, sh.d, qkn.wq, qkn.wk, qkn.eps, qkn.mode, cos, sin, sh.S)
         o, lse = K.attn_fwd(sh.q(qk), sh.k(qk), sh.v(qkv), scale, True, band=sh.band, sinks=sinks)
         return o, lse, qk, rstd
-    if sh.d not in ATTN_HEAD_DIMS and not ring_enabled():
+    if sh.d == ATTN_D256:
+        _req_d256(sh)
+    elif sh.d not in ATTN_HEAD_DIMS and not ring_enabled():
         _req_head_dim(sh.d, roped)
         return _attention_core_fwd_padded(qkv, sh, cos, sin, scale)
     if not roped:
@@ -997,7 +1016,7 @@ def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=No
             if part is not None:
                 norm_dw_from_partial(part, w)
         return dqkv
-    if sh.d not in ATTN_HEAD_DIMS and not ring_enabled():
+    if sh.d not in ATTN_HEAD_DIMS + (ATTN_D256,) and not ring_enabled():
         return _attention_core_bwd_padded(do, qkv, o, lse, sh, cos, sin, scale)
     dqkv = torch.empty_like(qkv)
     if ring_enabled():

@@ -2785,6 +2785,32 @@ def _sinks_for(sinks, H, device, what):
     _req(sinks.data_ptr() % 4 == 0, f"{what}: sinks must be 4-byte aligned (the kernels read them as dwords)")
 
 
+# Head dim 256 (csrc/attention_d256.hip, pt_attn_d256_fwd / _bwd): kernels of their own behind attn_fwd /
+# attn_bwd, plain causal self-attention only.
+ATTN_D256 = 256
+
+
+def _d256_only(causal_self, merge, band, sinks, what):
+    """Refuse, before any launch, what the head dim 256 kernels do not do."""
+    _req(causal_self, f"{what}: head dim 256 takes causal attention with Sq == Sk (no non-causal kernel)")
+    if merge:
+        raise NotImplementedError(f"{what}: head dim 256 has no merge form (context-parallel blocks)")
+    if band is not None:
+        raise NotImplementedError(f"{what}: head dim 256 has no band kernels (document masking, sliding windows, "
+                                  "context-parallel blocks)")
+    if sinks is not None:
+        raise NotImplementedError(f"{what}: head dim 256 has no sink kernels")
+
+
+def _rows2d(t, what):
+    """A [B, S, heads, d] view whose heads are packed and whose token rows are evenly spaced, as its
+    [B * S, heads * d] rows (rope_'s argument)."""
+    B, S, nh, d = t.shape
+    _req(t.stride(3) == 1 and (nh == 1 or t.stride(2) == d) and (B == 1 or t.stride(0) == S * t.stride(1)),
+         f"{what}: packed heads and evenly spaced token rows expected")
+    return t.as_strided((B * S, nh * d), (t.stride(1), 1))
+
+
 def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None, sinks=None):
     """q [B,Sq,H,D], k/v [B,Sk,Hkv,D] (token-major views).  Returns (out, lse[B,H,Sq] f32).
     merge=True: `out` is an f32 accumulator and `lse` the running LSE; this block is merged in.
@@ -2796,9 +2822,13 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None,
     sinks (bf16 [H], one learned logit per query head): every row's softmax gets one more column with
     that score and a zero value vector, and lse includes it (attention.hip, "Sinks"); causal, with an
     AttnBand or without, dense lse; the few-head split forms are not taken.  The backward is attn_bwd
-    on this lse, unchanged, plus attn_sink_bwd for the sinks' own gradient."""
+    on this lse, unchanged, plus attn_sink_bwd for the sinks' own gradient.
+    D = 256: causal with Sq == Sk and a dense lse only; merge, a band of either kind and sinks raise."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if D == ATTN_D256:
+        _d256_only(causal and Sq == Sk, merge, band, sinks, "attn_fwd")
+        _req(lse is None or _lse_ld(lse, B, H, Sq) == Sq, "attn_fwd: head dim 256 takes a dense lse")
     if sinks is not None:
         if merge or isinstance(band, AttnBlockBand):
             raise NotImplementedError("attn_fwd: sinks with merge=True or an AttnBlockBand (context-parallel blocks): "
@@ -2866,6 +2896,11 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None,
         out = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device)
     if lse is None:
         lse = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+    if D == ATTN_D256:
+        rc = _C.lib().pt_attn_d256_fwd(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                       _ptr(lse), B, H, HKV, Sq, float(scale), _C.stream_ptr(q.device))
+        _C.check(rc, "pt_attn_d256_fwd")
+        return out, lse
     if sinks is not None:   # always the regular launch (each split work item would take the sink again)
         rc = _C.lib().pt_attn_fwd_sink(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
                                        _ptr(lse), _ptr(sinks), B, H, HKV, Sq, Sk, D, float(scale),
@@ -2968,9 +3003,17 @@ def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, 
     band (an AttnBand): the backward of attn_fwd(band=); bf16 gradients, dense lse, D = rowsum(dO * O)
     always formed inside the dQ kernel (no `delta` argument).
     band (an AttnBlockBand): one block of a context-parallel schedule; bf16 stores or f32 accumulation,
-    a given (or separately formed) delta, a strided lse; no fused RoPE inverse."""
+    a given (or separately formed) delta, a strided lse; no fused RoPE inverse.
+    D = 256: bf16 gradients, delta formed in the dQ kernel and returned; grad_f32, a given delta and a
+    band raise; rope is honoured by rope_(inverse=True) on dq / dk after the kernels."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if D == ATTN_D256:
+        _d256_only(causal and Sq == Sk, False, band, None, "attn_bwd")
+        if grad_f32 or delta is not None:
+            raise NotImplementedError("attn_bwd: head dim 256 stores bf16 gradients and forms delta itself "
+                                      "(no grad_f32, no given delta)")
+        _req(_lse_ld(lse, B, H, Sq) == Sq, "attn_bwd: head dim 256 takes a dense lse")
     if isinstance(band, AttnBlockBand):
         _req(rope is None, "attn_bwd: a block band has no fused RoPE inverse")
         if delta is None:
@@ -3009,6 +3052,22 @@ def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, 
                 res.append(given)
         return res[0], res[1], res[2], dlt[:, :, :Sq]
     lib = _C.lib()
+    if D == ATTN_D256:
+        _req(out.shape == q.shape and out.dtype == BF16, "attn_bwd: out must be bf16 [B, Sq, H, D]")
+        dq = torch.empty(B, Sq, H, D, dtype=BF16, device=q.device) if dq is None else dq
+        dk = torch.empty(B, Sk, HKV, D, dtype=BF16, device=q.device) if dk is None else dk
+        dv = torch.empty(B, Sk, HKV, D, dtype=BF16, device=q.device) if dv is None else dv
+        _req(dq.dtype == BF16 and dk.dtype == BF16 and dv.dtype == BF16, "attn_bwd: head dim 256 gradients are bf16")
+        rows = None if rope is None else (_rows2d(dq, "attn_bwd dq"), _rows2d(dk, "attn_bwd dk"))
+        delta = torch.empty(B, H, Sq, dtype=torch.float32, device=q.device)
+        rc = lib.pt_attn_d256_bwd(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                  _ptr(dout), _str3(dout), _ptr(lse), _ptr(delta), _ptr(dq), _str3(dq), _ptr(dk),
+                                  _str3(dk), _ptr(dv), _str3(dv), B, H, HKV, Sq, float(scale), _C.stream_ptr(q.device))
+        _C.check(rc, "pt_attn_d256_bwd")
+        if rope is not None:   # the inverse rotation as its own pass (the fused store is not part of these kernels)
+            rope_(rows[0], H, D, rope[0], rope[1], Sq, inverse=True)
+            rope_(rows[1], HKV, D, rope[0], rope[1], Sq, inverse=True)
+        return dq, dk, dv, delta
     fuse_delta = delta is None and not grad_f32 and out.dtype == BF16 and SW.fuse_delta != 0
     if delta is None and not fuse_delta:
         ld0 = _lse_ld(lse, B, H, Sq)

@@ -85,9 +85,9 @@ class _FlashAttention(torch.autograd.Function):
         # padded columns add nothing to q . k and are sliced off o; the scale is the real D's)
         D = q.shape[-1]
         scale = 1.0 / math.sqrt(D)
-        dp = FN._head_pad_dim(D) if D not in FN.ATTN_HEAD_DIMS else D
+        dp = FN._head_pad_dim(D) if D not in FN.ATTN_HEAD_DIMS + (FN.ATTN_D256,) else D   # 256: kernels of its own
         if dp is None:
-            raise RuntimeError(f"flash_attention: head_dim {D} -- the kernels take 64 / 128 and pad dims below 128")
+            raise RuntimeError(f"flash_attention: head_dim {D} -- the kernels take 64 / 128 / 256 and pad dims below 128")
         qp, kp, vp = (_pad_d(t, dp) for t in (q, k, v))
         o, lse = K.attn_fwd(qp, kp, vp, scale, causal)
         ctx.save_for_backward(qp, kp, vp, o, lse)
@@ -254,6 +254,13 @@ class Attention(nn.Module):
         lt = layer_types(config)
         if lt is not None and lt[layer_idx] == "full_attention":
             self.sliding_window = None
+        if self.head_dim == FN.ATTN_D256:   # kernels of their own (csrc/attention_d256.hip): plain causal
+            if self.sliding_window is not None:
+                raise NotImplementedError("sliding_window with head_dim 256: the head dim 256 attention kernels "
+                                          "are plain causal")
+            if m.cp_world_size > 1:
+                raise NotImplementedError("context parallelism (cp > 1) with head_dim 256: the ring merges blocks, "
+                                          "and the head dim 256 attention kernels have no merge form")
         self.attention_sinks = bool(getattr(config, "attention_sinks", False))
         if self.attention_sinks:
             if m.tp_world_size > 1:
@@ -317,6 +324,9 @@ class Attention(nn.Module):
         sliding_window -- or an AttnBand built once by the caller, taken as it is.  Under context
         parallelism (cp > 1) a context_parallel.CPBand: x is this rank's chunk and document_ids its
         [B, S_local] chunk (all-gathered over the cp group) or the full rows."""
+        if self.head_dim == FN.ATTN_D256 and document_ids is not None:   # (before the band's own kernels)
+            raise NotImplementedError("document_ids with head_dim 256: the head dim 256 attention kernels are "
+                                      "plain causal")
         if FN.ring_enabled() and not isinstance(document_ids, K.AttnBand):   # (an AttnBand there: AttnShape refuses)
             return context_parallel.make_cp_band(x.shape[0], x.shape[1], x.device, document_ids, self.sliding_window)
         return FN.make_band(x.shape[0], x.shape[1], x.device, document_ids, self.sliding_window)
@@ -689,6 +699,10 @@ class Llama(nn.Module):
         rows; one context_parallel.CPBand is built and handed to every layer.
         With config.layer_types the window belongs to the "sliding_attention" layers only: at most two
         bands per forward, one per window a layer has (its own sliding_window, or none)."""
+        if document_ids is not None and self.head_dim == FN.ATTN_D256 and \
+                not isinstance(self.decoder_layers[0].attention, MLAttention):
+            raise NotImplementedError("document_ids with head_dim 256: the head dim 256 attention kernels are "
+                                      "plain causal")
         x = self.embedding(input_ids)
         bands = {}
 
