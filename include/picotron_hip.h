@@ -767,6 +767,33 @@ int pt_attn_fwd_band_sink(const void* q, const int64_t* q_str, const void* k, co
 int pt_attn_sink_bwd_partials(int64_t B, int64_t H, int64_t Sq);
 int pt_attn_sink_bwd(const float* lse, const float* delta, const void* sinks, void* dsinks, float* ws, int64_t B,
                      int64_t H, int64_t Sq, int64_t lse_ld, int64_t delta_ld, int sink_mode, hipStream_t stream);
+/* Logit soft-capping (Gemma-2's attn_logit_softcapping, Grok-1; flash-attn's softcap): the softmax runs
+ * over t = c tanh(q . k scale / c), c = softcap, so every logit lies in (-c, c).  Masked positions
+ * (causal, band) have probability exactly 0: the cap is applied before the masks.  lse is that of the
+ * capped scores, and the backward carries the factor (1 - tanh^2) on dS:
+ *   P = exp(t - lse), dT = P (dP - D), dS = dT (1 - tanh^2), dQ = scale dS K, dK = scale dS^T Q, dV = P^T dO.
+ * pt_attn_fwd_softcap = pt_attn_fwd (causal = 1, merge = 0, dense lse) when kv_lo and q_hi are both
+ * NULL, pt_attn_fwd_band when both are given; pt_attn_bwd_softcap = pt_attn_bwd_fused_delta /
+ * pt_attn_bwd_band likewise (bf16 gradients, dense lse, D = rowsum(dO * O) formed in the dQ kernel and
+ * left in delta_out, the optional RoPE inverse on dq / dk).  Checked before any launch, in this order:
+ * a NULL q / k / v / o / lse (backward: o, o_str, delta_out) PT_EINVAL; softcap not finite or <= 0
+ * PT_EINVAL; exactly one of kv_lo / q_hi NULL PT_EINVAL; Sq != Sk PT_EUNSUPPORTED; (backward) o off 16
+ * bytes or its strides off 8 elements PT_EALIGN, then pt_attn_bwd's own pointer and RoPE checks
+ * PT_EINVAL; D not in {64, 128} PT_EUNSUPPORTED; B, H, HKV PT_EINVAL; S % 128 != 0 PT_EUNSUPPORTED.  A
+ * refused call launches nothing.  Always the regular launches: the few-head split forms are not used,
+ * and dK/dV runs in one form per head dim (the block form at d64, the wave pairs at d128) whatever
+ * "attn_split" says.  No atomics: equal inputs give equal bits. */
+int pt_attn_fwd_softcap(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                        const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H,
+                        int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, float softcap,
+                        const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream);
+int pt_attn_bwd_softcap(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                        const int64_t* v_str, const void* o, const int64_t* o_str, const void* dout,
+                        const int64_t* do_str, const float* lse, float* delta_out, void* dq, const int64_t* dq_str,
+                        void* dk, const int64_t* dk_str, void* dv, const int64_t* dv_str, int64_t B, int64_t H,
+                        int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, float softcap,
+                        const void* rope_cos, const void* rope_sin, int64_t rope_stride, const int32_t* kv_lo,
+                        const int32_t* q_hi, hipStream_t stream);
 /* Block bands: the band of one block of a context-parallel schedule (a rank's queries against one
  * owner's keys), where the block is rectangular and usually not causal.  Key j of the block is
  * visible to query i of batch row b iff kv_lo[b, i] <= j, and also j <= i when causal = 1 (the

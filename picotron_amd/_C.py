@@ -139,6 +139,11 @@ SIGNATURES = {
                                 _i64, _f32, _vp]),
     "pt_attn_fwd_band_sink": (_i32, [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _i64, _i64, _i64, _i64,
                                      _i64, _i64, _f32, _vp, _vp, _vp]),
+    "pt_attn_fwd_softcap": (_i32, [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _i64, _i64, _i64, _i64,
+                                   _i64, _f32, _f32, _vp, _vp, _vp]),
+    "pt_attn_bwd_softcap": (_i32, [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _vp, _vp, _i64p,
+                                   _vp, _i64p, _vp, _i64p, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _vp, _vp,
+                                   _i64, _vp, _vp, _vp]),
     "pt_attn_sink_bwd_partials": (_i32, [_i64, _i64, _i64]),
     "pt_attn_sink_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _vp]),
     "pt_attn_fwd_block_band": (_i32, [_vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64p, _vp, _i64, _i64, _i64, _i64,

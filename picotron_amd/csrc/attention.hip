@@ -42,6 +42,26 @@
 // unchanged.  dsinks[h] = -sum_{b, i} exp(sinks[h] - lse[b, h, i]) delta[b, h, i] is formed from the
 // lse and the delta workspace the backward leaves (pt_attn_sink_bwd), in two stages without atomics.
 // Causal, merge = 0, dense lse; never the few-head split forms (the sink would enter once per item).
+// Soft-capping (pt_attn_fwd_softcap / pt_attn_bwd_softcap; the CAP instantiations of the forward, dQ and
+// dK/dV bodies; Gemma-2's attn_logit_softcapping, flash-attn's softcap): the softmax runs over
+// t = c tanh(s scale / c), c = softcap > 0.  With y = s scale / c, u = tanh(y):
+//   forward   e = exp2(s k1), k1 = 2 scale log2(e) / c;  u = 1 - 2 rcp(1 + e);  s' = u (c log2(e));
+//             then masks, row max, lazy rescale, exp2(s' - m), packed sums as without a cap (c2 = 1).  The
+//             cap comes BEFORE the masks: tanh(-inf) = -1 would hand a masked score back as -c.  The
+//             running max stays the rows' own: at c = 50 a row whose scores all sit near -c would
+//             underflow f32 against the constant bound c.
+//   backward  u recomputed by the same function (cap_u2), P = exp2(u (c log2(e)) - lse log2(e)),
+//             dS = P (dP - D) (1 - u^2) before its rounding to bf16; dQ = scale dS K, dK = scale dS^T Q,
+//             dV = P^T dO as ever.  A masked position holds a finite u far below -1 (masked_score).
+// Issue mix per 64-key tile and wave (32 queries: 32 score registers per lane): the forward's 32 v_exp
+// become 64 v_exp + 32 v_rcp -- three times the quarter-rate transcendentals -- plus 64 packed VALU
+// instructions (16 each of v_pk_mul, v_pk_add, v_pk_fma, v_pk_mul) beside the 16 MFMAs at d64 (32 at
+// d128), which are unchanged; the backward kernels gain the same stage plus one fma and one multiply per
+// score for (1 - u^2).  Causal or band (kv_lo / q_hi both NULL or both given), Sq == Sk on the 128-row
+// blocks, D 64 / 128, merge = 0, dense lse, bf16 gradients, the delta fused in the dQ kernel, the
+// optional RoPE inverse; never the few-head split forms, block bands or sinks.  dK/dV has one form
+// per head dim, the one the attn_split variant's default selects (block form at d64, wave pairs at
+// d128); the variant does not steer the soft-capped entry.  No atomics: equal inputs, equal bits.
 //
 // Fragment scheme (all v_mfma_f32_32x32x16_bf16): scores are computed "key on the row",
 // S^T = K . Q^T, so a lane owns one query column and softmax statistics are lane-local (plus one
@@ -54,6 +74,7 @@
 // K/V (fwd, dq) and Q/dO (dkdv) tiles arrive by global_load_lds_dwordx4 into a 2-deep ring.
 #include "common.h"
 
+#include <float.h>
 #include <stdlib.h>
 
 #include <type_traits>
@@ -414,13 +435,50 @@ __device__ __forceinline__ float mul_then_add(float a, float b, float c) {
   return a * b + c;
 }
 
+// CAP (the soft-capped kernels, see the header): the two constants of the capping stage, formed once
+// on the host so the forward and both backward kernels use the same bits.  They are the cap kernels'
+// own second argument: AttnArgs, and with it the code of every other kernel, stays as it was.
+struct CapArgs {
+  float k1;   // 2 scale log2(e) / c: e = exp2(s k1) = exp(2 y), y = s scale / c
+  float cl;   // c log2(e): the capped score in log2 units is u cl
+};
+// u = tanh(y) = 1 - 2 / (1 + e) for a pair of raw scores: one v_pk_mul, two v_exp, one v_pk_add, two
+// v_rcp, one v_pk_fma.  e = +inf gives u = 1, e = 0 gives u = -1; u lies in [-1, 1] for every
+// finite score.  The forward and the backward kernels call this one function, so the backward's P is
+// formed from the u the stored lse was summed from.
+__device__ __forceinline__ f32x2_t cap_u2(f32x2_t s, float k1) {
+  const f32x2_t y = s * (f32x2_t){k1, k1};
+  const f32x2_t e = {__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)};
+  const f32x2_t d = e + (f32x2_t){1.f, 1.f};
+  const f32x2_t r = {__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
+  return __builtin_elementwise_fma(r, (f32x2_t){-2.f, -2.f}, (f32x2_t){1.f, 1.f});
+}
+// the backward kernels' CAP stage on one 32x32 score tile: s <- u, in place
+__device__ __forceinline__ void cap_tile(f32x16_t& s, float k1) {
+#pragma unroll
+  for (int r = 0; r < 16; r += 2) {
+    const f32x2_t u = cap_u2((f32x2_t){s[r], s[r + 1]}, k1);
+    s[r] = u.x;
+    s[r + 1] = u.y;
+  }
+}
+// what a masked position holds in the backward kernels.  Plain: -inf, P = exp2(-inf) = 0.  CAP: the
+// registers hold u, and dS = P (dP - D) (1 - u^2) with u = -inf would be 0 * inf; a finite value far
+// below -1 gives P = exp2(u cl - lse) = 0 all the same and keeps 1 - u^2 finite (1e36), so dS = 0.
+template <bool CAP>
+constexpr float masked_score() { return CAP ? -1e18f : -INFINITY; }
+
 // SINK (causal, merge = 0, no split items): the row's softmax has one more column, the head's sink
 // logit with a zero value vector, as the initial state of the online softmax (see the header).  sinks
 // (bf16 [H]) is the sink kernels' own second argument: AttnArgs, and with it the code of every other
 // kernel, stays as it was.
-template <int D, int NWK, bool BAND = false, bool SINK = false>
+// CAP (causal or band, merge = 0, no split items): one stage between the score MFMAs and the masks turns
+// every raw score s into u cl, u = tanh(s scale / c) (cap_u2); from there the tile runs as it does
+// without a cap, on scores already in log2 units (c2 = 1).
+template <int D, int NWK, bool BAND = false, bool SINK = false, bool CAP = false>
 __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_or_hk, int b, int kt_lo = 0,
-                                               int kt_hi = -1, int item = -1, const uint16_t* sinks = nullptr) {
+                                               int kt_hi = -1, int item = -1, const uint16_t* sinks = nullptr,
+                                               CapArgs cap = {}) {
   constexpr int DT = D / 32, KS = D / 16;
   constexpr int TILE_B = KT * D * 2;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
@@ -457,7 +515,7 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
   const int kv_end = a.causal ? (qb + 1) * NWK * 32 : a.Sk;
   // this call's K/V tiles: all of the block's, or a split work item's [kt_lo, kt_hi)
   const int kt0 = kt_lo, nkt = (kt_hi < 0 ? kv_end / KT : kt_hi) - kt_lo;
-  const float c2 = a.scale * kLog2e;
+  const float c2 = CAP ? 1.f : a.scale * kLog2e;
 
   f32x16_t o[DT];
 #pragma unroll
@@ -547,6 +605,18 @@ __device__ __forceinline__ void attn_fwd_block(const AttnArgs& a, int bx, int h_
         s[kh] = zero16();
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) s[kh] = mfma(ka[kh][ks], qf[ks], s[kh]);
+      }
+      // soft cap, before the masks: tanh(-inf) = -1 would bring a masked score back as -c
+      if constexpr (CAP) {
+        const f32x2_t cl2 = {cap.cl, cap.cl};
+#pragma unroll
+        for (int kh = 0; kh < 2; ++kh)
+#pragma unroll
+          for (int r = 0; r < 16; r += 2) {
+            const f32x2_t t = cap_u2((f32x2_t){s[kh][r], s[kh][r + 1]}, cap.k1) * cl2;
+            s[kh][r] = t.x;
+            s[kh][r + 1] = t.y;
+          }
       }
       // causal mask, diagonal tiles only: key row 32 kh + crow(r) visible iff <= thr
       if (decltype(dg)::value == 1 || (decltype(dg)::value == 3 && a.causal && kv0 + KT - 1 > q0)) {
@@ -724,6 +794,18 @@ __global__ __launch_bounds__(NWK * 64) void attn_fwd_band_kernel(AttnArgs a) {
   for (int pass = 0; pass <= a.pair; ++pass) {
     if (pass) __syncthreads();
     attn_fwd_block<D, NWK, true>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b);
+  }
+}
+
+// the soft-capped forms of the two kernels above (separate kernels: those compile to what they did)
+template <int D, int NWK, bool BAND>
+__global__ __launch_bounds__(NWK * 64) void attn_fwd_cap_kernel(AttnArgs a, CapArgs cap) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_fwd_block<D, NWK, BAND, false, true>(a, pass ? a.Sq / (NWK * 32) - 1 - bx : bx, hh, b, 0, -1, -1, nullptr,
+                                              cap);
   }
 }
 
@@ -936,9 +1018,11 @@ __global__ __launch_bounds__(64) void attn_sink_bwd_reduce_kernel(const float* _
 // block's last key (the block maximum: q_hi is non-decreasing; at least one tile, so a block no query
 // sees still has a step to run); every step runs the edge form, which skips half tiles wholly past
 // the wave's greatest q_hi and masks queries at or past a lane's own q_hi.
-template <int D, bool BAND = false>
+// CAP (no split items): S <- u = tanh(S scale / c) before the masks (cap_tile), P = exp2(u cl - lse log2e),
+// dS = P (dP - D) (1 - u^2)
+template <int D, bool BAND = false, bool CAP = false>
 __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, int h_or_hk, int b, int it_lo = 0,
-                                                    int it_hi = -1, int item = -1) {
+                                                    int it_hi = -1, int item = -1, CapArgs cap = {}) {
   constexpr int DT = D / 32, KS = D / 16;
   constexpr int TILE_B = KT * D * 2;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
@@ -960,7 +1044,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
   f32x16_t dk[DT], dv[DT];
 #pragma unroll
   for (int i = 0; i < DT; ++i) { dk[i] = zero16(); dv[i] = zero16(); }
-  const float c2 = a.scale * kLog2e;
+  const float c2 = CAP ? cap.cl : a.scale * kLog2e;
 
   // q tiles: causal -> only those that can see this block's keys
   const int qt_begin = a.causal ? (kb * NW * 32) / KT : 0;
@@ -1019,18 +1103,19 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
         s = mfma(rd_row<D>(sq, 32 * qh, ks, lane), kf[ks], s);
         dp = mfma(rd_row<D>(sdo, 32 * qh, ks, lane), vf[ks], dp);
       }
+      if constexpr (CAP) cap_tile(s, cap.k1);
       if (decltype(edge)::value && a.causal && (qs < k0 + 31)) {  // diagonal: query row crow(r) sees my key iff >= thr
         const int thr = mykey - qs - 4 * (lane >> 5);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if ((r & 3) + 8 * (r >> 2) < thr) s[r] = -INFINITY;
+          if ((r & 3) + 8 * (r >> 2) < thr) s[r] = masked_score<CAP>();
       }
       if constexpr (BAND) {
         if (qs + 31 >= whi_min) {  // upper edge: query row crow(r) sees my key iff < thr_hi
           const int thr_hi = myhi - qs - 4 * (lane >> 5);
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if ((r & 3) + 8 * (r >> 2) >= thr_hi) s[r] = -INFINITY;
+            if ((r & 3) + 8 * (r >> 2) >= thr_hi) s[r] = masked_score<CAP>();
         }
       }
       // P = exp2(S c2 - lse log2e), dS = P (dP - D): packed pairs of rows (v_pk_fma / v_pk_add / v_pk_mul)
@@ -1041,7 +1126,11 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
         f32x2_t x = {s[r], s[r + 1]};
         x = __builtin_elementwise_fma(x, c22, (f32x2_t){-sl2[qi], -sl2[qj]});
         const f32x2_t pp = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
-        const f32x2_t ds = pp * ((f32x2_t){dp[r], dp[r + 1]} - (f32x2_t){sdel[qi], sdel[qj]});
+        f32x2_t ds = pp * ((f32x2_t){dp[r], dp[r + 1]} - (f32x2_t){sdel[qi], sdel[qj]});
+        if constexpr (CAP) {   // (1 - u^2), before dS is rounded to bf16
+          const f32x2_t u = {s[r], s[r + 1]};
+          ds *= __builtin_elementwise_fma(-u, u, (f32x2_t){1.f, 1.f});
+        }
         s[r] = pp.x;                          // P
         s[r + 1] = pp.y;
         dp[r] = ds.x;                         // dS
@@ -1100,6 +1189,18 @@ __device__ __forceinline__ void attn_bwd_dkdv_block(const AttnArgs& a, int bx, i
   store_dkdv<DT>(a, b, mykey, hk, dk, dv, lane);
 }
 
+// the soft-capped dK/dV kernel at d64 (this block form, whatever the attn_split variant says)
+template <bool BAND>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(2)))
+void attn_bwd_dkdv_cap_kernel(AttnArgs a, CapArgs cap) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_bwd_dkdv_block<64, BAND, true>(a, pass ? a.Sk / (NW * 32) - 1 - bx : bx, hh, b, 0, -1, -1, cap);
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(D == 64 ? 2 : 1)))
 void attn_bwd_dkdv_split_kernel(AttnArgs a) {
@@ -1152,8 +1253,10 @@ constexpr int kXchB = 4 * 2 * 2 * 1024;  // one step's P|dS hand-off: 4 pairs x 
 // BAND: as attn_bwd_dkdv_block's -- the q tiles end at the tile of q_hi of the block's last key, both
 // waves of a pair skip the half tiles wholly past the q_hi of the pair's last key (each reads that
 // bound itself: the skip must agree), and the score wave masks queries at or past a lane's own q_hi.
-template <int D, bool BAND = false>
-__device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int bx, int hk, int b) {
+// CAP: the score wave's softmax gains the capping stage (as attn_bwd_dkdv_block's); the accumulator wave
+// is unchanged.
+template <int D, bool BAND = false, bool CAP = false>
+__device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int bx, int hk, int b, CapArgs cap = {}) {
   constexpr int DT = D / 32, KS = D / 16;
   constexpr int TILE_B = KT * D * 2;
   constexpr int STAGE_B = 2 * TILE_B + 2 * KT * 4;  // Q tile, dO tile, lse [64], delta [64]
@@ -1169,7 +1272,7 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
   const int k0 = bx * 128 + pr * 32;
   const int mykey = k0 + (lane & 31);
   const int group = a.H / a.HKV;
-  const float c2 = a.scale * kLog2e;
+  const float c2 = CAP ? cap.cl : a.scale * kLog2e;
 
   const int qt_begin = a.causal ? (bx * 128) / KT : 0;
   int nqt = a.Sq / KT;
@@ -1269,25 +1372,27 @@ __device__ __forceinline__ void attn_bwd_dkdv_pair_block(const AttnArgs& a, int 
           lr[r] = sl[qi];
           dr[r] = sdel[qi];
         }
+        if constexpr (CAP) cap_tile(s, cap.k1);
         if (a.causal && (qs < k0 + 31)) {  // diagonal: query row crow(r) sees my key iff >= thr
           const int thr = mykey - qs - 4 * (lane >> 5);
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if ((r & 3) + 8 * (r >> 2) < thr) s[r] = -INFINITY;
+            if ((r & 3) + 8 * (r >> 2) < thr) s[r] = masked_score<CAP>();
         }
         if constexpr (BAND) {
           if (qs + 31 >= whi_min) {  // upper edge: query row crow(r) sees my key iff < thr_hi
             const int thr_hi = a.q_hi[(int64_t)b * a.Sk + mykey] - qs - 4 * (lane >> 5);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-              if ((r & 3) + 8 * (r >> 2) >= thr_hi) s[r] = -INFINITY;
+              if ((r & 3) + 8 * (r >> 2) >= thr_hi) s[r] = masked_score<CAP>();
           }
         }
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = __builtin_amdgcn_exp2f(fmaf(s[r], c2, -(lr[r] * kLog2e)));
+          if constexpr (CAP) dp[r] = p * (dp[r] - dr[r]) * __builtin_fmaf(-s[r], s[r], 1.f);   // (1 - u^2)
+          else dp[r] = p * (dp[r] - dr[r]);
           s[r] = p;
-          dp[r] = p * (dp[r] - dr[r]);
         }
         lds_u8* x = xch + (j & 1) * kXchB + pr * 4096 + lane * 16;
 #pragma unroll
@@ -1359,6 +1464,17 @@ __global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_kernel(AttnArgs a) 
   }
 }
 
+// the soft-capped dK/dV kernel at d128 (this wave-pair form, whatever the attn_split variant says)
+template <bool BAND>
+__global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_cap_kernel(AttnArgs a, CapArgs cap) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_bwd_dkdv_pair_block<128, BAND, true>(a, pass ? a.Sk / 128 - 1 - bx : bx, hh, b, cap);
+  }
+}
+
 template <int D>
 __global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_band_kernel(AttnArgs a) {
   int bx, hh, b;
@@ -1371,9 +1487,10 @@ __global__ __launch_bounds__(8 * 64) void attn_bwd_dkdv_pair_band_kernel(AttnArg
 
 // ============================================================================ dQ
 // BAND: the forward's tile range, skip and lower-edge mask (attn_fwd_block)
-template <int D, bool BAND = false>
+// CAP (no split items): as attn_bwd_dkdv_block's
+template <int D, bool BAND = false, bool CAP = false>
 __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int h_or_hk, int b, int kt_lo = 0,
-                                                  int kt_hi = -1, int item = -1) {
+                                                  int kt_hi = -1, int item = -1, CapArgs cap = {}) {
   constexpr int DT = D / 32, KS = D / 16;
   constexpr int TILE_B = KT * D * 2;
   extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
@@ -1416,7 +1533,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
   } else {
     del = a.delta[ri];
   }
-  const float c2 = a.scale * kLog2e;
+  const float c2 = CAP ? cap.cl : a.scale * kLog2e;
 
   const uint16_t* kbase = a.k.row(b, 0, hk);
   const uint16_t* vbase = a.v.row(b, 0, hk);
@@ -1467,12 +1584,13 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
         s = mfma(rd_row<D>(sk, 32 * kh, ks, lane), qf[ks], s);
         dp = mfma(rd_row<D>(sv, 32 * kh, ks, lane), dof[ks], dp);
       }
+      if constexpr (CAP) cap_tile(s, cap.k1);
       if (decltype(dg)::value == 1 || (decltype(dg)::value == 3 && a.causal && kv0 + KT - 1 > q0)) {
         // key row 32 kh + crow(r) visible iff <= thr
         const int thr = myq - kv0 - 32 * kh - 4 * (lane >> 5);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-          if ((r & 3) + 8 * (r >> 2) > thr) s[r] = -INFINITY;
+          if ((r & 3) + 8 * (r >> 2) > thr) s[r] = masked_score<CAP>();
       }
       if constexpr (BAND) {
         if (kv0 + 32 * kh < wlo_max) {  // wave-uniform: some row's bound lies past the half's first key
@@ -1487,7 +1605,7 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
           const int thr_lo = lo - kv0 - 32 * kh - 4 * (lane >> 5);   // key row visible iff >= thr_lo
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if ((r & 3) + 8 * (r >> 2) < thr_lo) s[r] = -INFINITY;
+            if ((r & 3) + 8 * (r >> 2) < thr_lo) s[r] = masked_score<CAP>();
         }
       }
       // dS = P (dP - D), P = exp2(S c2 - lse log2e): at d64 as packed pairs (v_pk_fma / v_pk_add /
@@ -1500,7 +1618,11 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
           x = __builtin_elementwise_fma(x, c22, nl2);
           const f32x2_t pp = {__builtin_amdgcn_exp2f(x.x), __builtin_amdgcn_exp2f(x.y)};
           const f32x2_t dd = (f32x2_t){dp[r], dp[r + 1]} + nd2;
-          const f32x2_t ds = pp * dd;
+          f32x2_t ds = pp * dd;
+          if constexpr (CAP) {   // (1 - u^2), before dS is rounded to bf16
+            const f32x2_t u = {s[r], s[r + 1]};
+            ds *= __builtin_elementwise_fma(-u, u, (f32x2_t){1.f, 1.f});
+          }
           s[r] = ds.x;
           s[r + 1] = ds.y;
         }
@@ -1508,7 +1630,8 @@ __device__ __forceinline__ void attn_bwd_dq_block(const AttnArgs& a, int bx, int
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const float p = __builtin_amdgcn_exp2f(fmaf(s[r], c2, nlse2));
-          s[r] = p * (dp[r] - del);
+          if constexpr (CAP) s[r] = p * (dp[r] - del) * __builtin_fmaf(-s[r], s[r], 1.f);   // (1 - u^2)
+          else s[r] = p * (dp[r] - del);
         }
       }
 #pragma unroll
@@ -1580,6 +1703,18 @@ void attn_bwd_dq_band_kernel(AttnArgs a) {
   for (int pass = 0; pass <= a.pair; ++pass) {
     if (pass) __syncthreads();
     attn_bwd_dq_block<D, true>(a, pass ? a.Sq / (NW * 32) - 1 - bx : bx, hh, b);
+  }
+}
+
+// the soft-capped dQ kernel
+template <int D, bool BAND>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(D == 128 ? 2 : 1)))
+void attn_bwd_dq_cap_kernel(AttnArgs a, CapArgs cap) {
+  int bx, hh, b;
+  attn_coords(bx, hh, b);
+  for (int pass = 0; pass <= a.pair; ++pass) {
+    if (pass) __syncthreads();
+    attn_bwd_dq_block<D, BAND, true>(a, pass ? a.Sq / (NW * 32) - 1 - bx : bx, hh, b, 0, -1, -1, cap);
   }
 }
 
@@ -1657,6 +1792,17 @@ void launch(void (*kern)(P...), dim3 grid, int block, int smem, hipStream_t stre
   set_smem(kern, smem);
   kern<<<grid, block, smem, stream>>>(a);
 }
+// the soft-capped kernels: the same, with their CapArgs as the second argument
+void launch(void (*kern)(AttnArgs, CapArgs), dim3 grid, int block, int smem, hipStream_t stream, const AttnArgs& a,
+            const CapArgs& cap) {
+  set_smem(kern, smem);
+  kern<<<grid, block, smem, stream>>>(a, cap);
+}
+// softcap as the kernels take it; k1 and cl are rounded here, once, for the forward and the backward
+CapArgs cap_args(float scale, float softcap) {
+  return {(float)(2.0 * scale * (double)kLog2e / softcap), (float)((double)softcap * kLog2e)};
+}
+bool cap_valid(float softcap) { return softcap > 0.f && softcap <= FLT_MAX; }   // finite, positive (NaN fails both)
 // grid of a streaming pass of `total` threads, 256 per block
 unsigned stream_grid(int64_t total) {
   const int64_t g = (total + 255) / 256;
@@ -1711,9 +1857,14 @@ int fill_common(AttnArgs& a, const Problem& p) {
 }
 
 template <int D, int NWK>
-void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream, const uint16_t* sinks) {
+void launch_fwd(const AttnArgs& a, dim3 grid, hipStream_t stream, const uint16_t* sinks, const CapArgs* cap) {
   // (d64: the Q image shares the last ring stage)
   const int smem = fwd_stages<D, NWK>() * 2 * KT * D * 2;
+  if (cap) {   // the soft-capped forms: the same grid, block and LDS
+    launch(a.kv_lo ? attn_fwd_cap_kernel<D, NWK, true> : attn_fwd_cap_kernel<D, NWK, false>, grid, NWK * 64, smem,
+           stream, a, *cap);
+    return;
+  }
   if (sinks) {   // the sink forms: the same grid, block and LDS, the sinks as a second argument
     auto kern = a.kv_lo ? attn_fwd_band_sink_kernel<D, NWK> : attn_fwd_sink_kernel<D, NWK>;
     set_smem(kern, smem);
@@ -1740,6 +1891,7 @@ struct BwdCall {
   int64_t rope_stride;
   int parts;                   // bit 0: dQ, bit 1: dK / dV
   const int32_t* kv_lo; const int32_t* q_hi;   // pt_attn_bwd_band: the band kernels
+  const CapArgs* cap;                          // pt_attn_bwd_softcap: the soft-capped kernels
 };
 
 // dQ first: with delta_w set it produces the D the dK/dV kernel reads (same stream, in order)
@@ -1762,6 +1914,28 @@ int launch_bwd(AttnArgs& a, int parts, dim3 gq, dim3 gk, bool wave_pairs, hipStr
     launch(attn_bwd_dkdv_band_kernel<D>, gk, NW * 64, 2 * stage_q, stream, a);
   } else {
     launch(attn_bwd_dkdv_kernel<D>, gk, NW * 64, 2 * stage_q, stream, a);
+  }
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+// the soft-capped backward: dQ with the fused delta, then dK/dV in the one form its head dim has -- the
+// block form at d64, the wave pairs at d128 (the attn_split variant's defaults; it does not steer these)
+template <int D>
+int launch_bwd_cap(AttnArgs& a, dim3 gq, dim3 gk, const CapArgs& cap, hipStream_t stream) {
+  constexpr int stage_q = 2 * KT * D * 2 + 2 * KT * 4;
+  const bool band = a.kv_lo != nullptr;
+  launch(band ? attn_bwd_dq_cap_kernel<D, true> : attn_bwd_dq_cap_kernel<D, false>, gq, NW * 64,
+         dq_stages<D>() * 2 * KT * D * 2, stream, a, cap);
+  PT_CHECK_LAUNCH();
+  a.delta = a.delta_w;
+  a.delta_w = nullptr;
+  if constexpr (D == 64) {
+    launch(band ? attn_bwd_dkdv_cap_kernel<true> : attn_bwd_dkdv_cap_kernel<false>, gk, NW * 64, 2 * stage_q, stream,
+           a, cap);
+  } else {
+    launch(band ? attn_bwd_dkdv_pair_cap_kernel<true> : attn_bwd_dkdv_pair_cap_kernel<false>, gk, 8 * 64,
+           3 * stage_q + 2 * kXchB, stream, a, cap);
   }
   PT_CHECK_LAUNCH();
   return PT_OK;
@@ -1801,6 +1975,7 @@ int attn_bwd(const BwdCall& c, hipStream_t stream) {
   a.pair = p.causal && nqb % 2 == 0 && nkb % 2 == 0 && pair_enabled();
   const dim3 gq((unsigned)(a.pair ? nqb / 2 : nqb), (unsigned)p.H, (unsigned)p.B);
   const dim3 gk((unsigned)(a.pair ? nkb / 2 : nkb), (unsigned)p.HKV, (unsigned)p.B);
+  if (c.cap) return p.D == 64 ? launch_bwd_cap<64>(a, gq, gk, *c.cap, stream) : launch_bwd_cap<128>(a, gq, gk, *c.cap, stream);
   const bool wave_pairs = (split_mask() >> (p.D == 64 ? 0 : 1)) & 1;
   return p.D == 64 ? launch_bwd<64>(a, parts, gq, gk, wave_pairs, stream)
                    : launch_bwd<128>(a, parts, gq, gk, wave_pairs, stream);
@@ -1829,8 +2004,9 @@ inline int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
 inline int64_t split_tile_bytes(int64_t items, int64_t width) { return align256(items * NW * 32 * width * 4); }
 
 // the forward's launch (pt_attn_fwd, pt_attn_fwd_band): fills and checks the common part, picks the form
-// (sinks: the sink forms, pt_attn_fwd_sink / pt_attn_fwd_band_sink)
-int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uint16_t* sinks = nullptr);
+// (sinks: the sink forms, pt_attn_fwd_sink / pt_attn_fwd_band_sink; cap: the soft-capped forms, pt_attn_fwd_softcap)
+int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uint16_t* sinks = nullptr,
+                    const CapArgs* cap = nullptr);
 
 }  // namespace
 
@@ -1953,6 +2129,48 @@ int pt_attn_bwd_band(const void* q, const int64_t* q_str, const void* k, const i
   return attn_bwd(c, stream);
 }
 
+// Soft-capped causal attention (see the header): softmax over c tanh(q . k scale / c), c = softcap.
+// kv_lo / q_hi both NULL: plain causal; both given: pt_attn_fwd_band's mask.  o bf16, lse f32 [B, H, S]
+// dense, of the capped scores.  Always the regular launch.
+int pt_attn_fwd_softcap(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                        const int64_t* v_str, void* o, const int64_t* o_str, float* lse, int64_t B, int64_t H,
+                        int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, float softcap,
+                        const int32_t* kv_lo, const int32_t* q_hi, hipStream_t stream) {
+  if (!q || !k || !v || !o || !lse) return PT_EINVAL;
+  if (!cap_valid(softcap) || !kv_lo != !q_hi) return PT_EINVAL;
+  if (Sq != Sk) return PT_EUNSUPPORTED;
+  AttnArgs a{};
+  a.lse_ld = Sq;
+  a.o = view(o, o_str);
+  a.lse = lse;
+  a.kv_lo = kv_lo; a.q_hi = q_hi;
+  const CapArgs cap = cap_args(scale, softcap);
+  return attn_fwd_launch(a, {q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1}, stream, nullptr, &cap);
+}
+
+// pt_attn_bwd_fused_delta / pt_attn_bwd_band of the soft-capped forward (bf16 gradients, dense lse, the
+// delta formed in the dQ kernel and left in delta_out; the optional fused RoPE inverse)
+int pt_attn_bwd_softcap(const void* q, const int64_t* q_str, const void* k, const int64_t* k_str, const void* v,
+                        const int64_t* v_str, const void* o, const int64_t* o_str, const void* dout,
+                        const int64_t* do_str, const float* lse, float* delta_out, void* dq, const int64_t* dq_str,
+                        void* dk, const int64_t* dk_str, void* dv, const int64_t* dv_str, int64_t B, int64_t H,
+                        int64_t HKV, int64_t Sq, int64_t Sk, int64_t D, float scale, float softcap,
+                        const void* rope_cos, const void* rope_sin, int64_t rope_stride, const int32_t* kv_lo,
+                        const int32_t* q_hi, hipStream_t stream) {
+  if (!o || !delta_out || !o_str) return PT_EINVAL;
+  if (!cap_valid(softcap) || !kv_lo != !q_hi) return PT_EINVAL;
+  if (Sq != Sk) return PT_EUNSUPPORTED;
+  if (!view_aligned(o, o_str)) return PT_EALIGN;
+  BwdCall c{{q, q_str, k, k_str, v, v_str, B, H, HKV, Sq, Sk, D, scale, 1},
+            dout, do_str, lse, dq, dq_str, dk, dk_str, dv, dv_str, 0, nullptr, o, o_str, delta_out};
+  c.rope_cos = rope_cos; c.rope_sin = rope_sin; c.rope_stride = rope_stride;
+  c.parts = 3;
+  c.kv_lo = kv_lo; c.q_hi = q_hi;
+  const CapArgs cap = cap_args(scale, softcap);
+  c.cap = &cap;
+  return attn_bwd(c, stream);
+}
+
 // pt_attn_fwd under a block band (one block of a context-parallel schedule; see the header): key j
 // visible to query i of batch row b iff kv_lo[b, i] <= j, and j <= i when causal.  kv_lo int32 [B, Sq]
 // and q_hi int32 [B, Sk], dense whatever lse_ld is.
@@ -1992,7 +2210,7 @@ int pt_attn_bwd_block_band(const void* q, const int64_t* q_str, const void* k, c
 
 namespace {
 
-int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uint16_t* sinks) {
+int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uint16_t* sinks, const CapArgs* cap) {
   const int64_t B = p.B, H = p.H, Sq = p.Sq, D = p.D;
   const int causal = p.causal;
   int rc = fill_common(a, p);
@@ -2003,9 +2221,9 @@ int attn_fwd_launch(AttnArgs& a, const Problem& p, hipStream_t stream, const uin
   const int nqb = (int)(Sq / (nwk * 32));
   a.pair = causal && nqb % 2 == 0 && pair_enabled();
   const dim3 grid((unsigned)(a.pair ? nqb / 2 : nqb), (unsigned)H, (unsigned)B);
-  if (D == 64) launch_fwd<64, NW>(a, grid, stream, sinks);
-  else if (nwk == 8) launch_fwd<128, 8>(a, grid, stream, sinks);
-  else launch_fwd<128, NW>(a, grid, stream, sinks);
+  if (D == 64) launch_fwd<64, NW>(a, grid, stream, sinks, cap);
+  else if (nwk == 8) launch_fwd<128, 8>(a, grid, stream, sinks, cap);
+  else launch_fwd<128, NW>(a, grid, stream, sinks, cap);
   PT_CHECK_LAUNCH();
   return PT_OK;
 }

@@ -791,8 +791,9 @@ def ring_enabled():
 class AttnShape:
     """Views of the fused [T, q | k | v] projection as token-major [B, S, heads, d] tensors."""
 
-    def __init__(self, B, S, nh, nkv, d, zz=False, band=None):
+    def __init__(self, B, S, nh, nkv, d, zz=False, band=None, softcap=None):
         self.B, self.S, self.nh, self.nkv, self.d = B, S, nh, nkv, d
+        self.softcap = softcap or None   # kernels.attn_fwd's softcap (None: the plain softmax)
         self.T = B * S
         self.wq, self.wkv = nh * d, nkv * d
         self.zz = zz    # the tokens are a zig-zag CP shard (context_parallel.apply_context_parallel)
@@ -954,6 +955,17 @@ def require_sinks(sh, tp, sp=False):
         raise NotImplementedError(f"attention sinks with head_dim {sh.d}: the sink kernels take 64 / 128")
 
 
+def require_softcap(sh, tp, sp=False):
+    """Refuse, before any launch, what logit soft-capping does not do."""
+    if tp.world_size > 1 or sp:
+        raise NotImplementedError("logit soft-capping under tensor parallelism (tp > 1): not built")
+    if ring_enabled():
+        raise NotImplementedError("logit soft-capping under context parallelism (cp > 1): the soft-capped kernels "
+                                  "have no merge form")
+    if sh.d not in ATTN_HEAD_DIMS:
+        raise NotImplementedError(f"logit soft-capping with head_dim {sh.d}: the soft-capped kernels take 64 / 128")
+
+
 def sinks_bwd(lse, delta, sinks):
     """The sinks' gradient from the attention backward's lse and delta, into the parameter's sink as a
     norm weight's goes (bf16 .grad store / accumulate, or main_grad); a frozen parameter gets none."""
@@ -971,13 +983,17 @@ def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None, sinks=No
     qkn (a QKNorm): q|k are normed per head and rotated by one kernel into their own [T, q|k] buffer
     -- qkv keeps the raw projection, which the norm's backward needs -- and attention reads q, k from
     that buffer and v from qkv; returns (o, lse, qk, rstd [T, nh + nkv] f32).
-    sinks (bf16 [nh]): the per-head sink logits of kernels.attn_fwd; lse then includes the sink."""
+    sinks (bf16 [nh]): the per-head sink logits of kernels.attn_fwd; lse then includes the sink.
+    sh.softcap: kernels.attn_fwd's softcap; lse is then that of the capped scores."""
     if sinks is not None:
         require_sinks(sh, TPContext.current())
+    if sh.softcap:
+        require_softcap(sh, TPContext.current())
     if qkn is not None:
         qkn.require(sh, TPContext.current())
         qk, rstd = K.qk_norm_rope_fwd(qkv, sh.nh, sh.nkv, sh.d, qkn.wq, qkn.wk, qkn.eps, qkn.mode, cos, sin, sh.S)
-        o, lse = K.attn_fwd(sh.q(qk), sh.k(qk), sh.v(qkv), scale, True, band=sh.band, sinks=sinks)
+        o, lse = K.attn_fwd(sh.q(qk), sh.k(qk), sh.v(qkv), scale, True, band=sh.band, sinks=sinks,
+                            softcap=sh.softcap)
         return o, lse, qk, rstd
     if sh.d == ATTN_D256:
         _req_d256(sh)
@@ -989,7 +1005,7 @@ def attention_core_fwd(qkv, sh, cos, sin, scale, roped=False, qkn=None, sinks=No
     if ring_enabled():
         from .context_parallel.context_parallel import ring_attention_tokens
         return ring_attention_tokens(qkv, sh, scale, True, resident=sh.zz)
-    return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True, band=sh.band, sinks=sinks)
+    return K.attn_fwd(sh.q(qkv), sh.k(qkv), sh.v(qkv), scale, True, band=sh.band, sinks=sinks, softcap=sh.softcap)
 
 
 def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=None, sinks=None):
@@ -1005,7 +1021,8 @@ def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=No
         dqkv = torch.empty_like(qkv)
         rope = (cos, sin) if _fuse() else None   # the RoPE backward fused into the dq / dk stores, or after
         *_, delta = K.attn_bwd(do, sh.q(qk), sh.k(qk), sh.v(qkv), o, lse, scale, True,
-                               dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band)
+                               dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band,
+                               softcap=sh.softcap)
         if sinks is not None:
             sinks_bwd(lse, delta, sinks)
         if rope is None:
@@ -1026,7 +1043,8 @@ def attention_core_bwd(do, qkv, o, lse, sh, cos, sin, scale, qkn=None, normed=No
     else:
         rope = (cos, sin) if _fuse() else None   # the RoPE backward fused into the dq / dk stores, or after
         *_, delta = K.attn_bwd(do, sh.q(qkv), sh.k(qkv), sh.v(qkv), o, lse, scale, True,
-                               dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band)
+                               dq=sh.q(dqkv), dk=sh.k(dqkv), dv=sh.v(dqkv), rope=rope, band=sh.band,
+                               softcap=sh.softcap)
         if rope is None:
             K.rope_(dqkv, sh.nh + sh.nkv, sh.d, cos, sin, sh.S, inverse=True)
         if sinks is not None:
@@ -1040,10 +1058,12 @@ def attn_block_fwd(h2, wq, wk, wv, wo, cos, sin, sh, tp, reduce=True, qkn=None, 
     qkn (a QKNorm): the plain q|k|v GEMM (the norm sits between the projection and the rotation, so
     the RoPE-epilogue GEMM cannot run), then the fused norm + RoPE kernel; saved grows by the normed,
     rotated [T, q|k] and rstd [T, nh + nkv] f32.
-    sinks (bf16 [nh]): the attention sinks (attention_core_fwd)."""
+    sinks (bf16 [nh]): the attention sinks (attention_core_fwd).  sh.softcap: logit soft-capping."""
     scale = 1.0 / math.sqrt(sh.d)
     if sinks is not None:
         require_sinks(sh, tp, not reduce)
+    if sh.softcap:
+        require_softcap(sh, tp, not reduce)
     if qkn is not None:
         qkn.require(sh, tp, not reduce)
         qkv = K.linear_fwd(h2, [wq, wk, wv])
@@ -1112,9 +1132,9 @@ class AttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, wq, wk, wv, wo, cos, sin, nh, nkv, d, band=None, wqn=None, wkn=None, qk_eps=None,
-                qk_mode=None, sinks=None):
+                qk_mode=None, sinks=None, softcap=None):
         B, S, _ = x.shape
-        sh = AttnShape(B, S, nh, nkv, d, band=band)
+        sh = AttnShape(B, S, nh, nkv, d, band=band, softcap=softcap)
         qkn = QKNorm.of(wqn, wkn, qk_eps, qk_mode)
         if qkn is not None:
             qkn.require(sh, TPContext.current())
@@ -1136,7 +1156,7 @@ class AttentionFunction(torch.autograd.Function):
         qkn = QKNorm(rest[2], rest[3], *ctx.qk) if rest else None   # rest: qk, rstd, q_norm, k_norm weights
         dh = attn_block_bwd(_contig2d(da), h2, (qkv, o, lse, *rest[:2]), wq, wk, wv, wo, cos, sin, sh,
                             TPContext.current(), need_dx=ctx.needs_input_grad[0], qkn=qkn, sinks=sinks)
-        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 15
+        return (dh.view(sh.B, sh.S, -1) if dh is not None else None,) + (None,) * 16
 
 
 # ------------------------------------------------------------------------ multi-head latent attention

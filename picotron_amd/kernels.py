@@ -2802,6 +2802,93 @@ def _d256_only(causal_self, merge, band, sinks, what):
         raise NotImplementedError(f"{what}: head dim 256 has no sink kernels")
 
 
+# Logit soft-capping (include/picotron_hip.h pt_attn_fwd_softcap): the softmax over c tanh(q.k scale / c).
+def _softcap_only(softcap, q, k, causal, merge, band, sinks, what):
+    """Refuse, before any launch, what the soft-capped kernels do not do; returns the cap as a float."""
+    c = float(softcap)
+    _req(math.isfinite(c) and c > 0.0, f"{what}: softcap must be a finite positive number, got {softcap!r}")
+    if q.shape[3] not in (64, 128):
+        raise NotImplementedError(f"{what}: softcap with head dim {q.shape[3]}: the soft-capped kernels take 64 / 128")
+    if merge or isinstance(band, AttnBlockBand):
+        raise NotImplementedError(f"{what}: softcap with merge=True or an AttnBlockBand (context-parallel blocks)")
+    if sinks is not None:
+        raise NotImplementedError(f"{what}: softcap with sinks: the combination is not defined here")
+    _req(bool(causal) and q.shape[1] == k.shape[1], f"{what}: softcap takes causal attention with Sq == Sk")
+    return c
+
+
+def _unpad_into(given, got, S):
+    """The first S rows (dim 1) of a padded result, as a new tensor or copied into the caller's."""
+    if given is None:
+        return got[:, :S].contiguous()
+    given.copy_(got[:, :S])
+    return given
+
+
+def _rope_tables(rope, Sq):
+    """(cos, sin, row stride) of attn_bwd's rope argument, checked; (None, None, 0) without one."""
+    if rope is None:
+        return None, None, 0
+    rc_cos, rc_sin = rope
+    _req(rc_cos.dtype == BF16 and rc_sin.dtype == BF16 and rc_cos.stride(-1) == 1 and rc_cos.shape[0] >= Sq,
+         "attn_bwd rope tables: bf16 [S, d]")
+    _req(rc_sin.stride(0) == rc_cos.stride(0), "attn_bwd rope tables share a stride")
+    return rc_cos, rc_sin, rc_cos.stride(0)
+
+
+def _attn_fwd_softcap(q, k, v, scale, c, out, lse, band):
+    B, S, H, D = q.shape
+    HKV = k.shape[2]
+    _req(lse is None or _lse_ld(lse, B, H, S) == S, "attn_fwd: softcap takes a dense lse")
+    bp = None if band is None else _band_for(band, q, k, True, "attn_fwd")
+    Sp = _attn_padded_len(S)
+    if Sp != S:   # the causal zero-padding path (a band: its pad rows their own documents)
+        op, lp = _attn_fwd_softcap(_pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp), scale, c, None, None, bp)
+        if lse is None:
+            return _unpad_into(out, op, S), lp[:, :, :S].contiguous()
+        lse.copy_(lp[:, :, :S])
+        return _unpad_into(out, op, S), lse
+    if out is None:
+        out = torch.empty(B, S, H, D, dtype=BF16, device=q.device)
+    if lse is None:
+        lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+    rc = _C.lib().pt_attn_fwd_softcap(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                      _ptr(lse), B, H, HKV, S, S, D, float(scale), c,
+                                      _ptr(bp.kv_lo) if bp else None, _ptr(bp.q_hi) if bp else None,
+                                      _C.stream_ptr(q.device))
+    _C.check(rc, "pt_attn_fwd_softcap")
+    return out, lse
+
+
+def _attn_bwd_softcap(dout, q, k, v, out, lse, scale, c, dq, dk, dv, rope, band):
+    B, S, H, D = q.shape
+    HKV = k.shape[2]
+    _req(_lse_ld(lse, B, H, S) == S, "attn_bwd: softcap takes a dense lse")
+    _req(out.dtype == BF16 and out.shape == q.shape, "attn_bwd: out must be bf16 [B, Sq, H, D]")
+    bp = None if band is None else _band_for(band, q, k, True, "attn_bwd")
+    Sp = _attn_padded_len(S)
+    if Sp != S:   # as attn_bwd's padded path: pad rows carry dO = 0 and lse = +inf, so P = 0
+        lsep = torch.full((B, H, Sp), float("inf"), dtype=torch.float32, device=q.device)
+        lsep[:, :, :S] = lse
+        rp = None if rope is None else tuple(t if t.shape[0] >= Sp else _pad_seq(t.unsqueeze(0), Sp)[0] for t in rope)
+        dqp, dkp, dvp, dlt = _attn_bwd_softcap(_pad_seq(dout, Sp), _pad_seq(q, Sp), _pad_seq(k, Sp), _pad_seq(v, Sp),
+                                               _pad_seq(out, Sp), lsep, scale, c, None, None, None, rp, bp)
+        return _unpad_into(dq, dqp, S), _unpad_into(dk, dkp, S), _unpad_into(dv, dvp, S), dlt[:, :, :S]
+    dq = torch.empty(B, S, H, D, dtype=BF16, device=q.device) if dq is None else dq
+    dk = torch.empty(B, S, HKV, D, dtype=BF16, device=q.device) if dk is None else dk
+    dv = torch.empty(B, S, HKV, D, dtype=BF16, device=q.device) if dv is None else dv
+    _req(dq.dtype == BF16 and dk.dtype == BF16 and dv.dtype == BF16, "attn_bwd: softcap gradients are bf16")
+    rc_cos, rc_sin, rstride = _rope_tables(rope, S)
+    delta = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
+    rc = _C.lib().pt_attn_bwd_softcap(_ptr(q), _str3(q), _ptr(k), _str3(k), _ptr(v), _str3(v), _ptr(out), _str3(out),
+                                      _ptr(dout), _str3(dout), _ptr(lse), _ptr(delta), _ptr(dq), _str3(dq), _ptr(dk),
+                                      _str3(dk), _ptr(dv), _str3(dv), B, H, HKV, S, S, D, float(scale), c,
+                                      _ptr(rc_cos), _ptr(rc_sin), rstride, _ptr(bp.kv_lo) if bp else None,
+                                      _ptr(bp.q_hi) if bp else None, _C.stream_ptr(q.device))
+    _C.check(rc, "pt_attn_bwd_softcap")
+    return dq, dk, dv, delta
+
+
 def _rows2d(t, what):
     """A [B, S, heads, d] view whose heads are packed and whose token rows are evenly spaced, as its
     [B * S, heads * d] rows (rope_'s argument)."""
@@ -2811,7 +2898,7 @@ def _rows2d(t, what):
     return t.as_strided((B * S, nh * d), (t.stride(1), 1))
 
 
-def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None, sinks=None):
+def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None, sinks=None, softcap=None):
     """q [B,Sq,H,D], k/v [B,Sk,Hkv,D] (token-major views).  Returns (out, lse[B,H,Sq] f32).
     merge=True: `out` is an f32 accumulator and `lse` the running LSE; this block is merged in.
     lse may be the Sq-column slice of a longer [B, H, S] LSE (rows evenly spaced).
@@ -2823,9 +2910,16 @@ def attn_fwd(q, k, v, scale, causal, out=None, lse=None, merge=False, band=None,
     that score and a zero value vector, and lse includes it (attention.hip, "Sinks"); causal, with an
     AttnBand or without, dense lse; the few-head split forms are not taken.  The backward is attn_bwd
     on this lse, unchanged, plus attn_sink_bwd for the sinks' own gradient.
-    D = 256: causal with Sq == Sk and a dense lse only; merge, a band of either kind and sinks raise."""
+    D = 256: causal with Sq == Sk and a dense lse only; merge, a band of either kind and sinks raise.
+    softcap (c > 0; None / 0: none): the softmax runs over c tanh(q.k scale / c) and lse is that of the
+    capped scores (attention.hip, "Soft-capping"); causal, with an AttnBand or without, D 64 / 128, dense
+    lse; D = 256, merge, an AttnBlockBand and sinks raise; the few-head split forms are not taken.  The
+    backward is attn_bwd with the same softcap."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if softcap:
+        c = _softcap_only(softcap, q, k, causal, merge, band, sinks, "attn_fwd")
+        return _attn_fwd_softcap(q, k, v, scale, c, out, lse, band)
     if D == ATTN_D256:
         _d256_only(causal and Sq == Sk, merge, band, sinks, "attn_fwd")
         _req(lse is None or _lse_ld(lse, B, H, Sq) == Sq, "attn_fwd: head dim 256 takes a dense lse")
@@ -2997,7 +3091,7 @@ def attn_bwd_part(dout, q, k, v, lse, delta, scale, causal, dq=None, dk=None, dv
 
 
 def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, grad_f32=False, delta=None,
-             rope=None, band=None):
+             rope=None, band=None, softcap=None):
     """rope = (cos, sin) [S, d] bf16 tables: dq / dk are stored rotated back by -theta (the RoPE
     backward fused into the attention backward; positions = sequence index).
     band (an AttnBand): the backward of attn_fwd(band=); bf16 gradients, dense lse, D = rowsum(dO * O)
@@ -3005,9 +3099,18 @@ def attn_bwd(dout, q, k, v, out, lse, scale, causal, dq=None, dk=None, dv=None, 
     band (an AttnBlockBand): one block of a context-parallel schedule; bf16 stores or f32 accumulation,
     a given (or separately formed) delta, a strided lse; no fused RoPE inverse.
     D = 256: bf16 gradients, delta formed in the dQ kernel and returned; grad_f32, a given delta and a
-    band raise; rope is honoured by rope_(inverse=True) on dq / dk after the kernels."""
+    band raise; rope is honoured by rope_(inverse=True) on dq / dk after the kernels.
+    softcap: the backward of attn_fwd(softcap=), dS carrying (1 - tanh^2); bf16 gradients, delta formed in
+    the dQ kernel and returned, dense lse, an AttnBand or none; grad_f32, a given delta, D = 256 and an
+    AttnBlockBand raise."""
     B, Sq, H, D = q.shape
     Sk, HKV = k.shape[1], k.shape[2]
+    if softcap:
+        c = _softcap_only(softcap, q, k, causal, False, band, None, "attn_bwd")
+        if grad_f32 or delta is not None:
+            raise NotImplementedError("attn_bwd: softcap stores bf16 gradients and forms delta itself "
+                                      "(no grad_f32, no given delta)")
+        return _attn_bwd_softcap(dout, q, k, v, out, lse, scale, c, dq, dk, dv, rope, band)
     if D == ATTN_D256:
         _d256_only(causal and Sq == Sk, False, band, None, "attn_bwd")
         if grad_f32 or delta is not None:

@@ -80,7 +80,7 @@ def _pad_d(t, dp):
 
 class _FlashAttention(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, q, k, v, causal):
+    def forward(ctx, q, k, v, causal, softcap=0.0):
         # q/k/v: [B, S, H, D] views (d contiguous); a D other than 64 / 128 runs zero-padded (the
         # padded columns add nothing to q . k and are sliced off o; the scale is the real D's)
         D = q.shape[-1]
@@ -89,9 +89,9 @@ class _FlashAttention(torch.autograd.Function):
         if dp is None:
             raise RuntimeError(f"flash_attention: head_dim {D} -- the kernels take 64 / 128 / 256 and pad dims below 128")
         qp, kp, vp = (_pad_d(t, dp) for t in (q, k, v))
-        o, lse = K.attn_fwd(qp, kp, vp, scale, causal)
+        o, lse = K.attn_fwd(qp, kp, vp, scale, causal, softcap=softcap)
         ctx.save_for_backward(qp, kp, vp, o, lse)
-        ctx.scale, ctx.causal, ctx.D = scale, causal, D
+        ctx.scale, ctx.causal, ctx.D, ctx.softcap = scale, causal, D, softcap
         return o[..., :D] if dp != D else o
 
     @staticmethod
@@ -101,15 +101,17 @@ class _FlashAttention(torch.autograd.Function):
         do = _pad_d(do, o.shape[-1])
         if do.stride(-1) != 1:
             do = do.contiguous()
-        dq, dk, dv, _ = K.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal)
+        dq, dk, dv, _ = K.attn_bwd(do, q, k, v, o, lse, ctx.scale, ctx.causal, softcap=ctx.softcap)
         if o.shape[-1] != D:
             dq, dk, dv = dq[..., :D], dk[..., :D], dv[..., :D]
-        return dq, dk, dv, None
+        return dq, dk, dv, None, None
 
 
-def flash_attention(q, k, v, causal=True):
-    """model.py:33-37: q/k/v [B, H, S, D] -> out [B, S, H, D] (flash_attn_func semantics)."""
-    return _FlashAttention.apply(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3), causal)
+def flash_attention(q, k, v, causal=True, softcap=0.0):
+    """model.py:33-37: q/k/v [B, H, S, D] -> out [B, S, H, D] (flash_attn_func semantics).
+    softcap (flash_attn_func's argument; 0.0: none): the softmax over softcap * tanh(scores / softcap);
+    causal only, head dims up to 128 (kernels.attn_fwd)."""
+    return _FlashAttention.apply(q.permute(0, 2, 1, 3), k.permute(0, 2, 1, 3), v.permute(0, 2, 1, 3), causal, softcap)
 
 
 # ---------------------------------------------------------------------------- norms / linear
@@ -231,7 +233,9 @@ def layer_types(config):
 class Attention(nn.Module):
     """model.py:88-162.  config.attention_sinks = True (gpt-oss; not in the reference) adds `sinks`
     [num_attention_heads] bf16 (HF's self_attn.sinks is attention.sinks here): one learned logit per
-    query head that joins every row's softmax as a column with a zero value vector (kernels.attn_fwd)."""
+    query head that joins every row's softmax as a column with a zero value vector (kernels.attn_fwd).
+    config.attn_logit_softcapping = c (HF's Gemma-2 field; None / 0: none): the softmax runs over
+    c tanh(scores / c) (kernels.attn_fwd's softcap); such layers run as separate autograd nodes."""
 
     def __init__(self, config, layer_idx):
         super().__init__()
@@ -274,6 +278,20 @@ class Attention(nn.Module):
                                           "64 / 128")
             self.sinks = nn.Parameter(torch.empty(self.num_heads, dtype=torch.bfloat16))
             self.sinks_std = float(getattr(config, "initializer_range", 0.02))
+        self.softcap = float(getattr(config, "attn_logit_softcapping", None) or 0.0)
+        if self.softcap:
+            if not (math.isfinite(self.softcap) and self.softcap > 0.0):
+                raise ValueError(f"attn_logit_softcapping must be a finite positive number, got {self.softcap!r}")
+            if m.tp_world_size > 1 or m.cp_world_size > 1:
+                raise NotImplementedError("attn_logit_softcapping under tensor or context parallelism (tp > 1, "
+                                          "cp > 1): the soft-capped kernels have no merge form, and the sharded "
+                                          "layers run as one fused node that does not carry the cap")
+            if self.head_dim not in FN.ATTN_HEAD_DIMS:
+                raise NotImplementedError(f"attn_logit_softcapping with head_dim {self.head_dim}: the soft-capped "
+                                          "kernels take 64 / 128")
+            if self.attention_sinks:
+                raise NotImplementedError("attn_logit_softcapping with attention_sinks: the combination is not "
+                                          "defined here")
         # QK-norm (config.qk_norm; Qwen3 / OLMo-2 / Gemma-3 / Chameleon): an RMSNorm of the layer norms'
         # flavour over each q head's and each k head's head_dim values, between the projection and
         # RoPE; one [head_dim] weight for the q heads, one for the k heads (Qwen3's layout)
@@ -311,12 +329,13 @@ class Attention(nn.Module):
         return self.q_norm.weight, self.k_norm.weight, _norm_eps(self.q_norm), _norm_mode(self.q_norm)
 
     def tail_args(self):
-        """AttentionFunction's arguments after the band: the QK-norm's four (None without one) and the
-        sinks -- or nothing when the layer has neither."""
+        """AttentionFunction's arguments after the band: the QK-norm's four (None without one), the
+        sinks and the soft cap -- as far as the layer has them."""
         qk = self.qk_norm_args()
-        if not self.attention_sinks:
+        if not self.attention_sinks and not self.softcap:
             return qk
-        return (qk or (None,) * 4) + (self.sinks,)
+        tail = (qk or (None,) * 4) + (self.sinks if self.attention_sinks else None,)
+        return tail + (self.softcap,) if self.softcap else tail
 
     def band(self, x, document_ids):
         """The kernels.AttnBand of this forward (None: plain causal): document_ids a [B, S] integer
@@ -363,6 +382,9 @@ class MLAttention(nn.Module):
             raise NotImplementedError("sliding_window with kv_lora_rank > 0: the MLA kernels are plain causal")
         if getattr(config, "attention_sinks", False):
             raise NotImplementedError("attention_sinks with kv_lora_rank > 0: the MLA kernels have no sink form")
+        if getattr(config, "attn_logit_softcapping", None):
+            raise NotImplementedError("attn_logit_softcapping with kv_lora_rank > 0: the MLA kernels have no "
+                                      "soft-capped form")
         self.num_heads = config.num_attention_heads
         self.q_lora_rank = getattr(config, "q_lora_rank", None) or None
         self.kv_lora_rank = int(config.kv_lora_rank)
@@ -618,7 +640,7 @@ class DecoderLayer(nn.Module):
         qk = at.qk_norm_args()   # (): no QK-norm; else its two weights, in the layer norms' flavour
         if qk and qk[2:] != (_norm_eps(n1), _norm_mode(n1)):
             raise ValueError("DecoderLayer: q_norm / k_norm must be the layer norms' flavour")
-        if isinstance(mlp, MoE) or at.attention_sinks:   # composed from the separate nodes
+        if isinstance(mlp, MoE) or at.attention_sinks or at.softcap:   # composed from the separate nodes
             if sp or zz:
                 raise NotImplementedError("a mixture-of-experts layer on a sharded residual stream (tp / cp > 1)")
             eps, mode = _norm_eps(n1), _norm_mode(n1)

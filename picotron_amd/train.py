@@ -235,6 +235,9 @@ class GraphedTrainStep:
         if any(getattr(m, "attention_sinks", False) for m in model.modules()):
             raise NotImplementedError("GraphedTrainStep: attention sinks (their layers run as separate autograd nodes "
                                       "and the sinks' gradient pass allocates its workspace: not shown to capture)")
+        if any(getattr(m, "softcap", 0.0) for m in model.modules()):
+            raise NotImplementedError("GraphedTrainStep: attn_logit_softcapping (its layers run as separate autograd "
+                                      "nodes: not shown to replay unchanged)")
         self.model, self.loader, self.device = model, data_loader, torch.device(device)
         self.warmup = max(1, warmup)
         self.graph = None
