@@ -300,6 +300,34 @@ int pt_cross_entropy_bwd_lse_shard_z(const void* logits, int64_t logits_stride, 
                                      int64_t vocab_shard, int64_t vocab_lo, const float* scale, int64_t scale_stride,
                                      int64_t ignore_index, float z_coef, hipStream_t stream);
 
+/* ---- final-logit soft-capping (Gemma-2 final_logit_softcapping, Grok-1): t = c tanh(raw / c) -------
+ * The lm_head stores the capped logits t (pt_gemm_ce_stats_cap below, or pt_softcap_fwd over a plain
+ * GEMM's output), the loss is the ordinary cross-entropy of t -- every forward entry above, unchanged --
+ * and the gradient of the raw logits is d loss / d t * (1 - (t / c)^2), a function of the stored t:
+ *   pt_softcap_fwd: y = bf16(c tanh(x / c)), tanh as 1 - 2 rcp(1 + exp2(x 2 log2(e) / c)); y may be x.
+ *   pt_softcap_bwd: dx = bf16(dy (1 - (y / c)^2)), y the forward's output; dx may be dy.
+ *     x, y, dy, dx: [rows, cols] bf16 views with row strides in elements.
+ *   The _cap cross-entropy entries are their _z namesakes (z_coef == 0: no z term) with the factor in the
+ *     store, dlogits = bf16((exp(t - lse) (1 + 2 z_coef lse) - onehot) scale[...] (1 - (t / c)^2)), all in
+ *     f32 and rounded once; a t of -inf (a padding column) and ignore_index rows give +0; row_loss,
+ *     row_z and *status as without the cap.
+ * Refusals, before any launch, in this order: a NULL required pointer (status, inv_count, row_z and the
+ * fused form's dlogits are optional) or a size < 1 -> PT_EINVAL; softcap not a finite f32 > 0 ->
+ * PT_EINVAL; then the namesake's checks in its order (the row kernels: cols or a stride off the
+ * 8-element grid or a pointer off 16 bytes -> PT_EALIGN, rows or cols > INT32_MAX -> PT_EUNSUPPORTED). */
+int pt_softcap_fwd(const void* x, int64_t ldx, void* y, int64_t ldy, int64_t rows, int64_t cols, float softcap,
+                   hipStream_t stream);
+int pt_softcap_bwd(const void* dy, int64_t lddy, const void* y, int64_t ldy, void* dx, int64_t lddx, int64_t rows,
+                   int64_t cols, float softcap, hipStream_t stream);
+int pt_cross_entropy_bwd_lse_cap(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                 const float* row_lse, void* dlogits, int64_t dlogits_stride, int64_t rows,
+                                 int64_t vocab, const float* scale, int64_t scale_stride, int64_t ignore_index,
+                                 float z_coef, float softcap, hipStream_t stream);
+int pt_cross_entropy_fwd_bwd_cap(const void* logits, int64_t logits_stride, const int64_t* targets, void* dlogits,
+                                 int64_t dlogits_stride, float* row_loss, int64_t rows, int64_t vocab, float scale,
+                                 const float* inv_count, int64_t ignore_index, int* status, float z_coef,
+                                 float* row_z, float softcap, hipStream_t stream);
+
 /* train.py:49's reduction='mean' over the per-row losses: loss = sum(row_loss) / #(target !=
  * ignore_index) in one deterministic launch; inv_count = 1 / #valid (the backward's scale);
  * reduce_sum != 0: reduction='sum' (loss = sum(row_loss), inv_count = 1);
@@ -572,6 +600,12 @@ int pt_gemm_rope(const void* A, int64_t lda, const void* const* B, const int64_t
  * stats[b * M + row] (block 256 or 128; M % 256 == 0, N % block == 0, K % 64 == 0). */
 int pt_gemm_ce_stats(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* stats,
                      int64_t block, int64_t M, int64_t N, int64_t K, hipStream_t stream);
+/* pt_gemm_ce_stats with final-logit soft-capping in the epilogue (see the soft-capping section): C =
+ * bf16(softcap tanh(acc / softcap)) from the f32 accumulators, one rounding, and the statistics of those
+ * stored values; same tiles, same LDS.  A NULL pointer or a size < 1, then softcap not a finite f32 > 0
+ * -> PT_EINVAL; then pt_gemm_ce_stats's checks in its order. */
+int pt_gemm_ce_stats_cap(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* stats,
+                         int64_t block, int64_t M, int64_t N, int64_t K, float softcap, hipStream_t stream);
 /* Grouped GEMM: nprob (<= 4) independent problems in ONE launch, each described like pt_gemm's
  * arguments, sharing layouts (a_kcontig, b_kcontig), epilogue and tile (-1 = auto over the
  * group).  Used where one problem alone would leave CUs idle (dW of q|k|v + dW of o_proj).

@@ -39,6 +39,28 @@ __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
 // one expression, so the fused epilogues and csrc/swiglu.hip stay bit-identical
 __device__ __forceinline__ float pt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+// Final-logit soft-capping (Gemma-2's final_logit_softcapping): t = c tanh(x / c), written as
+// csrc/attention.hip's soft-cap stage writes it -- e = exp2(x k1) = exp(2 x / c), tanh = 1 - 2 rcp(1 + e):
+// one v_mul, v_exp, v_add, v_rcp, v_fma, v_mul, no libm call.  e = +inf gives c, e = 0 gives -c.
+struct PtCap {
+  float c, k1, inv_c2;   // the cap, 2 log2(e) / c, 1 / c^2
+};
+// k1 as one IEEE f32 division: the host (pt_cap) and the GEMM epilogue, which is handed c alone, get the same bits
+__host__ __device__ __forceinline__ float pt_cap_k1(float c) { return 2.8853900817779268f / c; }
+static inline PtCap pt_cap(float softcap) {
+  return {softcap, pt_cap_k1(softcap), (float)(1.0 / ((double)softcap * softcap))};
+}
+static inline bool pt_cap_valid(float softcap) { return softcap > 0.f && softcap < __builtin_inff(); }   // NaN fails
+__device__ __forceinline__ float pt_softcap(float x, float k1, float c) {
+  const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * k1));
+  return fmaf(-2.0f, r, 1.0f) * c;
+}
+// d t / d x = 1 - (t / c)^2 from the stored t, as (c - t)(c + t) / c^2: exactly 0 at t = +-c (1 - u u
+// cancels there) and 0, not inf - inf, for the -inf padding columns of a vocabulary off the 8-column grid
+__device__ __forceinline__ float pt_softcap_grad(float t, float c, float inv_c2) {
+  return t == -INFINITY ? 0.f : (c - t) * (c + t) * inv_c2;
+}
+
 __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
   return (uint32_t)f2bf(lo) | ((uint32_t)f2bf(hi) << 16);
 }

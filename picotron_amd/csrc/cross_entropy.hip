@@ -24,6 +24,13 @@
 // z == 0 run Z = false, which is the arithmetic above without the z terms (z lse^2 is never formed
 // there: 0 * inf would be NaN), so a _z call with z == 0 writes its namesake's bits.
 //
+// Final-logit soft-capping (the _cap entry points; Gemma-2's final_logit_softcapping): the logits are
+// the capped ones, t = c tanh(raw / c), as the lm_head GEMM stores them (gemm.hip EPI_CE_STATS_CAP), and the
+// gradient that leaves here is the raw logits': each kernel's compile-time switch CAP multiplies the
+// element it is about to store by d t / d raw = 1 - (t / c)^2, a function of the t it already holds,
+//   dlogits[r,:] = (softmax(t) (1 + 2 z lse_r) - onehot(t_r)) * scale ... * (1 - (t / c)^2)
+// all in f32, rounded once.  The loss and the LSE are the ordinary ones of t: no forward kernel changes.
+//
 // One 256-thread workgroup per row; the row is held in registers (NC 16-byte chunks per
 // thread) so HBM sees exactly one read and one write of the logits: 4*V bytes per row, the
 // roofline figure in DESIGN.md.  Rows longer than 256*8*32 elements take the two-pass variant.
@@ -117,26 +124,30 @@ __device__ __forceinline__ float z_factor(bool valid, float lse, float z) {
 
 // chunk c of a gradient row: d[8c + j] = (p_j cz - onehot) g, with p_j = exp(x_j - lse) in one of two
 // roundings: EXP2 false: __expf(x_j - a), a = lse;  EXP2 true: exp2(fma(x_j, log2e, a)), a = -lse log2e
-template <bool Z, bool EXP2>
-__device__ __forceinline__ void grad_chunk(const bf16x8& v, uint16_t* d, int c, int64_t t, float a, float cz, float g) {
+// CAP: times 1 - (x_j / cap.c)^2 (pt_softcap_grad: +0 for a -inf padding column)
+template <bool Z, bool EXP2, bool CAP>
+__device__ __forceinline__ void grad_chunk(const bf16x8& v, uint16_t* d, int c, int64_t t, float a, float cz, float g,
+                                           const PtCap& cap) {
   float f[8];
   unpack8(v, f);
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     float p = EXP2 ? __builtin_amdgcn_exp2f(fmaf(f[j], kLog2e, a)) : __expf(f[j] - a);
     if (Z) p *= cz;
+    const float fac = CAP ? pt_softcap_grad(f[j], cap.c, cap.inv_c2) : 1.f;
     f[j] = (p - ((int64_t)(c * 8 + j) == t ? 1.f : 0.f)) * g;
+    if (CAP) f[j] *= fac;
   }
   st8(d + c * 8, pack8(f));
 }
 
-template <int NC, bool Z>
+template <int NC, bool Z, bool CAP>
 __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict__ logits, int64_t ls,
                                                       const int64_t* __restrict__ tgt, uint16_t* dlogits,
                                                       int64_t ds, float* __restrict__ row_loss, int V,
                                                       float scale, const float* __restrict__ inv_count,
                                                       int64_t ignore_index, int* __restrict__ status, float z,
-                                                      float* __restrict__ row_z) {
+                                                      float* __restrict__ row_z, PtCap cap) {
   __shared__ float red[kThreads / 64];
   const int64_t row = blockIdx.x;
   const uint16_t* x = logits + row * ls;
@@ -180,18 +191,18 @@ __global__ __launch_bounds__(kThreads) void ce_kernel(const uint16_t* __restrict
 #pragma unroll
   for (int i = 0; i < NC; ++i) {
     const int c = threadIdx.x + i * kThreads;
-    if (c < nch) grad_chunk<Z, false>(v[i], d, c, tg.t, lse, cz, g);
+    if (c < nch) grad_chunk<Z, false, CAP>(v[i], d, c, tg.t, lse, cz, g, cap);
   }
 }
 
 // long rows: online max/sum in one read, gradient in a second read
-template <bool Z>
+template <bool Z, bool CAP>
 __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __restrict__ logits, int64_t ls,
                                                             const int64_t* __restrict__ tgt, uint16_t* dlogits,
                                                             int64_t ds, float* __restrict__ row_loss, int V,
                                                             float scale, const float* __restrict__ inv_count,
                                                             int64_t ignore_index, int* __restrict__ status, float z,
-                                                            float* __restrict__ row_z) {
+                                                            float* __restrict__ row_z, PtCap cap) {
   __shared__ float red[kThreads / 64];
   __shared__ float red2[kThreads / 64];
   const int64_t row = blockIdx.x;
@@ -224,7 +235,8 @@ __global__ __launch_bounds__(kThreads) void ce_kernel_2pass(const uint16_t* __re
   if (!dlogits) return;
   const float cz = z_factor<Z>(tg.valid, lse, z);
   uint16_t* d = dlogits + row * ds;
-  for (int c = threadIdx.x; c < nch; c += kThreads) grad_chunk<Z, false>(ld8(x + c * 8), d, c, tg.t, lse, cz, g);
+  for (int c = threadIdx.x; c < nch; c += kThreads)
+    grad_chunk<Z, false, CAP>(ld8(x + c * 8), d, c, tg.t, lse, cz, g, cap);
 }
 
 // ---- streaming pair: the autograd forward saves the row LSE so the backward needs no reduction
@@ -371,14 +383,14 @@ __global__ __launch_bounds__(kMeanThreads) void ce_mean_kernel(const float* __re
   }
 }
 
-template <bool Z>
+template <bool Z, bool CAP>
 __global__ __launch_bounds__(kThreads) void ce_bwd_stream_kernel(const uint16_t* __restrict__ logits, int64_t ls,
                                                                  const int64_t* __restrict__ tgt,
                                                                  const float* __restrict__ row_lse,
                                                                  uint16_t* __restrict__ dl, int64_t ds, int V,
                                                                  const float* __restrict__ scale_dev,
                                                                  int64_t scale_stride, int64_t ignore_index,
-                                                                 int64_t vocab_lo, float z) {
+                                                                 int64_t vocab_lo, float z, PtCap cap) {
   const int64_t row = blockIdx.x;
   const uint16_t* x = logits + row * ls;
   uint16_t* d = dl + row * ds;
@@ -397,7 +409,7 @@ __global__ __launch_bounds__(kThreads) void ce_bwd_stream_kernel(const uint16_t*
 #pragma unroll
     for (int u = 0; u < kUnroll; ++u) {
       const int c = c0 + u * kThreads;
-      if (c < nch) grad_chunk<Z, true>(v[u], d, c, t, nl2, cz, g);
+      if (c < nch) grad_chunk<Z, true, CAP>(v[u], d, c, t, nl2, cz, g, cap);
     }
   }
 }
@@ -468,6 +480,54 @@ bool stats_ok(const float* stats, int64_t nblk, int64_t vocab) {
   return stats && nblk > 0 && vocab % nblk == 0 && pt_aligned16(stats);
 }
 
+// f(Z, CAP) with CAP = a cap is given (softcap > 0; the entry points without one pass 0)
+template <class F>
+void with_z_cap(float z_coef, float softcap, F&& f) {
+  with_z(z_coef, [&](auto Z) {
+    if (softcap > 0.f) f(Z, std::true_type{});
+    else f(Z, std::false_type{});
+  });
+}
+
+// dlogits = (exp(x - lse) (1 + 2 z lse) - onehot) scale on a vocab shard; softcap > 0: times 1 - (x / softcap)^2
+int bwd_lse_shard(const void* logits, int64_t logits_stride, const int64_t* targets, const float* row_lse,
+                  void* dlogits, int64_t dlogits_stride, int64_t rows, int64_t vocab_shard, int64_t vocab_lo,
+                  const float* scale, int64_t scale_stride, int64_t ignore_index, float z_coef, float softcap,
+                  hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
+  if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab_shard <= 0) return PT_EINVAL;
+  if (scale_stride != 0 && scale_stride != 1) return PT_EINVAL;
+  if (const int rc = logits_ok(logits, logits_stride, dlogits, dlogits_stride, rows, vocab_shard)) return rc;
+  with_z_cap(z_coef, softcap, [&](auto Z, auto CAP) {
+    constexpr bool kC = decltype(CAP)::value;
+    ce_bwd_stream_kernel<decltype(Z)::value, kC><<<(unsigned)rows, kThreads, 0, stream>>>(
+        (const uint16_t*)logits, logits_stride, targets, row_lse, (uint16_t*)dlogits, dlogits_stride, (int)vocab_shard,
+        scale, scale_stride, ignore_index, vocab_lo, z_coef, kC ? pt_cap(softcap) : PtCap{});
+  });
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
+// The one-read fused form with the z term in row_loss (and row_z, optional) and in dlogits; softcap as above.
+int fwd_bwd(const void* logits, int64_t logits_stride, const int64_t* targets, void* dlogits, int64_t dlogits_stride,
+            float* row_loss, int64_t rows, int64_t vocab, float scale, const float* inv_count, int64_t ignore_index,
+            int* status, float z_coef, float* row_z, float softcap, hipStream_t stream) {
+  if (!z_ok(z_coef)) return PT_EINVAL;
+  if (!logits || !targets || !row_loss || rows <= 0 || vocab <= 0) return PT_EINVAL;
+  if (const int rc = logits_ok(logits, logits_stride, dlogits, dlogits_stride, rows, vocab)) return rc;
+  const int nc = (int)((vocab / 8 + kThreads - 1) / kThreads);   // 16-byte chunks per thread
+  with_z_cap(z_coef, softcap, [&](auto Z, auto CAP) {
+    constexpr bool kZ = decltype(Z)::value, kC = decltype(CAP)::value;
+    auto* kernel = nc <= 4 ? ce_kernel<4, kZ, kC> : nc <= 8 ? ce_kernel<8, kZ, kC> : nc <= 16 ? ce_kernel<16, kZ, kC>
+                 : nc <= 24 ? ce_kernel<24, kZ, kC> : nc <= 32 ? ce_kernel<32, kZ, kC> : ce_kernel_2pass<kZ, kC>;
+    kernel<<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, (uint16_t*)dlogits,
+                                                    dlogits_stride, row_loss, (int)vocab, scale, inv_count, ignore_index,
+                                                    status, z_coef, row_z, kC ? pt_cap(softcap) : PtCap{});
+  });
+  PT_CHECK_LAUNCH();
+  return PT_OK;
+}
+
 }  // namespace
 
 extern "C" int pt_cross_entropy_vp_partial(const void* logits, int64_t logits_stride, const int64_t* targets,
@@ -514,17 +574,20 @@ extern "C" int pt_cross_entropy_bwd_lse_shard_z(const void* logits, int64_t logi
                                                 int64_t rows, int64_t vocab_shard, int64_t vocab_lo,
                                                 const float* scale, int64_t scale_stride, int64_t ignore_index,
                                                 float z_coef, hipStream_t stream) {
-  if (!z_ok(z_coef)) return PT_EINVAL;
-  if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab_shard <= 0) return PT_EINVAL;
-  if (scale_stride != 0 && scale_stride != 1) return PT_EINVAL;
-  if (const int rc = logits_ok(logits, logits_stride, dlogits, dlogits_stride, rows, vocab_shard)) return rc;
-  with_z(z_coef, [&](auto Z) {
-    ce_bwd_stream_kernel<decltype(Z)::value><<<(unsigned)rows, kThreads, 0, stream>>>(
-        (const uint16_t*)logits, logits_stride, targets, row_lse, (uint16_t*)dlogits, dlogits_stride, (int)vocab_shard,
-        scale, scale_stride, ignore_index, vocab_lo, z_coef);
-  });
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  return bwd_lse_shard(logits, logits_stride, targets, row_lse, dlogits, dlogits_stride, rows, vocab_shard, vocab_lo,
+                       scale, scale_stride, ignore_index, z_coef, 0.f, stream);
+}
+
+// The soft-capped elementwise backward (see the header): the null / size checks and the cap first, then
+// pt_cross_entropy_bwd_lse_z's checks in its order.
+extern "C" int pt_cross_entropy_bwd_lse_cap(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                            const float* row_lse, void* dlogits, int64_t dlogits_stride, int64_t rows,
+                                            int64_t vocab, const float* scale, int64_t scale_stride,
+                                            int64_t ignore_index, float z_coef, float softcap, hipStream_t stream) {
+  if (!logits || !targets || !row_lse || !dlogits || !scale || rows <= 0 || vocab <= 0) return PT_EINVAL;
+  if (!pt_cap_valid(softcap)) return PT_EINVAL;
+  return bwd_lse_shard(logits, logits_stride, targets, row_lse, dlogits, dlogits_stride, rows, vocab, 0, scale,
+                       scale_stride, ignore_index, z_coef, softcap, stream);
 }
 
 extern "C" int pt_cross_entropy_bwd_lse_shard(const void* logits, int64_t logits_stride, const int64_t* targets,
@@ -581,20 +644,21 @@ extern "C" int pt_cross_entropy_fwd_bwd_z(const void* logits, int64_t logits_str
                                           void* dlogits, int64_t dlogits_stride, float* row_loss, int64_t rows,
                                           int64_t vocab, float scale, const float* inv_count, int64_t ignore_index,
                                           int* status, float z_coef, float* row_z, hipStream_t stream) {
-  if (!z_ok(z_coef)) return PT_EINVAL;
+  return fwd_bwd(logits, logits_stride, targets, dlogits, dlogits_stride, row_loss, rows, vocab, scale, inv_count,
+                 ignore_index, status, z_coef, row_z, 0.f, stream);
+}
+
+// The soft-capped one-read fused form: dlogits (NULL: loss only, nothing for the cap to act on) carries the
+// factor; row_loss and row_z are the uncapped entry's.  Checked like pt_cross_entropy_bwd_lse_cap.
+extern "C" int pt_cross_entropy_fwd_bwd_cap(const void* logits, int64_t logits_stride, const int64_t* targets,
+                                            void* dlogits, int64_t dlogits_stride, float* row_loss, int64_t rows,
+                                            int64_t vocab, float scale, const float* inv_count, int64_t ignore_index,
+                                            int* status, float z_coef, float* row_z, float softcap,
+                                            hipStream_t stream) {
   if (!logits || !targets || !row_loss || rows <= 0 || vocab <= 0) return PT_EINVAL;
-  if (const int rc = logits_ok(logits, logits_stride, dlogits, dlogits_stride, rows, vocab)) return rc;
-  const int nc = (int)((vocab / 8 + kThreads - 1) / kThreads);   // 16-byte chunks per thread
-  with_z(z_coef, [&](auto Z) {
-    constexpr bool kZ = decltype(Z)::value;
-    auto* kernel = nc <= 4 ? ce_kernel<4, kZ> : nc <= 8 ? ce_kernel<8, kZ> : nc <= 16 ? ce_kernel<16, kZ>
-                 : nc <= 24 ? ce_kernel<24, kZ> : nc <= 32 ? ce_kernel<32, kZ> : ce_kernel_2pass<kZ>;
-    kernel<<<(unsigned)rows, kThreads, 0, stream>>>((const uint16_t*)logits, logits_stride, targets, (uint16_t*)dlogits,
-                                                    dlogits_stride, row_loss, (int)vocab, scale, inv_count, ignore_index,
-                                                    status, z_coef, row_z);
-  });
-  PT_CHECK_LAUNCH();
-  return PT_OK;
+  if (!pt_cap_valid(softcap)) return PT_EINVAL;
+  return fwd_bwd(logits, logits_stride, targets, dlogits, dlogits_stride, row_loss, rows, vocab, scale, inv_count,
+                 ignore_index, status, z_coef, row_z, softcap, stream);
 }
 
 extern "C" int pt_cross_entropy_fwd_bwd(const void* logits, int64_t logits_stride, const int64_t* targets,

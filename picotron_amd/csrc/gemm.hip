@@ -83,8 +83,13 @@ enum Epilogue {
   // (max m, sum exp(x - m)) as float2 stats[(col / BN) * M + row] (tile-major: each workgroup
   // writes its rows' pairs as one contiguous run) -- the CE forward (train.py:49) then combines
   // N / BN pairs per row instead of streaming the [M, N] logits again
-  EPI_CE_STATS = 8
+  EPI_CE_STATS = 8,
+  // EPI_CE_STATS_CAP: EPI_CE_STATS with final-logit soft-capping (Gemma-2): the f32 accumulators become
+  // c tanh(acc / c) (pt_softcap, c = GemmArgs::cap) before the one bf16 rounding, so the stored logits
+  // and the statistics taken from them are the capped ones
+  EPI_CE_STATS_CAP = 9
 };
+constexpr bool epi_ce(int e) { return e == EPI_CE_STATS || e == EPI_CE_STATS_CAP; }
 
 // SwiGLU backward of one element, the same expressions as csrc/swiglu.hip (torch's bf16 roundings):
 // d = dh (already a bf16 value), g / u the forward's activations -> og = dg, ou = du
@@ -123,6 +128,7 @@ struct GemmArgs {
   // split-K: the launch computes ksplit K-slices of K / ksplit each (EPI_F32 only); slice s writes
   // its f32 partial at C + s * kpart_stride (pt_gemm_splitk_reduce sums them into the real sink)
   int ksplit;
+  float cap;                 // EPI_CE_STATS_CAP: the soft cap c (read by that epilogue alone)
   int64_t kpart_stride;
 };
 
@@ -413,15 +419,35 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
   const int64_t mrow0 = m0 - a.cseg[cs] + wm * TM;
   const int ncol0 = n0 + wn * TN;
   if (EPI == EPI_BF16 || EPI == EPI_BF16_ACC || EPI == EPI_BF16_RES || EPI == EPI_SWIGLU_BWD || EPI == EPI_ROPE ||
-      EPI == EPI_CE_STATS) {
+      epi_ce(EPI)) {
     constexpr int ROWB = TN * 2 + 16;  // +16 B pad: spreads the staging writes over banks
+    if constexpr (EPI == EPI_CE_STATS_CAP) {
+      // the soft cap on the f32 accumulators, a fragment's 4 columns at a time (the multiplies, the add
+      // and the fma as packed pairs, 4 v_exp + 4 v_rcp), then the same 8-byte staging write
+      const float c = a.cap, k1 = pt_cap_k1(c);
 #pragma unroll
-    for (int i = 0; i < FM; ++i)
+      for (int i = 0; i < FM; ++i)
 #pragma unroll
-      for (int j = 0; j < FN; ++j) {  // 4 consecutive columns of one row: one 8-byte write
-        const u32x2_t w = {pack_bf2(acc[i][j][0], acc[i][j][1]), pack_bf2(acc[i][j][2], acc[i][j][3])};
-        *(__attribute__((address_space(3))) u32x2_t*)(st + acc_row(i, lane) * ROWB + acc_col(j, 0, lane) * 2) = w;
-      }
+        for (int j = 0; j < FN; ++j) {
+          f32x4_t e = acc[i][j] * k1;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_exp2f(e[r]);
+          e += 1.0f;
+#pragma unroll
+          for (int r = 0; r < 4; ++r) e[r] = __builtin_amdgcn_rcpf(e[r]);
+          const f32x4_t t = __builtin_elementwise_fma(e, (f32x4_t)(-2.0f), (f32x4_t)(1.0f)) * c;   // pt_softcap
+          const u32x2_t w = {pack_bf2(t[0], t[1]), pack_bf2(t[2], t[3])};
+          *(__attribute__((address_space(3))) u32x2_t*)(st + acc_row(i, lane) * ROWB + acc_col(j, 0, lane) * 2) = w;
+        }
+    } else {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int j = 0; j < FN; ++j) {  // 4 consecutive columns of one row: one 8-byte write
+          const u32x2_t w = {pack_bf2(acc[i][j][0], acc[i][j][1]), pack_bf2(acc[i][j][2], acc[i][j][3])};
+          *(__attribute__((address_space(3))) u32x2_t*)(st + acc_row(i, lane) * ROWB + acc_col(j, 0, lane) * 2) = w;
+        }
+    }
     __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): wave-private staging, no barrier needed
     // keep the epilogue's loads below the staging (the accumulators die there): hoisted above it,
     // they would be live next to all of acc and spill
@@ -501,7 +527,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
         const int row = (g0 + q) * RPI + lane / CPR, ch = lane % CPR;
         bf16x8 v = lds_ld8(st + row * ROWB + ch * 16);
         uint16_t* dst = C + (mrow0 + row) * ldc + ncol0 + ch * 8;
-        if constexpr (EPI == EPI_CE_STATS) {
+        if constexpr (epi_ce(EPI)) {
           // the row's TN = 64 columns of this wave are the CPR = 8 consecutive lanes sharing
           // lane / 8: max and sum-exp of the stored (bf16) values over the 8 x 8, one pair per row
           static_assert(TN == 64, "CE statistics: 64-column wave tiles (8 lanes per row)");
@@ -888,7 +914,7 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
     float2* xs = (float2*)(smem + 8 * (TM * (TN * 2 + 16)));
     epilogue<TM, TN, EPI>(a, acc, smem + wave * (TM * (TN * 2 + 16)), m0, n0, wm, wn, lane, xs + wave * TM,
                           (int64_t)ks * a.kpart_stride);
-    if constexpr (EPI == EPI_CE_STATS) {
+    if constexpr (epi_ce(EPI)) {
       __syncthreads();
       if (wn == 0) ce_stats_merge<4, TM, TN>(a, xs, m0, n0, wm, lane);
     }
@@ -1128,7 +1154,7 @@ __device__ __forceinline__ void gemm_ring3_tile(const GemmArgs& a, const int til
     float2* xs = (float2*)(smem + 8 * (64 * (64 * 2 + 16)));  // EPI_CE_STATS row statistics
     epilogue<64, 64, EPI>(a, acc, smem + wave * (64 * (64 * 2 + 16)), m0, n0, wm, wn, lane, xs + wave * 64,
                           (int64_t)ks * a.kpart_stride);
-    if constexpr (EPI == EPI_CE_STATS) {
+    if constexpr (epi_ce(EPI)) {
       __syncthreads();
       if (wn == 0) ce_stats_merge<2, 64, 64>(a, xs, m0, n0, wm, lane);
     }
@@ -1450,10 +1476,11 @@ constexpr TileDesc kTiles[] = {
     {TILE_S128, 128, 128, 256, 2 * (128 + 128) * BK * 2, 4 * 64 * kWaveStage64, 0, kEpiPlain, kAllLayouts},
     {TILE_S64, 64, 64, 256, 2 * (64 + 64) * BK * 2, 4 * 32 * (32 * 2 + 16), 0, kEpiPlain, kAllLayouts},
     {TILE_8PH, 256, 256, 512, 2 * 4 * 128 * BK * 2, 8 * 128 * kWaveStage64, 8 * 128 * 8,
-     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_SWIGLU_FWD) | epi_bit(EPI_SWIGLU_BWD),
+     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_CE_STATS_CAP) | epi_bit(EPI_SWIGLU_FWD) |
+         epi_bit(EPI_SWIGLU_BWD),
      kPhasedLayouts},
     {TILE_4PH, 256, 128, 512, 3 * 3 * 128 * BK * 2, 8 * 64 * kWaveStage64, 8 * 64 * 8,
-     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS), kPhasedLayouts},
+     kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_CE_STATS_CAP), kPhasedLayouts},
     {TILE_KH, 256, 128, 512, 3 * 3 * 128 * BK * 2, cmax(8 * 16 * 64 * 16, 8 * 64 * kWaveStage64), 0,
      kEpiPlain | epi_bit(EPI_ROPE), kPhasedLayouts},
     {TILE_HQ, 128, 128, 512, 4 * 2 * 128 * BK * 2, cmax(8 * 8 * 64 * 16, 8 * 32 * kWaveStage64), 0, kEpiPlain,
@@ -1470,7 +1497,7 @@ constexpr bool tile_built(const TileDesc& t, bool ak, bool bkc, int epi) {
   return (t.epis & epi_bit(epi)) && (t.layouts & epi_layouts(epi) & layout_bit(ak, bkc));
 }
 constexpr int tile_smem(const TileDesc& t, int epi) {
-  return cmax(t.smem_main, t.smem_epi + (epi == EPI_CE_STATS ? t.smem_ce : 0));
+  return cmax(t.smem_main, t.smem_epi + (epi_ce(epi) ? t.smem_ce : 0));
 }
 
 // The one launch: the kernel's dynamic-LDS attribute is set on the first launch of each instantiation.
@@ -1562,6 +1589,9 @@ int dispatch(GemmGroup& g, int tile, int a_kcontig, int b_kcontig, int epilogue,
     case EPI_SWIGLU_BWD: return dispatch_layout<EPI_SWIGLU_BWD>(g, tile, a_kcontig, b_kcontig, s);
     case EPI_ROPE: return dispatch_layout<EPI_ROPE>(g, tile, a_kcontig, b_kcontig, s);
     case EPI_CE_STATS: return dispatch_layout<EPI_CE_STATS>(g, tile, a_kcontig, b_kcontig, s);
+    // reached with a cap from pt_gemm_ce_stats_cap alone: the generic entries have none to give
+    case EPI_CE_STATS_CAP:
+      return g.p[0].cap > 0.f ? dispatch_layout<EPI_CE_STATS_CAP>(g, tile, a_kcontig, b_kcontig, s) : PT_EINVAL;
     default: return PT_EINVAL;
   }
 }
@@ -1791,7 +1821,7 @@ int launch_group(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int t
   const bool auto_tile = tile < 0;
   if (epilogue == EPI_ROPE && tile < 0) tile = args_fit(g.p[0], TILE_4PH) ? TILE_4PH : TILE_8PH;
   if (tile < 0) tile = pick_group_tile(g, !a_kcontig && b_kcontig);
-  if (auto_tile && tile == TILE_4PH && kh_enabled(g) && epilogue != EPI_CE_STATS) tile = TILE_KH;
+  if (auto_tile && tile == TILE_4PH && kh_enabled(g) && !epi_ce(epilogue)) tile = TILE_KH;
   // A K-segmented (A2): the 8-phase kernel only; the RoPE projection has no such operand
   for (int i = 0; i < g.nprob; ++i)
     if (!args_fit(g.p[i], tile) || (g.p[i].A2 && tile != TILE_8PH && epilogue != EPI_ROPE)) return PT_EUNSUPPORTED;
@@ -2065,21 +2095,37 @@ int pt_gemm_rope(const void* A, int64_t lda, const void* const* B, const int64_t
 // W[N, K]^T stored bf16, and float2 stats[N / block][M] = (max, sum exp(x - max)) of the stored
 // values per row and block-column tile (block 256: the 8-phase 256x256 kernel, 128: the 4-phase
 // 256x128 one).  M % 256 == 0, N % block == 0.
-int pt_gemm_ce_stats(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* stats,
-                     int64_t block, int64_t M, int64_t N, int64_t K, hipStream_t stream) {
+static int gemm_ce_stats(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* stats,
+                         int64_t block, int64_t M, int64_t N, int64_t K, float softcap, hipStream_t stream) {
   if (!stats || !pt_aligned16(stats)) return PT_EINVAL;
   if (block != 256 && block != 128) return PT_EUNSUPPORTED;
   const int tile = block == 256 ? TILE_8PH : TILE_4PH;
+  const int epilogue = softcap > 0.f ? EPI_CE_STATS_CAP : EPI_CE_STATS;
   pt_gemm_problem q = problem_a(A, lda, M, N, K);
   problem_b(q, &W, &ldw, nullptr, 1, 0);
   problem_c(q, &C, &ldc, nullptr, 1);
   GemmGroup g{};
-  const int rc = fill_group(g, &q, 1, EPI_CE_STATS);
+  const int rc = fill_group(g, &q, 1, epilogue);
   if (rc) return rc;
   if (!args_fit(g.p[0], tile)) return PT_EUNSUPPORTED;
   if (ldc & 7) return PT_EALIGN;
   g.p[0].stats = stats;
-  return launch_group(g, 1, 1, EPI_CE_STATS, tile, stream);
+  g.p[0].cap = softcap;
+  return launch_group(g, 1, 1, epilogue, tile, stream);
+}
+
+int pt_gemm_ce_stats(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* stats,
+                     int64_t block, int64_t M, int64_t N, int64_t K, hipStream_t stream) {
+  return gemm_ce_stats(A, lda, W, ldw, C, ldc, stats, block, M, N, K, 0.f, stream);
+}
+
+// pt_gemm_ce_stats with final-logit soft-capping (EPI_CE_STATS_CAP): C = bf16(softcap tanh(acc / softcap)) and the
+// statistics of those stored values.  The null / size checks and the cap first, then pt_gemm_ce_stats's own.
+int pt_gemm_ce_stats_cap(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, float* stats,
+                         int64_t block, int64_t M, int64_t N, int64_t K, float softcap, hipStream_t stream) {
+  if (!A || !W || !C || !stats || M <= 0 || N <= 0 || K <= 0) return PT_EINVAL;
+  if (!pt_cap_valid(softcap)) return PT_EINVAL;
+  return gemm_ce_stats(A, lda, W, ldw, C, ldc, stats, block, M, N, K, softcap, stream);
 }
 
 // Tile the auto-pick chooses for one [M, N] problem with the given segment boundaries (see

@@ -563,20 +563,49 @@ def linear(x, weight, tp_reduce_fwd=False, tp_reduce_bwd=False):
 _CE_STATS = {}
 
 
-def _stash_ce_stats(y, stats):
+def _stash_ce_stats(y, stats, cap=None):
     for key in [k for k, e in _CE_STATS.items() if e[0]() is None]:
         del _CE_STATS[key]
-    _CE_STATS[y.data_ptr()] = (weakref.ref(y), y._version, y.numel(), stats)
+    _CE_STATS[y.data_ptr()] = (weakref.ref(y), y._version, y.numel(), stats, cap)
+
+
+def _ce_entry_of(e, lg):
+    """The stashed (stats, cap record) if the entry e is of exactly these logits, else (None, None)."""
+    if e is None:
+        return None, None
+    ref, version, numel, stats, cap = e
+    if ref() is None or lg._version != version or lg.numel() != numel or \
+            (stats is not None and stats.shape[1] != lg.shape[0]):
+        return None, None
+    return stats, cap
 
 
 def _take_ce_stats(lg):
-    e = _CE_STATS.pop(lg.data_ptr(), None)
-    if e is None:
-        return None
-    ref, version, numel, stats = e
-    if ref() is None or lg._version != version or lg.numel() != numel or stats.shape[1] != lg.shape[0]:
-        return None
-    return stats
+    return _ce_entry_of(_CE_STATS.pop(lg.data_ptr(), None), lg)[0]
+
+
+class _CapRecord:
+    """What travels beside soft-capped logits (see CappedLMHeadFunction): the cap and, weakly, the lm_head
+    node's second output, the stand-in for the raw logits that a cross-entropy on these logits differentiates.
+    Weakly, because the stand-in owns the autograd graph: the logits the caller holds keep it alive
+    (_carry_raw), the module-level table never does, so logits that are dropped free their graph and their
+    entry is purged like an uncapped one."""
+
+    def __init__(self, cap):
+        self.cap, self.raw = cap, lambda: None
+
+
+def _carry_raw(src, dst):
+    """dst (the logits handed on: a view, a HipLogits of src) keeps src's raw stand-in alive as src does."""
+    raw = getattr(src, "_pt_raw", None)
+    if raw is not None and dst is not src:
+        dst._pt_raw = raw
+    return dst
+
+
+def _peek_cap(lg):
+    """The cap record of exactly these logits (same storage, version and size as stashed), if any."""
+    return _ce_entry_of(_CE_STATS.get(lg.data_ptr()), lg)[1]
 
 
 def ce_stats_enabled():
@@ -612,8 +641,70 @@ class LMHeadFunction(torch.autograd.Function):
         return (dx.view(ctx.xshape) if dx is not None else None), None, None
 
 
-def lm_head_linear(x, weight):
-    """Y = x W^T for the lm_head: with the CE statistics when the shape tiles, else plain linear."""
+class CappedLMHeadFunction(torch.autograd.Function):
+    """final_proj(x) with final-logit soft-capping (Gemma-2's final_logit_softcapping, tp 1): returns
+    (t, raw).  t = bf16(c tanh(acc / c)) [.., V] are the logits, capped in the GEMM's epilogue together with
+    the CE statistics (csrc/gemm.hip EPI_CE_STATS_CAP) -- or, where the shape does not tile or ce_stats is off,
+    by the row kernel in place over the plain GEMM's output.  raw [T, V] is a stand-in without storage (one
+    element, strides 0) for the logits before the cap: nothing reads it, it exists so that a consumer which
+    can produce d loss / d raw itself has an edge of its own to send it along.  The cross-entropy is that
+    consumer (CrossEntropyFunction's raw / cap): its backward kernel folds 1 - (t / c)^2 into the store it
+    makes anyway.  Every other consumer differentiates t as usual, and this node applies the factor to
+    that gradient (pt_softcap_bwd) before the dX / dW GEMMs.  Autograd sums each edge on its own,
+    so a second consumer of the logits can never meet a gradient that already carries the factor.
+    What this costs: the cross-entropy's share never passes through t, so torch.autograd.grad(loss, logits)
+    finds no path and logits.retain_grad() shows the other consumers' share only."""
+
+    @staticmethod
+    def forward(ctx, x, weight, cap):
+        x2 = _contig2d(x)
+        T, V = x2.shape[0], weight.shape[0]
+        if ce_stats_enabled() and K.ce_stats_fusable(T, V) and x2.shape[1] % 64 == 0:
+            t, stats = K.linear_ce_stats(x2, weight, softcap=cap)
+        else:
+            t, stats = K.softcap_fwd_(K.linear_fwd(x2, [weight]), cap), None
+        _stash_ce_stats(t, stats, _CapRecord(cap))
+        ctx.save_for_backward(x2, weight, t)
+        ctx.xshape, ctx.cap = x.shape, cap
+        ctx.set_materialize_grads(False)
+        raw = torch.empty_strided((T, V), (0, 0), dtype=t.dtype, device=t.device)
+        return t.view(*x.shape[:-1], V), raw
+
+    @staticmethod
+    def backward(ctx, dt, draw):
+        x2, weight, t = ctx.saved_tensors
+        if _peek_cap(t) is not None:   # no cross-entropy took the record: it (and raw's graph) ends here
+            del _CE_STATS[t.data_ptr()]
+        dy2 = None
+        if dt is not None:
+            # in place over a copy _contig2d made; out of place over the caller's own tensor (autograd may
+            # hand the same gradient to a sibling node, and backward(gradient=g) hands in the user's g)
+            dt2 = _contig2d(dt)
+            dy2 = K.softcap_bwd_(dt2, t, ctx.cap, out=None if dt2.data_ptr() != dt.data_ptr() else torch.empty_like(dt2))
+        if draw is not None:
+            dy2 = _contig2d(draw) if dy2 is None else dy2.add_(draw)
+        dx = None
+        if dy2 is not None and ctx.needs_input_grad[0]:
+            dx = K.linear_dgrad(dy2, [weight])
+        if dy2 is not None and ctx.needs_input_grad[1]:
+            wgrad(dy2, x2, [weight])
+        return (dx.view(ctx.xshape) if dx is not None else None), None, None
+
+
+def lm_head_linear(x, weight, softcap=None):
+    """Y = x W^T for the lm_head: with the CE statistics when the shape tiles, else plain linear.
+    softcap c (a finite float > 0; None or 0: none, and every path above as it is): Y = c tanh(x W^T / c),
+    HF's final_logit_softcapping (CappedLMHeadFunction)."""
+    cap = K.softcap_coef(softcap, "lm_head_linear")
+    if cap is not None:
+        if x.dtype != torch.bfloat16 or weight.dtype != torch.bfloat16:
+            raise NotImplementedError("lm_head_linear: softcap takes bf16 activations and weights")
+        t, raw = CappedLMHeadFunction.apply(x, weight, cap)
+        t._pt_raw = raw
+        rec = _peek_cap(_contig2d(t))
+        if rec is not None:
+            rec.raw = weakref.ref(raw)
+        return t
     T = x.numel() // x.shape[-1]
     if (ce_stats_enabled() and x.dtype == torch.bfloat16 and weight.dtype == torch.bfloat16
             and K.ce_stats_fusable(T, weight.shape[0]) and x.shape[-1] % 64 == 0):
@@ -1747,10 +1838,14 @@ class CrossEntropyFunction(torch.autograd.Function):
     z > 0 (the auxiliary z-loss, z lse^2 per valid row): the same two launches through the _z kernels --
     the forward adds the term from the LSE it already holds, the backward multiplies the softmax by
     1 + 2 z lse -- and the outputs are (loss, z_part), z_part f32, reduced like the loss, not
-    differentiable."""
+    differentiable.
+    raw, cap (_ce_apply): the logits are a soft-capped lm_head's, c tanh(raw / c), given detached; the
+    gradient goes to that node's stand-in `raw` as d loss / d raw, written by the same backward launch with
+    1 - (logits / c)^2 folded into the store (the _cap kernel)."""
 
     @staticmethod
-    def forward(ctx, logits, targets, ignore_index, reduction, z=0.0):
+    def forward(ctx, logits, targets, ignore_index, reduction, z=0.0, raw=None, cap=None):
+        ctx.cap = cap
         lg = _contig2d(logits)
         tg = targets.reshape(-1)
         stats = _take_ce_stats(lg)   # the lm_head GEMM's statistics of exactly these logits, if any
@@ -1787,9 +1882,14 @@ class CrossEntropyFunction(torch.autograd.Function):
             scale = g.float().reshape(1)
         else:
             scale = g.float().reshape(1) * inv[0]
-        dl = K.cross_entropy_grad_lse(lg, tg, row_lse, scale, ctx.ignore_index, z_loss=ctx.z)
+        if ctx.cap is None:
+            dl = K.cross_entropy_grad_lse(lg, tg, row_lse, scale, ctx.ignore_index, z_loss=ctx.z)
+        else:
+            dl = K.cross_entropy_grad_lse(lg, tg, row_lse, scale, ctx.ignore_index, z_loss=ctx.z, softcap=ctx.cap)
         if dl.shape[1] != ctx.vocab:
             dl = dl[:, :ctx.vocab]
+        if ctx.cap is not None:   # (the detached logits take none)
+            return None, None, None, None, None, dl, None
         return dl.reshape(ctx.shape), None, None, None, None
 
 
@@ -1835,7 +1935,8 @@ class HipLogits(torch.Tensor):
             kwargs = {k: (_vp_real(v) if _is_vp(v) else v) for k, v in kwargs.items()}
             return HipLogits.__torch_function__(func, types, args, kwargs)
         if func in cls._KEEP:
-            return super().__torch_function__(func, types, args, kwargs)
+            out = super().__torch_function__(func, types, args, kwargs)
+            return _carry_raw(args[0], out) if args and isinstance(out, HipLogits) else out
         with torch._C.DisableTorchFunctionSubclass():
             return func(*args, **kwargs)
 
@@ -1859,9 +1960,18 @@ class HipHidden(torch.Tensor):
 
 
 def _dispatch_linear(input, weight, bias=None):
-    x, weight = _plain(input), _plain(weight)
-    y = lm_head_linear(x, weight) if bias is None else linear(x, weight) + bias
-    return as_logits(y)
+    # (the hidden state carries Llama's final_logit_softcapping: model._tag_final)
+    return lm_head_logits(_plain(input), _plain(weight), bias, getattr(input, "_pt_final_softcap", None))
+
+
+def lm_head_logits(x, weight, bias=None, softcap=None):
+    """The lm_head as every holder of its weight runs it (model.Linear, model.lm_head, an nn.Linear on a
+    HipHidden): HipLogits of lm_head_linear, or of linear + bias; the cap and a bias do not combine."""
+    if softcap is not None:
+        if bias is not None:
+            raise NotImplementedError("final_logit_softcapping on an lm_head with a bias")
+        return as_logits(lm_head_linear(x, weight, softcap=softcap))
+    return as_logits(lm_head_linear(x, weight) if bias is None else linear(x, weight) + bias)
 
 
 def as_hidden(t):
@@ -1892,7 +2002,7 @@ def as_logits(t):
     """Tag an lm_head output so F.cross_entropy on it (or on its views) takes the HIP kernel.
     (Tensor.as_subclass is not dispatched to __torch_function__: a HipLogits -- a vocab-parallel
     stand-in among them -- is returned as it is.)"""
-    return t if isinstance(t, HipLogits) else t.as_subclass(HipLogits)
+    return t if isinstance(t, HipLogits) else _carry_raw(t, t.as_subclass(HipLogits))
 
 
 def cross_entropy(input, target, reduction="mean", ignore_index=-100, z_loss=0.0, return_z_loss=False):
@@ -1936,11 +2046,22 @@ def _cross_entropy(input, target, reduction, ignore_index, z):
             raise ValueError(f"cross_entropy: input [B, V, S] = {tuple(input.shape)} needs target [B, S], got "
                              f"{tuple(target.shape)}")
         rows = input.transpose(1, 2).reshape(B * S, V)
-        out = CrossEntropyFunction.apply(rows, target.reshape(-1), ignore_index, reduction, z)
+        out = _ce_apply(rows, target.reshape(-1), ignore_index, reduction, z)
         if reduction != "none":
             return out
         return tuple(o.view(B, S) for o in out) if z > 0 else out.view(B, S)
     if input.dim() != 2 or target.dim() != 1 or target.shape[0] != input.shape[0]:
         raise ValueError(f"cross_entropy: expected input [N, V] and target [N] (or [B, V, S] / [B, S]), got "
                          f"{tuple(input.shape)} / {tuple(target.shape)}")
-    return CrossEntropyFunction.apply(input, target, ignore_index, reduction, z)
+    return _ce_apply(input, target, ignore_index, reduction, z)
+
+
+def _ce_apply(rows, target, ignore_index, reduction, z):
+    """CrossEntropyFunction on [N, V] rows.  Rows that are a soft-capped lm_head's logits, unmodified (their
+    cap record is still beside them), are differentiated through that node's raw stand-in instead: the
+    node gets d loss / d raw, the factor folded in by the backward kernel, on an edge of its own."""
+    rec = _peek_cap(rows) if torch.is_grad_enabled() and rows.requires_grad and rows.is_contiguous() else None
+    raw = rec.raw() if rec is not None else None   # (None: the logits it rode on were dropped for a bare view)
+    if raw is None or not raw.requires_grad:
+        return CrossEntropyFunction.apply(rows, target, ignore_index, reduction, z)
+    return CrossEntropyFunction.apply(rows.detach(), target, ignore_index, reduction, z, raw, rec.cap)

@@ -1268,10 +1268,51 @@ def z_coef(z_loss):
     return z
 
 
+def softcap_coef(softcap, what="softcap"):
+    """Final-logit soft-capping's cap as the float the kernels receive (its f32 value), None for no cap (None
+    or 0); ValueError unless a finite Python number > 0 otherwise.  Checked before the library is touched."""
+    if softcap is None or (not isinstance(softcap, bool) and isinstance(softcap, (int, float)) and softcap == 0):
+        return None
+    if isinstance(softcap, bool) or not isinstance(softcap, (int, float)):
+        raise ValueError(f"{what}: softcap must be a Python float or None, got {type(softcap).__name__} {softcap!r}")
+    c = ctypes.c_float(softcap).value if math.isfinite(softcap) else softcap
+    if not (math.isfinite(c) and c > 0):
+        raise ValueError(f"{what}: softcap must be a finite float > 0 (None or 0: no cap), got {softcap!r}")
+    return c
+
+
+def softcap_fwd_(x, softcap, out=None):
+    """y = bf16(c tanh(x / c)) over a [rows, cols] bf16 view (row stride free), in place unless `out` is given."""
+    c = softcap_coef(softcap, "softcap_fwd_")
+    _req(c is not None, "softcap_fwd_: a cap is required")
+    y = x if out is None else out
+    _bf16_rowmajor(x, "x")
+    _bf16_rowmajor(y, "out")
+    _req(y.shape == x.shape, "softcap_fwd_: out shaped like x")
+    rc = _C.lib().pt_softcap_fwd(_ptr(x), x.stride(0), _ptr(y), y.stride(0), x.shape[0], x.shape[1], c,
+                                 _C.stream_ptr(x.device))
+    _C.check(rc, "pt_softcap_fwd")
+    return y
+
+
+def softcap_bwd_(dy, y, softcap, out=None):
+    """dx = bf16(dy (1 - (y / c)^2)), y the capped forward output: in place over dy unless `out` is given."""
+    c = softcap_coef(softcap, "softcap_bwd_")
+    _req(c is not None, "softcap_bwd_: a cap is required")
+    dx = dy if out is None else out
+    for t, name in ((dy, "dy"), (y, "y"), (dx, "out")):
+        _bf16_rowmajor(t, name)
+    _req(y.shape == dy.shape and dx.shape == dy.shape, "softcap_bwd_: dy, y and out of one shape")
+    rc = _C.lib().pt_softcap_bwd(_ptr(dy), dy.stride(0), _ptr(y), y.stride(0), _ptr(dx), dx.stride(0), dy.shape[0],
+                                 dy.shape[1], c, _C.stream_ptr(dy.device))
+    _C.check(rc, "pt_softcap_bwd")
+    return dx
+
+
 def _ce_native(name, device, args, z=0.0, row_z=None, what=None):
     """One CE native call on torch's current stream: name(*args, stream) when z == 0; with z > 0 its _z
     namesake, which takes z (and row_z [rows] f32, where the entry point writes one) between args and
-    the stream."""
+    the stream.  (The _cap entries take z, row_z where there is one, and the cap as part of args.)"""
     if z > 0:
         name, args = name + "_z", (*args, z) if row_z is None else (*args, z, _ptr(row_z))
     rc = getattr(_C.lib(), name)(*args, _C.stream_ptr(device))
@@ -1297,11 +1338,14 @@ def _ce_bwd_args(rows, targets, row_lse, scale_dev):
     return targets, scale_dev.contiguous()
 
 
-def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace=True, z_loss=0.0):
+def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace=True, z_loss=0.0, softcap=None):
     """logits [rows, V] bf16, targets [rows] int64.  Returns (loss (f32 scalar tensor, mean over
     valid rows, *not* multiplied by scale), dlogits (aliases logits when inplace), inv_count); with
-    z_loss > 0 the loss and dlogits carry the z term and a fourth element is the mean z part."""
+    z_loss > 0 the loss and dlogits carry the z term and a fourth element is the mean z part.
+    softcap c: the logits are soft-capped ones, c tanh(raw / c), and dlogits is the raw logits' gradient
+    (times 1 - (logits / c)^2)."""
     z = z_coef(z_loss)
+    cap = softcap_coef(softcap, "cross_entropy_fwd_bwd")
     _bf16_rowmajor(logits, "logits")
     targets = targets.contiguous().to(torch.int64)
     rows, vocab = logits.shape
@@ -1310,9 +1354,12 @@ def cross_entropy_fwd_bwd(logits, targets, scale=1.0, ignore_index=-100, inplace
     row_loss = torch.empty(rows, dtype=torch.float32, device=logits.device)
     dlogits = logits if inplace else torch.empty_like(logits)
     row_z = torch.empty(rows, dtype=torch.float32, device=logits.device) if z > 0 else None
-    _ce_native("pt_cross_entropy_fwd_bwd", logits.device,
-               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits), dlogits.stride(0), _ptr(row_loss), rows,
-                vocab, float(scale), _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device))), z, row_z)
+    args = (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(dlogits), dlogits.stride(0), _ptr(row_loss), rows,
+            vocab, float(scale), _ptr(inv_count), int(ignore_index), _ptr(status_word(logits.device)))
+    if cap is None:
+        _ce_native("pt_cross_entropy_fwd_bwd", logits.device, args, z, row_z)
+    else:
+        _ce_native("pt_cross_entropy_fwd_bwd_cap", logits.device, (*args, z, _ptr(row_z), cap))
     _status_posted(logits.device)
     loss = row_loss.sum() * inv_count[0]
     return (loss, dlogits, inv_count) if row_z is None else (loss, dlogits, inv_count, row_z.sum() * inv_count[0])
@@ -1383,18 +1430,23 @@ def cross_entropy_loss_lse(logits, targets, ignore_index=-100, out_dtype=torch.f
     return _ce_lse_result(row_loss, row_lse, row_z, targets, ignore_index, out_dtype, reduction)
 
 
-def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-100, z_loss=0.0):
+def cross_entropy_grad_lse(logits, targets, row_lse, scale_dev, ignore_index=-100, z_loss=0.0, softcap=None):
     """dlogits = (exp(x - row_lse) - onehot) * scale_dev[0] (one f32 device scalar) or
     * scale_dev[row] (f32 [rows]: reduction='none'): elementwise, no row reduction.  z_loss > 0: the
-    softmax term times 1 + 2 z_loss row_lse."""
+    softmax term times 1 + 2 z_loss row_lse.  softcap c (the logits are soft-capped ones): the whole
+    times 1 - (x / c)^2, the gradient of the raw logits."""
     z = z_coef(z_loss)
+    cap = softcap_coef(softcap, "cross_entropy_grad_lse")
     _bf16_rowmajor(logits, "logits")
     rows, vocab = logits.shape
     targets, scale_dev = _ce_bwd_args(rows, targets, row_lse, scale_dev)
     dl = torch.empty(rows, vocab, dtype=BF16, device=logits.device)
-    _ce_native("pt_cross_entropy_bwd_lse", logits.device,
-               (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vocab,
-                _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index)), z)
+    args = (_ptr(logits), logits.stride(0), _ptr(targets), _ptr(row_lse), _ptr(dl), dl.stride(0), rows, vocab,
+            _ptr(scale_dev), int(scale_dev.numel() != 1), int(ignore_index))
+    if cap is None:
+        _ce_native("pt_cross_entropy_bwd_lse", logits.device, args, z)
+    else:
+        _ce_native("pt_cross_entropy_bwd_lse_cap", logits.device, (*args, z, cap))
     return dl
 
 
@@ -1958,10 +2010,12 @@ def ce_stats_fusable(T, V):
     return ce_stats_block(T, V) is not None
 
 
-def linear_ce_stats(x2d, weight):
+def linear_ce_stats(x2d, weight, softcap=None):
     """lm_head (model.py:270) with the CE forward's statistics in the GEMM epilogue: returns (logits
     [T, V] bf16, stats [V / block, T, 2] f32 = per column tile and row (max, sum exp(x - max)) of
-    the stored bf16 logits)."""
+    the stored bf16 logits).  softcap c: the stored logits are bf16(c tanh(acc / c)), capped on the f32
+    accumulators in the same epilogue, and the statistics are theirs."""
+    cap = softcap_coef(softcap, "linear_ce_stats")
     _bf16_rowmajor(x2d, "x")
     T, K = x2d.shape
     V = weight.shape[0]
@@ -1970,10 +2024,14 @@ def linear_ce_stats(x2d, weight):
     _req(block is not None and K % 64 == 0, "linear_ce_stats: T % 256, V % 128, K % 64")
     y = torch.empty(T, V, dtype=BF16, device=x2d.device)
     stats = torch.empty(V // block, T, 2, dtype=torch.float32, device=x2d.device)
-    rc = _timed("linear_ce_stats", 2.0 * T * V * K, (T, V, K, EPI_BF16), _C.lib().pt_gemm_ce_stats, _ptr(x2d),
-                x2d.stride(0), _ptr(weight), K, _ptr(y), y.stride(0), _ptr(stats), block, T, V, K,
-                _C.stream_ptr(x2d.device))
-    _C.check(rc, "pt_gemm_ce_stats")
+    args = (_ptr(x2d), x2d.stride(0), _ptr(weight), K, _ptr(y), y.stride(0), _ptr(stats), block, T, V, K)
+    if cap is None:
+        rc = _timed("linear_ce_stats", 2.0 * T * V * K, (T, V, K, EPI_BF16), _C.lib().pt_gemm_ce_stats, *args,
+                    _C.stream_ptr(x2d.device))
+    else:
+        rc = _timed("linear_ce_stats_cap", 2.0 * T * V * K, (T, V, K, EPI_BF16), _C.lib().pt_gemm_ce_stats_cap, *args,
+                    cap, _C.stream_ptr(x2d.device))
+    _C.check(rc, "pt_gemm_ce_stats" if cap is None else "pt_gemm_ce_stats_cap")
     return y, stats
 
 

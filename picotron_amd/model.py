@@ -160,7 +160,13 @@ def _tag_final(norm, y):
     """Llama's final_norm hands its output on as functional.HipHidden, so whatever module holds the
     lm_head -- also a torch nn.Linear called directly (PipelineParallel.forward,
     pipeline_parallel.py:62-63, after checkpoint.py:89-90) -- runs the HIP lm_head GEMM."""
-    return FN.as_hidden(y) if getattr(norm, "_pt_final_norm", False) else y
+    if not getattr(norm, "_pt_final_norm", False):
+        return y
+    h = FN.as_hidden(y)
+    cap = getattr(norm, "_pt_final_softcap", None)
+    if cap is not None:   # final_logit_softcapping travels with the hidden state to such an lm_head
+        h._pt_final_softcap = cap
+    return h
 
 
 def _norm_mode(norm):
@@ -195,8 +201,9 @@ class Linear(nn.Module):
 
     def forward(self, x):
         x = FN._plain(x)
-        if getattr(self, "_pt_lm_head", False) and self.bias is None:
-            return FN.as_logits(FN.lm_head_linear(x, self.weight))
+        cap = getattr(self, "_pt_final_softcap", None)   # Llama's final_logit_softcapping, on its lm_head
+        if cap is not None or (getattr(self, "_pt_lm_head", False) and self.bias is None):
+            return FN.lm_head_logits(x, self.weight, self.bias, cap)
         y = FN.linear(x, self.weight)
         y = y if self.bias is None else y + self.bias
         # the lm_head (Llama tags its final_proj): keep F.cross_entropy on the HIP kernel also when
@@ -692,13 +699,24 @@ class Llama(nn.Module):
         self.num_layers = config.num_hidden_layers
         self.model_config = config
         layer_types(config)   # (refused here, before any layer is built)
+        # HF's final_logit_softcapping (Gemma-2: 30; Grok-1): logits = c tanh(logits / c), capped in the lm_head
+        # GEMM's epilogue and differentiated in the cross-entropy backward's store (FN.CappedLMHeadFunction)
+        self.final_logit_softcapping = K.softcap_coef(getattr(config, "final_logit_softcapping", None),
+                                                      "final_logit_softcapping")
+        if self.final_logit_softcapping is not None and pgm.current().tp_world_size > 1:
+            raise NotImplementedError("final_logit_softcapping under tensor parallelism (tp > 1): the "
+                                      "vocab-parallel lm_head and its 16-byte parts do not carry the cap")
         self.embedding = Embedding(self.vocab_size, self.hidden_size)
         self.decoder_layers = nn.ModuleList([DecoderLayer(config, layer_idx=i) for i in range(self.num_layers)])
         self.final_proj = Linear(self.hidden_size, self.vocab_size, bias=False)
         self.final_proj._pt_lm_head = True
+        if self.final_logit_softcapping is not None:
+            self.final_proj._pt_final_softcap = self.final_logit_softcapping
         RMSNorm = TritonRMSNorm if _flash() else LlamaRMSNorm
         self.final_norm = RMSNorm(self.hidden_size, eps=config.rms_norm_eps)
         self.final_norm._pt_final_norm = True
+        if self.final_logit_softcapping is not None:
+            self.final_norm._pt_final_softcap = self.final_logit_softcapping
         self.reset_parameters()
 
     def reset_parameters(self):
@@ -759,12 +777,6 @@ def lm_head(final_proj, x):
     build's Linear / ColumnParallelLinear call it themselves; a plain torch nn.Linear -- what
     init_model_with_materialized_weights swaps in (checkpoint.py:89-91) -- is run through
     functional.linear on its weight (+ bias) instead of torch's GEMM."""
-    x = FN._plain(x)
-    if type(final_proj) is nn.Linear:
-        if final_proj.bias is None:
-            y = FN.lm_head_linear(x, final_proj.weight)
-        else:
-            y = FN.linear(x, final_proj.weight) + final_proj.bias
-    else:
-        y = final_proj(x)
-    return FN.as_logits(y)
+    if type(final_proj) is nn.Linear:   # (F.linear on the final norm's HipHidden: its route, cap included)
+        return FN._dispatch_linear(x, final_proj.weight, final_proj.bias)
+    return FN.as_logits(final_proj(FN._plain(x)))
