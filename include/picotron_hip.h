@@ -105,6 +105,17 @@ int pt_swiglu_fwd(const void* g, int64_t g_stride, const void* u, int64_t u_stri
 int pt_swiglu_bwd(const void* dh, int64_t dh_stride, const void* g, int64_t g_stride, const void* u,
                   int64_t u_stride, void* dg, int64_t dg_stride, void* du, int64_t du_stride, int64_t rows,
                   int64_t cols, hipStream_t stream);
+/* GeGLU: h = gelu_tanh(g) * u, the gated MLP of the Gemma family (hidden_act "gelu_pytorch_tanh"; not in the
+ * reference, whose MLP is SwiGLU).  gelu_tanh(g) = 0.5 g (1 + tanh(sqrt(2 / pi) (g + 0.044715 g^3))), with
+ * torch's bf16 rounding points: h = bf16(bf16(gelu(g)) u), du = bf16(dh bf16(gelu(g))), dg = bf16(bf16(dh u)
+ * gelu'(g)); finite for every finite bf16 g.  pt_swiglu_fwd / pt_swiglu_bwd's arguments, checks and check
+ * order.  The GEMM forms: pt_gemm / pt_gemm_grouped epilogues 10 (forward, as 5) and 11 (backward, as 6),
+ * pt_gemm_dual group-0 epilogue 11, pt_gemm_splitk_reduce mode 11 -- the same bits as these row kernels. */
+int pt_geglu_fwd(const void* g, int64_t g_stride, const void* u, int64_t u_stride, void* h, int64_t h_stride,
+                 int64_t rows, int64_t cols, hipStream_t stream);
+int pt_geglu_bwd(const void* dh, int64_t dh_stride, const void* g, int64_t g_stride, const void* u,
+                 int64_t u_stride, void* dg, int64_t dg_stride, void* du, int64_t du_stride, int64_t rows,
+                 int64_t cols, hipStream_t stream);
 
 /* ---- mixture-of-experts routing ---------------------------------------------------------------
  * Not in the reference (its MLP is dense, model.py:184-186): the routing of an MoE MLP (Mixtral,
@@ -645,7 +656,7 @@ int pt_gemm_grouped(const pt_gemm_problem* probs, int nprob, int a_kcontig, int 
  * SwiGLU backward, residual = g|u), group 1 = wgrad (dY^T X; both operands MN-contiguous;
  * epilogue 0, 1 or 3; or 2 with ksplit problems: a split-K dW's f32 slices, pt_gemm_splitk_reduce).  The dX of a layer's projection beside its dW (both read only dY and saved
  * activations): the down_proj dX's HBM-bound SwiGLU-backward tail overlaps the dW's MFMA work.
- * Group 0's epilogue: 0 (bf16), 6 (SwiGLU backward) or 2 (f32: the two K halves of a split-K dX,
+ * Group 0's epilogue: 0 (bf16), 6 (SwiGLU backward), 11 (GeGLU backward, as 6) or 2 (f32: the two K halves of a split-K dX,
  * finished by pt_gemm_splitk_sum).
  * order: 0 group 0 first, 1 group 1 first, inside each XCD's share; 2 staggered (even XCDs group 0 first,
  * odd XCDs group 1 first).
@@ -663,7 +674,7 @@ int pt_gemm_splitk_sum(const float* p0, const float* p1, const void* residual, v
  * the sum in part order through `mode` = the GEMM epilogue it completes -- 0 bf16 store, 1 bf16
  * accumulate, 2 f32 store, 3 f32 accumulate (main_grad), 4 bf16 residual (residual [M, N], ld ldr),
  * 6 SwiGLU backward (the sum is dh of a split-K down_proj dX, model.py:186; residual = g|u [M, 2N]
- * ld ldr; C[0] = dg|du [M, 2N], nc = 1) -- into nc (<= 4) row segments of C (c_bounds, NULL = one),
+ * ld ldr; C[0] = dg|du [M, 2N], nc = 1), 11 GeGLU backward (as 6) -- into nc (<= 4) row segments of C (c_bounds, NULL = one),
  * each with its own ld.  N % 4 == 0. */
 int pt_gemm_splitk_reduce(const float* parts, int nparts, int64_t part_stride, int64_t M, int64_t N, void* const* C,
                           const int64_t* ldc, const int64_t* c_bounds, int nc, int mode, const void* residual,

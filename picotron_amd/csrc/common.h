@@ -39,6 +39,51 @@ __device__ __forceinline__ float round_bf(float f) { return bf2f(f2bf(f)); }
 // one expression, so the fused epilogues and csrc/swiglu.hip stay bit-identical
 __device__ __forceinline__ float pt_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+// The gate activation of a gated MLP and its derivative, one element: the ONE definition the row kernels
+// (csrc/swiglu.hip) and the GEMM epilogues (csrc/gemm.hip) share, so fused and unfused give the same bits.
+//   PT_ACT_SILU:       act = g s,  s = sigmoid(g),  act' = s (1 + g (1 - s))
+//   PT_ACT_GELU_TANH:  gelu(g) = 0.5 g (1 + tanh(k (g + c g^3))), k = sqrt(2 / pi), c = 0.044715, written
+//     with tanh(x) = 2 sigmoid(2 x) - 1 as  z = 2 k g (1 + c g^2),  s = sigmoid(z),  act = g s,
+//     act' = s + g s (1 - s) z',  z' = 2 k (1 + 3 c g^2):  one pt_sigmoid (v_exp + v_rcp) as SiLU has,
+//     no libm tanhf.
+// g^2 is clamped at 2^100: a finite bf16 |g| > 1.8e19 overflows g g to inf, and z' = inf meets
+// s (1 - s) = 0 as NaN (torch's gelu_backward has the same hole).  The sigmoid saturates to exactly 0 / 1
+// from |z| ~ 104, i.e. |g| ~ 11, so where the clamp binds (|g| >= 2^50) g s (1 - s) is exactly +-0 and
+// finite z' gives act' = s; below it the min returns g g itself, so no value on the common path changes.
+// One v_min_f32 per element, no compare / select pair and no branch.
+enum PtAct { PT_ACT_SILU = 0, PT_ACT_GELU_TANH = 1 };
+template <int ACT>
+struct PtGlu {
+  float s, g2;   // the sigmoid the activation is written with; (clamped) g^2 of the GELU polynomial
+  __device__ __forceinline__ explicit PtGlu(float g) {
+    constexpr float k2 = 1.5957691216057308f, c = 0.044715f;   // 2 sqrt(2 / pi)
+    if constexpr (ACT == PT_ACT_SILU) {
+      s = pt_sigmoid(g);
+    } else {
+      g2 = fminf(g * g, 0x1p100f);
+      s = pt_sigmoid(g * fmaf(k2 * c, g2, k2));
+    }
+  }
+  __device__ __forceinline__ float act(float g) const { return g * s; }
+  // a = act(g), the f32 value before any rounding
+  __device__ __forceinline__ float dact(float g, float a) const {
+    constexpr float k2 = 1.5957691216057308f, c = 0.044715f;
+    if constexpr (ACT == PT_ACT_SILU) return s * (1.0f + g * (1.0f - s));
+    else return fmaf(a * (1.0f - s), fmaf(3.0f * k2 * c, g2, k2), s);
+  }
+};
+template <int ACT>
+__device__ __forceinline__ float pt_glu_act(float g) { return PtGlu<ACT>(g).act(g); }
+// one element of the gated MLP's backward with torch's bf16 rounding points: d = dh (already a bf16 value),
+// g / u the forward's activations -> og = dg = bf16(dh u) act'(g), ou = du = dh bf16(act(g)) (stored as bf16)
+template <int ACT>
+__device__ __forceinline__ void pt_glu_bwd_elem(float d, float g, float u, float& og, float& ou) {
+  const PtGlu<ACT> f(g);
+  const float a = f.act(g);
+  ou = d * round_bf(a);
+  og = round_bf(d * u) * f.dact(g, a);
+}
+
 // Final-logit soft-capping (Gemma-2's final_logit_softcapping): t = c tanh(x / c), written as
 // csrc/attention.hip's soft-cap stage writes it -- e = exp2(x k1) = exp(2 x / c), tanh = 1 - 2 rcp(1 + e):
 // one v_mul, v_exp, v_add, v_rcp, v_fma, v_mul, no libm call.  e = +inf gives c, e = 0 gives -c.

@@ -87,17 +87,17 @@ enum Epilogue {
   // EPI_CE_STATS_CAP: EPI_CE_STATS with final-logit soft-capping (Gemma-2): the f32 accumulators become
   // c tanh(acc / c) (pt_softcap, c = GemmArgs::cap) before the one bf16 rounding, so the stored logits
   // and the statistics taken from them are the capped ones
-  EPI_CE_STATS_CAP = 9
+  EPI_CE_STATS_CAP = 9,
+  // EPI_GEGLU_FWD / EPI_GEGLU_BWD: EPI_SWIGLU_FWD / EPI_SWIGLU_BWD with the tanh-GELU gate (the Gemma family's
+  // hidden_act "gelu_pytorch_tanh") -- the same operands, tiles, staging and stores, instantiated on
+  // PT_ACT_GELU_TANH (common.h's pt_glu_act) instead of PT_ACT_SILU
+  EPI_GEGLU_FWD = 10, EPI_GEGLU_BWD = 11
 };
 constexpr bool epi_ce(int e) { return e == EPI_CE_STATS || e == EPI_CE_STATS_CAP; }
-
-// SwiGLU backward of one element, the same expressions as csrc/swiglu.hip (torch's bf16 roundings):
-// d = dh (already a bf16 value), g / u the forward's activations -> og = dg, ou = du
-__device__ __forceinline__ void swiglu_bwd_elem(float d, float g, float u, float& og, float& ou) {
-  const float sg = pt_sigmoid(g);
-  ou = d * round_bf(g * sg);
-  og = round_bf(d * u) * (sg * (1.0f + g * (1.0f - sg)));
-}
+// the gated-MLP epilogues of either activation: the paired gate|up projection, the down_proj dX
+constexpr bool epi_glu_fwd(int e) { return e == EPI_SWIGLU_FWD || e == EPI_GEGLU_FWD; }
+constexpr bool epi_glu_bwd(int e) { return e == EPI_SWIGLU_BWD || e == EPI_GEGLU_BWD; }
+constexpr int epi_act(int e) { return e == EPI_GEGLU_FWD || e == EPI_GEGLU_BWD ? PT_ACT_GELU_TANH : PT_ACT_SILU; }
 
 struct GemmArgs {
   const uint16_t* A;
@@ -309,7 +309,7 @@ __device__ __forceinline__ void ce_stats_merge(const GemmArgs& a, const float2* 
 // issuing all 2 x NIT loads before any math measured 3 % slower than 2 chunks per group
 // (profiles/r02_notes.md).
 constexpr int kSwigluGroup = 2;   // chunks per load group (4: equal, 16: -0.4 %; profiles/r04/notes_r04.md)
-template <int TM, int TN>
+template <int TM, int TN, int ACT>   // ACT: the gate activation (EPI_GEGLU_BWD runs this tail on PT_ACT_GELU_TANH)
 __device__ __forceinline__ void swiglu_bwd_tail(const GemmArgs& a, const lds_u8* st, int64_t mrow0, int ncol0,
                                                 int64_t ldc, uint16_t* C, int lane) {
   constexpr int ROWB = TN * 2 + 16, CPR = TN / 8, RPI = 64 / CPR, NIT = TM / RPI, SG = kSwigluGroup;
@@ -340,7 +340,7 @@ __device__ __forceinline__ void swiglu_bwd_tail(const GemmArgs& a, const lds_u8*
       unpack8(g[k], gg);
       unpack8(u[k], uu);
 #pragma unroll
-      for (int e = 0; e < 8; ++e) swiglu_bwd_elem(d[e], gg[e], uu[e], og[e], ou[e]);
+      for (int e = 0; e < 8; ++e) pt_glu_bwd_elem<ACT>(d[e], gg[e], uu[e], og[e], ou[e]);
       st8((uint16_t*)(cbase + q * cstep + coff), pack8(og));
       st8((uint16_t*)(cbase + q * cstep + ustep + coff), pack8(ou));
     }
@@ -418,7 +418,7 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
   const int64_t ldc = a.ldc[cs];
   const int64_t mrow0 = m0 - a.cseg[cs] + wm * TM;
   const int ncol0 = n0 + wn * TN;
-  if (EPI == EPI_BF16 || EPI == EPI_BF16_ACC || EPI == EPI_BF16_RES || EPI == EPI_SWIGLU_BWD || EPI == EPI_ROPE ||
+  if (EPI == EPI_BF16 || EPI == EPI_BF16_ACC || EPI == EPI_BF16_RES || epi_glu_bwd(EPI) || EPI == EPI_ROPE ||
       epi_ce(EPI)) {
     constexpr int ROWB = TN * 2 + 16;  // +16 B pad: spreads the staging writes over banks
     if constexpr (EPI == EPI_CE_STATS_CAP) {
@@ -453,8 +453,8 @@ __device__ __forceinline__ void epilogue(const GemmArgs& a, const f32x4_t (&acc)
     // they would be live next to all of acc and spill
     __builtin_amdgcn_sched_barrier(0);
     uint16_t* C = (uint16_t*)a.C[cs];
-    if constexpr (EPI == EPI_SWIGLU_BWD) {
-      swiglu_bwd_tail<TM, TN>(a, st, mrow0, ncol0, ldc, C, lane);
+    if constexpr (epi_glu_bwd(EPI)) {
+      swiglu_bwd_tail<TM, TN, epi_act(EPI)>(a, st, mrow0, ncol0, ldc, C, lane);
       return;
     }
     if constexpr (EPI == EPI_ROPE && TN == 64) {
@@ -616,7 +616,8 @@ __device__ __forceinline__ void write_128x32(lds_u8* st, int lane, uint16_t* dst
 }
 
 // EPI_SWIGLU_FWD: the wave's 128 x 64 accumulators are 32 gate columns (acc[.][0..1]) and the
-// SAME 32 up columns (acc[.][2..3]) of output columns hc0 .. hc0+31.
+// SAME 32 up columns (acc[.][2..3]) of output columns hc0 .. hc0+31.  ACT: the gate activation.
+template <int ACT>
 __device__ __forceinline__ void epilogue_swiglu_fwd(const GemmArgs& a, f32x4_t (&acc)[8][4], lds_u8* st, int64_t row0,
                                                     int hc0, int lane) {
   uint16_t* H = (uint16_t*)a.C[0];
@@ -631,8 +632,7 @@ __device__ __forceinline__ void epilogue_swiglu_fwd(const GemmArgs& a, f32x4_t (
   write_128x32(st, lane, GU + row0 * ldgu + hc0, ldgu, [&](int i, int j, int r) { return acc[i][j][r]; });
   write_128x32(st, lane, GU + row0 * ldgu + a.N + hc0, ldgu, [&](int i, int j, int r) { return acc[i][j + 2][r]; });
   write_128x32(st, lane, H + row0 * ldh + hc0, ldh, [&](int i, int j, int r) {
-    const float g = acc[i][j][r];
-    return round_bf(g * pt_sigmoid(g)) * acc[i][j + 2][r];
+    return round_bf(pt_glu_act<ACT>(acc[i][j][r])) * acc[i][j + 2][r];
   });
 }
 
@@ -765,7 +765,7 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
 
   // B segment for this tile (N-segments) or the first K-segment; ld is per tile (host checks
   // that K-segments share one ld)
-  constexpr bool PAIR = EPI == EPI_SWIGLU_FWD;  // Bl = W_gate rows, Br = W_up rows of tile n
+  constexpr bool PAIR = epi_glu_fwd(EPI);  // Bl = W_gate rows, Br = W_up rows of tile n
   const BImg bi = bimg_make(a, BKC, PAIR ? 0 : n0);
   const int64_t ldb = PAIR ? a.ldb[0] : bi.ld;
   const uint16_t* const pairB0 = a.B[0];
@@ -908,7 +908,7 @@ __device__ __forceinline__ void gemm_8ph_tile(const GemmArgs& a, const int tile_
   if (!late) phase_bar();  // balance the barrier count of the two wave groups
   __syncthreads();
   if constexpr (PAIR) {
-    epilogue_swiglu_fwd(a, acc, smem + wave * (TM * (32 * 2 + 16)), m0 + wm * TM, tile_n * 128 + wn * 32, lane);
+    epilogue_swiglu_fwd<epi_act(EPI)>(a, acc, smem + wave * (TM * (32 * 2 + 16)), m0 + wm * TM, tile_n * 128 + wn * 32, lane);
   } else {
     // EPI_CE_STATS: per-wave row statistics beside the 8 staging areas (kTiles sizes the LDS)
     float2* xs = (float2*)(smem + 8 * (TM * (TN * 2 + 16)));
@@ -1458,7 +1458,7 @@ constexpr unsigned kPhasedLayouts = kAllLayouts & ~layout_bit(false, true);
 // the layouts an epilogue is built for: the plain sinks every one; the residual, RoPE, CE-statistics
 // and SwiGLU forward projections the forward's (weights K-contiguous); the SwiGLU backward the dX's
 constexpr unsigned epi_layouts(int e) {
-  return e <= EPI_F32_ACC ? kAllLayouts : e == EPI_SWIGLU_BWD ? layout_bit(true, false) : layout_bit(true, true);
+  return e <= EPI_F32_ACC ? kAllLayouts : epi_glu_bwd(e) ? layout_bit(true, false) : layout_bit(true, true);
 }
 
 // What the launch layer knows of a tile: its block, the LDS of its main loop (the ring of operand
@@ -1477,7 +1477,7 @@ constexpr TileDesc kTiles[] = {
     {TILE_S64, 64, 64, 256, 2 * (64 + 64) * BK * 2, 4 * 32 * (32 * 2 + 16), 0, kEpiPlain, kAllLayouts},
     {TILE_8PH, 256, 256, 512, 2 * 4 * 128 * BK * 2, 8 * 128 * kWaveStage64, 8 * 128 * 8,
      kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_CE_STATS_CAP) | epi_bit(EPI_SWIGLU_FWD) |
-         epi_bit(EPI_SWIGLU_BWD),
+         epi_bit(EPI_SWIGLU_BWD) | epi_bit(EPI_GEGLU_FWD) | epi_bit(EPI_GEGLU_BWD),
      kPhasedLayouts},
     {TILE_4PH, 256, 128, 512, 3 * 3 * 128 * BK * 2, 8 * 64 * kWaveStage64, 8 * 64 * 8,
      kEpiPlain | epi_bit(EPI_ROPE) | epi_bit(EPI_CE_STATS) | epi_bit(EPI_CE_STATS_CAP), kPhasedLayouts},
@@ -1556,8 +1556,8 @@ int launch_tile(GemmGroup& g, hipStream_t s) {
   if constexpr (!tile_built(t, AK, BKC, EPI)) {
     return PT_EUNSUPPORTED;
   } else {
-    // EPI_SWIGLU_FWD consumes B in paired tiles: the grid is 256 x 128 of h
-    const int tiles = group_tiles(g, t.bm, EPI == EPI_SWIGLU_FWD ? t.bn / 2 : t.bn);
+    // EPI_SWIGLU_FWD / EPI_GEGLU_FWD consume B in paired tiles: the grid is 256 x 128 of h
+    const int tiles = group_tiles(g, t.bm, epi_glu_fwd(EPI) ? t.bn / 2 : t.bn);
     return launch_kernel<tile_kernel<t.id, AK, BKC, EPI>(), tile_smem(t, EPI)>(tiles, t.threads, s, g);
   }
 }
@@ -1587,6 +1587,8 @@ int dispatch(GemmGroup& g, int tile, int a_kcontig, int b_kcontig, int epilogue,
     case EPI_BF16_RES: return dispatch_layout<EPI_BF16_RES>(g, tile, a_kcontig, b_kcontig, s);
     case EPI_SWIGLU_FWD: return dispatch_layout<EPI_SWIGLU_FWD>(g, tile, a_kcontig, b_kcontig, s);
     case EPI_SWIGLU_BWD: return dispatch_layout<EPI_SWIGLU_BWD>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_GEGLU_FWD: return dispatch_layout<EPI_GEGLU_FWD>(g, tile, a_kcontig, b_kcontig, s);
+    case EPI_GEGLU_BWD: return dispatch_layout<EPI_GEGLU_BWD>(g, tile, a_kcontig, b_kcontig, s);
     case EPI_ROPE: return dispatch_layout<EPI_ROPE>(g, tile, a_kcontig, b_kcontig, s);
     case EPI_CE_STATS: return dispatch_layout<EPI_CE_STATS>(g, tile, a_kcontig, b_kcontig, s);
     // reached with a cap from pt_gemm_ce_stats_cap alone: the generic entries have none to give
@@ -1612,7 +1614,7 @@ int launch_dual_t(GemmGroup g0, GemmGroup g1, int order, hipStream_t stream) {
 int fill_args(GemmArgs& a, const pt_gemm_problem& q, int epilogue) {
   const int nb = q.nb, nc = q.nc;
   const int64_t M = q.M, N = q.N, K = q.K;
-  const bool fwd = epilogue == EPI_SWIGLU_FWD;
+  const bool fwd = epi_glu_fwd(epilogue);
   if (!q.A || nb < 1 || nb > 4 || nc < 1 || nc > 4 || M <= 0 || N <= 0 || K <= 0) return PT_EINVAL;
   if (epilogue == EPI_BF16_RES && (!q.residual || nc != 1 || !pt_aligned16(q.residual) || (q.ldr & 7)))
     return PT_EINVAL;
@@ -1620,7 +1622,7 @@ int fill_args(GemmArgs& a, const pt_gemm_problem& q, int epilogue) {
     if (nb != 2 || q.b_seg_dim != 0 || nc != 2 || (N & 1) || q.ldb[0] != q.ldb[1]) return PT_EINVAL;
     if (q.b_bounds[0] != 0 || q.b_bounds[1] != N / 2 || q.b_bounds[2] != N) return PT_EINVAL;
   }
-  if (epilogue == EPI_SWIGLU_BWD &&
+  if (epi_glu_bwd(epilogue) &&
       (!q.residual || nc != 1 || !pt_aligned16(q.residual) || (q.ldr & 7) || (q.ldc[0] & 7)))
     return PT_EINVAL;
   if (!fwd) {   // (the paired projection answers K % BK with PT_EALIGN, below)
@@ -1803,14 +1805,14 @@ int launch_swiglu(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int 
   if (tile != -1 && tile != TILE_8PH) return PT_EUNSUPPORTED;
   for (int i = 0; i < g.nprob; ++i) {
     const GemmArgs& a = g.p[i];
-    if (a.M % 256 || a.N % (epilogue == EPI_SWIGLU_FWD ? 128 : 256)) return PT_EUNSUPPORTED;
-    if (epilogue == EPI_SWIGLU_BWD && (a.ncseg != 1 || a.bdim != 0 || a.nbseg != 1)) return PT_EUNSUPPORTED;
+    if (a.M % 256 || a.N % (epi_glu_fwd(epilogue) ? 128 : 256)) return PT_EUNSUPPORTED;
+    if (epi_glu_bwd(epilogue) && (a.ncseg != 1 || a.bdim != 0 || a.nbseg != 1)) return PT_EUNSUPPORTED;
   }
   return dispatch(g, TILE_8PH, a_kcontig, b_kcontig, epilogue, stream);
 }
 
 int launch_group(GemmGroup& g, int a_kcontig, int b_kcontig, int epilogue, int tile, hipStream_t stream) {
-  if (epilogue == EPI_SWIGLU_FWD || epilogue == EPI_SWIGLU_BWD)
+  if (epi_glu_fwd(epilogue) || epi_glu_bwd(epilogue))
     return launch_swiglu(g, a_kcontig, b_kcontig, epilogue, tile, stream);
   // RoPE: wave tiles 64 columns wide, the phased kernels only; the 256x128 one (twice the tiles) when
   // it divides -- the q|k|v projection never fills more than a few rounds of 256x256 tiles
@@ -1846,12 +1848,13 @@ int launch_dual(GemmGroup& g0, int ak0, int bk0, int e0, GemmGroup& g1, int ak1,
   if (!ak0 || bk0 || ak1 || bk1 || order < 0 || order > 2) return PT_EUNSUPPORTED;
   for (int i = 0; i < g0.nprob; ++i) {
     if (!args_fit(g0.p[i], TILE_8PH)) return PT_EUNSUPPORTED;
-    if (e0 == EPI_SWIGLU_BWD && (g0.p[i].ncseg != 1 || g0.p[i].bdim != 0 || g0.p[i].nbseg != 1)) return PT_EUNSUPPORTED;
+    if (epi_glu_bwd(e0) && (g0.p[i].ncseg != 1 || g0.p[i].bdim != 0 || g0.p[i].nbseg != 1)) return PT_EUNSUPPORTED;
   }
   for (int i = 0; i < g1.nprob; ++i)
     if (!args_fit(g1.p[i], TILE_8PH)) return PT_EUNSUPPORTED;
   if (e0 == EPI_BF16) return launch_dual_e1<EPI_BF16>(g0, g1, e1, order, s);
   if (e0 == EPI_SWIGLU_BWD) return launch_dual_e1<EPI_SWIGLU_BWD>(g0, g1, e1, order, s);
+  if (e0 == EPI_GEGLU_BWD) return launch_dual_e1<EPI_GEGLU_BWD>(g0, g1, e1, order, s);
   if (e0 == EPI_F32) return launch_dual_e1<EPI_F32>(g0, g1, e1, order, s);  // split-K dX halves
   return PT_EUNSUPPORTED;
 }
@@ -1881,7 +1884,7 @@ int pt_gemm(const void* A, int64_t lda, int a_kcontig, const void* const* B, con
             const void* residual, int64_t ldr, int tile, hipStream_t stream) {
   pt_gemm_problem q = problem_a(A, lda, M, N, K);
   if (!problem_b(q, B, ldb, b_bounds, nb, b_seg_dim) || !problem_c(q, C, ldc, c_bounds, nc)) return PT_EINVAL;
-  if (!b_bounds && epilogue == EPI_SWIGLU_FWD) q.b_bounds[1] = N / 2;   // gate | up: the paired halves
+  if (!b_bounds && epi_glu_fwd(epilogue)) q.b_bounds[1] = N / 2;   // gate | up: the paired halves
   q.residual = residual;
   q.ldr = ldr;
   GemmGroup g{};
@@ -1908,7 +1911,7 @@ namespace {
 // part order (deterministic), through the sink's epilogue -- 0 bf16 store, 1 bf16 accumulate
 // (bf16(C + bf16(sum)), the wgrad's .grad accumulation), 2 f32 store, 3 f32 accumulate (main_grad),
 // 4 bf16 residual (bf16(R + bf16(sum))), 6 the SwiGLU backward of a split-K down_proj dX (sum = dh,
-// R = g|u [M, 2N], C = dg|du [M, 2N]: the fused epilogue's math) -- into up to 4 row segments of C
+// R = g|u [M, 2N], C = dg|du [M, 2N]: the fused epilogue's math), 11 the same with the GeGLU gate -- into up to 4 row segments of C
 // (c_bounds), each with its own pointer and leading dimension.  4 columns per thread-iteration
 // (16-B partial loads).
 struct ReduceArgs {
@@ -1940,7 +1943,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs r) 
       if (j < r.nc && row >= r.cseg[j]) seg = j;
     const int64_t off = (row - r.cseg[seg]) * r.ldc[seg] + c4 * 4;
     const float v[4] = {acc.x, acc.y, acc.z, acc.w};
-    if (MODE == EPI_SWIGLU_BWD) {
+    if (epi_glu_bwd(MODE)) {
       // the sum is dh (rounded to bf16 as the fused epilogue stages it); R = g|u, C = dg|du [M, 2N]
       const uint16_t* gr = r.R + row * r.ldr + c4 * 4;
       const uint2 gw = *(const uint2*)gr, uw = *(const uint2*)(gr + r.N);
@@ -1948,7 +1951,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const ReduceArgs r) 
       const float u[4] = {lo_bf(uw.x), hi_bf(uw.x), lo_bf(uw.y), hi_bf(uw.y)};
       float og[4], ou[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) swiglu_bwd_elem(round_bf(v[e]), g[e], u[e], og[e], ou[e]);
+      for (int e = 0; e < 4; ++e) pt_glu_bwd_elem<epi_act(MODE)>(round_bf(v[e]), g[e], u[e], og[e], ou[e]);
       uint16_t* o = (uint16_t*)r.C[0] + off;
       *(uint2*)o = make_uint2(pack_bf2(og[0], og[1]), pack_bf2(og[2], og[3]));
       *(uint2*)(o + r.N) = make_uint2(pack_bf2(ou[0], ou[1]), pack_bf2(ou[2], ou[3]));
@@ -1986,9 +1989,9 @@ int pt_gemm_splitk_reduce(const float* parts, int nparts, int64_t part_stride, i
                           int64_t ldr, hipStream_t stream) {
   if (!parts || nparts < 1 || M <= 0 || N <= 0 || (N & 3) || !C || nc < 1 || nc > 4) return PT_EINVAL;
   if (part_stride < M * N || !pt_aligned16(parts) || (part_stride & 3)) return PT_EALIGN;
-  if ((mode == EPI_BF16_RES || mode == EPI_SWIGLU_BWD) && (!residual || ((uintptr_t)residual & 7) || (ldr & 3)))
+  if ((mode == EPI_BF16_RES || epi_glu_bwd(mode)) && (!residual || ((uintptr_t)residual & 7) || (ldr & 3)))
     return PT_EINVAL;
-  if (mode == EPI_SWIGLU_BWD && nc != 1) return PT_EINVAL;   // one dg|du [M, 2N] output
+  if (epi_glu_bwd(mode) && nc != 1) return PT_EINVAL;   // one dg|du [M, 2N] output
   ReduceArgs r{};
   r.parts = parts; r.nparts = nparts; r.M = M; r.N = N; r.part_stride = part_stride;
   r.nc = nc;
@@ -2012,6 +2015,7 @@ int pt_gemm_splitk_reduce(const float* parts, int nparts, int64_t part_stride, i
     case EPI_F32_ACC: splitk_reduce_kernel<EPI_F32_ACC><<<(int)grid, 256, 0, stream>>>(r); break;
     case EPI_BF16_RES: splitk_reduce_kernel<EPI_BF16_RES><<<(int)grid, 256, 0, stream>>>(r); break;
     case EPI_SWIGLU_BWD: splitk_reduce_kernel<EPI_SWIGLU_BWD><<<(int)grid, 256, 0, stream>>>(r); break;
+    case EPI_GEGLU_BWD: splitk_reduce_kernel<EPI_GEGLU_BWD><<<(int)grid, 256, 0, stream>>>(r); break;
     default: return PT_EINVAL;
   }
   PT_CHECK_LAUNCH();

@@ -134,18 +134,21 @@ def wgrad_group(jobs, notify=True):
         _launch_group(*_resolve_sinks(jobs), notify)
 
 
-def dgrad_with_wgrad(dy2d, weights, wjobs, gu=None, keep_parts=False, split_min=None, order=None, notify=True):
+def dgrad_with_wgrad(dy2d, weights, wjobs, gu=None, keep_parts=False, split_min=None, order=None, notify=True,
+                     act="silu"):
     """dX = dY . [W_0; ...] (with gu: the down_proj dX's SwiGLU backward, dg|du) AND the wgrads
     wjobs [(dy2d, x2d, params)] of the same layer in ONE launch (K.linear_dgrad_dual) when the
     shapes tile for it and every sink takes one epilogue; otherwise the separate launches.
     Returns dX / dg|du.  Under weight-gradient pairing a deferring micro-batch launches the dX alone
     (the split-K halves kept for the consumer as in the dual), the completing one the dual with the
-    paired (K = 2 T) weight gradients."""
+    paired (K = 2 T) weight gradients.  act: the gate activation of the gu form (K.swiglu_fwd's keyword),
+    handed on only when it is not "silu"."""
+    akw = K._act_kw(act)
     pairing = WgradPairing.phase is not None
     wjobs = pair_jobs(wjobs)
     if pairing and not wjobs:
         if gu is not None:
-            return K.linear_dgrad_swiglu(dy2d, weights[0], gu)
+            return K.linear_dgrad_swiglu(dy2d, weights[0], gu, **akw)
         return K.linear_dgrad(dy2d, weights, keep_parts=keep_parts, split_min=split_min)
     frozen = any(not p.requires_grad for _, _, params in wjobs for p in params)
     mns = [(dy.shape[1], x.shape[1]) for dy, x, _ in wjobs]
@@ -155,9 +158,9 @@ def dgrad_with_wgrad(dy2d, weights, wjobs, gu=None, keep_parts=False, split_min=
     dx = None
     if dual and epi is not None:
         dx = K.linear_dgrad_dual(dy2d, weights, [l[:3] for l in launches], epi, gu=gu, keep_parts=keep_parts,
-                                 split_min=split_min, order=order)
+                                 split_min=split_min, order=order, **akw)
     if dx is None:   # not tileable (after all), or mixed sinks: the same sinks, separate launches
-        dx = K.linear_dgrad_swiglu(dy2d, weights[0], gu) if gu is not None else K.linear_dgrad(dy2d, weights)
+        dx = K.linear_dgrad_swiglu(dy2d, weights[0], gu, **akw) if gu is not None else K.linear_dgrad(dy2d, weights)
         _launch_group(launches, epi, notify and not dual)
     if notify and dual:   # the jobs of a dual launch tell their owners together
         _notify(p for _, _, params in wjobs for p in params)
@@ -1326,15 +1329,17 @@ class MLAttentionFunction(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------ MLP block
-def mlp_block_fwd(h2, wg, wu, wd, tp, residual=None, reduce=True):
+def mlp_block_fwd(h2, wg, wu, wd, tp, residual=None, reduce=True, act="silu"):
     """h2 [T,H] -> down(silu(gate) * up) (+ residual, entering the tp sum once, from tp rank 0;
-    reduce=False: this rank's partial, no residual, for the sequence-parallel reduce-scatter)."""
+    reduce=False: this rank's partial, no residual, for the sequence-parallel reduce-scatter).
+    act="gelu_tanh": the GeGLU MLP, down(gelu_tanh(gate) * up), through the same forms."""
     I = wg.shape[0]
+    akw = K._act_kw(act)
     if _fuse() and K.swiglu_fuse_pays(h2.shape[0], I, H=h2.shape[1]):   # SwiGLU in the gate|up GEMM's epilogue
-        gu, hh = K.linear_swiglu_fwd(h2, wg, wu)
+        gu, hh = K.linear_swiglu_fwd(h2, wg, wu, **akw)
     else:
         gu = K.linear_fwd(h2, [wg, wu])
-        hh = K.swiglu_fwd(gu[:, :I], gu[:, I:])
+        hh = K.swiglu_fwd(gu[:, :I], gu[:, I:], **akw)
     res = residual if (residual is not None and tp.rank == 0) else None
     m = K.linear_fwd(hh, [wd], residual=res)
     if reduce:
@@ -1352,21 +1357,22 @@ GU_DUAL_ORDER = 1
 
 
 def mlp_block_bwd(dm, h2, saved, wg, wu, wd, tp, need_dx=True, keep_parts=False, sp=False, rs_out=None,
-                  notify=True):
+                  notify=True, act="silu"):
     """keep_parts: the gate|up dX may come back as K.SplitKParts (its split-K halves unsummed) for a
     following rmsnorm backward to sum.  sp: the column-parallel dX is reduce-scattered onto this
     rank's token rows instead of all-reduced.  rs_out / notify: one token chunk of the chunked
     sequence-parallel layer (attn_block_bwd): returns the reduce-scatter's handle, not waited for."""
     gu, hh = saved
     I = wg.shape[0]
+    akw = K._act_kw(act)
     if _fuse() and K.swiglu_fuse_pays(dm.shape[0], I, backward=True, H=dm.shape[1]):   # SwiGLU bwd in the down dX epilogue
         # ... in one launch with the down_proj dW: the epilogue's HBM-bound g|u / dg|du tail
         # overlaps the dW's MFMA work (K.linear_dgrad_dual)
-        dgu = dgrad_with_wgrad(dm, [wd], [(dm, hh, [wd])], gu=gu, notify=notify)
+        dgu = dgrad_with_wgrad(dm, [wd], [(dm, hh, [wd])], gu=gu, notify=notify, **akw)
     else:
         dhh = K.linear_dgrad(dm, [wd])
         dgu = torch.empty_like(gu)
-        K.swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:])
+        K.swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:], **akw)
         wgrad(dm, hh, [wd], notify)
     dh = handle = None
     split = SW.gu_splitk != 0
@@ -1399,24 +1405,25 @@ def mlp_block_bwd(dm, h2, saved, wg, wu, wd, tp, need_dx=True, keep_parts=False,
 class MLPFunction(torch.autograd.Function):
     """MLP.forward (model.py:184-186): gate|up in one GEMM, SwiGLU, down_proj.  residual (x's shape; None:
     none): out = residual + MLP(x), added in the down_proj epilogue -- how an MoE layer's shared experts
-    enter its residual stream; its gradient is dm itself."""
+    enter its residual stream; its gradient is dm itself.  act: the gate activation ("gelu_tanh": GeGLU)."""
 
     @staticmethod
-    def forward(ctx, x, wg, wu, wd, residual=None):
+    def forward(ctx, x, wg, wu, wd, residual=None, act="silu"):
+        # act stays the LAST parameter: model._act_tail pads the optional ones before it by position
         h2 = _contig2d(x)
         m, saved = mlp_block_fwd(h2, wg, wu, wd, TPContext.current(),
-                                 residual=None if residual is None else _contig2d(residual))
+                                 residual=None if residual is None else _contig2d(residual), **K._act_kw(act))
         ctx.save_for_backward(h2, *saved, wg, wu, wd)
-        ctx.shape = x.shape
+        ctx.shape, ctx.act = x.shape, act
         return m.view(*x.shape[:-1], -1)
 
     @staticmethod
     def backward(ctx, dm):
         h2, gu, hh, wg, wu, wd = ctx.saved_tensors
         dh = mlp_block_bwd(_contig2d(dm), h2, (gu, hh), wg, wu, wd, TPContext.current(),
-                           need_dx=ctx.needs_input_grad[0])
+                           need_dx=ctx.needs_input_grad[0], **K._act_kw(ctx.act))
         dres = dm if len(ctx.needs_input_grad) > 4 and ctx.needs_input_grad[4] else None
-        return (dh.view(ctx.shape) if dh is not None else None), None, None, None, dres
+        return (dh.view(ctx.shape) if dh is not None else None), None, None, None, dres, None
 
 
 # ------------------------------------------------------------------------ mixture-of-experts block
@@ -1464,28 +1471,29 @@ def _moe_route_bwd(dgate, probs, idx, gate, counts, d_aux, norm_topk_prob, route
 
 
 def moe_block_fwd(h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None,
-                  router=None):
+                  router=None, act="silu"):
     """h2 [T, H] -> (residual + sum_j gate_j Expert_{idx_j}(h2), aux, saved): router GEMM (bf16
     logits), top-k on the stored logits, capacity slots (K.moe_capacity; items past an expert's C
     rows are dropped and the residual carries the token), dispatch into the [E C, H] buffer, the
     expert MLPs as grouped GEMMs, weighted combine with the residual in one rounding.  Static shapes,
-    nothing read on the host."""
+    nothing read on the host.  act: the experts' gate activation ("gelu_tanh": GeGLU experts)."""
     T, E = h2.shape[0], len(wgs)
+    akw = K._act_kw(act)
     if capacity_factor is None:
-        return _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages, router)
+        return _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages, router, **akw)
     C = K.moe_capacity(T, E, k, capacity_factor)
     logits = K.linear_fwd(h2, [router_w])
     idx, gate, probs, counts, aux = _moe_route(logits, k, norm_topk_prob, router)
     slot, src = K.moe_plan(idx, E, C)
     xe = K.moe_dispatch(h2, src, k)
-    gu, hh, ye = K.moe_experts_fwd(xe, wgs, wus, wds, C, fuse=_fuse())
+    gu, hh, ye = K.moe_experts_fwd(xe, wgs, wus, wds, C, fuse=_fuse(), **akw)
     out = K.moe_combine(ye, slot, gate, residual)
     _stage(stages, h2=h2, logits=logits, idx=idx, gate=gate, probs=probs, counts=counts, aux=aux, slot=slot, src=src, xe=xe,
            gu=gu, hh=hh, ye=ye, out=out)
     return out, aux, (idx, gate, probs, counts, slot, src, xe, gu, hh, ye)
 
 
-def _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages, router=None):
+def _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_prob, stages, router=None, act="silu"):
     """moe_block_fwd with capacity_factor None: no item is dropped.  The experts' rows are packed back to
     back in [R, *] buffers (K.moe_plan_dropless: R = K.moe_dropless_rows, a static bound; segments on the
     128-grid) and every product is one segment-GEMM launch over all experts."""
@@ -1494,7 +1502,7 @@ def _moe_block_fwd_dropless(h2, residual, router_w, wgs, wus, wds, k, norm_topk_
     idx, gate, probs, counts, aux = _moe_route(logits, k, norm_topk_prob, router)
     slot, src, seg, tile_expert = K.moe_plan_dropless(idx, E)
     xe = K.moe_dispatch(h2, src, k)
-    gu, hh, ye = K.moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert)
+    gu, hh, ye = K.moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert, **K._act_kw(act))
     out = K.moe_combine(ye, slot, gate, residual)
     _stage(stages, h2=h2, logits=logits, idx=idx, gate=gate, probs=probs, counts=counts, aux=aux, slot=slot, src=src, xe=xe,
            gu=gu, hh=hh, ye=ye, out=out, seg=seg, tile_expert=tile_expert)
@@ -1521,10 +1529,10 @@ def _wgrad_seg(dy, x, params_per_expert, seg, notify=True):
 
 
 def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages,
-                            router=None):
+                            router=None, act="silu"):
     idx, gate, probs, counts, slot, src, xe, gu, hh, ye, seg, tile_expert = saved
     dye, dgate = K.moe_combine_bwd(dout, ye, slot, src, gate)
-    dgu, dhh = K.moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert)
+    dgu, dhh = K.moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert, **K._act_kw(act))
     _stage(stages, dhh=dhh)
     _wgrad_seg(dye, hh, [[w] for w in wds], seg)
     dxe = K.moe_experts_dgrad_gate_up_seg(dgu, wgs, wus, seg, tile_expert) if need_dx else None
@@ -1541,7 +1549,7 @@ def _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, 
 
 
 def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob=True, need_dx=True, stages=None,
-                  dropless=False, router=None):
+                  dropless=False, router=None, act="silu"):
     """Backward of moe_block_fwd's expert path and router: returns dh2 (the residual's gradient is
     dout itself).  d_aux: the gradient of aux, an f32 device scalar or None.  Expert and router
     weight gradients go to their sinks through wgrad_group / wgrad, MOE_GROUP experts to a launch, so
@@ -1549,13 +1557,13 @@ def moe_block_bwd(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_
     layer (an expert's jobs pair on its own parameters; C is the same for every micro-batch)."""
     if dropless:   # `saved` of moe_block_fwd(capacity_factor=None): with its segments
         return _moe_block_bwd_dropless(dout, d_aux, h2, saved, router_w, wgs, wus, wds, k, norm_topk_prob, need_dx, stages,
-                                       router)
+                                       router, **K._act_kw(act))
     idx, gate, probs, counts, slot, src, xe, gu, hh, ye = saved
     E = len(wgs)
     C = xe.shape[0] // E
     rows = [slice(e * C, (e + 1) * C) for e in range(E)]
     dye, dgate = K.moe_combine_bwd(dout, ye, slot, src, gate)
-    dgu, dhh = K.moe_experts_dgrad_down(dye, wds, gu, C, fuse=_fuse())
+    dgu, dhh = K.moe_experts_dgrad_down(dye, wds, gu, C, fuse=_fuse(), **K._act_kw(act))
     if dhh is not None:
         _stage(stages, dhh=dhh)
     for lo in range(0, E, K.MOE_GROUP):
@@ -1587,7 +1595,8 @@ class MoEFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h2, residual, router_w, wgs, wus, wds, k, capacity_factor, norm_topk_prob=True, stages=None,
-                router=None):
+                router=None, act="silu"):
+        # act stays the LAST parameter: model._act_tail pads the optional ones before it by position
         tp = TPContext.current()
         if tp.world_size > 1:
             raise NotImplementedError("mixture-of-experts layers under tensor parallelism (experts are not sharded)")
@@ -1595,9 +1604,9 @@ class MoEFunction(torch.autograd.Function):
         wgs, wus, wds = list(wgs), list(wus), list(wds)
         out, aux, saved = moe_block_fwd(x2, r2, router_w, wgs, wus, wds, int(k),
                                         None if capacity_factor is None else float(capacity_factor),
-                                        bool(norm_topk_prob), stages, router)
+                                        bool(norm_topk_prob), stages, router, **K._act_kw(act))
         ctx.save_for_backward(x2, router_w, *saved, *wgs, *wus, *wds)
-        ctx.router = router
+        ctx.router, ctx.act = router, act
         ctx.E, ctx.k, ctx.norm, ctx.shape, ctx.stages = len(wgs), int(k), bool(norm_topk_prob), h2.shape, stages
         ctx.dropless, ctx.nsaved = capacity_factor is None, len(saved)
         return out.view(h2.shape), aux.view(())
@@ -1614,8 +1623,9 @@ class MoEFunction(torch.autograd.Function):
         if daux is not None:
             daux = daux.to(torch.float32).reshape(1).contiguous()
         dh = moe_block_bwd(d2, daux, x2, saved, router_w, wgs, wus, wds, ctx.k, ctx.norm,
-                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages, dropless=ctx.dropless, router=ctx.router)
-        return (dh.view(ctx.shape) if dh is not None else None, dout if ctx.needs_input_grad[1] else None) + (None,) * 9
+                           need_dx=ctx.needs_input_grad[0], stages=ctx.stages, dropless=ctx.dropless, router=ctx.router,
+                           **K._act_kw(ctx.act))
+        return (dh.view(ctx.shape) if dh is not None else None, dout if ctx.needs_input_grad[1] else None) + (None,) * 10
 
 
 def update_moe_router_bias(model, group=None):
@@ -1656,11 +1666,14 @@ class DecoderLayerFunction(torch.autograd.Function):
 
     Backward runs the same kernels in reverse; the residual gradients are fused into the norm
     backward kernels (dres) and the TP dX all-reduces overlap the dW GEMMs.  zz: x is a zig-zag CP
-    shard (cos / sin its positions' tables): the ring runs on it with no re-lay."""
+    shard (cos / sin its positions' tables): the ring runs on it with no re-lay.  act: the MLP's gate
+    activation ("gelu_tanh": GeGLU), elementwise on the column-parallel shard under tp > 1."""
 
     @staticmethod
     def forward(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode, nh, nkv, d, zz=False, sp=0,
-                band=None, wqn=None, wkn=None):
+                band=None, wqn=None, wkn=None, act="silu"):
+        # act stays the LAST parameter: model._act_tail pads the optional ones before it by position
+        ctx.act = act
         qkn = QKNorm.of(wqn, wkn, eps, mode)   # the q_norm / k_norm weights: the layer norms' flavour
         if qkn is not None:
             qkn.require(AttnShape(1, x.shape[1], nh, nkv, d), TPContext.current(), bool(sp))
@@ -1669,7 +1682,7 @@ class DecoderLayerFunction(torch.autograd.Function):
                                       "layout (its chunks re-batch the rows the band describes)")
         if sp:   # sp = the chunk count of the sequence-parallel layout (0: the replicated stream)
             return DecoderLayerFunction._forward_sp(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode,
-                                                    nh, nkv, d, int(sp))
+                                                    nh, nkv, d, int(sp), **K._act_kw(act))
         ctx.sp = False
         B, S, H = x.shape
         sh = AttnShape(B, S, nh, nkv, d, zz, band)
@@ -1678,7 +1691,7 @@ class DecoderLayerFunction(torch.autograd.Function):
         h1, rstd1, _ = K.rmsnorm_fwd(x2, w1, eps, mode)
         a, asaved = attn_block_fwd(h1, wq, wk, wv, wo, cos, sin, sh, tp, qkn=qkn)
         h2, rstd2, z = K.rmsnorm_fwd(a, w2, eps, mode, residual=x2)
-        out, msaved = mlp_block_fwd(h2, wg, wu, wd, tp, residual=z)
+        out, msaved = mlp_block_fwd(h2, wg, wu, wd, tp, residual=z, **K._act_kw(act))
         ctx.save_for_backward(x2, h1, rstd1, *asaved[:3], z, h2, rstd2, *msaved,
                               w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin,
                               *((*asaved[3:], wqn, wkn) if qkn is not None else ()))
@@ -1686,7 +1699,7 @@ class DecoderLayerFunction(torch.autograd.Function):
         return out.view(B, S, H)
 
     @staticmethod
-    def _forward_sp(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode, nh, nkv, d, c):
+    def _forward_sp(ctx, x, w1, w2, wq, wk, wv, wo, wg, wu, wd, cos, sin, eps, mode, nh, nkv, d, c, act="silu"):
         """Sequence-parallel TP layer (tensor_parallel/sequence_parallel.py): x is this rank's shard
         of the residual stream in the chunked token-row layout (TPContext.gather_chunk: c chunks of
         B / c whole sequences; rank r holds rows [r n, (r + 1) n) of each), viewed [B, S/tp, H].  The
@@ -1728,7 +1741,7 @@ class DecoderLayerFunction(torch.autograd.Function):
         msaved, rs = [], []
         for j in range(c):
             wait_all(ag[j:j + 1])
-            m, sv = mlp_block_fwd(h2[j * Tc:(j + 1) * Tc], wg, wu, wd, tp, reduce=False)
+            m, sv = mlp_block_fwd(h2[j * Tc:(j + 1) * Tc], wg, wu, wd, tp, reduce=False, **K._act_kw(act))
             msaved += list(sv)
             rs.append(tp.scatter_chunk(mr, m, c, j, async_op=True))
         wait_all(rs)
@@ -1757,7 +1770,7 @@ class DecoderLayerFunction(torch.autograd.Function):
             rows = slice(j * Tc, (j + 1) * Tc)
             n = dout2.shape[0] // c
             rs.append(mlp_block_bwd(dm[rows], h2[rows], msaved[2 * j:2 * j + 2], wg, wu, wd, tp,
-                                    rs_out=dh2[j * n:(j + 1) * n], notify=j == c - 1))
+                                    rs_out=dh2[j * n:(j + 1) * n], notify=j == c - 1, **K._act_kw(ctx.act)))
         wait_all(rs)
         dz = norm_bwd(dh2, z, w2, rstd2, mode, dres=dout2, sp=tp)
         da = torch.empty_like(h1)
@@ -1772,7 +1785,7 @@ class DecoderLayerFunction(torch.autograd.Function):
                                      rs_out=dh1[j * n:(j + 1) * n], notify=j == c - 1))
         wait_all(rs)
         dx = norm_bwd(dh1, x2, w1, rstd1, mode, dres=dz, sp=tp)
-        return (dx.view(dout.shape),) + (None,) * 21
+        return (dx.view(dout.shape),) + (None,) * 22
 
     @staticmethod
     def backward(ctx, dout):
@@ -1785,12 +1798,13 @@ class DecoderLayerFunction(torch.autograd.Function):
         tp = TPContext.current()
         dout2 = _contig2d(dout)
         # the gate|up dX's split-K halves go straight into the norm backward (summed there)
-        dh2 = mlp_block_bwd(dout2, h2, (gu, hh), wg, wu, wd, tp, keep_parts=K.norm_splitk_enabled())
+        dh2 = mlp_block_bwd(dout2, h2, (gu, hh), wg, wu, wd, tp, keep_parts=K.norm_splitk_enabled(),
+                            **K._act_kw(ctx.act))
         dz = norm_bwd(dh2, z, w2, rstd2, mode, dres=dout2)
         dh1 = attn_block_bwd(dz, h1, (qkv, o, lse, *rest[:2]), wq, wk, wv, wo, cos, sin, sh, tp,
                              keep_parts=K.norm_splitk_enabled(), qkn=qkn)
         dx = norm_bwd(dh1, x2, w1, rstd1, mode, dres=dz)   # (norm_bwd skips dW of frozen weights)
-        return (dx.view(sh.B, sh.S, -1),) + (None,) * 21
+        return (dx.view(sh.B, sh.S, -1),) + (None,) * 22
 
 
 # ------------------------------------------------------------------------ cross entropy

@@ -845,24 +845,40 @@ def qk_norm_bwd(dy, x, wq, wk, rstd, nq, nk, d, mode, dx=None, need_dw=(True, Tr
     return dx, pq, pk
 
 
-# ---------------------------------------------------------------------------------- SwiGLU
-def swiglu_fwd(g, u, out=None):
+# ---------------------------------------------------------------------------------- SwiGLU / GeGLU
+# The gate activation of the gated MLP, a keyword of every form below: "silu" (SwiGLU, the default) or
+# "gelu_tanh" (GeGLU: the Gemma family's hidden_act "gelu_pytorch_tanh").  It selects the row kernel and the
+# GEMM epilogue id -- the activation travels in the id, pt_gemm_problem has no field for it.
+_GLU_ROW = {"silu": "pt_swiglu", "gelu_tanh": "pt_geglu"}
+_GLU_EPI = {"silu": (5, 6), "gelu_tanh": (10, 11)}   # (forward, backward)
+
+
+def _act_kw(act):
+    """The keyword for a callee: SiLU calls pass exactly the arguments they always passed."""
+    return {} if act == "silu" else {"act": act}
+
+
+def swiglu_fwd(g, u, out=None, act="silu"):
+    _req(act in _GLU_ROW, f"act must be one of {sorted(_GLU_ROW)}, got {act!r}")
     rows, cols = g.shape
     h = out if out is not None else torch.empty(rows, cols, dtype=BF16, device=g.device)
-    rc = _C.lib().pt_swiglu_fwd(_ptr(g), g.stride(0), _ptr(u), u.stride(0), _ptr(h), h.stride(0), rows, cols,
-                                _C.stream_ptr(g.device))
-    _C.check(rc, "pt_swiglu_fwd")
+    name = _GLU_ROW[act] + "_fwd"
+    rc = getattr(_C.lib(), name)(_ptr(g), g.stride(0), _ptr(u), u.stride(0), _ptr(h), h.stride(0), rows, cols,
+                                 _C.stream_ptr(g.device))
+    _C.check(rc, name)
     return h
 
 
-def swiglu_bwd(dh, g, u, dg=None, du=None):
+def swiglu_bwd(dh, g, u, dg=None, du=None, act="silu"):
+    _req(act in _GLU_ROW, f"act must be one of {sorted(_GLU_ROW)}, got {act!r}")
     rows, cols = g.shape
     dh = dh if dh.stride(-1) == 1 else dh.contiguous()
     dg = dg if dg is not None else torch.empty(rows, cols, dtype=BF16, device=g.device)
     du = du if du is not None else torch.empty(rows, cols, dtype=BF16, device=g.device)
-    rc = _C.lib().pt_swiglu_bwd(_ptr(dh), dh.stride(0), _ptr(g), g.stride(0), _ptr(u), u.stride(0), _ptr(dg),
-                                dg.stride(0), _ptr(du), du.stride(0), rows, cols, _C.stream_ptr(g.device))
-    _C.check(rc, "pt_swiglu_bwd")
+    name = _GLU_ROW[act] + "_bwd"
+    rc = getattr(_C.lib(), name)(_ptr(dh), dh.stride(0), _ptr(g), g.stride(0), _ptr(u), u.stride(0), _ptr(dg),
+                                 dg.stride(0), _ptr(du), du.stride(0), rows, cols, _C.stream_ptr(g.device))
+    _C.check(rc, name)
     return dg, du
 
 
@@ -1523,9 +1539,9 @@ def _alg_bytes(M, N, K, epilogue):
     two [M, N] bf16 tensors more)."""
     elem = 4 if epilogue in (EPI_F32, EPI_F32_ACC) else 2
     c = M * N * elem * (2 if epilogue in (EPI_BF16_ACC, EPI_F32_ACC, EPI_BF16_RES) else 1)
-    if epilogue == 5:      # gate|up: reads x, Wg, Wu; writes g|u and h
+    if epilogue in (5, 10):      # gate|up (SwiGLU / GeGLU): reads x, Wg, Wu; writes g|u and h
         c = M * N * 2 + M * (N // 2) * 2
-    elif epilogue == 6:    # down dX: reads g|u, writes dg|du
+    elif epilogue in (6, 11):    # down dX: reads g|u, writes dg|du
         c = 4 * M * N * 2
     return 2 * (M * K + N * K) + c
 
@@ -1955,7 +1971,13 @@ def linear_fwd(x2d, weights, out=None, tile=-1, residual=None):
     return y
 
 
-EPI_SWIGLU_FWD, EPI_SWIGLU_BWD = 5, 6
+EPI_SWIGLU_FWD, EPI_SWIGLU_BWD = _GLU_EPI["silu"]
+EPI_GEGLU_FWD, EPI_GEGLU_BWD = _GLU_EPI["gelu_tanh"]
+
+
+def _glu_epi(act, backward=False):
+    _req(act in _GLU_EPI, f"act must be one of {sorted(_GLU_EPI)}, got {act!r}")
+    return _GLU_EPI[act][int(backward)]
 
 
 def rope_fusable(T, head_dim, seq_len, widths=()):
@@ -2120,9 +2142,9 @@ def swiglu_fuse_pays(T, I, backward=False, H=None):
         tiles >= (SW.swiglu_bwd_min_tiles if backward else SW.swiglu_fuse_min_tiles)
 
 
-def linear_swiglu_fwd(x2d, wg, wu):
+def linear_swiglu_fwd(x2d, wg, wu, act="silu"):
     """gate|up projection with SwiGLU in the GEMM epilogue (model.py:186): returns (gu [T, 2I] =
-    [x Wg^T | x Wu^T], h = bf16(bf16(silu(g)) * u) [T, I]) in one launch."""
+    [x Wg^T | x Wu^T], h = bf16(bf16(silu(g)) * u) [T, I]) in one launch.  act="gelu_tanh": GeGLU."""
     _bf16_rowmajor(x2d, "x")
     T, K = x2d.shape
     I = wg.shape[0]
@@ -2132,13 +2154,13 @@ def linear_swiglu_fwd(x2d, wg, wu):
     gu = torch.empty(T, 2 * I, dtype=BF16, device=x2d.device)
     h = torch.empty(T, I, dtype=BF16, device=x2d.device)
     _gemm(x2d, x2d.stride(0), 1, [wg, wu], [K, K], [0, I, 2 * I], 1, 0, [h, gu], [I, 2 * I], [0, T], T, 2 * I, K,
-          EPI_SWIGLU_FWD)
+          _glu_epi(act))
     return gu, h
 
 
-def linear_dgrad_swiglu(dy2d, wd, gu):
-    """dh = dY W_down (model.py:186 backward) with the SwiGLU backward in the epilogue: returns
-    dgu = [dg | du] [T, 2I] (dh is never materialised)."""
+def linear_dgrad_swiglu(dy2d, wd, gu, act="silu"):
+    """dh = dY W_down (model.py:186 backward) with the SwiGLU (act="gelu_tanh": GeGLU) backward in the
+    epilogue: returns dgu = [dg | du] [T, 2I] (dh is never materialised)."""
     _bf16_rowmajor(dy2d, "dy")
     _bf16_rowmajor(gu, "gu")
     T, H = dy2d.shape
@@ -2147,8 +2169,8 @@ def linear_dgrad_swiglu(dy2d, wd, gu):
     _req(tuple(gu.shape) == (T, 2 * I), "gu must be [T, 2I]")
     _req(swiglu_fusable(T, I, backward=True, H=dy2d.shape[1]), "linear_dgrad_swiglu: T % 256, I % 256 and H % 64 required")
     dgu = torch.empty(T, 2 * I, dtype=BF16, device=dy2d.device)
-    _gemm(dy2d, dy2d.stride(0), 1, [wd], [I], [0, I], 0, 0, [dgu], [dgu.stride(0)], [0, T], T, I, H, EPI_SWIGLU_BWD,
-          residual=gu, ldr=gu.stride(0))
+    _gemm(dy2d, dy2d.stride(0), 1, [wd], [I], [0, I], 0, 0, [dgu], [dgu.stride(0)], [0, T], T, I, H,
+          _glu_epi(act, True), residual=gu, ldr=gu.stride(0))
     return dgu
 
 
@@ -2187,7 +2209,7 @@ def _moe_weights(ws, shape, what):
         _req(w.dtype == BF16 and w.is_contiguous() and tuple(w.shape) == tuple(shape), f"{what}: contiguous bf16 {shape}")
 
 
-def moe_experts_fwd(xe, wgs, wus, wds, C, fuse=True):
+def moe_experts_fwd(xe, wgs, wus, wds, C, fuse=True, act="silu"):
     """xe [E C, H] -> (gu [E C, 2I] = [x Wg_e^T | x Wu_e^T], hh [E C, I] = swiglu, ye [E C, H] =
     hh Wd_e^T), each expert on its own C rows."""
     E = _moe_expert_shapes(xe, wgs, C, "xe")
@@ -2203,17 +2225,17 @@ def moe_experts_fwd(xe, wgs, wus, wds, C, fuse=True):
     if fuse and swiglu_fusable(C, I, H=H):
         _moe_gemm("gate|up+swiglu", [_problem(xe[r], H, [wg, wu], [H, H], [0, I, 2 * I], 0, [hh[r], gu[r]], [I, 2 * I],
                                               [0, C], C, 2 * I, H) for r, wg, wu in zip(rows, wgs, wus)],
-                  1, 1, EPI_SWIGLU_FWD, (C, 2 * I, H), dev)
+                  1, 1, _glu_epi(act), (C, 2 * I, H), dev)
     else:
         _moe_gemm("gate|up", [_problem(xe[r], H, [wg, wu], [H, H], [0, I, 2 * I], 0, [gu[r]], [2 * I], [0, C], C, 2 * I, H)
                               for r, wg, wu in zip(rows, wgs, wus)], 1, 1, EPI_BF16, (C, 2 * I, H), dev)
-        swiglu_fwd(gu[:, :I], gu[:, I:], out=hh)
+        swiglu_fwd(gu[:, :I], gu[:, I:], out=hh, **_act_kw(act))
     _moe_gemm("down", [_problem(hh[r], I, [wd], [I], [0, H], 0, [ye[r]], [H], [0, C], C, H, I)
                        for r, wd in zip(rows, wds)], 1, 1, EPI_BF16, (C, H, I), dev)
     return gu, hh, ye
 
 
-def moe_experts_dgrad_down(dye, wds, gu, C, fuse=True):
+def moe_experts_dgrad_down(dye, wds, gu, C, fuse=True, act="silu"):
     """dye [E C, H] -> (dgu [E C, 2I] = the SwiGLU backward of dhh = dye Wd_e on the saved gate|up,
     dhh [E C, I] or None where the epilogue-fused form never stores it)."""
     E = _moe_expert_shapes(dye, wds, C, "dye")
@@ -2230,12 +2252,12 @@ def moe_experts_dgrad_down(dye, wds, gu, C, fuse=True):
             pr = _problem(dye[r], H, [wd], [I], [0, I], 0, [dgu[r]], [2 * I], [0, C], C, I, H)
             pr.residual, pr.ldr = _ptr(gu[r]), 2 * I
             probs.append(pr)
-        _moe_gemm("down dX+swiglu", probs, 1, 0, EPI_SWIGLU_BWD, (C, I, H), dev)
+        _moe_gemm("down dX+swiglu", probs, 1, 0, _glu_epi(act, True), (C, I, H), dev)
         return dgu, None
     dhh = torch.empty(E * C, I, dtype=BF16, device=dev)
     _moe_gemm("down dX", [_problem(dye[r], H, [wd], [I], [0, H], 1, [dhh[r]], [I], [0, C], C, I, H)
                           for r, wd in zip(rows, wds)], 1, 0, EPI_BF16, (C, I, H), dev)
-    swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:])
+    swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:], **_act_kw(act))
     return dgu, dhh
 
 
@@ -2315,7 +2337,7 @@ def _moe_seg_shapes(buf, ws, seg, tile_expert, what):
     return E
 
 
-def moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert):
+def moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert, act="silu"):
     """The dropless form of moe_experts_fwd: xe [R, H] -> (gu [R, 2I], hh [R, I], ye [R, H]), one
     launch per product for all experts; the SwiGLU is the row kernel over the whole buffer."""
     E = _moe_seg_shapes(xe, wgs, seg, tile_expert, "xe")
@@ -2327,13 +2349,13 @@ def moe_experts_fwd_seg(xe, wgs, wus, wds, seg, tile_expert):
     tgu = _moe_seg_table([_ptr(w) for w in wgs], [_ptr(w) for w in wus], H, dev)
     gu = moe_gemm_seg(0, xe, tgu, seg, tile_expert, 2 * I, H, I, E, label="gate|up")
     hh = torch.empty(xe.shape[0], I, dtype=BF16, device=dev)
-    swiglu_fwd(gu[:, :I], gu[:, I:], out=hh)
+    swiglu_fwd(gu[:, :I], gu[:, I:], out=hh, **_act_kw(act))
     td = _moe_seg_table([_ptr(w) for w in wds], None, I, dev)
     ye = moe_gemm_seg(0, hh, td, seg, tile_expert, H, I, H, E, label="down")
     return gu, hh, ye
 
 
-def moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert):
+def moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert, act="silu"):
     """dye [R, H] -> (dgu [R, 2I], dhh [R, I] = dye Wd_e), the dropless form of moe_experts_dgrad_down."""
     E = _moe_seg_shapes(dye, wds, seg, tile_expert, "dye")
     H, I = dye.shape[1], wds[0].shape[1]
@@ -2343,7 +2365,7 @@ def moe_experts_dgrad_down_seg(dye, wds, gu, seg, tile_expert):
     td = _moe_seg_table([_ptr(w) for w in wds], None, I, dye.device)
     dhh = moe_gemm_seg(1, dye, td, seg, tile_expert, I, H, H, E, label="down dX")
     dgu = torch.empty_like(gu)
-    swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:])
+    swiglu_bwd(dhh, gu[:, :I], gu[:, I:], dg=dgu[:, :I], du=dgu[:, I:], **_act_kw(act))
     return dgu, dhh
 
 
@@ -2526,14 +2548,17 @@ class _DualRefused(Exception):
     """pt_gemm_dual answered PT_EUNSUPPORTED: nothing was launched."""
 
 
-def linear_dgrad_dual(dy2d, weights, wjobs, wepilogue, gu=None, order=None, keep_parts=False, split_min=None):
+def linear_dgrad_dual(dy2d, weights, wjobs, wepilogue, gu=None, order=None, keep_parts=False, split_min=None,
+                      act="silu"):
     """dX = dY . [W_0; ...] (or, with gu, the SwiGLU backward dg|du of the down_proj dX:
     linear_dgrad_swiglu) AND the wgrads wjobs [(dy2d, x2d, outs)] (linear_wgrad, epilogue
     wepilogue) in ONE launch (pt_gemm_dual).  Returns dX / dg|du, or None (nothing launched) when
-    the problems do not tile for it -- the caller then launches them separately."""
+    the problems do not tile for it -- the caller then launches them separately.  act: the gate activation
+    of the gu form ("gelu_tanh": epilogue / reduce mode 11 for 6)."""
     _bf16_rowmajor(dy2d, "dy")
     T, N = dy2d.shape
     dev = dy2d.device
+    ebwd = _glu_epi(act, True)
     parts = dxsink = None   # the dX as two f32 K halves / the real sink of a K-sliced SwiGLU dX
     if gu is not None:
         wd = weights[0]
@@ -2548,13 +2573,13 @@ def linear_dgrad_dual(dy2d, weights, wjobs, wepilogue, gu=None, order=None, keep
             dxpart = torch.empty(dxs * T * I, dtype=torch.float32, device=dev)
             p0 = _problem(dy2d, dy2d.stride(0), [wd], [I], [0, I], 0, [dxpart], [I], [0, T], T, I, N)
             p0.ksplit, p0.kpart_stride = dxs, T * I
-            e0, dxsink = EPI_F32, ([dx], [0, T], EPI_SWIGLU_BWD, gu, gu.stride(0))
+            e0, dxsink = EPI_F32, ([dx], [0, T], ebwd, gu, gu.stride(0))
         else:
             p0 = _problem(dy2d, dy2d.stride(0), [wd], [I], [0, I], 0, [dx], [dx.stride(0)], [0, T], T, I, N)
             p0.residual, p0.ldr = _ptr(gu), gu.stride(0)
-            e0 = EPI_SWIGLU_BWD
+            e0 = ebwd
         p0s = (_C.GemmProblem * 1)(p0)
-        flops, nbytes = 2.0 * T * I * N, _alg_bytes(T, I, N, EPI_SWIGLU_BWD)
+        flops, nbytes = 2.0 * T * I * N, _alg_bytes(T, I, N, ebwd)
     else:
         ncols = Kin = weights[0].shape[1]
         ns = [w.shape[0] for w in weights]

@@ -438,11 +438,38 @@ class MLAttention(nn.Module):
                                             _norm_eps(n), _norm_mode(n))
 
 
+def mlp_activation(config):
+    """The gated MLP's activation from config.hidden_act, or config.hidden_activation where hidden_act is
+    absent (Gemma-2/3's field): "silu" (also when neither is set) or "gelu_tanh" for "gelu_pytorch_tanh" /
+    "gelu_tanh" -- kernels.swiglu_fwd's act keyword.  Anything else, the exact erf "gelu" included, raises."""
+    name = getattr(config, "hidden_act", None)
+    if name is None:
+        name = getattr(config, "hidden_activation", None)
+    if name is None or name == "silu":
+        return "silu"
+    if name in ("gelu_pytorch_tanh", "gelu_tanh"):
+        return "gelu_tanh"
+    raise NotImplementedError(f'hidden_act {name!r}: the gated MLP kernels take "silu" and "gelu_pytorch_tanh" '
+                              '(alias "gelu_tanh")')
+
+
+def _act_tail(act, given=(), slots=0):
+    """The trailing positional arguments of an autograd Function whose LAST parameter is `act`, with `slots`
+    optional parameters between the required ones and it (MLPFunction: residual, 1; DecoderLayerFunction after
+    band: wqn, wkn, 2; MoEFunction after router: 0), of which the caller has `given`.  SiLU passes `given` alone,
+    the call it always made; another activation pads with None up to the act slot."""
+    given = tuple(given)
+    return given if act == "silu" else given + (None,) * (slots - len(given)) + (act,)
+
+
 class MLP(nn.Module):
-    """model.py:164-186 (parameter order up, gate, down as in the reference)."""
+    """model.py:164-186 (parameter order up, gate, down as in the reference).  config.hidden_act /
+    hidden_activation = "gelu_pytorch_tanh" makes it the Gemma family's GeGLU MLP (mlp_activation), the
+    same parameters."""
 
     def __init__(self, config) -> None:
         super().__init__()
+        self.act = mlp_activation(config)
         self.up_proj = Linear(config.hidden_size, config.intermediate_size, bias=False)
         self.gate_proj = Linear(config.hidden_size, config.intermediate_size, bias=False)
         self.down_proj = Linear(config.intermediate_size, config.hidden_size, bias=False)
@@ -453,7 +480,8 @@ class MLP(nn.Module):
             _init_uniform_fan_in(t)
 
     def forward(self, x):
-        return FN.MLPFunction.apply(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight)
+        return FN.MLPFunction.apply(x, self.gate_proj.weight, self.up_proj.weight, self.down_proj.weight,
+                                    *_act_tail(self.act, (), 1))
 
 
 class MoE(nn.Module):
@@ -525,11 +553,13 @@ class MoE(nn.Module):
         if self.n_shared_experts < 0 or not (self.bias_update_rate >= 0.0 and math.isfinite(self.bias_update_rate)):
             raise ValueError("MoE: n_shared_experts >= 0 and a finite moe_bias_update_rate >= 0")
         self.router = Linear(config.hidden_size, self.num_experts, bias=False)
-        expert = types.SimpleNamespace(hidden_size=config.hidden_size, intermediate_size=inter)
+        self.act = mlp_activation(config)   # the routed and the shared experts' gate activation
+        expert = types.SimpleNamespace(hidden_size=config.hidden_size, intermediate_size=inter, hidden_act=self.act)
         self.experts = nn.ModuleList([MLP(expert) for _ in range(self.num_experts)])
         if self.n_shared_experts:
             self.shared_experts = MLP(types.SimpleNamespace(hidden_size=config.hidden_size,
-                                                            intermediate_size=self.n_shared_experts * inter))
+                                                            intermediate_size=self.n_shared_experts * inter,
+                                                            hidden_act=self.act))
         if self.scoring_func == "sigmoid":
             self.register_buffer(self._F32_BUFFER, torch.zeros(self.num_experts, dtype=torch.float32))
             if self.bias_update_rate > 0.0:
@@ -565,13 +595,15 @@ class MoE(nn.Module):
     def forward(self, x, residual=None):
         if self.n_shared_experts:   # residual + shared(x) out of the dense block's down_proj epilogue
             sh = self.shared_experts
-            residual = FN.MLPFunction.apply(x, sh.gate_proj.weight, sh.up_proj.weight, sh.down_proj.weight, residual)
+            residual = FN.MLPFunction.apply(x, sh.gate_proj.weight, sh.up_proj.weight, sh.down_proj.weight,
+                                            *_act_tail(sh.act, (residual,), 1))
         elif residual is None:
             residual = torch.zeros_like(x)
         out, self.aux_loss = FN.MoEFunction.apply(
             x, residual, self.router.weight, [e.gate_proj.weight for e in self.experts],
             [e.up_proj.weight for e in self.experts], [e.down_proj.weight for e in self.experts], self.top_k,
-            None if self.dropless else self.capacity_factor, self.norm_topk_prob, self.stages, self.router_variant())
+            None if self.dropless else self.capacity_factor, self.norm_topk_prob, self.stages, self.router_variant(),
+            *_act_tail(self.act))
         return out
 
 
@@ -637,7 +669,8 @@ class DecoderLayer(nn.Module):
             h2, z = FN.AddRMSNormFunction.apply(a, x, n2.weight, eps, mode)
             if isinstance(mlp, MoE):
                 return mlp(h2, z)
-            return FN.MLPFunction.apply(h2, mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight, z)
+            return FN.MLPFunction.apply(h2, mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
+                                        *_act_tail(mlp.act, (z,), 1))
         band = document_ids if isinstance(document_ids, (K.AttnBand, context_parallel.CPBand)) else None
         if band is None and (document_ids is not None or at.sliding_window is not None):
             if sp or (zz and not FN.ring_enabled()):
@@ -657,11 +690,12 @@ class DecoderLayer(nn.Module):
             h2, z = FN.AddRMSNormFunction.apply(a, x, n2.weight, eps, mode)
             if isinstance(mlp, MoE):
                 return mlp(h2, z)
-            return FN.MLPFunction.apply(h2, mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight, z)
+            return FN.MLPFunction.apply(h2, mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
+                                        *_act_tail(mlp.act, (z,), 1))
         return FN.DecoderLayerFunction.apply(
             x, n1.weight, n2.weight, *at.weights(), mlp.gate_proj.weight, mlp.up_proj.weight, mlp.down_proj.weight,
             cos, sin, _norm_eps(n1), _norm_mode(n1), at.num_local_heads, at.num_local_kv_heads, at.head_dim, zz, sp,
-            band, *qk[:2])
+            band, *_act_tail(mlp.act, qk[:2], 2))
 
 
 class Embedding(nn.Module):
